@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the sweep + replica-exchange path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--strong]
+    python bench.py --gpus N --steps K --warmup W [--strong] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps of the headline leg, the
+outputs (--dump-outputs) and the result line.  --full adds everything else described below: the second leg, the CPU
+baselines, the per-kernel figures from HIP events, the roofline objects with their probe runs, and the check of the tracked
+energies against a recomputation.  --dump-outputs DIR writes what the last timed step left behind (the final replica
+configurations, their tracked energies and the temperature slot table) as DIR/<name>.npy in float32 / float64, at most
+64 MB in all; the inputs depend on the arguments only, so two builds can be compared output for output.
 
 With N > 1 and no torch.distributed environment this script starts `python -m torch.distributed.run --nproc-per-node N
 bench.py ...` itself as a CHILD process (before anything touches the GPU) and exits with the child's code; launched by
@@ -9,8 +16,8 @@ torch.distributed.run it is one rank per GPU over RCCL.
 
 A "step" is ROUNDS_PER_STEP = 5120 replica-exchange rounds of NPT (~0.6 s of GPU time: the driver's --steps 20 times ~12 s
 per leg, the default 4 steps 2.4 s); a round is S_SWAP = 10 heat-bath sweeps of every replica at its ladder temperature
-followed by one swap-attempt round.  TWO legs of equal standing run with the same --steps / --warmup, GPU work first, CPU
-baselines last: the headline leg in the reference's arithmetic (fp64 field, 53-bit uniform: NMC/nmc.py:86-87 -- the "f64"
+followed by one swap-attempt round.  With --full, TWO legs of equal standing run with the same --steps / --warmup, GPU work
+first, CPU baselines last: the headline leg in the reference's arithmetic (fp64 field, 53-bit uniform: NMC/nmc.py:86-87 -- the "f64"
 mode, on fused windows because the +-J instance makes the fp64 field an exact integer, bit-identical to the sweep-by-sweep
 fp64 kernel and the fp64 oracle) and the fixed-point "f32" throughput mode (`fixed_point_f32`; its own stated tolerance,
 DESIGN.md section 2).  Workload (SURVEY.md section 8d, config C4 on
@@ -24,7 +31,8 @@ EVERYTHING a round needs is inside the timed region: the per-sweep visiting orde
 selections (k_pt_select) are built chunk by chunk (256 rounds) by the round that first needs them, after t0.  Only
 the instance, the replica states and the ladder are resident in HBM before the timed region starts.
 
-Prints ONE JSON line (rank 0).  `value` = end-to-end spin-updates/s of the whole job (headline leg); `value_kernel_loop` = the same
+Prints ONE JSON line (rank 0).  `value` = end-to-end spin-updates/s of the whole job (headline leg); `ms_per_step` = the
+milliseconds of one timed step; with --full also: `value_kernel_loop` = the same
 updates over the summed durations of the sweep kernel alone; `roofline` prices the dominant kernel (HIP events recorded on the
 stream it runs on) against the bound that binds it -- levels per second of a level-synchronous workgroup against the floor of one
 level (barrier + LDS gather + write), MEASURED in the same run by nlmc_probe_level_round -- and `roofline_algorithmic` keeps the
@@ -76,6 +84,31 @@ def load_pmc():
             return json.load(f)
     except OSError:
         return {}
+
+
+DUMP_BUDGET_BYTES = (64 << 20) - (64 << 10)   # --dump-outputs: 64 MB in all, less room for the .npy headers
+DUMP_SAMPLE_SEED = 20250226
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> ndarray, written as out_dir/<name>.npy (float32 for float32 and integers of up to 16 bits, float64
+    for the rest: both exact).  If they would pass DUMP_BUDGET_BYTES, the rows of the largest one (all axes but the last
+    flattened) are cut to a fixed, seeded sample (its row indices are written as <name>_rows.npy)."""
+    import numpy as np
+    out = {k: np.ascontiguousarray(v, dtype=np.float32 if (v.dtype == np.float32 or (v.dtype.kind in "iub" and v.dtype.itemsize <= 2))
+                                   else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_BUDGET_BYTES:
+        big = max(out, key=lambda k: out[k].nbytes)
+        v = out[big].reshape(-1, out[big].shape[-1]) if out[big].ndim > 1 else out[big]
+        row_bytes = v.nbytes // v.shape[0]
+        keep = (DUMP_BUDGET_BYTES - (total - v.nbytes) - 8 * v.shape[0]) // row_bytes
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(v.shape[0], size=int(keep), replace=False))
+        out[big] = np.ascontiguousarray(v[rows])
+        out[big + "_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def cpu_baseline(J, h, seconds=12.0, chain=0, use_f64=True):
@@ -195,12 +228,12 @@ def run_c5(a, P, inst, torch, dist, world, rank, local_rank):
             dist.barrier()
         torch.cuda.synchronize()
 
-    def leg(precision):
+    def leg(precision, dump=None):
         apt = P.distributed.SlotShardedAPT(mk, inst, betas, K, PHILOX_SEED, n_pairs, torch=torch, dist=dist, device=dev, precision=precision)
         rng = np.random.default_rng(1000)
         spins = (2 * rng.integers(0, 2, size=(K, R, N_SPINS), dtype=np.int8) - 1).astype(np.int8)
         apt.set_spins_by_slot(spins)
-        e0 = apt.gather_by_slot()[1].min()
+        e0 = apt.gather_by_slot()[1].min() if a.full else None
         wr, tr = a.warmup * C5_ROUNDS_PER_STEP, a.steps * C5_ROUNDS_PER_STEP
         apt.plan(wr + tr, S_SWAP, chunk_rounds=PLAN_CHUNK_ROUNDS)
         for _ in range(wr):
@@ -215,19 +248,25 @@ def run_c5(a, P, inst, torch, dist, world, rank, local_rank):
             t = torch.tensor([dt], dtype=torch.float64, device="cpu" if gloo else "cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        cfg, en = apt.gather_by_slot()
-        ok = bool(np.array_equal(en[:, :C5_BETAS_PER_GPU], np.stack([apt.engs[0].energy_of(c[:C5_BETAS_PER_GPU]) for c in cfg])))
         coll = ("rccl ncclAllGather + grouped ncclSend/ncclRecv issued by libnlmc_hip.so on the kernels' stream" if apt.lib_collective
                 else "torch.distributed all_gather + batch_isend_irecv" if (dist is not None and world > 1) else None)
+        res = {"value": float(K * R) * N_SPINS * S_SWAP * tr / dt, "unit": "spin-updates/s", "precision": precision, "rounds_timed": tr,
+               "seconds_timed": dt, "ms_per_round": dt / tr * 1e3, "collective": coll}
+        if dump or a.full:
+            cfg, en = apt.gather_by_slot()
+            if dump and rank == 0:
+                # configurations [sub-replica, global slot, spin] and their tracked energies
+                dump_outputs(dump, {"spins": cfg, "energies": en})
+            if a.full:
+                ok = bool(np.array_equal(en[:, :C5_BETAS_PER_GPU], np.stack([apt.engs[0].energy_of(c[:C5_BETAS_PER_GPU]) for c in cfg])))
+                res.update({"min_energy": {"start": float(e0), "end": float(en.min())}, "tracked_energies_equal_fp64_recomputation": ok})
         apt.check()
         apt.close()
-        return {"value": float(K * R) * N_SPINS * S_SWAP * tr / dt, "unit": "spin-updates/s", "precision": precision, "rounds_timed": tr,
-                "seconds_timed": dt, "ms_per_round": dt / tr * 1e3, "collective": coll,
-                "min_energy": {"start": float(e0), "end": float(en.min())}, "tracked_energies_equal_fp64_recomputation": ok}
+        return res
 
     first, second = a.headline, ("f32" if a.headline == "f64" else "f64")
-    r1 = leg(first)
-    r2 = None if a.no_second_leg else leg(second)
+    r1 = leg(first, a.dump_outputs)
+    r2 = leg(second) if (a.full and not a.no_second_leg) else None
     if rank == 0:
         out = {"metric": "spin-updates/s (replicas x spins x sweeps / s), APT sweeps + iso-cluster moves + swap rounds (BASELINE config 5)",
                "value": r1["value"], "unit": "spin-updates/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -238,7 +277,7 @@ def run_c5(a, P, inst, torch, dist, world, rank, local_rank):
                           "temperatures_per_gpu": C5_BETAS_PER_GPU, "subreplicas": K, "replicas_per_gpu": C5_BETAS_PER_GPU * K,
                           "sweeps_per_round": S_SWAP, "rounds_per_step": C5_ROUNDS_PER_STEP, "swap_pairs_per_round": n_pairs,
                           "sharding": "temperature-slot blocks, all sub-replicas of a temperature on one GPU"},
-               "ranks_seen": world}
+               "ranks_seen": world, "full": a.full}
         out.update({k: v for k, v in r1.items() if k not in ("value", "unit", "precision")})
         if r2 is not None:
             out["second_leg"] = r2
@@ -261,10 +300,19 @@ def main():
     ap.add_argument("--workload", choices=["c4", "c5"], default="c4",
                     help="c4 (default, the headline): replica-sharded NPT; c5: APT + iso-cluster moves, 32 temperatures x 8 sub-replicas "
                          "per GPU, the temperature ladder cut into slot blocks over the GPUs (BASELINE config 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the second leg, the CPU baselines, per-kernel and roofline figures and the energy check "
+                         "(a plain run times the headline leg only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--dry-run-launch", action="store_true", help="print the launcher command of --gpus N and exit")
     ap.add_argument("--cpu-worker", type=float, default=0.0, help=argparse.SUPPRESS)     # child of cpu_baseline_all_cores
     ap.add_argument("--cpu-chain", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)
 
     if a.cpu_worker > 0:                       # CPU-only child process: never touches the GPU
         from helpers import make_instance
@@ -341,15 +389,25 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run_leg(precision, steps, warmup):
+    def gather_rows(x):
+        """Rows of every rank's local array, in chain order (read-out only)."""
+        if dist is None:
+            return x
+        t = torch.from_numpy(np.ascontiguousarray(x)).to(red_dev)
+        parts = [torch.empty_like(t) for _ in range(world)]
+        dist.all_gather(parts, t)
+        return np.concatenate([p.cpu().numpy() for p in parts])
+
+    def run_leg(precision, steps, warmup, full, dump=None):
         """warmup + steps steps of ROUNDS_PER_STEP rounds; every schedule / pair selection of the timed rounds is built
-        inside the timed region (lazy chunks)."""
+        inside the timed region (lazy chunks).  `full`: HIP events, schedule statistics, probe and energy check as well;
+        `dump`: directory for what the last timed step left behind."""
         st = P.distributed.ShardedTempering(make_engine, inst, betas, G, PHILOX_SEED, n_pairs, torch=torch, dist=dist,
                                             device=torch.device("cuda", local_rank), precision=precision)
         base, count = st.base, st.count
         st.set_spins(np.concatenate([np.zeros((base, N_SPINS), np.int8), init_spins(count, N_SPINS, base=1000 + base),
                                      np.zeros((G - base - count, N_SPINS), np.int8)]) if world > 1 else init_spins(G, N_SPINS))
-        e_start = st.eng.energy()
+        e_start = st.eng.energy() if full else None
         fused = precision in st.eng.fused_modes(S_SWAP)
         chunk = PLAN_CHUNK_ROUNDS if fused else 8
         wr = warmup * ROUNDS_PER_STEP
@@ -359,7 +417,7 @@ def main():
             st.run_rounds(wr, S_SWAP, persistent=a.persistent)
         tr = steps * ROUNDS_PER_STEP
         st.plan(tr * S_SWAP, tr, chunk_rounds=chunk, lazy=True)     # a fresh, EMPTY planner: nothing is built yet
-        st.eng.timing_reset(True, every=EVENT_EVERY if fused else 1)
+        st.eng.timing_reset(full, every=EVENT_EVERY if fused else 1)          # a plain run records no events
         sync()
         t0 = time.perf_counter()
         # one process, whole ladders: one launch per round (the sweep launch decides the previous round's swap in its prologue); ranks
@@ -368,18 +426,26 @@ def main():
         st.run_rounds(tr, S_SWAP, persistent=a.persistent)
         sync()
         dt = time.perf_counter() - t0
-        tm = st.eng.timing_total()
+        tm = st.eng.timing_total() if full else None
         st.eng.timing_reset(False)
         if dist is not None:
             t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+        coll = ("rccl ncclAllGather issued by libnlmc_hip.so on the kernels' stream" if st.lib_collective else
+                "torch.distributed all_gather_into_tensor" if st.collective else None)
+        if dump:
+            # the final configurations (chain order), their tracked energies and the slot table
+            spins, energies, slots = st.gather_spins(), gather_rows(st.eng.energy_tracked()), st.eng.pt_slots()
+            if rank == 0:
+                dump_outputs(dump, {"spins": spins, "energies": energies, "slots": slots})
+        if not full:
+            st.close()
+            return {"dt": dt, "rounds": tr, "count": count, "collective": coll, "precision": precision}
         e_end = st.eng.energy()
         e_exact = st.eng.energy_of(st.eng.get_spins())            # tracked fixed-point energies == fp64 recomputation (untimed)
         sched = st.eng.last_schedule_stats()
         chunks = st._planner.chunks_planned if getattr(st, "_planner", None) is not None else 0
-        coll = ("rccl ncclAllGather issued by libnlmc_hip.so on the kernels' stream" if st.lib_collective else
-                "torch.distributed all_gather_into_tensor" if st.collective else None)
         # the floor of one level-synchronous step on THIS device, measured now (include/nlmc.h: nlmc_probe_level_round)
         probe = {"conflict_free_ns": st.eng.probe_level_round(16, True), "random_gather_ns": st.eng.probe_level_round(16, False)}
         st.close()
@@ -479,11 +545,13 @@ def main():
         return out
 
     first, second = a.headline, ("f32" if a.headline == "f64" else "f64")
-    r = run_leg(first, a.steps, a.warmup)
-    r2 = None if a.no_second_leg else run_leg(second, a.steps, a.warmup)
+    r = run_leg(first, a.steps, a.warmup, a.full, a.dump_outputs)
+    r2 = run_leg(second, a.steps, a.warmup, True) if (a.full and not a.no_second_leg) else None
 
     if rank == 0:
-        head = leg_report(r)
+        head = leg_report(r) if a.full else {
+            "value": float(G) * N_SPINS * S_SWAP * r["rounds"] / r["dt"], "dtype": DTYPE[r["precision"]], "rounds_timed": r["rounds"],
+            "seconds_timed": r["dt"], "ms_per_round": r["dt"] / r["rounds"] * 1e3}
         out = {
             "metric": "spin-updates/s (replicas x spins x sweeps / s), NPT sweep + swap rounds, schedule construction included",
             "value": head["value"],
@@ -505,17 +573,18 @@ def main():
             "collective": r["collective"],         # the one collective of a round (None: a single process, nothing to gather)
             "ranks_seen": world,
             "plan_in_timed_region": True,
+            "full": a.full,
         }
         for k, v in head.items():
             if k not in ("value", "unit", "dtype"):
                 out[k] = v
         if r2 is not None:
             out["fixed_point_f32" if second == "f32" else "f64_field"] = leg_report(r2)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(J, h, use_f64=(first == "f64"))
             out["cpu_baseline_numpy_path"] = numpy_path_baseline(J, h)
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(use_f64=(first == "f64"))
-        else:
+        elif a.full:
             out["cpu_baseline"] = None
         if backend != "nccl":
             out["rehearsal"] = f"process group '{backend}', ranks share {torch.cuda.device_count()} GPU(s): code-path rehearsal, not a measurement"

@@ -31,7 +31,7 @@ cp "$OUT/lbp/s_kernel_stats.csv" "$REPO/profiles/${TAG}_lbp_kernel_stats.csv"
 cp "$OUT/c5/s_kernel_stats.csv" "$REPO/profiles/${TAG}_c5_kernel_stats.csv"
 fi
 cp "$REPO"/profiles/${TAG}_* "$REPO"/profiles/current_sweep_pmc.json "$OUT"/
-python3 "$REPO/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 "$REPO/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 cp "$OUT/bench.json" "$REPO/profiles/${TAG}_bench_n1.json"
 cp "$REPO/profiles/${TAG}_bench_n1.json" "$OUT"/
 tail -1 "$OUT/bench.json"

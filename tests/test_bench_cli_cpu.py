@@ -53,3 +53,40 @@ def test_fused_plans_stay_within_the_memory_budget_for_default_arguments():
         assert eng.sweeps_per_plan_piece(per_window, 10000, 50, eng.Engine.FUSED_PLAN_BUDGET, record_stride=4) % 100 == 0
     # a budget below one window still makes progress, one window at a time
     assert eng.sweeps_per_plan_piece(eng.fused_plan_bytes(10000, 0, 50), 10000, 50, 1) == 50
+
+
+def test_the_launcher_forwards_full_and_dump_outputs(tmp_path):
+    d = run("--gpus", "2", "--steps", "2", "--warmup", "0", "--full", "--dump-outputs", str(tmp_path), "--dry-run-launch")
+    tail = d["would_run"][d["would_run"].index(BENCH) + 1:]
+    assert "--full" in tail and tail[tail.index("--dump-outputs") + 1] == str(tmp_path)
+
+
+def test_dump_outputs_are_exact_floats_within_the_budget(tmp_path):
+    """Spins (int8) as float32, slots (int32) and energies (float64) as float64; past 64 MB a fixed, seeded sample of rows."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    spins = (2 * rng.integers(0, 2, size=(256, 1000)) - 1).astype(np.int8)
+    slots = rng.permutation(256).astype(np.int32)
+    energies = rng.standard_normal(256) * 1e4
+    bench.dump_outputs(str(tmp_path / "a"), {"spins": spins, "energies": energies, "slots": slots})
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in ("spins", "energies", "slots")}
+    assert got["spins"].dtype == np.float32 and np.array_equal(got["spins"], spins)
+    assert got["slots"].dtype == np.float64 and np.array_equal(got["slots"], slots)
+    assert got["energies"].dtype == np.float64 and np.array_equal(got["energies"], energies)
+    assert sorted(os.listdir(tmp_path / "a")) == ["energies.npy", "slots.npy", "spins.npy"]
+
+    big = np.ones((8, 256, 10000), np.int8)                     # 80 MB as float32
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"spins": big, "energies": np.arange(2048, dtype=np.int64).reshape(8, 256)})
+    files = os.listdir(tmp_path / "b")
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 64 << 20
+    rows = np.load(tmp_path / "b" / "spins_rows.npy")
+    assert np.load(tmp_path / "b" / "spins.npy").shape == (rows.size, 10000) and rows.size > 1000
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "spins_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "energies.npy"), np.arange(2048).reshape(8, 256))
+
+
+def test_steps_must_be_positive():
+    p = subprocess.run([sys.executable, BENCH, "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert p.returncode != 0 and "--steps" in p.stderr
