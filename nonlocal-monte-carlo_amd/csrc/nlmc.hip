@@ -75,6 +75,8 @@ struct nlmc_ctx {
                                        // 2^-qs, the fp64 mode may run on fused windows (k_sweep_fused<.., F64>)
     int xmax = 0;                      // max over rows of sum |Jq| + |hq|: the range of the integer field
     unsigned knob_tie_mask = 0xFFFFFFFFu;   // NLMC_F64_TIE_MASK (test knob, read at nlmc_create)
+    bool f64_real = false;             // nlmc_set_fused_f64_real: the fp64 mode runs on fused windows for real couplings / fields too
+                                       // (k_sweep_fused<.., R64>; plans then carry the fp64 value plane)
     // diagnostic switches read ONCE, at nlmc_create (NLMC_NO_WARM, NLMC_FUSED_NOPRIO, NLMC_NO_DBUF, NLMC_DBG_FLAGS): not
     // looked up again on the launch path
     bool knob_no_warm = false, knob_no_prio = false, knob_no_dbuf = false;
@@ -87,8 +89,8 @@ struct nlmc_ctx {
     bool has_flags = false;
     bool has_diag = false;
     bool has_zero_vals = false;   // a stored entry is 0.0 (or underflows to 0 in fp32)
-    size_t lds_opt[96] = {};      // dynamic-LDS opt-in already granted, one slot per kernel: 0 k_levelize, 1 k_icm_components,
-                                  // 2..7 sweep-by-sweep kernels, 8 k_stream_scatter, 16 k_levelize_fused, 17..20 k_lbp_lds, 21 k_icm_round, 22..23 packed fp64 sweep kernels, 24..47 k_sweep_fused variants, 48..59 its fp64 variants, 60..71 k_rounds_fused, 72..83 k_sweep_fused with the deferred swap
+    size_t lds_opt[128] = {};      // dynamic-LDS opt-in already granted, one slot per kernel: 0 k_levelize, 1 k_icm_components,
+                                  // 2..7 sweep-by-sweep kernels, 8 k_stream_scatter, 16 k_levelize_fused, 17..20 k_lbp_lds, 21 k_icm_round, 22..23 packed fp64 sweep kernels, 24..47 k_sweep_fused variants, 48..59 its fp64 variants, 60..71 k_rounds_fused, 72..83 k_sweep_fused with the deferred swap, 84..101 its real-valued fp64 variants
 
     DevBuf<int32_t> rowptr, col;
     DevBuf<double> val64, h64;
@@ -189,11 +191,13 @@ struct nlmc_ctx {
         std::vector<int32_t> nlev_host, npos_host;
         int pstride = 0, gen0 = 0;
         int fmt = 0;                  // entry format of the plan (NLMC_FMT_*)
+        bool has_val = false;         // the plan carries the fp64 value plane (entries in row order): the real-valued fp64 variant
         DevBuf<int32_t> npos;
         DevBuf<int2> head;
         DevBuf<EdgeQ> ell;
+        DevBuf<double> val;           // [windows][NLMC_FZ_VAL_WORDS * pstride] (has_val only)
         DevBuf<int32_t> loff, nlev, himax, send;
-        void release() { npos.release(); head.release(); ell.release(); loff.release(); nlev.release(); himax.release(); send.release(); }
+        void release() { npos.release(); head.release(); ell.release(); val.release(); loff.release(); nlev.release(); himax.release(); send.release(); }
     };
     FusedPlan fz[2];
     int fz_slot = 0;                  // slot the planning entry points write to
@@ -541,10 +545,28 @@ bool fused_f64_supported(const nlmc_ctx *c, int T)
     return fused_lds(c->n, c->n_pad, false, false, fused_addr_format(c), 2 * c->xmax + 1).total <= (size_t)156 * 1024;
 }
 
+// The fp64 mode on fused windows for real couplings and fields (opt-in, nlmc_set_fused_f64_real): instances that are not dyadic
+// (those keep the integer-threshold kernel), no phase flags in force (checked per call), no K tables -- the f32 mode's LDS.
+bool fused_f64_real_supported(const nlmc_ctx *c, int T)
+{
+    if (!c->f64_real || c->f64_exact || getenv("NLMC_NO_FUSED64")) return false;
+    return fused_supported(c, T);
+}
+
+bool fused_f64_any(const nlmc_ctx *c, int T) { return fused_f64_supported(c, T) || fused_f64_real_supported(c, T); }
+
 // k_sweep_fused<DIAG, FLAGS, OUT, FMT>: 24 kernels, picked by the instance (self-couplings, entry format of the plan) and the
 // call (phase flags on, per-sweep outputs)
-const void *fused_kernel(bool diag, bool flags, bool outs, int fmt, bool f64 = false)
+const void *fused_kernel(bool diag, bool flags, bool outs, int fmt, bool f64 = false, bool real = false)
 {
+    if (f64 && real) {   // real-valued fp64 variant (12 more)
+#define NLMC_KR(D, O) {reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_WIDE, true, false, true>), \
+                       reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_COMPACT, true, false, true>), \
+                       reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_ADDR, true, false, true>)}
+        static const void *const tr[2][2][3] = {{NLMC_KR(false, false), NLMC_KR(false, true)}, {NLMC_KR(true, false), NLMC_KR(true, true)}};
+#undef NLMC_KR
+        return flags ? nullptr : tr[diag][outs][fmt];
+    }
     if (f64) {           // fp64 mode: plain chains only (12 more kernels)
 #define NLMC_K64(D, O) {reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_WIDE, true>), reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_COMPACT, true>), \
                         reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_ADDR, true>)}
@@ -579,14 +601,17 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
     const nlmc_ctx::FusedPlan &P = c->fz[slot];
     const int R = c->sub_count(), n = c->n, T = P.T;
     const size_t PS = (size_t)P.pstride;
+    const bool real = f64 && !c->f64_exact;      // the real-valued fp64 variant (the caller checked fused_f64_real_supported)
+    if (real && !P.has_val) return fail(c, NLMC_ERR_STATE, "run_fused: the plan has no fp64 value plane");
     // per-sweep outputs: three snapshot slots in LDS when they fit beside the threshold tables, in global memory otherwise
-    const int kt = f64 ? 2 * c->xmax + 1 : 0;
+    const int kt = (f64 && !real) ? 2 * c->xmax + 1 : 0;
     const bool snap_lds = outs && fused_lds(c->n, c->n_pad, c->has_flags, true, P.fmt == NLMC_FMT_ADDR, kt).total <= (size_t)150 * 1024;
     const FusedLds L = fused_lds(c->n, c->n_pad, c->has_flags, snap_lds, P.fmt == NLMC_FMT_ADDR, kt);
     if (outs && !snap_lds) HIP_TRY(c, c->snap_g.reserve((size_t)R * (3 * (size_t)c->n_pad + 16)));
     const int variant = (outs ? 4 : 0) + (c->has_diag ? 2 : 0) + (c->has_flags ? 1 : 0);
-    const void *kfun = fused_kernel(c->has_diag, c->has_flags, outs, P.fmt, f64);
-    int lds_slot = f64 ? 48 + ((c->has_diag ? 2 : 0) + (outs ? 1 : 0)) * 3 + P.fmt : 24 + variant * 3 + P.fmt;
+    const void *kfun = fused_kernel(c->has_diag, c->has_flags, outs, P.fmt, f64, real);
+    int lds_slot = real ? 84 + ((c->has_diag ? 2 : 0) + (outs ? 1 : 0)) * 3 + P.fmt
+                 : f64 ? 48 + ((c->has_diag ? 2 : 0) + (outs ? 1 : 0)) * 3 + P.fmt : 24 + variant * 3 + P.fmt;
     if (defer) {             // the previous round's swap decided in this launch's prologue (plain chains, no outputs: checked by the caller)
 #define NLMC_KD(D, F64_) {reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_WIDE, F64_, true>), reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_COMPACT, F64_, true>), \
                           reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_ADDR, F64_, true>)}
@@ -594,6 +619,15 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
 #undef NLMC_KD
         kfun = (c->has_flags || outs) ? nullptr : dtable[c->has_diag][f64][P.fmt];
         lds_slot = 72 + ((c->has_diag ? 2 : 0) + (f64 ? 1 : 0)) * 3 + P.fmt;
+        if (real) {
+#define NLMC_KDR(D) {reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_WIDE, true, true, true>), \
+                     reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_COMPACT, true, true, true>), \
+                     reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_ADDR, true, true, true>)}
+            static const void *const drtable[2][3] = {NLMC_KDR(false), NLMC_KDR(true)};
+#undef NLMC_KDR
+            kfun = (c->has_flags || outs) ? nullptr : drtable[c->has_diag][P.fmt];
+            lds_slot = 96 + (c->has_diag ? 1 : 0) * 3 + P.fmt;
+        }
     }
     if (!kfun) return fail(c, NLMC_ERR_STATE, "run_fused: no kernel for this combination (fp64 mode or deferred swap with phase flags / outputs)");
     { int rc = ensure_lds(c, lds_slot, kfun, L.total); if (rc) return rc; }
@@ -665,6 +699,7 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
     a.f64_xmax = c->xmax;
     a.f64_tie_mask = c->knob_tie_mask;
     a.qinv64 = std::ldexp(1.0, -c->qs);
+    a.fz_val = real ? P.val.p + (size_t)w * NLMC_FZ_VAL_WORDS * PS : nullptr;
     a.rng_stride = c->rng_stride; a.rng_base = c->rng_base; a.rng_ladder_len = std::max(1, c->ladder_len);
 #ifdef NLMC_STAMPS
     HIP_TRY(c, c->dbg.reserve((size_t)R * 16 * 8 + 96));
@@ -805,7 +840,8 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
     const bool f64_fused = precision == NLMC_F64 && !c->has_flags && tab_ss == 0;
     if (!stream_mode && (precision == NLMC_F32 || f64_fused) && order_mode == NLMC_ORDER_SHARED && !getenv("NLMC_NO_FUSED"))
         fslot = fused_plan_for(c, sweep0, n_sweeps, seed);
-    if (fslot >= 0 && f64_fused && !fused_f64_supported(c, c->fz[fslot].T)) fslot = -1;
+    if (fslot >= 0 && f64_fused && !fused_f64_supported(c, c->fz[fslot].T) &&
+        !(fused_f64_real_supported(c, c->fz[fslot].T) && c->fz[fslot].has_val)) fslot = -1;
     if (fslot >= 0) {
         const nlmc_ctx::FusedPlan &P = c->fz[fslot];
         const int w0 = (int)((sweep0 - P.sweep0) / (uint32_t)P.T), nw = n_sweeps / P.T;
@@ -1609,10 +1645,11 @@ int nlmc_plan_philox(nlmc_ctx *c, int precision, int order_mode, uint32_t sweep0
     return NLMC_OK;
 }
 
-static int reserve_fused_plan(nlmc_ctx *c, int n_windows, int T)
+static int reserve_fused_plan(nlmc_ctx *c, int n_windows, int T, bool with_val = false)
 {
     nlmc_ctx::FusedPlan &P = c->fz[c->fz_slot];
     const size_t W = (size_t)n_windows, TN = (size_t)T * c->n, PS = (size_t)fused_pstride(c->n, c->n_long, T);
+    if (with_val) HIP_TRY(c, P.val.reserve(W * PS * NLMC_FZ_VAL_WORDS));
     HIP_TRY(c, c->fz_glv.reserve(W * TN));
     HIP_TRY(c, c->fz_perm.reserve(W * PS));
     HIP_TRY(c, P.head.reserve(W * PS));
@@ -1632,7 +1669,7 @@ int nlmc_plan_reserve_fused(nlmc_ctx *c, int n_windows, int window)
     HIP_TRY(c, hipSetDevice(c->device));
     if (n_windows == 0 || !fused_supported(c, window)) return NLMC_OK;
     c->fz[c->fz_slot].valid = false;              // (growing a buffer drops its contents)
-    return reserve_fused_plan(c, n_windows, window);
+    return reserve_fused_plan(c, n_windows, window, c->f64_real && !c->f64_exact);
 }
 
 int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int window, uint64_t seed, int32_t *out_planned)
@@ -1646,8 +1683,10 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
     if (n_windows == 0 || !fused_supported(c, window)) return NLMC_OK;
     const int n = c->n, T = window;
     const size_t W = (size_t)n_windows;
+    // the fp64 value plane only where the real-valued fp64 variant may run on the plan: other plans stay byte for byte as they were
+    const bool with_val = c->f64_real && !c->f64_exact;
     P.pstride = fused_pstride(n, c->n_long, T);
-    if (reserve_fused_plan(c, n_windows, T) != NLMC_OK) {
+    if (reserve_fused_plan(c, n_windows, T, with_val) != NLMC_OK) {
         // no room for this many windows: not an error -- nothing is planned, the caller's sweeps take the
         // sweep-by-sweep path (or it asks again for fewer windows); what was allocated for the attempt is given back
         (void)hipGetLastError();
@@ -1669,8 +1708,10 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
     a.fmt = fused_addr_format(c) ? NLMC_FMT_ADDR : c->compact16 ? NLMC_FMT_COMPACT : NLMC_FMT_WIDE;
     a.k_zero = c->n_pad + 8;
     a.neg_off = c->n_pad + 16;
-    a.bank_aware = getenv("NLMC_NO_BANK_AWARE") ? 0 : 1;
+    a.bank_aware = (with_val || getenv("NLMC_NO_BANK_AWARE")) ? 0 : 1;    // (the fp64 sum runs in row order)
+    a.val = with_val ? P.val.p : nullptr;
     P.fmt = a.fmt;
+    P.has_val = with_val;
     a.adj = reinterpret_cast<const uint4 *>(c->fz_adj.p); a.glv = c->fz_glv.p; a.perm = c->fz_perm.p; a.head = P.head.p; a.ell = P.ell.p; a.loff = P.loff.p; a.nlev = P.nlev.p;
     a.hi_max = P.himax.p; a.send = P.send.p; a.npos = P.npos.p;
     const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
@@ -1711,7 +1752,7 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
 int nlmc_fused_modes(nlmc_ctx *c, int window)
 {
     if (!c) return 0;
-    return (fused_supported(c, window) ? 1 : 0) | (fused_f64_supported(c, window) ? 2 : 0);
+    return (fused_supported(c, window) ? 1 : 0) | (fused_f64_any(c, window) ? 2 : 0);
 }
 
 int nlmc_probe_level_round(nlmc_ctx *c, int waves, int conflict_free, int rounds, int n_workgroups, double *out_ns_per_round)
@@ -2434,7 +2475,8 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
     if (n_pairs < 1 || n_pairs > std::max(0, L - 1)) return n_pairs < 1 ? no("no swap pairs") : fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
     const int fslot = fused_plan_for(c, sweep0, n_rounds * T, seed);
     if (fslot < 0 || c->fz[fslot].T != T) return no("no fused-window plan of one window per round covers these sweeps");
-    if (precision == NLMC_F64 && !fused_f64_supported(c, T)) return no("the fp64 mode does not run on fused windows for this instance");
+    if (precision == NLMC_F64 && !fused_f64_supported(c, T) && !(fused_f64_real_supported(c, T) && c->fz[fslot].has_val))
+        return no("the fp64 mode does not run on fused windows for this instance");
     if (!(c->pt_plan_valid && c->pt_plan_seed == seed && c->pt_plan_npairs == n_pairs && round0 >= c->pt_plan_round0 &&
           (uint64_t)round0 + (uint64_t)n_rounds <= (uint64_t)c->pt_plan_round0 + (uint64_t)c->pt_plan_rounds))
         return no("the pair selections of these rounds are not planned (nlmc_pt_plan)");
@@ -3126,6 +3168,18 @@ int nlmc_set_phase(nlmc_ctx *c, int kind, double temp_x)
     }
     c->has_flags = true;
     c->temp_x = temp_x;
+    return NLMC_OK;
+}
+
+int nlmc_set_fused_f64_real(nlmc_ctx *c, int on)
+{
+    if (!c) return NLMC_ERR_ARG;
+    const bool v = on != 0;
+    if (v != c->f64_real) {                 // plans are made for one setting (value plane, entry order): drop them
+        c->f64_real = v;
+        c->fz[0].valid = false;
+        c->fz[1].valid = false;
+    }
     return NLMC_OK;
 }
 

@@ -262,7 +262,14 @@ struct FusedLevelizeArgs {
     int32_t *hi_max;          // [n_windows] leading chunks of a level that may hold PAIRS (rows longer than 8 entries)
     int32_t *send;            // [n_windows][T] published index of the last level that holds an item of sweep t
     int32_t *npos;            // [n_windows] schedule positions in use (multiple of 64)
+    double *val;              // nullptr, or [n_windows][NLMC_FZ_VAL_WORDS * pstride] fp64 value plane of the real-valued fp64 variant
+                              // (k_sweep_fused<.., R64>): entries in CSR order, so bank_aware must be 0 (see NLMC_FZ_VAL_WORDS)
 };
+// fp64 value plane of a fused plan (real couplings and fields, nlmc_set_fused_f64_real), doubles per schedule position: planes
+// 0-3 hold { v(2q), v(2q+1) } of the position's eight entries (16 B per position and plane, laid out like the entry planes), plane
+// 4 the field h_k.  v is the coupling J the gathered byte multiplies -- J for the wide / compact formats, J Jq (= |J|, Jq = +-1) for
+// the address format, whose byte is Jq s already -- and 0 for padding entries and dummy items.
+#define NLMC_FZ_VAL_WORDS 9
 
 // 16-bit neighbour lists, 32 B per spin (absent slots hold the spin's own index, which every consumer skips): one
 // pair of 16-byte loads instead of a chain of dependent 4-byte CSR reads per spin in k_levelize_fused.
@@ -498,7 +505,13 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
         if (it_a != 0xFFFFFFFFu) { rs_a = a.g.rowptr[it_a & 0xFFFFu]; re_a = a.g.rowptr[(it_a & 0xFFFFu) + 1]; }
         it_b = pos + 2 * nt < npos ? perm[pos + 2 * nt] : 0xFFFFFFFFu;
         const uint32_t dpack = (uint32_t)a.k_dummy << 16;
+        double *vplane = a.val ? a.val + (size_t)w * NLMC_FZ_VAL_WORDS * PS : nullptr;
         if (it == 0xFFFFFFFFu) {
+            if (vplane) {
+#pragma unroll
+                for (int q = 0; q < NLMC_FZ_W / 2; ++q) reinterpret_cast<double2 *>(vplane)[(size_t)q * PS + pos] = make_double2(0.0, 0.0);
+                vplane[(size_t)(NLMC_FZ_W) * PS + pos] = 0.0;
+            }
             // (threshold word 3 tab_words: behind the three tables / snapshot slots, so that a dummy's threshold read and
             // snapshot write touch nothing that belongs to a spin)
             head[pos] = make_int2(a.k_dummy | ((3 * a.tab_words) << 16), 0);
@@ -524,6 +537,17 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
         for (int q = 0; q < NLMC_FZ_W; ++q) ed[q] = a.g.edge32[rs + e0 + q];    // unconditional (the array is padded by a
                                                                                 // full window): independent loads
         const int hy = second ? 0 : a.g.hq[k];
+        if (vplane) {      // (bank_aware is off: entry q of this lane is row entry e0 + q, padding behind the row's end)
+            double v[NLMC_FZ_W];
+#pragma unroll
+            for (int q = 0; q < NLMC_FZ_W; ++q) {
+                const double j = a.g.val64[rs + e0 + q];          // (the array is padded by a full window, like edge32)
+                v[q] = q < left ? (a.fmt == NLMC_FMT_ADDR ? j * (double)ed[q].q : j) : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < NLMC_FZ_W / 2; ++q) reinterpret_cast<double2 *>(vplane)[(size_t)q * PS + pos] = make_double2(v[2 * q], v[2 * q + 1]);
+            vplane[(size_t)(NLMC_FZ_W) * PS + pos] = a.g.h64[k];   // both lanes of a pair: the field is added after the whole row
+        }
         if (a.bank_aware) {
             const int nreal = min(max(left, 0), NLMC_FZ_W);
             unsigned long long banks = 0ull;                   // 5 bits per entry
@@ -755,6 +779,7 @@ struct SweepArgs {
     int lds_kt_off;           // LDS offset of the threshold tables: Khi u32[2 xmax + 1] | Klo u32[2 xmax + 1]
     int f64_xmax;             // largest |X| any row can reach: max_k (sum |Jq| + |hq|)
     unsigned f64_tie_mask;    // 0xFFFFFFFF; a test knob (NLMC_F64_TIE_MASK) clears low bits so that the rare exact path runs often
+    const double *fz_val;     // k_sweep_fused<.., R64>: the window's fp64 value plane (NLMC_FZ_VAL_WORDS doubles per position)
     int dbg_flags;            // -DNLMC_DEBUG_KNOBS builds only (NLMC_DBG_FLAGS): 1 = no threshold production, 2 = no updates, 4 = no item loads,
                               // 512 / 1024 = bank-conflict-free addresses for the neighbour gather / the spin's own accesses (wrong results)
 };
@@ -1644,7 +1669,27 @@ struct FusedWin {
     int npos_next;
     int nl, hi_max;
     uint32_t sweep0;              // global index of the window's first sweep
+    const double *val;            // fp64 value plane (k_sweep_fused<.., R64> only)
 };
+// the fp64 value-plane entries of one schedule chunk (k_sweep_fused<.., R64>): eight couplings and the field, see NLMC_FZ_VAL_WORDS
+struct FusedVals {
+    nlmc_i4 v[NLMC_FZ_W / 2];
+    nlmc_i2 h;
+    __device__ __forceinline__ double val(int q) const
+    {
+        const nlmc_i4 &w = v[q >> 1];
+        return (q & 1) ? __hiloint2double(w.w, w.z) : __hiloint2double(w.y, w.x);
+    }
+    __device__ __forceinline__ double field() const { return __hiloint2double(h.y, h.x); }
+};
+// a cross-lane move of a double inside each quad of lanes (DPP quad_perm CTRL)
+template <int CTRL>
+__device__ __forceinline__ double quad_move_f64(double v)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_mov_dpp((int)b, CTRL, 0xF, 0xF, true), hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), CTRL, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
 #ifdef NLMC_DEBUG_KNOBS
 #define NLMC_GEN_DBG_OFF_COND (a.dbg_flags & 1)
 #define NLMC_GEN_DBG_PHILOX if (a.dbg_flags & 8) g_r = u32x4{(uint32_t)b * 2654435761u, (uint32_t)b ^ gp.gc, (uint32_t)g_u * 40503u + (uint32_t)b, ~(uint32_t)b}; else
@@ -1717,12 +1762,15 @@ struct FusedWin {
 // when a sweep ends its sum is reduced over the workgroup (one LDS atomic per wave, read after the level's barrier):
 // that gives E after every sweep, the strict running minimum (first argmin, like np.argmin) and, from the snapshot,
 // the argmin / recorded states -- NMC/nmc.py:386-395 -- without giving up the overlap of consecutive sweeps.
-template <bool DIAG, bool FLAGS, bool PAIR, bool GEN, int FMT, bool OUT = false, bool F64 = false>
+//
+// R64 (with F64): the fp64 mode for REAL couplings and fields, see k_sweep_fused.  cb64: the chain's coefficient cb (one temperature).
+template <bool DIAG, bool FLAGS, bool PAIR, bool GEN, int FMT, bool OUT = false, bool F64 = false, bool R64 = false>
 __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin &W, unsigned char *lds_raw, int wv, int lane, int nl, float cq0,
-                                             float cq1, long long &e_loc, const FusedGenParams gp)
+                                             float cq1, long long &e_loc, const FusedGenParams gp, double cb64 = 0.0)
 {
     constexpr bool g_f64 = F64;
     static_assert(!(F64 && FLAGS), "fused fp64 windows: plain chains only (a scaled row's field is not an exact integer)");
+    static_assert(!R64 || F64, "the real-valued fp64 variant rides on the fp64 uniform tables");
     NLMC_GEN_STATE
     NLMC_GEN_ARM(a, gp)
     typedef const int32_t __attribute__((address_space(4))) *const_i32o;
@@ -1757,12 +1805,18 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
     // fp64 mode: LDS address of Khi[X = 0] (entry X sits 4 X bytes from it), bytes from a Khi entry to its Klo entry
     unsigned v_kt0 = (unsigned)(a.lds_kt_off + 4 * a.f64_xmax), v_tie = a.f64_tie_mask;
     if (F64) asm volatile("" : "+v"(v_kt0), "+v"(v_tie));
+    // real-valued fp64 variant: 2^escale (energy deltas of fixed_delta_slow), every update to the exact path (tie mask 0)
+    const double v_esc = __longlong_as_double((long long)(1023 + a.escale) << 52);
+    const bool r_all_exact = a.f64_tie_mask == 0u;
     typedef const unsigned __attribute__((address_space(3))) *lds_u32;
     constexpr int NP = Item::NP, NE = Item::NE;
     const int plane_bytes = a.fz_pstride * 16;
     const __amdgpu_buffer_rsrc_t r_ell = __builtin_amdgcn_make_buffer_rsrc(const_cast<EdgeQ *>(W.ell), 0, (NLMC_FZ_W / 2) * plane_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t r_head = __builtin_amdgcn_make_buffer_rsrc(const_cast<int2 *>(W.head), 0, a.fz_pstride * 8, 0x00020000);
-    // level offsets in chunks, read with SCALAR loads (uniform index): no VGPR, no VALU, no vector-memory slot
+    // (R64: value planes 0-3 laid out like the entry planes, plane 4 -- the fields -- like the heads)
+    const __amdgpu_buffer_rsrc_t r_val = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(W.val), 0, R64 ? (NLMC_FZ_W / 2) * plane_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_hval = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(W.val) + (R64 ? (size_t)NLMC_FZ_W * a.fz_pstride : 0), 0,
+                                                                            R64 ? a.fz_pstride * 8 : 0, 0x00020000);    // level offsets in chunks, read with SCALAR loads (uniform index): no VGPR, no VALU, no vector-memory slot
     // (constant address space: the plan is read-only while sweep kernels run, and a uniform index then gives s_load_dword;
     // a register-resident window of offsets picked with v_readlane measured slower)
     typedef const int32_t __attribute__((address_space(4))) *const_i32;
@@ -1780,12 +1834,130 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
         if (a.dbg_flags & 32) return;                // timing experiment: no vector-memory instructions at all
 #endif
         const int v16 = has ? lane16 : oob;
-        it.hd = __builtin_amdgcn_raw_buffer_load_b64(r_head, v16 >> 1, c * 512, 0);
+        if constexpr (R64 && FMT == NLMC_FMT_WIDE) {
+            // (the real-valued fp64 variant takes its couplings from the value plane: of a wide entry it loads the column only,
+            // of the head the first word -- eight fewer registers per chunk in flight, which keeps the level loop out of scratch)
+            it.hd.x = (int)__builtin_amdgcn_raw_buffer_load_b32(r_head, v16 >> 1, c * 512, 0);
+            it.hd.y = 0;
 #pragma unroll
-        for (int q = 0; q < NP; ++q) it.pk[q] = __builtin_amdgcn_raw_buffer_load_b128(r_ell, v16, c * 1024 + q * plane_bytes, 0);
+            for (int q = 0; q < NP; ++q) {
+                it.pk[q].x = (int)__builtin_amdgcn_raw_buffer_load_b32(r_ell, v16, c * 1024 + q * plane_bytes, 0);
+                it.pk[q].z = (int)__builtin_amdgcn_raw_buffer_load_b32(r_ell, v16, c * 1024 + q * plane_bytes + 8, 0);
+                it.pk[q].y = it.pk[q].w = 0;
+            }
+        } else {
+            it.hd = __builtin_amdgcn_raw_buffer_load_b64(r_head, v16 >> 1, c * 512, 0);
+#pragma unroll
+            for (int q = 0; q < NP; ++q) it.pk[q] = __builtin_amdgcn_raw_buffer_load_b128(r_ell, v16, c * 1024 + q * plane_bytes, 0);
+        }
     };
-    auto update = [&](const Item &it, int lv) __attribute__((always_inline)) {
-        (void)lv;
+    // (R64) the chunk's couplings and fields, issued with its entries: they reach the lane with the schedule item
+    auto issue_v = [&](FusedVals &fv, int c, bool has) __attribute__((always_inline)) {
+        if constexpr (R64) {
+            const int v16 = has ? lane16 : oob;
+            fv.h = __builtin_amdgcn_raw_buffer_load_b64(r_hval, v16 >> 1, c * 512, 0);
+#pragma unroll
+            for (int q = 0; q < NLMC_FZ_W / 2; ++q) fv.v[q] = __builtin_amdgcn_raw_buffer_load_b128(r_val, v16, c * 1024 + q * plane_bytes, 0);
+        } else {
+            (void)fv; (void)c; (void)has;
+        }
+    };
+    auto update = [&](const Item &it, const FusedVals &fv, int lv) __attribute__((always_inline)) {
+        (void)lv; (void)fv;
+        if constexpr (R64) {
+            // The real-valued fp64 variant: update_spin<double> step by step.  xs = fma(J_e, s_e, xs) in CSR order over the whole
+            // row (padding entries add +-0 and leave xs unchanged), x = xs + h_k, z = cb x, s' = +1 iff fma(u, 2^z, u) < 1.
+            const int hx = it.hd.x;
+            const unsigned ka = (unsigned)hx & 0x3FFFu;
+            const unsigned hw = *(lds_u32)(uintptr_t)((((unsigned)hx >> 16) << 2) + v_u_off);   // the 27 high bits of u
+            int so = (int)*(lds_i8)(uintptr_t)ka;
+            int sj[NE];
+#pragma unroll
+            for (int q = 0; q < NE; ++q) sj[q] = (int)*(lds_i8)(uintptr_t)it.col(q);
+            asm volatile("" : "+v"(so));
+            auto is_diag = [&](int q) __attribute__((always_inline)) {
+                return FMT == NLMC_FMT_ADDR ? (it.col(q) == ka || it.col(q) == ka + v_neg_off) : it.col(q) == ka;
+            };
+            // this lane's eight entries, continuing the sums (xs_, xd_)
+            auto part = [&](double &xs_, double &xd_) __attribute__((always_inline)) {
+#pragma unroll
+                for (int q = 0; q < NE; ++q) {
+                    const double sv = (double)sj[q];
+                    xs_ = fma_rn(fv.val(q), sv, xs_);
+                    if (DIAG) { const double nd = fma_rn(fv.val(q), sv, xd_); xd_ = is_diag(q) ? nd : xd_; }
+                }
+            };
+            double xs = 0.0, xd = 0.0;
+            part(xs, xd);
+            bool second = false;
+            if (PAIR && __builtin_amdgcn_ballot_w64((hx & 0x8000) != 0) != 0ull) {
+                // A row of 9-16 entries on an even / odd lane pair: the odd lane continues the even lane's sums with entries 8-15
+                // (the sum stays in row order; the lane-pair split of the integer field would reassociate it), then takes what is
+                // left of a longer row from the CSR arrays, and hands the row's sums back to the even lane.
+                const bool pair = (hx & 0x8000) != 0;
+                second = pair && (lane & 1);
+                const double ps = quad_move_f64<0xA0>(xs);                 // quad_perm [0,0,2,2]: the even lane's sums
+                const double pd = DIAG ? quad_move_f64<0xA0>(xd) : 0.0;
+                const int hxe = __builtin_amdgcn_mov_dpp(hx, 0xA0, 0xF, 0xF, true);
+                double s2 = ps, d2 = pd;
+                part(s2, d2);
+                if (second) { xs = s2; xd = d2; }
+                const bool tail = second && (hxe & 0x4000) != 0;
+                if (__builtin_amdgcn_ballot_w64(tail) != 0ull) {
+                    if (tail) {
+                        const int rs = a.g.rowptr[ka], re = a.g.rowptr[ka + 1];
+#pragma clang loop vectorize(disable) unroll(disable)
+                        for (int e = rs + 2 * NLMC_FZ_W; e < re; ++e) {
+                            const int j = a.g.col[e];
+                            const double v = a.g.val64[e], sv = (double)*(lds_i8)(uintptr_t)(unsigned)j;
+                            xs = fma_rn(v, sv, xs);
+                            if (DIAG && (unsigned)j == ka) xd = fma_rn(v, sv, xd);
+                        }
+                    }
+                }
+                const double bs = quad_move_f64<0xF5>(xs);                 // quad_perm [1,1,3,3]: the odd lane's (whole row)
+                const double bd = DIAG ? quad_move_f64<0xF5>(xd) : 0.0;
+                if (pair) { xs = bs; xd = bd; }
+            }
+            const double hk = fv.field();
+            const double x_true = DIAG ? ((xs - xd) + hk) : (xs + hk);
+            const double xf = xs + hk;
+            const double E = exp2_spec(cb64 * xf);
+            // fma(u, E, u) is monotone in u: the test at both ends of the high word's interval of u decides unless they differ
+            // (the tie mask widens the interval; 0: every update takes the exact path)
+            const unsigned hlo = hw & v_tie, hhi = hw | (~v_tie & 0x7FFFFFFu);
+            const double ulo = (double)hlo * 0x1p-27, uhi = ((double)hhi * 67108864.0 + 67108863.0) * 0x1p-53;
+            bool up = __fma_rn(ulo, E, ulo) < 1.0;
+            const bool tie = r_all_exact || (up != (__fma_rn(uhi, E, uhi) < 1.0));
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(tie) != 0ull, 0)) {
+                if (tie) {
+                    // the update's sweep, as in the integer variant below; then the 26 low bits with one Philox call
+                    typedef const int32_t __attribute__((address_space(4))) *const_i32s;
+                    const unsigned tw_ = (unsigned)hx >> 16, np_ = (unsigned)a.g.n_pad;
+                    int t_ = tw_ >= 3u * np_ ? 3 : tw_ >= 2u * np_ ? 2 : tw_ >= np_ ? 1 : 0;
+                    while (t_ + 3 < a.n_sweeps && lv > ((const_i32s)(uintptr_t)W.fsend)[t_]) t_ += 3;
+                    const u32x4 r_ = philox4x32_10(ka >> 2, W.sweep0 + (uint32_t)t_, gp.gc, NLMC_TAG_UNIFORM_LO, a.seed_lo, a.seed_hi);
+                    const unsigned lw_ = (ka & 2u) ? ((ka & 1u) ? r_.w : r_.z) : ((ka & 1u) ? r_.y : r_.x);
+                    const double u = uniform53_spec(hw << 5, lw_);
+                    up = __fma_rn(u, E, u) < 1.0;
+                }
+            }
+            const int sn = up ? 1 : -1, ds = sn - so;
+            const long long d = (ds != 0 && !(PAIR && second)) ? fixed_delta_slow(x_true, ds, v_esc) : 0ll;
+            *(lds_i8w)(uintptr_t)ka = (int8_t)sn;
+            if (FMT == NLMC_FMT_ADDR) *(lds_i8w)(uintptr_t)(ka + v_neg_off) = (int8_t)-sn;
+            if (OUT) {
+                const unsigned tw = (unsigned)hx >> 16;
+                const bool is_old = tw - o_lo < (unsigned)o_npad;
+                e_loc += is_old ? d : 0ll;
+                e_new += is_old ? 0ll : d;
+                if (snapg) snapg[tw] = (int8_t)sn;
+                else *(lds_i8w)(uintptr_t)(tw + (unsigned)a.lds_snap_off) = (int8_t)sn;
+            } else {
+                e_loc += d;
+            }
+            return;
+        }
 #ifdef NLMC_DEBUG_KNOBS
         if (a.dbg_flags & 2) { asm volatile("" :: "v"(it.hd.x), "v"(it.pk[0].x), "v"(it.pk[Item::NP - 1].x)); return; }   // timing experiment: loads only
 #endif
@@ -1860,7 +2032,7 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
         // the sweep holds the 27 high bits; they decide unless they EQUAL the high word of K(X) (probability 2^-27 per
         // update: ~0.2 updates per launch of the bench shape) -- then the low 26 bits are made again with one Philox call.
         bool up64 = false;
-        if (F64) {
+        if (F64 && !R64) {
             const unsigned hk = __float_as_uint(wk);
             const unsigned kaddr = ((unsigned)X << 2) + v_kt0;
 #ifdef NLMC_DEBUG_KNOBS
@@ -1967,17 +2139,21 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
 #endif
     {
         Item I0, I1, I2;
+        FusedVals V0, V1, V2;                                  // (R64 only; otherwise never loaded nor read)
         int r0 = lo(0), r1 = lo(1), r2 = lo(2), r3 = lo(3), r4 = lo(4), r5 = lo(5);    // offsets of levels l .. l+5
         bool h0 = r0 + wv < r1, h1 = (1 < nl) && (r1 + wv < r2), h2;
         issue(I0, r0 + wv, h0);
+        issue_v(V0, r0 + wv, h0);
         issue(I1, r1 + wv, h1);
-#define NLMC_FSTAGE(lv, cur, hcur, nxt, hnxt, b2, b3)                                       \
+        issue_v(V1, r1 + wv, h1);
+#define NLMC_FSTAGE(lv, cur, vcur, hcur, nxt, vnxt, hnxt, b2, b3)                           \
         {                                                                                   \
             NLMC_FW0                                                                        \
             hnxt = ((lv) + 2 < nl) && ((b2) + wv < (b3));                                   \
             if (GEN) NLMC_GEN(a, gp, lv)                                                    \
-            if (hcur) { update(cur, lv); NLMC_FCALL }                                       \
+            if (hcur) { update(cur, vcur, lv); NLMC_FCALL }                                 \
             issue(nxt, (b2) + wv, hnxt NLMC_DBG_NOLOAD);                                    \
+            issue_v(vnxt, (b2) + wv, hnxt NLMC_DBG_NOLOAD);                                 \
             const bool end_ = OUT && __builtin_expect((lv) == o_end, 0);   /* rare: once per sweep */ \
             if (end_) NLMC_OUT_PRE                                                          \
             NLMC_FW1                                                                        \
@@ -1987,9 +2163,9 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
         }
         for (int l = 0; l < nl; l += 3) {
             const int n3 = lo(l + 6), n4 = lo(l + 7), n5 = lo(l + 8);
-            NLMC_FSTAGE(l, I0, h0, I2, h2, r2, r3)
-            if (l + 1 < nl) NLMC_FSTAGE(l + 1, I1, h1, I0, h0, r3, r4)
-            if (l + 2 < nl) NLMC_FSTAGE(l + 2, I2, h2, I1, h1, r4, r5)
+            NLMC_FSTAGE(l, I0, V0, h0, I2, V2, h2, r2, r3)
+            if (l + 1 < nl) NLMC_FSTAGE(l + 1, I1, V1, h1, I0, V0, h0, r3, r4)
+            if (l + 2 < nl) NLMC_FSTAGE(l + 2, I2, V2, h2, I1, V1, h1, r4, r5)
             r0 = r3; r1 = r4; r2 = r5; r3 = n3; r4 = n4; r5 = n5;
         }
 #undef NLMC_FSTAGE
@@ -2041,7 +2217,7 @@ __device__ __forceinline__ void fused_state_load(const SweepArgs &a, unsigned ch
 
 // One planned window on the chain whose state sits in LDS: threshold tables of its first two sweeps (+ the fp64 mode's K tables at
 // the chain's temperature `row`), then the level loop.  Energy deltas of this thread come back in e_loc (plain variant).
-template <bool DIAG, bool FLAGS, bool OUT, int FMT, bool F64>
+template <bool DIAG, bool FLAGS, bool OUT, int FMT, bool F64, bool R64 = false>
 __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin &W, unsigned char *lds_raw, int row, uint32_t gc, long long &e_loc)
 {
     constexpr bool g_f64 = F64;
@@ -2068,7 +2244,8 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
         if (F64) fill_uniform_words(reinterpret_cast<unsigned *>(tab_t), n, W.sweep0 + (uint32_t)t, gc, a.seed_lo, a.seed_hi, tid, nt);
         else fill_uniforms(tab_t, n, W.sweep0 + (uint32_t)t, gc, a.seed_lo, a.seed_hi, tid, nt);
     }
-    if (F64) {
+    const double cb64 = R64 ? a.tab[(size_t)row * a.tab_cs] : 0.0;      // (R64: z = cb x in the update itself, no tables)
+    if (F64 && !R64) {
         // K(X) for every field value a row can reach, at this chain's temperature: z = cb (X 2^-qs) as in update_spin<double>.
         // The trailing lanes of the workgroup take it (they have one Philox call less than the others above).
         const int ne = 2 * a.f64_xmax + 1;
@@ -2095,7 +2272,7 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
     if (wv < a.f_workers) {
         const bool role_long = wv < W.hi_max;           // chunks that may hold lane PAIRS (rows longer than 8 entries) come first
         const int variant = (role_long ? 2 : 0) + (is_gen ? 1 : 0);
-#define NLMC_FL(P, G) fused_levels<DIAG, FLAGS, P, G, FMT, OUT, F64>(a, W, lds_raw, wv, lane, nl, cq0, cq1, e_loc, gp)
+#define NLMC_FL(P, G) fused_levels<DIAG, FLAGS, P, G, FMT, OUT, F64, R64>(a, W, lds_raw, wv, lane, nl, cq0, cq1, e_loc, gp, cb64)
         switch (variant) { case 0: NLMC_FL(false, false); break; case 1: NLMC_FL(false, true); break;
                            case 2: NLMC_FL(true, false); break; default: NLMC_FL(true, true); break; }
 #undef NLMC_FL
@@ -2240,7 +2417,14 @@ __device__ __forceinline__ int pt_swap_step_of_chain(int slot, uint32_t gc, int 
     return out;
 }
 
-template <bool DIAG, bool FLAGS, bool OUT, int FMT, bool F64 = false, bool DEFER = false>
+//
+// R64 (with F64): the fp64 mode on fused windows for REAL couplings and fields (nlmc_set_fused_f64_real).  Every update is
+// update_spin<double> operation for operation: the field is summed with fma in CSR order from the plan's fp64 value plane (entries
+// in row order; a row of 9-16 entries hands its partial sum from the even to the odd lane of its pair instead of adding two
+// halves), z = cb x, and the test fma(u, 2^z, u) < 1 is taken at both ends of the interval of u that the 27 high bits in the LDS
+// table leave open -- it is monotone in u, so equal answers decide; otherwise the 26 low bits are made with one Philox call and
+// the test is taken on u itself.  Energy deltas are fixed_delta_slow's.  Same bits as the sweep-by-sweep fp64 kernel.
+template <bool DIAG, bool FLAGS, bool OUT, int FMT, bool F64 = false, bool DEFER = false, bool R64 = false>
 __global__ __launch_bounds__(1024) void k_sweep_fused(SweepArgs a)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -2257,7 +2441,7 @@ __global__ __launch_bounds__(1024) void k_sweep_fused(SweepArgs a)
 #ifdef NLMC_STAMPS
     const long long st_begin = (long long)__builtin_readcyclecounter();
 #endif
-    const FusedWin W{a.lvl_off, a.fsend, a.ell32, a.head32, a.warm_head, a.warm_ell, a.fz_npos_next, a.nlev[0], a.hi_max[0], a.sweep0};
+    const FusedWin W{a.lvl_off, a.fsend, a.ell32, a.head32, a.warm_head, a.warm_ell, a.fz_npos_next, a.nlev[0], a.hi_max[0], a.sweep0, a.fz_val};
     fused_state_load<FLAGS>(a, lds_raw, c);
     if (DEFER) {                                                   // the chain's slot after the swap, to every wave
         volatile int *sh = reinterpret_cast<volatile int *>(lds_raw + a.lds_red_off);
@@ -2270,7 +2454,7 @@ __global__ __launch_bounds__(1024) void k_sweep_fused(SweepArgs a)
     }
     const uint32_t gc = (a.rng_stride && a.slot_of_chain) ? (uint32_t)((c / a.rng_ladder_len) * a.rng_stride + a.rng_base + row) : gc_chain;
     long long e_loc = 0;
-    fused_window<DIAG, FLAGS, OUT, FMT, F64>(a, W, lds_raw, row, gc, e_loc);
+    fused_window<DIAG, FLAGS, OUT, FMT, F64, R64>(a, W, lds_raw, row, gc, e_loc);
     fused_state_store<OUT>(a, lds_raw, c, e_loc);
 #ifdef NLMC_STAMPS
     if (a.dbg && (threadIdx.x & 63) == 0) a.dbg[((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 8 + 7] = (long long)__builtin_readcyclecounter() - st_begin;

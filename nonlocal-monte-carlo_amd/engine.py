@@ -73,6 +73,7 @@ class Engine:
             self._ck(self._L.nlmc_own_stream(self._ctx))
         self.ladder_len = 0
         self._ahead = None
+        self.fused_f64_real = False
         self.energy_scale = int(self._L.nlmc_energy_scale(self._ctx))
         self.field_scale = int(self._L.nlmc_field_scale(self._ctx))      # qs of the "f32" path: Jq = rint(J 2^qs)
 
@@ -216,16 +217,25 @@ class Engine:
     FUSED_PLAN_BUDGET = 1 << 30        # bytes of fused-window plan one sweep_philox_windows piece may hold
 
     def fused_plan_bytes(self, window):
-        return fused_plan_bytes(self.n, int(np.count_nonzero(np.diff(self.inst.indptr) > 8)), window)
+        return fused_plan_bytes(self.n, int(np.count_nonzero(np.diff(self.inst.indptr) > 8)), window,
+                                value_plane=self.fused_f64_real)
+
+    def set_fused_f64_real(self, on=True):
+        """Opt-in: the fp64 mode runs on fused windows for real couplings and fields too (include/nlmc.h:
+        nlmc_set_fused_f64_real) -- same bits as sweep by sweep.  Plans made while it is on carry an fp64 value plane (72 more
+        bytes per schedule position).  Changing the setting drops the current fused plans."""
+        self._ck(self._L.nlmc_set_fused_f64_real(self._ctx, 1 if on else 0))
+        self.fused_f64_real = bool(on)
 
     def sweep_philox_windows(self, n_sweeps, seed, sweep0=0, beta=None, window=None, budget_bytes=None, record_stride=0,
-                             want_energy=False, want_min=False, want_state=False, want_recorded_energy=False):
+                             want_energy=False, want_min=False, want_state=False, want_recorded_energy=False, precision="f32"):
         """sweep_philox on fused windows planned piece by piece against a memory budget (one planning call for a
         whole run of 10^4 sweeps takes 23 GB at N = 10^3, 230 GB at N = 10^4): the call is cut into pieces of at most
         budget_bytes / fused_plan_bytes windows, each planned, swept and dropped; pieces whose plan is refused (instance or
         window outside what the fused kernels take) run sweep by sweep -- same bits.  Outputs are stitched together exactly
         as one call would return them (trace, energies, first argmin).  want_recorded_energy: o["energy_recorded"] = fp64
-        energies of the recorded configurations [rows, n_recorded], computed on the device copy of each piece's trace."""
+        energies of the recorded configurations [rows, n_recorded], computed on the device copy of each piece's trace.
+        precision: "f32" or "f64" (the fp64 mode takes the fused windows where fused_modes says so, sweep by sweep otherwise)."""
         S = int(n_sweeps)
         T = fused_window(S) if window is None else int(window)
         budget = self.FUSED_PLAN_BUDGET if budget_bytes is None else int(budget_bytes)
@@ -238,16 +248,16 @@ class Engine:
             if not (a._fused_from <= ii < a._fused_to):  # planned together with those of the launches that follow
                 a._plan(ii, True)
             if a._fused_from <= ii < a._fused_to:
-                self.fused_last_call = True
+                self.fused_last_call = precision == "f32" or precision in self.fused_modes(a.window)
                 o = self.sweep_philox(S, seed, sweep0=sweep0, beta=beta, record_stride=record_stride, want_energy=want_energy,
-                                      want_min=want_min, want_state=want_state)
+                                      want_min=want_min, want_state=want_state, precision=precision)
                 if rec_e:
                     o["energy_recorded"] = self.energy_of_recorded(o["spins"].shape[1])
                 return o
         if not T or S % T or S == 0:
             self.fused_last_call = False
             o = self.sweep_philox(S, seed, sweep0=sweep0, beta=beta, record_stride=record_stride, want_energy=want_energy,
-                                  want_min=want_min, want_state=want_state)
+                                  want_min=want_min, want_state=want_state, precision=precision)
             if rec_e and S > 0:
                 o["energy_recorded"] = self.energy_of_recorded(o["spins"].shape[1])
             return o
@@ -263,24 +273,25 @@ class Engine:
                 fused = self.plan_philox_fused(sweep0 + t0, (t1 - t0) // T, T, seed) == (t1 - t0) // T     # refused once: stop asking
             outs.append(self.sweep_philox(t1 - t0, seed, sweep0=sweep0 + t0, beta=b if (b is None or b.ndim < 2) else b[:, t0:t1],
                                           record_stride=record_stride, want_energy=want_energy, want_min=want_min,
-                                          want_state=want_state))
+                                          want_state=want_state, precision=precision))
             if rec_e:
                 outs[-1]["energy_recorded"] = self.energy_of_recorded(outs[-1]["spins"].shape[1])
-        self.fused_last_call = fused
+        self.fused_last_call = fused and (precision == "f32" or precision in self.fused_modes(T))
         o = outs[0] if len(outs) == 1 else _stitch_outputs(outs, per_piece, record_stride, want_energy, want_min, want_state)
         if rec_e and len(outs) > 1:
             o["energy_recorded"] = np.concatenate([p["energy_recorded"] for p in outs], axis=1)
         return o
 
-    def plan_ahead(self, sweep0, n_launches, sweeps_per_launch, seed, budget_bytes=None):
+    def plan_ahead(self, sweep0, n_launches, sweeps_per_launch, seed, budget_bytes=None, precision="f32"):
         """Announce `n_launches` sweep_philox_windows calls of `sweeps_per_launch` sweeps each at consecutive sweep indices from
         `sweep0` (the phases of an NMC run): their fused windows depend on the RNG only and are planned a budget's worth of
         LAUNCHES at a time instead of one launch at a time -- a planning launch is latency-bound (~1.5 ms whether it builds 9
-        windows or 200; per phase launch that was 27 % of C2 through NMC.run_restarts).  plan_ahead(None) ends it."""
+        windows or 200; per phase launch that was 27 % of C2 through NMC.run_restarts).  plan_ahead(None) ends it.
+        precision: that of the announced calls ("f32" / "f64")."""
         if sweep0 is None or n_launches <= 0 or sweeps_per_launch <= 0:
             self._ahead = None
             return
-        self._ahead = RoundPlanner(self, sweep0, n_launches, sweeps_per_launch, seed,
+        self._ahead = RoundPlanner(self, sweep0, n_launches, sweeps_per_launch, seed, precision=precision,
                                    budget_bytes=self.FUSED_PLAN_BUDGET if budget_bytes is None else budget_bytes, slot=0,
                                    fused_outputs=True)
 
@@ -661,12 +672,13 @@ def device_count():
     return int(_abi.lib().nlmc_device_count())
 
 
-def fused_plan_bytes(n, n_long, window):
+def fused_plan_bytes(n, n_long, window, value_plane=False):
     """Upper estimate of the device memory one planned window of `window` sweeps takes (head 8 + row planes <= 64 + item ids
     4 bytes per schedule position, 2 bytes per update of level scratch): what nlmc_plan_philox_fused allocates per window
-    (csrc/nlmc.hip: reserve_fused_plan, fused_pstride).  n_long: rows longer than 8 entries (two positions each)."""
+    (csrc/nlmc.hip: reserve_fused_plan, fused_pstride).  n_long: rows longer than 8 entries (two positions each).
+    value_plane: plans of the real-valued fp64 variant (Engine.set_fused_f64_real) add 9 doubles per position."""
     pstride = -(-int(window) * (int(n) + int(n_long)) // 64) * 64 + 64 * 1024
-    return pstride * 76 + int(window) * int(n) * 2 + 8192
+    return pstride * (76 + (72 if value_plane else 0)) + int(window) * int(n) * 2 + 8192
 
 
 def sweeps_per_plan_piece(bytes_per_window, n_sweeps, window, budget_bytes, record_stride=0):

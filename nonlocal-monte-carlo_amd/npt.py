@@ -30,6 +30,17 @@ class NPT(Common):
     """NMC + Adaptive Parallel Tempering (NPT/npt.py:15)."""
     _variant = "npt"
 
+    def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32"):
+        """`precision` (additive keyword, rng="philox" only): "f32" (default) -- the throughput mode's fixed-point couplings and
+        logistic thresholds; "f64" -- the device-resident rounds in the reference's arithmetic (fp64 field, 53-bit uniform), on
+        fused windows for real couplings too (Engine.set_fused_f64_real).  Replicas with doNMC set are not supported with "f64"."""
+        if precision not in ("f32", "f64"):
+            raise ValueError("precision must be 'f32' or 'f64'")
+        super().__init__(J, h, rng=rng, seed=seed, device=device, lbp=lbp)
+        if precision != "f32" and self.rng != "philox":
+            raise ValueError("precision applies to rng='philox' (rng='numpy' runs the reference's own arithmetic)")
+        self.precision = precision
+
     # ------------------------------------------------------------------------------------------------
     def replica_energy(self, M, num_sweeps):
         """min and trace of E = -(m^T J m / 2 + m^T h) over the first num_sweeps columns (NPT/npt.py:31-45)."""
@@ -101,6 +112,8 @@ class NPT(Common):
         if return_trace not in ("float64", "int8", None):
             raise ValueError("return_trace must be 'float64', 'int8' or None")
         any_nmc = any(bool(v) for v in doNMC)
+        if any_nmc and self.precision != "f32":
+            raise ValueError("precision='f64' runs plain replicas only: doNMC slots are not supported")
         # (with NMC replicas and M_skip > 1 the phases' traces and argmin hand-offs are strided on the device; a phase length that M_skip
         # does not divide raises the reference's own shape error on the host-managed path)
         device_resident = self.rng == "philox" and (not any_nmc or (int(M_skip) >= 1 and self.num_sweeps_per_NMC_phase_per_swap % int(M_skip) == 0))
@@ -338,14 +351,23 @@ class NPT(Common):
             while t > nmc["threshold_cutoff"]:
                 thr.append(float(t))
                 t -= 0.01
+        prec = self.precision
+
+        def opt_in(e):                                   # fp64 rounds: fused windows for real couplings as well
+            if prec == "f64":
+                e.set_fused_f64_real(True)
+            return e
         if ctx is None:
-            lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs)
+            lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, precision=prec)
         elif not cut:
-            lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, parts=[(base_, count_)])
+            lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, parts=[(base_, count_)], precision=prec)
         else:
             lt = ShardedAsLocal(ShardedTempering(
-                lambda i, n, b, g: Engine(i, None, n, device=lrank_, chain_base=b, n_chains_global=g), inst, beta_list, G, self.seed,
-                self.num_swapping_pairs, torch=torch_, dist=dist_, device=torch_.device("cuda", lrank_)))
+                lambda i, n, b, g: opt_in(Engine(i, None, n, device=lrank_, chain_base=b, n_chains_global=g)), inst, beta_list, G,
+                self.seed, self.num_swapping_pairs, torch=torch_, dist=dist_, device=torch_.device("cuda", lrank_), precision=prec))
+        if ctx is None or not cut:
+            for e in lt.engs:
+                opt_in(e)
         lo_, hi_ = (0, G) if (ctx is None or cut) else (base_, base_ + count_)       # global chains the arrays below cover
         M_buf = M_touch = None
         if return_trace == "float64" and R * N * S * 8 >= (32 << 20):
