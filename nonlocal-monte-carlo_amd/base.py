@@ -40,6 +40,7 @@ class _EngineCache:
 
     def __init__(self, device=0):
         self.device = device
+        self.setup = None                          # callable applied to every engine this cache creates (or None)
         self._key = None
         self._inst = None
         self._J_obj = self._h_obj = None
@@ -69,6 +70,8 @@ class _EngineCache:
         inst = self.instance(J, h)
         if n_chains not in self._engines:
             self._engines[n_chains] = Engine(inst, None, n_chains, device=self.device)
+            if self.setup is not None:
+                self.setup(self._engines[n_chains])
         return self._engines[n_chains]
 
     def close(self):
@@ -95,6 +98,10 @@ class SweepMixin:
         # NMC/nmc.py:74-76: the reference insists on an LRUCache only when the table is actually used
         if use_hash_table and hash_table is None:
             raise ValueError("hash_table must be an instance of cachetools.LRUCache")
+
+    def _phase_precision(self):
+        """Arithmetic of the device-RNG sweeps at N >= 256 ("f32": the fixed-point model); NMC(precision="f64") overrides it."""
+        return "f32"
 
     def _mcmc_on(self, eng, num_sweeps, m_start, beta_run, record=True, flags=None, temp_x=1.0, record_stride=1):
         """Run `num_sweeps` sweeps of ONE chain on `eng` (n_chains == 1).  Returns the engine's output dict (configurations
@@ -133,14 +140,17 @@ class SweepMixin:
         # batched path (24-bit fixed-point couplings + logistic thresholds; DESIGN.md section 2 states the tolerance: the
         # chain samples the Boltzmann law of (Jq, hq) 2^-qs with |Jq 2^-qs - J| <= 2^-(qs+1), nothing lost for +-J / integer
         # instances), on fused windows planned piece by piece within a memory budget where the instance qualifies, sweep by
-        # sweep otherwise (same bits).  Smaller instances: fp64 fields.  o["energy_recorded"] holds the fp64 energies of the
+        # sweep otherwise (same bits).  NMC(precision="f64"): the reference's arithmetic (fp64 field, 53-bit uniform) instead, on
+        # fused windows where fused_modes says so (phases with their flags included; the anneal, a temperature per sweep, sweep by
+        # sweep).  Smaller instances: fp64 fields.  o["energy_recorded"] holds the fp64 energies of the
         # recorded configurations, computed on the device copy of the trace -- what the reference's list comprehension
         # (NMC/nmc.py:386-387) would give for them; NMC_subroutine's argmin hand-off (NMC/nmc.py:394-395) uses THEM whenever every
         # sweep was recorded (M_skip == 1) and the kernel's tracked minimum (exact integers of the quantised model in the "f32"
         # arithmetic) only for strided recording.
         if n >= 256:
             o = eng.sweep_philox_windows(num_sweeps, self.seed, sweep0=self._sweep_counter, beta=beta2, record_stride=rs,
-                                         want_energy=True, want_min=True, want_state=True, want_recorded_energy=True)
+                                         want_energy=True, want_min=True, want_state=True, want_recorded_energy=True,
+                                         precision=self._phase_precision())
         else:
             o = eng.sweep_philox(num_sweeps, self.seed, sweep0=self._sweep_counter, beta=beta2, precision="f64", record_stride=rs,
                                  want_energy=True, want_min=True, want_state=True)
@@ -313,7 +323,7 @@ class Common(SweepMixin):
             all_clusters = detect(m_star)
         if self.rng == "philox" and N >= 256:             # (device RNG: the phases' level schedules do not depend on the spins)
             eng.plan_ahead(self._sweep_counter, sum(2 + (1 if c % full_update_frequency == 0 else 0) for c in range(num_cycles)),
-                           S, self.seed)
+                           S, self.seed, precision=self._phase_precision())
         try:
             for cycle in range(num_cycles):
                 if self._variant == "nmc":                   # NMC/nmc.py:365-373: clusters re-detected every cycle

@@ -90,7 +90,8 @@ struct nlmc_ctx {
     bool has_diag = false;
     bool has_zero_vals = false;   // a stored entry is 0.0 (or underflows to 0 in fp32)
     size_t lds_opt[128] = {};      // dynamic-LDS opt-in already granted, one slot per kernel: 0 k_levelize, 1 k_icm_components,
-                                  // 2..7 sweep-by-sweep kernels, 8 k_stream_scatter, 16 k_levelize_fused, 17..20 k_lbp_lds, 21 k_icm_round, 22..23 packed fp64 sweep kernels, 24..47 k_sweep_fused variants, 48..59 its fp64 variants, 60..71 k_rounds_fused, 72..83 k_sweep_fused with the deferred swap, 84..101 its real-valued fp64 variants
+                                  // 2..7 sweep-by-sweep kernels, 8 k_stream_scatter, 16 k_levelize_fused, 17..20 k_lbp_lds, 21 k_icm_round, 22..23 packed fp64 sweep kernels, 24..47 k_sweep_fused variants, 48..59 its fp64 variants, 60..71 k_rounds_fused, 72..83 k_sweep_fused with the deferred swap, 84..101 its real-valued fp64 variants, 102..113 / 114..125 the fp64 /
+                                  // real-valued fp64 variants with phase flags
 
     DevBuf<int32_t> rowptr, col;
     DevBuf<double> val64, h64;
@@ -555,24 +556,35 @@ bool fused_f64_real_supported(const nlmc_ctx *c, int T)
 
 bool fused_f64_any(const nlmc_ctx *c, int T) { return fused_f64_supported(c, T) || fused_f64_real_supported(c, T); }
 
+// An fp64 call with phase flags in force on an instance fused_f64_any accepts: the real-valued variant needs nothing more (the f32
+// mode's LDS counts the flags); the integer-threshold variant needs a second K table (scaled rows) beside the flags.  Counted at its
+// worst (negated copy of the spins in), so that the answer depends on n and xmax alone; otherwise the call runs sweep by sweep.
+bool fused_f64_flags_fit(const nlmc_ctx *c)
+{
+    if (!c->f64_exact) return true;
+    return fused_lds(c->n, c->n_pad, true, false, true, 2 * (2 * c->xmax + 1)).total <= (size_t)156 * 1024;
+}
+
 // k_sweep_fused<DIAG, FLAGS, OUT, FMT>: 24 kernels, picked by the instance (self-couplings, entry format of the plan) and the
-// call (phase flags on, per-sweep outputs)
+// call (phase flags on, per-sweep outputs); 24 more for each of the two fp64 variants
 const void *fused_kernel(bool diag, bool flags, bool outs, int fmt, bool f64 = false, bool real = false)
 {
-    if (f64 && real) {   // real-valued fp64 variant (12 more)
-#define NLMC_KR(D, O) {reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_WIDE, true, false, true>), \
-                       reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_COMPACT, true, false, true>), \
-                       reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_ADDR, true, false, true>)}
-        static const void *const tr[2][2][3] = {{NLMC_KR(false, false), NLMC_KR(false, true)}, {NLMC_KR(true, false), NLMC_KR(true, true)}};
+    if (f64 && real) {   // real-valued fp64 variant (24 more)
+#define NLMC_KR(D, F, O) {reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_WIDE, true, false, true>), \
+                          reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_COMPACT, true, false, true>), \
+                          reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_ADDR, true, false, true>)}
+        static const void *const tr[2][2][2][3] = {{{NLMC_KR(false, false, false), NLMC_KR(false, false, true)}, {NLMC_KR(false, true, false), NLMC_KR(false, true, true)}},
+                                                   {{NLMC_KR(true, false, false), NLMC_KR(true, false, true)}, {NLMC_KR(true, true, false), NLMC_KR(true, true, true)}}};
 #undef NLMC_KR
-        return flags ? nullptr : tr[diag][outs][fmt];
+        return tr[diag][flags][outs][fmt];
     }
-    if (f64) {           // fp64 mode: plain chains only (12 more kernels)
-#define NLMC_K64(D, O) {reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_WIDE, true>), reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_COMPACT, true>), \
-                        reinterpret_cast<const void *>(k_sweep_fused<D, false, O, NLMC_FMT_ADDR, true>)}
-        static const void *const t64[2][2][3] = {{NLMC_K64(false, false), NLMC_K64(false, true)}, {NLMC_K64(true, false), NLMC_K64(true, true)}};
+    if (f64) {           // fp64 mode, integer thresholds (24 more kernels)
+#define NLMC_K64(D, F, O) {reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_WIDE, true>), reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_COMPACT, true>), \
+                           reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_ADDR, true>)}
+        static const void *const t64[2][2][2][3] = {{{NLMC_K64(false, false, false), NLMC_K64(false, false, true)}, {NLMC_K64(false, true, false), NLMC_K64(false, true, true)}},
+                                                    {{NLMC_K64(true, false, false), NLMC_K64(true, false, true)}, {NLMC_K64(true, true, false), NLMC_K64(true, true, true)}}};
 #undef NLMC_K64
-        return flags ? nullptr : t64[diag][outs][fmt];
+        return t64[diag][flags][outs][fmt];
     }
 #define NLMC_K(D, F, O) {reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_WIDE>), reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_COMPACT>), \
                          reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_ADDR>)}
@@ -604,14 +616,14 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
     const bool real = f64 && !c->f64_exact;      // the real-valued fp64 variant (the caller checked fused_f64_real_supported)
     if (real && !P.has_val) return fail(c, NLMC_ERR_STATE, "run_fused: the plan has no fp64 value plane");
     // per-sweep outputs: three snapshot slots in LDS when they fit beside the threshold tables, in global memory otherwise
-    const int kt = (f64 && !real) ? 2 * c->xmax + 1 : 0;
+    const int kt = (f64 && !real) ? (c->has_flags ? 2 : 1) * (2 * c->xmax + 1) : 0;     // (phase flags: K0 and K1)
     const bool snap_lds = outs && fused_lds(c->n, c->n_pad, c->has_flags, true, P.fmt == NLMC_FMT_ADDR, kt).total <= (size_t)150 * 1024;
     const FusedLds L = fused_lds(c->n, c->n_pad, c->has_flags, snap_lds, P.fmt == NLMC_FMT_ADDR, kt);
     if (outs && !snap_lds) HIP_TRY(c, c->snap_g.reserve((size_t)R * (3 * (size_t)c->n_pad + 16)));
     const int variant = (outs ? 4 : 0) + (c->has_diag ? 2 : 0) + (c->has_flags ? 1 : 0);
     const void *kfun = fused_kernel(c->has_diag, c->has_flags, outs, P.fmt, f64, real);
-    int lds_slot = real ? 84 + ((c->has_diag ? 2 : 0) + (outs ? 1 : 0)) * 3 + P.fmt
-                 : f64 ? 48 + ((c->has_diag ? 2 : 0) + (outs ? 1 : 0)) * 3 + P.fmt : 24 + variant * 3 + P.fmt;
+    const int v64 = ((c->has_diag ? 2 : 0) + (outs ? 1 : 0)) * 3 + P.fmt;
+    int lds_slot = real ? (c->has_flags ? 114 : 84) + v64 : f64 ? (c->has_flags ? 102 : 48) + v64 : 24 + variant * 3 + P.fmt;
     if (defer) {             // the previous round's swap decided in this launch's prologue (plain chains, no outputs: checked by the caller)
 #define NLMC_KD(D, F64_) {reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_WIDE, F64_, true>), reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_COMPACT, F64_, true>), \
                           reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_ADDR, F64_, true>)}
@@ -629,7 +641,7 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
             lds_slot = 96 + (c->has_diag ? 1 : 0) * 3 + P.fmt;
         }
     }
-    if (!kfun) return fail(c, NLMC_ERR_STATE, "run_fused: no kernel for this combination (fp64 mode or deferred swap with phase flags / outputs)");
+    if (!kfun) return fail(c, NLMC_ERR_STATE, "run_fused: no kernel for this combination (deferred swap with phase flags / outputs)");
     { int rc = ensure_lds(c, lds_slot, kfun, L.total); if (rc) return rc; }
     // events around the launch (two stream commands) only while timings accumulate (nlmc_timing_reset): every launch or
     // every ev_every-th one.  An event record costs ~2.5 us of stream time: none on the plain product path.
@@ -835,9 +847,10 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
     // slots fit in LDS next to the rest; any whole number of planned windows per call either way.
     int fslot = -1;
     bool fused_out = false;
-    // (fp64 mode: on the same windows when the field is an exact integer, no phase flags are in force and the call has one
-    // temperature per chain -- fused_f64_supported; the same bits as the sweep-by-sweep fp64 kernel)
-    const bool f64_fused = precision == NLMC_F64 && !c->has_flags && tab_ss == 0;
+    // (fp64 mode: on the same windows when fused_f64_supported / fused_f64_real_supported say so and the call has one temperature
+    // per chain; with phase flags in force when their layout fits too -- fused_f64_flags_fit; the same bits as the sweep-by-sweep
+    // fp64 kernel)
+    const bool f64_fused = precision == NLMC_F64 && tab_ss == 0 && (!c->has_flags || fused_f64_flags_fit(c));
     if (!stream_mode && (precision == NLMC_F32 || f64_fused) && order_mode == NLMC_ORDER_SHARED && !getenv("NLMC_NO_FUSED"))
         fslot = fused_plan_for(c, sweep0, n_sweeps, seed);
     if (fslot >= 0 && f64_fused && !fused_f64_supported(c, c->fz[fslot].T) &&

@@ -1763,13 +1763,17 @@ __device__ __forceinline__ double quad_move_f64(double v)
 // that gives E after every sweep, the strict running minimum (first argmin, like np.argmin) and, from the snapshot,
 // the argmin / recorded states -- NMC/nmc.py:386-395 -- without giving up the overlap of consecutive sweeps.
 //
-// R64 (with F64): the fp64 mode for REAL couplings and fields, see k_sweep_fused.  cb64: the chain's coefficient cb (one temperature).
+// R64 (with F64): the fp64 mode for REAL couplings and fields, see k_sweep_fused.  cb64 / cb64_1: the chain's coefficients cb of
+// plain / scaled rows (one temperature per chain).
+//
+// FLAGS with F64 (NMC phases in the fp64 mode, oracle/nlo.c: nlo_sweeps_philox(use_f64=1, flags)): a frozen row (flag 2 or 3) keeps
+// its spin and adds no energy; a scaled row (flag 1) takes cb_run[2t+1].  The integer-threshold variant reads a second K table, built
+// at cb1 beside the first one (Khi0 | Khi1 | Klo0 | Klo1); the real-valued one takes z = cb1 x.
 template <bool DIAG, bool FLAGS, bool PAIR, bool GEN, int FMT, bool OUT = false, bool F64 = false, bool R64 = false>
 __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin &W, unsigned char *lds_raw, int wv, int lane, int nl, float cq0,
-                                             float cq1, long long &e_loc, const FusedGenParams gp, double cb64 = 0.0)
+                                             float cq1, long long &e_loc, const FusedGenParams gp, double cb64 = 0.0, double cb64_1 = 0.0)
 {
     constexpr bool g_f64 = F64;
-    static_assert(!(F64 && FLAGS), "fused fp64 windows: plain chains only (a scaled row's field is not an exact integer)");
     static_assert(!R64 || F64, "the real-valued fp64 variant rides on the fp64 uniform tables");
     NLMC_GEN_STATE
     NLMC_GEN_ARM(a, gp)
@@ -1802,9 +1806,11 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
     unsigned v_u_off = (unsigned)a.lds_u_off, v_neg_off = (unsigned)a.lds_neg_off;
     int v_eshift = a.eshift;
     asm volatile("" : "+v"(v_u_off), "+v"(v_neg_off), "+v"(v_eshift));
-    // fp64 mode: LDS address of Khi[X = 0] (entry X sits 4 X bytes from it), bytes from a Khi entry to its Klo entry
+    // fp64 mode: LDS address of Khi[X = 0] (entry X sits 4 X bytes from it); with FLAGS the scaled rows' table Khi1 follows Khi0
+    // (k_ne4 bytes further), and the low words follow all high words (k_lo bytes from a Khi entry to its Klo entry)
     unsigned v_kt0 = (unsigned)(a.lds_kt_off + 4 * a.f64_xmax), v_tie = a.f64_tie_mask;
     if (F64) asm volatile("" : "+v"(v_kt0), "+v"(v_tie));
+    const unsigned k_ne4 = 4u * (unsigned)(2 * a.f64_xmax + 1), k_lo = FLAGS ? 2u * k_ne4 : k_ne4;
     // real-valued fp64 variant: 2^escale (energy deltas of fixed_delta_slow), every update to the exact path (tie mask 0)
     const double v_esc = __longlong_as_double((long long)(1023 + a.escale) << 52);
     const bool r_all_exact = a.f64_tie_mask == 0u;
@@ -1871,6 +1877,7 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
             const unsigned ka = (unsigned)hx & 0x3FFFu;
             const unsigned hw = *(lds_u32)(uintptr_t)((((unsigned)hx >> 16) << 2) + v_u_off);   // the 27 high bits of u
             int so = (int)*(lds_i8)(uintptr_t)ka;
+            const unsigned fr = FLAGS ? (unsigned)*(lds_u8)(uintptr_t)(ka + (unsigned)a.lds_flags_off) : 0u;
             int sj[NE];
 #pragma unroll
             for (int q = 0; q < NE; ++q) sj[q] = (int)*(lds_i8)(uintptr_t)it.col(q);
@@ -1922,13 +1929,14 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
             const double hk = fv.field();
             const double x_true = DIAG ? ((xs - xd) + hk) : (xs + hk);
             const double xf = xs + hk;
-            const double E = exp2_spec(cb64 * xf);
+            // (a frozen row goes through the sum like the others -- its lane may carry half of a pair -- and keeps its spin below)
+            const double E = exp2_spec(((FLAGS && fr == 1u) ? cb64_1 : cb64) * xf);
             // fma(u, E, u) is monotone in u: the test at both ends of the high word's interval of u decides unless they differ
             // (the tie mask widens the interval; 0: every update takes the exact path)
             const unsigned hlo = hw & v_tie, hhi = hw | (~v_tie & 0x7FFFFFFu);
             const double ulo = (double)hlo * 0x1p-27, uhi = ((double)hhi * 67108864.0 + 67108863.0) * 0x1p-53;
             bool up = __fma_rn(ulo, E, ulo) < 1.0;
-            const bool tie = r_all_exact || (up != (__fma_rn(uhi, E, uhi) < 1.0));
+            const bool tie = (r_all_exact || (up != (__fma_rn(uhi, E, uhi) < 1.0))) && !(FLAGS && fr >= 2u);
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(tie) != 0ull, 0)) {
                 if (tie) {
                     // the update's sweep, as in the integer variant below; then the 26 low bits with one Philox call
@@ -1942,7 +1950,7 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
                     up = __fma_rn(u, E, u) < 1.0;
                 }
             }
-            const int sn = up ? 1 : -1, ds = sn - so;
+            const int sn = (FLAGS && fr >= 2u) ? so : up ? 1 : -1, ds = sn - so;          // frozen: unchanged, no energy
             const long long d = (ds != 0 && !(PAIR && second)) ? fixed_delta_slow(x_true, ds, v_esc) : 0ll;
             *(lds_i8w)(uintptr_t)ka = (int8_t)sn;
             if (FMT == NLMC_FMT_ADDR) *(lds_i8w)(uintptr_t)(ka + v_neg_off) = (int8_t)-sn;
@@ -2034,7 +2042,7 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
         bool up64 = false;
         if (F64 && !R64) {
             const unsigned hk = __float_as_uint(wk);
-            const unsigned kaddr = ((unsigned)X << 2) + v_kt0;
+            const unsigned kaddr = ((unsigned)X << 2) + v_kt0 + ((FLAGS && f == 1u) ? k_ne4 : 0u);     // (scaled row: K1)
 #ifdef NLMC_DEBUG_KNOBS
             // 16384: timing experiment -- no dependent table read behind the field sum (wrong results)
             const unsigned kh = (a.dbg_flags & 16384) ? (unsigned)(X * 3000000 + 0x4000000) : *(lds_u32)(uintptr_t)kaddr;
@@ -2042,7 +2050,7 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
             const unsigned kh = *(lds_u32)(uintptr_t)kaddr;
 #endif
             up64 = hk < kh;
-            const bool tie = ((hk ^ kh) & v_tie) == 0u;
+            const bool tie = ((hk ^ kh) & v_tie) == 0u && !(FLAGS && f >= 2u);     // (a frozen row draws nothing)
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(tie) != 0ull, 0)) {
                 if (tie) {
                     // sweep of the item: the first t = slot (mod 3) whose last level is not before this one (sweep t + 3
@@ -2054,7 +2062,7 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
                     const u32x4 r_ = philox4x32_10(ka >> 2, W.sweep0 + (uint32_t)t_, gp.gc, NLMC_TAG_UNIFORM_LO, a.seed_lo, a.seed_hi);
                     const unsigned lw_ = (ka & 2u) ? ((ka & 1u) ? r_.w : r_.z) : ((ka & 1u) ? r_.y : r_.x);
                     const unsigned lo_ = lw_ >> 6;
-                    const unsigned kl = *(lds_u32)(uintptr_t)(kaddr + 4u * (unsigned)(2 * a.f64_xmax + 1));
+                    const unsigned kl = *(lds_u32)(uintptr_t)(kaddr + k_lo);
                     up64 = hk < kh || (hk == kh && lo_ < kl);
                 }
             }
@@ -2244,18 +2252,21 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
         if (F64) fill_uniform_words(reinterpret_cast<unsigned *>(tab_t), n, W.sweep0 + (uint32_t)t, gc, a.seed_lo, a.seed_hi, tid, nt);
         else fill_uniforms(tab_t, n, W.sweep0 + (uint32_t)t, gc, a.seed_lo, a.seed_hi, tid, nt);
     }
-    const double cb64 = R64 ? a.tab[(size_t)row * a.tab_cs] : 0.0;      // (R64: z = cb x in the update itself, no tables)
+    // (R64: z = cb x in the update itself, no tables; cb1 for the scaled rows of a phase)
+    const double cb64 = R64 ? a.tab[(size_t)row * a.tab_cs] : 0.0, cb64_1 = (R64 && FLAGS) ? a.tab[(size_t)row * a.tab_cs + 1] : 0.0;
     if (F64 && !R64) {
         // K(X) for every field value a row can reach, at this chain's temperature: z = cb (X 2^-qs) as in update_spin<double>.
-        // The trailing lanes of the workgroup take it (they have one Philox call less than the others above).
-        const int ne = 2 * a.f64_xmax + 1;
+        // The trailing lanes of the workgroup take it (they have one Philox call less than the others above).  With FLAGS a
+        // second table K1 at cb1 (the scaled rows): Khi0 | Khi1 | Klo0 | Klo1.
+        const int ne = 2 * a.f64_xmax + 1, nk = FLAGS ? 2 : 1;
         unsigned *kt = reinterpret_cast<unsigned *>(lds_raw + a.lds_kt_off);
-        const double cb = a.tab[(size_t)row * a.tab_cs];
-        for (int i = nt - 1 - tid; i < ne; i += nt) {
-            const double xf = (double)(i - a.f64_xmax) * a.qinv64;
+        for (int i = nt - 1 - tid; i < nk * ne; i += nt) {
+            const int j = i >= ne ? 1 : 0, x = i - j * ne;
+            const double cb = a.tab[(size_t)row * a.tab_cs + j];
+            const double xf = (double)(x - a.f64_xmax) * a.qinv64;
             const unsigned long long K = accept_count_spec(cb * xf);
             kt[i] = (unsigned)(K >> 26);
-            kt[ne + i] = (unsigned)(K & 0x3FFFFFFull);
+            kt[nk * ne + i] = (unsigned)(K & 0x3FFFFFFull);
         }
     }
     __syncthreads();
@@ -2272,7 +2283,7 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
     if (wv < a.f_workers) {
         const bool role_long = wv < W.hi_max;           // chunks that may hold lane PAIRS (rows longer than 8 entries) come first
         const int variant = (role_long ? 2 : 0) + (is_gen ? 1 : 0);
-#define NLMC_FL(P, G) fused_levels<DIAG, FLAGS, P, G, FMT, OUT, F64, R64>(a, W, lds_raw, wv, lane, nl, cq0, cq1, e_loc, gp, cb64)
+#define NLMC_FL(P, G) fused_levels<DIAG, FLAGS, P, G, FMT, OUT, F64, R64>(a, W, lds_raw, wv, lane, nl, cq0, cq1, e_loc, gp, cb64, cb64_1)
         switch (variant) { case 0: NLMC_FL(false, false); break; case 1: NLMC_FL(false, true); break;
                            case 2: NLMC_FL(true, false); break; default: NLMC_FL(true, true); break; }
 #undef NLMC_FL

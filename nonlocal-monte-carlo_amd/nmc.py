@@ -14,6 +14,24 @@ class NMC(Common):
     """The NMC class implements the Non-equilibrium (non-local) Monte Carlo algorithm (NMC/nmc.py:13)."""
     _variant = "nmc"
 
+    def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32"):
+        """`precision` (additive keyword, rng="philox" only): "f32" (default) -- at N >= 256 the device-RNG sweeps use the
+        throughput mode's fixed-point couplings and logistic thresholds; "f64" -- the reference's arithmetic (fp64 field, 53-bit
+        uniform) for MCMC(), the anneal and every NMC phase of run() / NMC_subroutine() / run_restarts(), on fused windows for
+        real couplings too (Engine.set_fused_f64_real)."""
+        if precision not in ("f32", "f64"):
+            raise ValueError("precision must be 'f32' or 'f64'")
+        super().__init__(J, h, rng=rng, seed=seed, device=device, lbp=lbp)
+        if precision != "f32" and self.rng != "philox":
+            raise ValueError("precision applies to rng='philox' (rng='numpy' runs the reference's own arithmetic)")
+        self.precision = precision
+        if precision == "f64":
+            for cache in (self._cache, self._phase_cache):
+                cache.setup = lambda e: e.set_fused_f64_real(True)
+
+    def _phase_precision(self):
+        return self.precision
+
     # ------------------------------------------------------------------------------------------------
     def run(self, num_sweeps_initial=int(1e4), num_sweeps_per_NMC_phase=int(1e4), num_NMC_cycles=10,
             full_update_frequency=1, M_skip=1, temp_x=20, global_beta=2.5, lambda_start=0.5, lambda_end=0.01,
@@ -52,7 +70,8 @@ class NMC(Common):
         """Throughput extension (not in the reference): `num_restarts` independent NMC runs of run()'s algorithm batched
         in ONE context -- anneal, then per cycle the three phases (NMC/nmc.py:365-433), every phase one launch over all
         restarts with per-restart cluster flags, the argmin-energy state of each phase handed to the next.  Device RNG
-        (philox) whatever `rng` says, "f32" arithmetic (24-bit fixed-point couplings).  `all_clusters`: one index array used by
+        (philox) whatever `rng` says, in the arithmetic `precision` names ("f32": 24-bit fixed-point couplings, DESIGN.md section 2;
+        "f64": fp64 field and 53-bit uniform).  `all_clusters`: one index array used by
         every restart and cycle (skips the host-side backbone inference), or None to infer clusters per restart and
         cycle like run() does.  Returns (min_energy [R], best_state [R, N] int8, energy_of_phase_minima [R, phases])."""
         norm_factor = np.max(np.abs(self.J))
@@ -86,7 +105,8 @@ class NMC(Common):
 
         def launch(n_sweeps, beta):
             nonlocal sweep0, best_e
-            o = eng.sweep_philox_windows(n_sweeps, self.seed, sweep0=sweep0, beta=beta, want_min=True, want_state=True)
+            o = eng.sweep_philox_windows(n_sweeps, self.seed, sweep0=sweep0, beta=beta, want_min=True, want_state=True,
+                                         precision=self.precision)
             sweep0 += n_sweeps
             better = o["min_energy"] < best_e
             best_e = np.where(better, o["min_energy"], best_e)
@@ -114,7 +134,7 @@ class NMC(Common):
                 mask[:, np.asarray(all_clusters, dtype=int)] = 1
                 eng.set_cluster_mask(mask)
             n_launches = sum(2 + (1 if cycle % full_update_frequency == 0 else 0) for cycle in range(num_NMC_cycles))
-            eng.plan_ahead(sweep0, n_launches, S, self.seed)              # the phase launches' windows, planned together
+            eng.plan_ahead(sweep0, n_launches, S, self.seed, precision=self.precision)     # the phase launches' windows, planned together
             try:
                 for cycle in range(num_NMC_cycles):
                     if all_clusters is None:
@@ -131,7 +151,7 @@ class NMC(Common):
                 eng.set_flags(None)
                 eng.backbone_seed(False)
         self._sweep_counter = sweep0
-        # the running minima were tracked in the fixed-point model; report the fp64 energies of the kept states
+        # the running minima were tracked incrementally (in the fixed-point model with "f32"); report the fp64 energies of the kept states
         return eng.energy_of(best_s), best_s, np.stack(trail, axis=1) if trail else np.zeros((R, 0))
 
     def _run_restarts_host(self, eng, inst, m, S0, S, num_NMC_cycles, full_update_frequency, temp_x, global_beta, all_clusters,
@@ -153,7 +173,8 @@ class NMC(Common):
             eng.set_flags(flags, temp_x)
             # fused windows planned piece by piece against a memory budget (Engine.sweep_philox_windows; instances / lengths
             # the fused kernels do not take run sweep by sweep, same bits)
-            o = eng.sweep_philox_windows(n_sweeps, self.seed, sweep0=sweep0, beta=beta_tab, want_min=True, want_state=True)
+            o = eng.sweep_philox_windows(n_sweeps, self.seed, sweep0=sweep0, beta=beta_tab, want_min=True, want_state=True,
+                                         precision=self.precision)
             sweep0 += n_sweeps
             better = o["min_energy"] < best_e
             best_e = np.where(better, o["min_energy"], best_e)
@@ -167,7 +188,7 @@ class NMC(Common):
         m_star = m.copy()
         flat = np.full((R, S), float(global_beta)) if S > 0 else None
         n_launches = sum(2 + (1 if cycle % full_update_frequency == 0 else 0) for cycle in range(num_NMC_cycles))
-        eng.plan_ahead(sweep0, n_launches, S, self.seed)
+        eng.plan_ahead(sweep0, n_launches, S, self.seed, precision=self.precision)
         for cycle in range(num_NMC_cycles):
             if S == 0:
                 break
@@ -185,7 +206,7 @@ class NMC(Common):
         eng.plan_ahead(None, 0, 0, 0)
         eng.set_flags(None)
         self._sweep_counter = sweep0
-        # the running minima were tracked incrementally from fp32 fields; report the fp64 energies of the kept states
+        # the running minima were tracked incrementally (from fp32 fields with "f32"); report the fp64 energies of the kept states
         return eng.energy_of(best_s), best_s, np.stack(trail, axis=1) if trail else np.zeros((R, 0))
 
     def plot_results(self, M_overall, energy_overall, all_clusters, M_skip, num_NMC_cycles, full_update_frequency,
