@@ -147,8 +147,12 @@ int nlmc_plan_philox_fused(nlmc_ctx *ctx, uint32_t sweep0, int n_windows, int wi
  * the spec's own test.  A plan is shared by both precisions; an fp64 call runs on it when the call has one temperature per chain
  * (otherwise: sweep by sweep).  Phase flags are a property of the call, not of this answer: with flags in force the scaled rows take
  * a second threshold table at cb1, frozen rows keep their spin; where the two tables and the flags do not fit in LDS (large max_k
- * sum |Jq| + |hq| at large n) such a call runs sweep by sweep.  Bit-identical to the sweep-by-sweep fp64 kernel either way. */
+ * sum |Jq| + |hq| at large n) such a call runs sweep by sweep.  Bit-identical to the sweep-by-sweep fp64 kernel either way.  The
+ * answer comes from the same rule the sweep and round calls follow; whether a given call ran on fused windows: nlmc_last_sweep_fused. */
 int nlmc_fused_modes(nlmc_ctx *ctx, int window);
+/* 1 when every launch of the most recent sweep call (nlmc_sweep_philox, nlmc_sweep_stream, nlmc_pt_rounds_fused,
+ * nlmc_pt_rounds_deferred) ran on fused windows, 0 otherwise (sweep by sweep, or no such call yet). */
+int nlmc_last_sweep_fused(const nlmc_ctx *ctx);
 /* Opt-in (default off): the fp64 mode also runs on fused windows for REAL couplings and fields (instances that are not dyadic,
  * e.g. couplings k/75 or Gaussian ones; dyadic instances keep the integer-threshold kernel whatever this says).  Plans made while
  * it is on carry an fp64 value plane beside the entry planes, in row order; the kernel is update_spin<double> operation for

@@ -20,6 +20,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -51,6 +53,57 @@ template <typename T> struct DevBuf {
     void release() { if (p && !borrowed) (void)hipFree(p); p = nullptr; cap = 0; borrowed = false; }
 };
 
+// Every NLMC_* environment variable of the library: tuning, test and diagnostic switches.  read_knobs() reads them when a context is
+// created (nlmc_create); they hold for the context's life, and setting a variable later does not reach a context that exists.
+struct Knobs {
+    bool force_big = false;          // NLMC_FORCE_BIG: every chain runs the global-memory kernels (tests compare both sets at one size)
+    bool no_compact = false;         // NLMC_NO_COMPACT: fused-window schedules never use 4-byte entries
+    bool no_pack64 = false;          // NLMC_NO_PACK64: the fp64 schedule window never holds 16-bit columns
+    bool no_signfmt = false;         // NLMC_NO_SIGNFMT: fused-window schedules never use 2-byte entries
+    int sweep_nt = -1;               // NLMC_SWEEP_NT: threads of a sweep workgroup (64..1024, multiple of 64; -1: unset, 0: invalid)
+    int fused_workers = 0;           // NLMC_FUSED_WORKERS: worker waves of a 16-wave fused workgroup (8..16; 0: the default)
+    int fused_gen0 = -1;             // NLMC_FUSED_GEN0: first wave that produces thresholds (-1: the default)
+    bool no_fused = false;           // NLMC_NO_FUSED: nothing runs on fused windows
+    bool no_fused64 = false;         // NLMC_NO_FUSED64: the fp64 mode never runs on fused windows
+    bool no_fused_out = false;       // NLMC_NO_FUSED_OUT: calls with per-sweep outputs or temperatures run sweep by sweep
+    bool no_warm = false;            // NLMC_NO_WARM: a fused launch does not pull the next window's schedule towards the chip
+    bool no_prio = false;            // NLMC_FUSED_NOPRIO: the producing waves of a fused launch keep the default issue priority
+    bool no_dbuf = false;            // NLMC_NO_DBUF: sweep-by-sweep kernels keep one copy of the per-sweep uniforms in LDS
+    int big_per_level = -1;          // NLMC_BIG_PER_LEVEL: long chains run one launch per level (1) / per window (0); -1: by count
+    bool no_bank_aware = false;      // NLMC_NO_BANK_AWARE: the fused planner does not place items by LDS bank
+    bool fz_stats = false;           // NLMC_FZ_STATS: the fused planner prints the phase cycle counts of window 0 on stderr
+    unsigned tie_mask = 0xFFFFFFFFu; // NLMC_F64_TIE_MASK: high-word mask of the fp64 fused kernels' exact-path test (test knob)
+    bool no_persistent = false;      // NLMC_NO_PERSISTENT: nlmc_pt_rounds_fused refuses
+    bool no_deferred = false;        // NLMC_NO_DEFERRED: nlmc_pt_rounds_deferred refuses
+    int lbp_group = 0;               // NLMC_LBP_GROUP: workgroups per loopy-BP problem (1..8; 0: by size)
+    int lbp_poll_budget = 0;         // NLMC_LBP_POLL_BUDGET: polls of the loopy-BP group barrier (0: the default; test knob)
+    bool lbp_global = false;         // NLMC_LBP_GLOBAL: loopy BP never takes the LDS-resident kernel
+    int dbg_flags = 0;               // NLMC_DBG_FLAGS: timing experiments of NLMC_DEBUG_KNOBS builds
+    std::string stamp_file;          // NLMC_STAMP_FILE: NLMC_STAMPS builds dump the last launch's per-wave cycle sums here
+};
+
+Knobs read_knobs()
+{
+    auto on = [](const char *name) { return getenv(name) != nullptr; };
+    auto num = [](const char *name, int unset) { const char *s = getenv(name); return s ? atoi(s) : unset; };
+    Knobs k;
+    k.force_big = on("NLMC_FORCE_BIG"); k.no_compact = on("NLMC_NO_COMPACT"); k.no_pack64 = on("NLMC_NO_PACK64"); k.no_signfmt = on("NLMC_NO_SIGNFMT");
+    k.sweep_nt = on("NLMC_SWEEP_NT") ? std::max(0, num("NLMC_SWEEP_NT", 0)) : -1;
+    k.fused_workers = num("NLMC_FUSED_WORKERS", 0);
+    if (k.fused_workers < 8 || k.fused_workers > 16) k.fused_workers = 0;
+    k.fused_gen0 = num("NLMC_FUSED_GEN0", -1);
+    k.no_fused = on("NLMC_NO_FUSED"); k.no_fused64 = on("NLMC_NO_FUSED64"); k.no_fused_out = on("NLMC_NO_FUSED_OUT");
+    k.no_warm = on("NLMC_NO_WARM"); k.no_prio = on("NLMC_FUSED_NOPRIO"); k.no_dbuf = on("NLMC_NO_DBUF");
+    k.big_per_level = on("NLMC_BIG_PER_LEVEL") ? num("NLMC_BIG_PER_LEVEL", 0) != 0 : -1;
+    k.no_bank_aware = on("NLMC_NO_BANK_AWARE"); k.fz_stats = on("NLMC_FZ_STATS");
+    if (const char *s = getenv("NLMC_F64_TIE_MASK")) k.tie_mask = (unsigned)strtoul(s, nullptr, 0);
+    k.no_persistent = on("NLMC_NO_PERSISTENT"); k.no_deferred = on("NLMC_NO_DEFERRED");
+    k.lbp_group = num("NLMC_LBP_GROUP", 0); k.lbp_poll_budget = num("NLMC_LBP_POLL_BUDGET", 0); k.lbp_global = on("NLMC_LBP_GLOBAL");
+    k.dbg_flags = num("NLMC_DBG_FLAGS", 0);
+    if (const char *s = getenv("NLMC_STAMP_FILE")) k.stamp_file = s;
+    return k;
+}
+
 }  // namespace
 
 struct nlmc_ctx {
@@ -74,13 +127,9 @@ struct nlmc_ctx {
     bool f64_exact = false;            // every J AND every h is an exact multiple of 2^-qs: the fp64 field is the integer field times
                                        // 2^-qs, the fp64 mode may run on fused windows (k_sweep_fused<.., F64>)
     int xmax = 0;                      // max over rows of sum |Jq| + |hq|: the range of the integer field
-    unsigned knob_tie_mask = 0xFFFFFFFFu;   // NLMC_F64_TIE_MASK (test knob, read at nlmc_create)
     bool f64_real = false;             // nlmc_set_fused_f64_real: the fp64 mode runs on fused windows for real couplings / fields too
                                        // (k_sweep_fused<.., R64>; plans then carry the fp64 value plane)
-    // diagnostic switches read ONCE, at nlmc_create (NLMC_NO_WARM, NLMC_FUSED_NOPRIO, NLMC_NO_DBUF, NLMC_DBG_FLAGS): not
-    // looked up again on the launch path
-    bool knob_no_warm = false, knob_no_prio = false, knob_no_dbuf = false;
-    int knob_dbg_flags = 0;
+    Knobs knobs;                       // the environment switches, read at nlmc_create
     int ev_every = 1;                  // fused-window launches: events around every ev_every-th one (nlmc_timing_reset)
     long long launches_timed = 0;      // launches that contributed to the event sums since nlmc_timing_reset
     int qs = 0;                        // field scale of the fixed-point ("f32") path: Jq = rint(J 2^qs)
@@ -89,9 +138,7 @@ struct nlmc_ctx {
     bool has_flags = false;
     bool has_diag = false;
     bool has_zero_vals = false;   // a stored entry is 0.0 (or underflows to 0 in fp32)
-    size_t lds_opt[128] = {};      // dynamic-LDS opt-in already granted, one slot per kernel: 0 k_levelize, 1 k_icm_components,
-                                  // 2..7 sweep-by-sweep kernels, 8 k_stream_scatter, 16 k_levelize_fused, 17..20 k_lbp_lds, 21 k_icm_round, 22..23 packed fp64 sweep kernels, 24..47 k_sweep_fused variants, 48..59 its fp64 variants, 60..71 k_rounds_fused, 72..83 k_sweep_fused with the deferred swap, 84..101 its real-valued fp64 variants, 102..113 / 114..125 the fp64 /
-                                  // real-valued fp64 variants with phase flags
+    std::vector<std::pair<const void *, size_t>> lds_granted;   // dynamic-LDS opt-in already granted: (kernel, bytes) (ensure_lds)
 
     DevBuf<int32_t> rowptr, col;
     DevBuf<double> val64, h64;
@@ -323,32 +370,40 @@ int triple_ms(nlmc_ctx *c, size_t t, float &lev, float &sw)
     return NLMC_OK;
 }
 
-int sweep_block(int n)
+int sweep_block(const nlmc_ctx *c)
 {
-    if (const char *s = getenv("NLMC_SWEEP_NT")) {
-        int v = atoi(s);
-        if (v >= 64 && v <= 1024 && v % 64 == 0) return v;
-    }
-    int nt = ((n + 7) / 8 + 63) / 64 * 64;
+    const int v = c->knobs.sweep_nt;
+    if (v >= 64 && v <= 1024 && v % 64 == 0) return v;
+    int nt = ((c->n + 7) / 8 + 63) / 64 * 64;
     return std::min(1024, std::max(64, nt));
 }
 
 // fp64-field philox kernels: 8 waves at most (256 registers per lane; with 16 waves the 128-register cap spilled 13-27
 // registers per lane to scratch inside the level loop); levels wider than the workgroup are split when the schedule is built
 // (fixed-point kernel with self-couplings: 12 waves, 170 registers: at 16 waves it spilled 2)
-int sweep_block_for(int n, bool f64_philox, bool f32_diag = false)
+int sweep_block_for(const nlmc_ctx *c, bool f64_philox, bool f32_diag = false)
 {
-    return std::min(f64_philox ? 512 : f32_diag ? 768 : 1024, sweep_block(n));
+    return std::min(f64_philox ? 512 : f32_diag ? 768 : 1024, sweep_block(c));
 }
 
-// beyond the default dynamic-LDS window a kernel has to opt in (once per size step)
-int ensure_lds(nlmc_ctx *c, int slot, const void *func, size_t bytes)
+// beyond the default dynamic-LDS window a kernel has to opt in (once per kernel and size step)
+int ensure_lds(nlmc_ctx *c, const void *func, size_t bytes)
 {
     if (bytes > (size_t)158 * 1024) return fail(c, NLMC_ERR_UNSUPPORTED, "instance too large for the LDS-resident kernels of this build");
-    if (bytes <= (size_t)60 * 1024 || bytes <= c->lds_opt[slot]) return NLMC_OK;
+    if (bytes <= (size_t)60 * 1024) return NLMC_OK;
+    auto it = std::find_if(c->lds_granted.begin(), c->lds_granted.end(), [&](const auto &e) { return e.first == func; });
+    if (it != c->lds_granted.end() && bytes <= it->second) return NLMC_OK;
     HIP_TRY(c, hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    c->lds_opt[slot] = bytes;
+    if (it != c->lds_granted.end()) it->second = bytes;
+    else c->lds_granted.emplace_back(func, bytes);
     return NLMC_OK;
+}
+
+// Pointer table of a kernel family: entry k is Entry<k>::get(), nullptr for a combination that is not instantiated.  Built once.
+template <template <int> class Entry, size_t... K> const void *kernel_at(size_t k, std::index_sequence<K...>)
+{
+    static const void *const table[] = {Entry<(int)K>::get()...};
+    return table[k];
 }
 
 int level_block(int n)
@@ -441,7 +496,7 @@ int run_levelize(nlmc_ctx *c, int n_orders, const uint32_t *keys_in, int per_cha
     a.per_chain = per_chain;
     a.n_sweeps = n_sweeps;
     a.chain_base = c->chain_base;
-    a.level_cap = sweep_block_for(c->n, ell_mode == 2, ell_mode == 1 && c->has_diag);
+    a.level_cap = sweep_block_for(c, ell_mode == 2, ell_mode == 1 && c->has_diag);
     a.ord2 = sc.order.p;
     a.lvl_off = sc.lvl_off.p;
     a.nlev = sc.nlev.p;
@@ -452,7 +507,7 @@ int run_levelize(nlmc_ctx *c, int n_orders, const uint32_t *keys_in, int per_cha
     const size_t lds_two = lds_one + (size_t)(c->n + 2) * 4;
     a.two_sided = lds_two + 16 <= (size_t)150 * 1024;
     const size_t lds = (a.two_sided ? lds_two : lds_one) + 16;
-    { int rc = ensure_lds(c, 0, reinterpret_cast<const void *>(k_levelize), lds); if (rc) return rc; }
+    { int rc = ensure_lds(c, reinterpret_cast<const void *>(k_levelize), lds); if (rc) return rc; }
     hipLaunchKernelGGL(k_levelize, dim3(n_orders), dim3(level_block(c->n)), lds, c->cur, a);
     HIP_TRY(c, hipGetLastError());
     return NLMC_OK;
@@ -464,18 +519,18 @@ int run_levelize(nlmc_ctx *c, int n_orders, const uint32_t *keys_in, int per_cha
 // threads of a fused sweep workgroup: at least 4 waves (3 workers + 1 helper) also for small instances
 // (3 n / 16 threads: 6-14 % faster than the n / 8 of the sweep-by-sweep kernels between N = 2000 and N = 6000 -- more worker
 // waves per level, fewer levels split at the workgroup's width; N = 10^3 is flat from 256 to 768 threads, N >= 5500 has 1024)
-int fused_block(int n)
+int fused_block(const nlmc_ctx *c)
 {
-    if (getenv("NLMC_SWEEP_NT")) return std::max(256, sweep_block(n));
-    const int nt = ((3 * n + 15) / 16 + 63) / 64 * 64;
+    if (c->knobs.sweep_nt >= 0) return std::max(256, sweep_block(c));
+    const int nt = ((3 * c->n + 15) / 16 + 63) / 64 * 64;
     return std::min(1024, std::max(256, nt));
 }
 
-int fused_workers(int nt)
+int fused_workers(const nlmc_ctx *c, int nt)
 {
     const int waves = nt / 64;
     if (waves < 16) return waves - 1;
-    if (const char *s = getenv("NLMC_FUSED_WORKERS")) { const int v = atoi(s); if (v >= 8 && v <= 16) return v; }
+    if (c->knobs.fused_workers) return c->knobs.fused_workers;
     return 15;      // (one wave left to pull the next window's schedule towards the chip: 16 workers measured 137 vs 124 us
                     // per launch when the plans of 256 windows lie cold in HBM)
 }
@@ -516,10 +571,10 @@ int fused_pstride(int n, int n_long, int T) { return (int)((((size_t)T * ((size_
 
 // first wave that produces thresholds (NLMC_FUSED_GEN0: tuning knob): the trailing half of the workgroup -- the
 // waves that rarely or never hold a chunk
-int fused_gen0(int nt)
+int fused_gen0(const nlmc_ctx *c, int nt)
 {
-    const int waves = nt / 64;
-    if (const char *s = getenv("NLMC_FUSED_GEN0")) { const int v = atoi(s); if (v >= 0 && v < waves) return v; }
+    const int waves = nt / 64, v = c->knobs.fused_gen0;
+    if (v >= 0 && v < waves) return v;
     return waves / 2;
 }
 
@@ -527,7 +582,7 @@ int fused_gen0(int nt)
 // uniform tables next to the spins in LDS (flags counted in: they may be switched on later).
 bool fused_supported(const nlmc_ctx *c, int T)
 {
-    if (getenv("NLMC_NO_FUSED") || c->big) return false;
+    if (c->knobs.no_fused || c->big) return false;
     if (c->n < 256 || c->n > NLMC_FZ_SPT * 1024 || c->max_deg > 0x3FFF || T < 3 || T > NLMC_FUSED_TMAX) return false;
     if ((size_t)T * ((size_t)c->n + c->n_long) > ((size_t)1 << 22)) return false;   // 32-bit buffer offsets of the packed planes
     if (c->n_pad + 16 > 0x3FFF) return false;                          // spin address in 14 bits of the item head
@@ -537,62 +592,97 @@ bool fused_supported(const nlmc_ctx *c, int T)
     return L.total <= (size_t)150 * 1024;
 }
 
-// The fp64 mode on fused windows: exact dyadic couplings and fields (the field is an integer), its per-chain threshold tables in
-// LDS beside the rest, no phase flags in force (a scaled row's field is a sum of rounded quotients, not an integer).
-bool fused_f64_supported(const nlmc_ctx *c, int T)
-{
-    if (!c->f64_exact || c->xmax > 4095 || getenv("NLMC_NO_FUSED64")) return false;
-    if (!fused_supported(c, T)) return false;
-    return fused_lds(c->n, c->n_pad, false, false, fused_addr_format(c), 2 * c->xmax + 1).total <= (size_t)156 * 1024;
-}
+// k_sweep_fused's arithmetic: fixed point ("f32"), fp64 with integer thresholds (F64), fp64 real-valued (F64 + R64)
+enum { NOT_FUSED = -1, ARITH_F32 = 0, ARITH_F64 = 1, ARITH_R64 = 2 };
+// the launchers on fused windows: run_sweeps, nlmc_pt_rounds_deferred, nlmc_pt_rounds_fused
+enum class Via { sweeps, deferred, rounds };
 
-// The fp64 mode on fused windows for real couplings and fields (opt-in, nlmc_set_fused_f64_real): instances that are not dyadic
-// (those keep the integer-threshold kernel), no phase flags in force (checked per call), no K tables -- the f32 mode's LDS.
-bool fused_f64_real_supported(const nlmc_ctx *c, int T)
+// The one rule for whether a call runs on fused windows, and on which arithmetic: NOT_FUSED or ARITH_*.  `slot`: the plan slot whose
+// windows of T sweeps cover the call (fused_plan_for), or -1 to ask whether such windows could carry the precision at all
+// (nlmc_fused_modes).  `sweep_temps`, `flags`: the call has a temperature per sweep, phase flags in force.
+int fused_route(const nlmc_ctx *c, int precision, int order_mode, bool sweep_temps, bool flags, int slot, int T, Via via)
 {
-    if (!c->f64_real || c->f64_exact || getenv("NLMC_NO_FUSED64")) return false;
-    return fused_supported(c, T);
-}
-
-bool fused_f64_any(const nlmc_ctx *c, int T) { return fused_f64_supported(c, T) || fused_f64_real_supported(c, T); }
-
-// An fp64 call with phase flags in force on an instance fused_f64_any accepts: the real-valued variant needs nothing more (the f32
-// mode's LDS counts the flags); the integer-threshold variant needs a second K table (scaled rows) beside the flags.  Counted at its
-// worst (negated copy of the spins in), so that the answer depends on n and xmax alone; otherwise the call runs sweep by sweep.
-bool fused_f64_flags_fit(const nlmc_ctx *c)
-{
-    if (!c->f64_exact) return true;
-    return fused_lds(c->n, c->n_pad, true, false, true, 2 * (2 * c->xmax + 1)).total <= (size_t)156 * 1024;
-}
-
-// k_sweep_fused<DIAG, FLAGS, OUT, FMT>: 24 kernels, picked by the instance (self-couplings, entry format of the plan) and the
-// call (phase flags on, per-sweep outputs); 24 more for each of the two fp64 variants
-const void *fused_kernel(bool diag, bool flags, bool outs, int fmt, bool f64 = false, bool real = false)
-{
-    if (f64 && real) {   // real-valued fp64 variant (24 more)
-#define NLMC_KR(D, F, O) {reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_WIDE, true, false, true>), \
-                          reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_COMPACT, true, false, true>), \
-                          reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_ADDR, true, false, true>)}
-        static const void *const tr[2][2][2][3] = {{{NLMC_KR(false, false, false), NLMC_KR(false, false, true)}, {NLMC_KR(false, true, false), NLMC_KR(false, true, true)}},
-                                                   {{NLMC_KR(true, false, false), NLMC_KR(true, false, true)}, {NLMC_KR(true, true, false), NLMC_KR(true, true, true)}}};
-#undef NLMC_KR
-        return tr[diag][flags][outs][fmt];
+    if (order_mode != NLMC_ORDER_SHARED || !fused_supported(c, T)) return NOT_FUSED;
+    if (precision == NLMC_F32) return ARITH_F32;
+    if (sweep_temps || c->knobs.no_fused64) return NOT_FUSED;         // the fp64 mode: one temperature per chain
+    if (c->f64_exact) {
+        // exact dyadic couplings and fields (the field is an integer): a per-chain threshold table per value of the field in LDS beside
+        // the rest; with phase flags a second one (scaled rows), counted at its worst (negated copy of the spins in), so that the
+        // answer depends on n and xmax alone -- otherwise the call runs sweep by sweep
+        if (c->xmax > 4095 || fused_lds(c->n, c->n_pad, false, false, fused_addr_format(c), 2 * c->xmax + 1).total > (size_t)156 * 1024)
+            return NOT_FUSED;
+        if (flags && fused_lds(c->n, c->n_pad, true, false, true, 2 * (2 * c->xmax + 1)).total > (size_t)156 * 1024) return NOT_FUSED;
+        return ARITH_F64;
     }
-    if (f64) {           // fp64 mode, integer thresholds (24 more kernels)
-#define NLMC_K64(D, F, O) {reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_WIDE, true>), reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_COMPACT, true>), \
-                           reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_ADDR, true>)}
-        static const void *const t64[2][2][2][3] = {{{NLMC_K64(false, false, false), NLMC_K64(false, false, true)}, {NLMC_K64(false, true, false), NLMC_K64(false, true, true)}},
-                                                    {{NLMC_K64(true, false, false), NLMC_K64(true, false, true)}, {NLMC_K64(true, true, false), NLMC_K64(true, true, true)}}};
-#undef NLMC_K64
-        return t64[diag][flags][outs][fmt];
+    // real couplings or fields: opt-in (nlmc_set_fused_f64_real), plans with the fp64 value plane, no tables (the f32 mode's LDS);
+    // k_rounds_fused has no such variant
+    if (!c->f64_real || via == Via::rounds || (slot >= 0 && !c->fz[slot].has_val)) return NOT_FUSED;
+    return ARITH_R64;
+}
+
+// k_sweep_fused<DIAG, FLAGS, OUT, FMT, F64, DEFER, R64> by {diag, flags, outs, fmt, arith, defer}: 90 kernels, the deferred swap
+// (DEFER) without phase flags and per-sweep outputs
+template <int K> struct FusedKernel {
+    static constexpr bool diag = K & 1, flags = K >> 1 & 1, outs = K >> 2 & 1, defer = K / 72;
+    static constexpr int fmt = K / 8 % 3, arith = K / 24 % 3;
+    static const void *get()
+    {
+        if constexpr (defer && (flags || outs)) return nullptr;
+        else return reinterpret_cast<const void *>(k_sweep_fused<diag, flags, outs, fmt, arith != ARITH_F32, defer, arith == ARITH_R64>);
     }
-#define NLMC_K(D, F, O) {reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_WIDE>), reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_COMPACT>), \
-                         reinterpret_cast<const void *>(k_sweep_fused<D, F, O, NLMC_FMT_ADDR>)}
-    static const void *const table[2][2][2][3] = {{{NLMC_K(false, false, false), NLMC_K(false, false, true)}, {NLMC_K(false, true, false), NLMC_K(false, true, true)}},
-                                                  {{NLMC_K(true, false, false), NLMC_K(true, false, true)}, {NLMC_K(true, true, false), NLMC_K(true, true, true)}}};
-#undef NLMC_K
-    static_assert(NLMC_FMT_WIDE == 0 && NLMC_FMT_COMPACT == 1 && NLMC_FMT_ADDR == 2, "table order");
-    return table[diag][flags][outs][fmt];
+};
+const void *fused_kernel(bool diag, bool flags, bool outs, int fmt, int arith, bool defer)
+{
+    static_assert(NLMC_FMT_WIDE == 0 && NLMC_FMT_COMPACT == 1 && NLMC_FMT_ADDR == 2, "key order");
+    const size_t key = (((size_t)defer * 3 + arith) * 3 + fmt) * 8 + (outs ? 4 : 0) + (flags ? 2 : 0) + (diag ? 1 : 0);
+    return kernel_at<FusedKernel>(key, std::make_index_sequence<144>{});
+}
+
+// k_rounds_fused<DIAG, FMT, F64> by {diag, fmt, arith}: 12 kernels, none real-valued
+template <int K> struct RoundsKernel {
+    static constexpr bool diag = K & 1;
+    static constexpr int fmt = K / 2 % 3, arith = K / 6;
+    static const void *get()
+    {
+        if constexpr (arith == ARITH_R64) return nullptr;
+        else return reinterpret_cast<const void *>(k_rounds_fused<diag, fmt, arith == ARITH_F64>);
+    }
+};
+const void *rounds_kernel(bool diag, int fmt, int arith)
+{
+    return kernel_at<RoundsKernel>(((size_t)arith * 3 + fmt) * 2 + (diag ? 1 : 0), std::make_index_sequence<18>{});
+}
+
+// the sweep-by-sweep kernels: k_sweep_stream, or k_sweep_philox<float | double, DIAG, PK> by {diag, pk, f64} (PK, the packed 16-bit
+// schedule window: fp64 only)
+template <int K> struct PhiloxKernel {
+    static constexpr bool diag = K & 1, pk = K >> 1 & 1, f64 = K >> 2 & 1;
+    static const void *get()
+    {
+        if constexpr (pk && !f64) return nullptr;
+        else return reinterpret_cast<const void *>(k_sweep_philox<std::conditional_t<f64, double, float>, diag, pk>);
+    }
+};
+const void *sweep_kernel(bool stream_mode, bool f64, bool diag, bool pk)
+{
+    if (stream_mode) return reinterpret_cast<const void *>(k_sweep_stream);
+    return kernel_at<PhiloxKernel>((f64 ? 4 : 0) + (pk ? 2 : 0) + (diag ? 1 : 0), std::make_index_sequence<8>{});
+}
+
+// The SweepArgs fields every sweep launch sets: graph, chains and state, temperatures (`tab` with strides tab_cs / tab_ss; use_slots:
+// its rows by temperature slot), random numbers, energy bookkeeping, running minimum.  The launchers add their own.
+SweepArgs sweep_args(const nlmc_ctx *c, uint32_t sweep0, int n_sweeps, uint64_t seed, const double *tab, int tab_cs, int tab_ss,
+                     bool use_slots)
+{
+    SweepArgs a{};
+    a.g = c->g; a.chain_base = c->chain_base; a.chain_list = c->sub_list(); a.spins = c->spins.p;
+    a.flags = c->has_flags ? c->flags.p : nullptr; a.temp_x = c->temp_x;
+    a.n_sweeps = n_sweeps; a.sweep0 = sweep0; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
+    a.tab = tab; a.tab_cs = tab_cs; a.tab_ss = tab_ss; a.slot_of_chain = use_slots ? c->slot_of_chain.p : nullptr;
+    a.efix = c->efix.p; a.escale = c->escale; a.eshift = c->escale - c->qs; a.qinv = std::ldexp(1.0f, -c->qs); a.qinv64 = std::ldexp(1.0, -c->qs);
+    a.rng_stride = c->rng_stride; a.rng_base = c->rng_base; a.rng_ladder_len = std::max(1, c->ladder_len);
+    a.min_stride = c->track_min ? c->track_min_stride : 1; a.argmin = c->argmin.p;
+    return a;
 }
 
 struct SweepOut {
@@ -604,45 +694,26 @@ struct SweepOut {
     int8_t *out_argmin_state;
 };
 
-// One fused window.  `outs` (nullable): the launch also produces per-sweep outputs into the context's device buffers
-// (etrace / emin / argmin / best / strace, sized by the caller) as sweeps [t0, t0 + T) of a call of n_total sweeps.
+// One fused window on arithmetic `arith` (fused_route).  `outs`: the launch also produces per-sweep outputs into the context's device
+// buffers (etrace / emin / argmin / best / strace, sized by the caller) as sweeps [t0, t0 + T) of a call of n_total sweeps.  `defer`
+// (nullable): the previous round's swap decided in this launch's prologue (plain chains, no outputs: checked by the caller).
 int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, const double *tab_dev, int tab_cs, int tab_ss, bool use_slots,
-              bool outs, bool want_energy, bool want_min, bool want_state, int rec, int t0, int n_total, bool f64 = false,
+              bool outs, bool want_energy, bool want_min, bool want_state, int rec, int t0, int n_total, int arith,
               const DeferSwap *defer = nullptr, double *sink_override = nullptr)
 {
     const nlmc_ctx::FusedPlan &P = c->fz[slot];
-    const int R = c->sub_count(), n = c->n, T = P.T;
+    const int R = c->sub_count(), T = P.T;
     const size_t PS = (size_t)P.pstride;
-    const bool real = f64 && !c->f64_exact;      // the real-valued fp64 variant (the caller checked fused_f64_real_supported)
+    const bool real = arith == ARITH_R64;
     if (real && !P.has_val) return fail(c, NLMC_ERR_STATE, "run_fused: the plan has no fp64 value plane");
     // per-sweep outputs: three snapshot slots in LDS when they fit beside the threshold tables, in global memory otherwise
-    const int kt = (f64 && !real) ? (c->has_flags ? 2 : 1) * (2 * c->xmax + 1) : 0;     // (phase flags: K0 and K1)
+    const int kt = arith == ARITH_F64 ? (c->has_flags ? 2 : 1) * (2 * c->xmax + 1) : 0;     // (phase flags: K0 and K1)
     const bool snap_lds = outs && fused_lds(c->n, c->n_pad, c->has_flags, true, P.fmt == NLMC_FMT_ADDR, kt).total <= (size_t)150 * 1024;
     const FusedLds L = fused_lds(c->n, c->n_pad, c->has_flags, snap_lds, P.fmt == NLMC_FMT_ADDR, kt);
     if (outs && !snap_lds) HIP_TRY(c, c->snap_g.reserve((size_t)R * (3 * (size_t)c->n_pad + 16)));
-    const int variant = (outs ? 4 : 0) + (c->has_diag ? 2 : 0) + (c->has_flags ? 1 : 0);
-    const void *kfun = fused_kernel(c->has_diag, c->has_flags, outs, P.fmt, f64, real);
-    const int v64 = ((c->has_diag ? 2 : 0) + (outs ? 1 : 0)) * 3 + P.fmt;
-    int lds_slot = real ? (c->has_flags ? 114 : 84) + v64 : f64 ? (c->has_flags ? 102 : 48) + v64 : 24 + variant * 3 + P.fmt;
-    if (defer) {             // the previous round's swap decided in this launch's prologue (plain chains, no outputs: checked by the caller)
-#define NLMC_KD(D, F64_) {reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_WIDE, F64_, true>), reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_COMPACT, F64_, true>), \
-                          reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_ADDR, F64_, true>)}
-        static const void *const dtable[2][2][3] = {{NLMC_KD(false, false), NLMC_KD(false, true)}, {NLMC_KD(true, false), NLMC_KD(true, true)}};
-#undef NLMC_KD
-        kfun = (c->has_flags || outs) ? nullptr : dtable[c->has_diag][f64][P.fmt];
-        lds_slot = 72 + ((c->has_diag ? 2 : 0) + (f64 ? 1 : 0)) * 3 + P.fmt;
-        if (real) {
-#define NLMC_KDR(D) {reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_WIDE, true, true, true>), \
-                     reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_COMPACT, true, true, true>), \
-                     reinterpret_cast<const void *>(k_sweep_fused<D, false, false, NLMC_FMT_ADDR, true, true, true>)}
-            static const void *const drtable[2][3] = {NLMC_KDR(false), NLMC_KDR(true)};
-#undef NLMC_KDR
-            kfun = (c->has_flags || outs) ? nullptr : drtable[c->has_diag][P.fmt];
-            lds_slot = 96 + (c->has_diag ? 1 : 0) * 3 + P.fmt;
-        }
-    }
+    const void *kfun = fused_kernel(c->has_diag, c->has_flags, outs, P.fmt, arith, defer != nullptr);
     if (!kfun) return fail(c, NLMC_ERR_STATE, "run_fused: no kernel for this combination (deferred swap with phase flags / outputs)");
-    { int rc = ensure_lds(c, lds_slot, kfun, L.total); if (rc) return rc; }
+    { int rc = ensure_lds(c, kfun, L.total); if (rc) return rc; }
     // events around the launch (two stream commands) only while timings accumulate (nlmc_timing_reset): every launch or
     // every ev_every-th one.  An event record costs ~2.5 us of stream time: none on the plain product path.
     const bool timed = c->ev_accumulate && (c->ev_every <= 1 || c->launches_total % c->ev_every == 0);
@@ -655,13 +726,7 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
         tag_triple(c, 1);
         HIP_TRY(c, hipEventRecord(e0, c->cur));
     }
-    SweepArgs a{};
-    a.g = c->g;
-    a.chain_base = c->chain_base;
-    a.chain_list = c->sub_list();
-    a.spins = c->spins.p;
-    a.flags = c->has_flags ? c->flags.p : nullptr;
-    a.temp_x = c->temp_x;
+    SweepArgs a = sweep_args(c, sweep0, T, seed, tab_dev, tab_cs, tab_ss, use_slots);
     a.lvl_off = P.loff.p + (size_t)w * (NLMC_LCAP + 1);
     a.nlev = P.nlev.p + w;
     a.hi_max = P.himax.p + w;
@@ -670,33 +735,22 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
     a.fsend = P.send.p + (size_t)w * T;
     a.fz_pstride = P.pstride;
     a.fz_fmt = P.fmt;
-    if (w + 1 < P.windows && P.nlev_host[(size_t)w + 1] > 0 && !c->knob_no_warm) {
+    if (w + 1 < P.windows && P.nlev_host[(size_t)w + 1] > 0 && !c->knobs.no_warm) {
         a.warm_head = P.head.p + (size_t)(w + 1) * PS;
         a.warm_ell = P.ell.p + (size_t)(w + 1) * PS * NLMC_FZ_W;
         a.fz_npos_next = P.npos_host[(size_t)w + 1];
     }
     a.f_workers = P.workers;
     a.f_gen0 = P.gen0;
-    a.f_gen_prio = c->knob_no_prio ? 0 : 1;
+    a.f_gen_prio = c->knobs.no_prio ? 0 : 1;
 #ifdef NLMC_DEBUG_KNOBS
-    a.dbg_flags = c->knob_dbg_flags;
+    a.dbg_flags = c->knobs.dbg_flags;
 #endif
-    a.n_sweeps = T;
-    a.sweep0 = sweep0;
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-    a.tab = tab_dev; a.tab_cs = tab_cs; a.tab_ss = tab_ss;
-    a.slot_of_chain = use_slots ? c->slot_of_chain.p : nullptr;
-    a.efix = c->efix.p;
     a.energy_sink = sink_override ? sink_override : c->energy_sink;
     if (defer) a.defer = *defer;
-    a.escale = c->escale;
-    a.eshift = c->escale - c->qs;
-    a.qinv = std::ldexp(1.0f, -c->qs);
     a.trace_sweeps = outs ? n_total : T;
     a.t0 = t0;
     a.rec_stride = rec ? rec : 1;
-    a.min_stride = c->track_min ? c->track_min_stride : 1;
-    a.argmin = c->argmin.p;
     if (outs) {
         a.etrace = want_energy ? c->etrace.p : nullptr;
         a.strace = rec ? c->strace.p : nullptr;
@@ -709,18 +763,15 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
     a.snap_g = (outs && !snap_lds) ? c->snap_g.p : nullptr;
     a.lds_kt_off = L.kt_off;
     a.f64_xmax = c->xmax;
-    a.f64_tie_mask = c->knob_tie_mask;
-    a.qinv64 = std::ldexp(1.0, -c->qs);
+    a.f64_tie_mask = c->knobs.tie_mask;
     a.fz_val = real ? P.val.p + (size_t)w * NLMC_FZ_VAL_WORDS * PS : nullptr;
-    a.rng_stride = c->rng_stride; a.rng_base = c->rng_base; a.rng_ladder_len = std::max(1, c->ladder_len);
 #ifdef NLMC_STAMPS
     HIP_TRY(c, c->dbg.reserve((size_t)R * 16 * 8 + 96));
     HIP_TRY(c, hipMemsetAsync(c->dbg.p, 0, ((size_t)R * 16 * 8 + 96) * sizeof(long long), c->cur));
     a.dbg = c->dbg.p;
 #endif
-    const int nt = fused_block(n);
     void *kargs[] = {&a};
-    HIP_TRY(c, hipLaunchKernel(kfun, dim3(R), dim3(nt), kargs, L.total, c->cur));
+    HIP_TRY(c, hipLaunchKernel(kfun, dim3(R), dim3(fused_block(c)), kargs, L.total, c->cur));
     HIP_TRY(c, hipGetLastError());
     if (timed) { HIP_TRY(c, hipEventRecord(e2, c->cur)); c->launches_timed++; }
     c->launches_sweep++;
@@ -777,6 +828,23 @@ int read_sweep_outputs(nlmc_ctx *c, const SweepOut &o, int n_sweeps, int rec, in
     if (o.out_energy) for (size_t i = 0; i < h_ll.size(); ++i) o.out_energy[i] = (double)h_ll[i] * inv;
     if (o.out_min_energy) for (int i = 0; i < R; ++i) o.out_min_energy[i] = (double)h_min[(size_t)row(i)] * inv;
     if (o.out_argmin) for (int i = 0; i < R; ++i) o.out_argmin[i] = h_arg[(size_t)row(i)];
+    return NLMC_OK;
+}
+
+// the ladder's temperature table (-2 log2(e) {beta, beta / temp_x} per slot), uploaded on `st` only when temp_x changed since the
+// last upload (no host sync on the hot path)
+int upload_ladder_tab(nlmc_ctx *c, hipStream_t st)
+{
+    if (c->pt_tab_valid && c->pt_tab_temp_x == c->temp_x) return NLMC_OK;
+    std::vector<double> tab((size_t)c->ladder_len * 2);
+    for (int r = 0; r < c->ladder_len; ++r) {
+        tab[2 * r + 0] = -2.0 * LOG2E * c->beta_list[r];
+        tab[2 * r + 1] = -2.0 * LOG2E * (c->beta_list[r] / c->temp_x);
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->pt_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    c->pt_tab_valid = true;
+    c->pt_tab_temp_x = c->temp_x;
     return NLMC_OK;
 }
 
@@ -843,31 +911,13 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
     const bool any_out = o.out_spins || o.out_energy || want_min;
     // Fused-window schedule: planned ahead (nlmc_plan_philox_fused), same results.  Calls without per-sweep outputs
     // and with one temperature per chain take the plain variant; calls WITH outputs (energy trace, running minimum /
-    // argmin state, recorded configurations) or a temperature per sweep take the output variant when its three snapshot
-    // slots fit in LDS next to the rest; any whole number of planned windows per call either way.
-    int fslot = -1;
-    bool fused_out = false;
-    // (fp64 mode: on the same windows when fused_f64_supported / fused_f64_real_supported say so and the call has one temperature
-    // per chain; with phase flags in force when their layout fits too -- fused_f64_flags_fit; the same bits as the sweep-by-sweep
-    // fp64 kernel)
-    const bool f64_fused = precision == NLMC_F64 && tab_ss == 0 && (!c->has_flags || fused_f64_flags_fit(c));
-    if (!stream_mode && (precision == NLMC_F32 || f64_fused) && order_mode == NLMC_ORDER_SHARED && !getenv("NLMC_NO_FUSED"))
-        fslot = fused_plan_for(c, sweep0, n_sweeps, seed);
-    if (fslot >= 0 && f64_fused && !fused_f64_supported(c, c->fz[fslot].T) &&
-        !(fused_f64_real_supported(c, c->fz[fslot].T) && c->fz[fslot].has_val)) fslot = -1;
-    if (fslot >= 0) {
-        const nlmc_ctx::FusedPlan &P = c->fz[fslot];
-        const int w0 = (int)((sweep0 - P.sweep0) / (uint32_t)P.T), nw = n_sweeps / P.T;
-        if (!any_out && tab_ss == 0) {
-            for (int j = 0; j < nw; ++j) {
-                int rc = run_fused(c, fslot, w0 + j, sweep0 + (uint32_t)(j * P.T), seed, tab_dev, tab_cs, 0, use_slots, false, false,
-                                   false, false, 0, 0, n_sweeps, f64_fused);
-                if (rc) return rc;
-            }
-            return NLMC_OK;
-        }
-        if (!getenv("NLMC_NO_FUSED_OUT")) fused_out = true;     // (snapshots in LDS or, for large n, in a global ring: run_fused)
-    }
+    // argmin state, recorded configurations) or a temperature per sweep take the output variant (its three snapshot slots in
+    // LDS or, for large n, in a global ring: run_fused); any whole number of planned windows per call either way.  Which calls
+    // run there, and on which arithmetic: fused_route.
+    const bool outs = any_out || tab_ss != 0;
+    const int fslot = fused_plan_for(c, sweep0, n_sweeps, seed);
+    int arith = fslot < 0 ? NOT_FUSED : fused_route(c, precision, order_mode, tab_ss != 0, c->has_flags, fslot, c->fz[fslot].T, Via::sweeps);
+    if (outs && c->knobs.no_fused_out) arith = NOT_FUSED;
     if (o.out_energy) HIP_TRY(c, c->etrace.reserve((size_t)R * n_sweeps));
     if (rec) HIP_TRY(c, c->strace.reserve((size_t)R * n_rec * n));
     c->strace_nrec = n_rec;
@@ -876,12 +926,12 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
         hipLaunchKernelGGL(k_fill_min, dim3((R + 255) / 256), dim3(256), 0, c->cur, R, c->sub_list(), c->emin.p, c->argmin.p);
         HIP_TRY(c, hipGetLastError());
     }
-    if (fused_out) {
+    if (arith != NOT_FUSED) {
         const nlmc_ctx::FusedPlan &P = c->fz[fslot];
         const int w0 = (int)((sweep0 - P.sweep0) / (uint32_t)P.T), nw = n_sweeps / P.T;
         for (int j = 0; j < nw; ++j) {
-            int rc = run_fused(c, fslot, w0 + j, sweep0 + (uint32_t)(j * P.T), seed, tab_dev + (size_t)j * P.T * tab_ss, tab_cs,
-                               tab_ss, use_slots, true, o.out_energy != nullptr, want_min, want_state, rec, j * P.T, n_sweeps, f64_fused);
+            int rc = run_fused(c, fslot, w0 + j, sweep0 + (uint32_t)(j * P.T), seed, tab_dev + (size_t)j * P.T * tab_ss, tab_cs, tab_ss,
+                               use_slots, outs, o.out_energy != nullptr, want_min, want_state, rec, outs ? j * P.T : 0, n_sweeps, arith);
             if (rc) return rc;
         }
         return read_sweep_outputs(c, o, n_sweeps, rec, n_rec);
@@ -911,7 +961,7 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
         else HIP_TRY(c, c->scratch.reserve(orders, (size_t)n, ell_mode));
     }
 
-    const int nt = big ? 1024 : sweep_block_for(n, !stream_mode && f64, !stream_mode && !f64 && c->has_diag);
+    const int nt = big ? 1024 : sweep_block_for(c, !stream_mode && f64, !stream_mode && !f64 && c->has_diag);
     // LDS carve-up: spins | flags | uniforms of one sweep (philox) | level offsets (philox) | reduction scratch
     const int lds_flags_off = c->n_pad;
     int cur = c->n_pad * (c->has_flags ? 2 : 1);
@@ -921,21 +971,14 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
     // second copy of the per-sweep uniforms / level offsets when it fits: lets the idle waves prepare sweep t+1 while
     // wave 0 runs the narrow tail of sweep t
     const bool dbuf = !stream_mode && (size_t)cur + 2 * (size_t)u_bytes + 2 * NLMC_LCAP * 4 + 32 <= (size_t)150 * 1024 &&
-                      !c->knob_no_dbuf;
+                      !c->knobs.no_dbuf;
     cur += u_bytes * (dbuf ? 2 : 1);
     const int lds_loff_off = cur;
     cur += NLMC_LCAP * 4 * (dbuf ? 2 : 1);               // (stream mode: one copy, the level offsets of the running sweep)
     const int lds_red_off = cur;
     const size_t lds = (size_t)cur + 16;
-    const void *kfun = stream_mode ? reinterpret_cast<const void *>(k_sweep_stream)
-                       : f64 ? (c->f64_pack16 ? (c->has_diag ? reinterpret_cast<const void *>(k_sweep_philox<double, true, true>)
-                                                             : reinterpret_cast<const void *>(k_sweep_philox<double, false, true>))
-                                              : (c->has_diag ? reinterpret_cast<const void *>(k_sweep_philox<double, true>)
-                                                             : reinterpret_cast<const void *>(k_sweep_philox<double, false>)))
-                             : (c->has_diag ? reinterpret_cast<const void *>(k_sweep_philox<float, true>)
-                                            : reinterpret_cast<const void *>(k_sweep_philox<float, false>));
-    const int kslot = stream_mode ? 2 : (f64 ? (c->f64_pack16 ? 22 : 3) : 5) + (c->has_diag ? 1 : 0);
-    if (!big) { int rc = ensure_lds(c, kslot, kfun, lds); if (rc) return rc; }
+    const void *kfun = sweep_kernel(stream_mode, f64, c->has_diag, f64 && c->f64_pack16);
+    if (!big) { int rc = ensure_lds(c, kfun, lds); if (rc) return rc; }
 
     for (int t0 = 0; t0 < n_sweeps; t0 += W) {
         const int w = std::min(W, n_sweeps - t0);
@@ -960,13 +1003,7 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
         }
         if (e1) HIP_TRY(c, hipEventRecord(e1, c->cur));
 
-        SweepArgs a{};
-        a.g = c->g;
-        a.chain_base = c->chain_base;
-        a.chain_list = c->sub_list();
-        a.spins = c->spins.p;
-        a.flags = c->has_flags ? c->flags.p : nullptr;
-        a.temp_x = c->temp_x;
+        SweepArgs a = sweep_args(c, sweep0 + (uint32_t)t0, w, seed, tab_dev + (size_t)t0 * tab_ss, tab_cs, tab_ss, use_slots);
         a.ord2 = sc.order.p + o0 * n;
         a.lvl_off = sc.lvl_off.p + o0 * (size_t)(n + 1);
         a.nlev = sc.nlev.p + o0;
@@ -978,28 +1015,14 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
             a.headh64 = sc.headh64.p + o0 * n;
         }
         a.per_chain = per_chain;
-        a.n_sweeps = w;
-        a.sweep0 = sweep0 + (uint32_t)t0;
-        a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-        a.tab = tab_dev + (size_t)t0 * tab_ss;
-        a.tab_cs = tab_cs; a.tab_ss = tab_ss;
-        a.slot_of_chain = use_slots ? c->slot_of_chain.p : nullptr;
         a.ustream = ustream_dev;
-        a.efix = c->efix.p;
         a.energy_sink = c->energy_sink;
-        a.escale = c->escale;
-        a.eshift = c->escale - c->qs;
-        a.qinv = std::ldexp(1.0f, -c->qs);
-        a.qinv64 = std::ldexp(1.0, -c->qs);
-        a.rng_stride = c->rng_stride; a.rng_base = c->rng_base; a.rng_ladder_len = std::max(1, c->ladder_len);
         a.etrace = o.out_energy ? c->etrace.p : nullptr;
         a.trace_sweeps = n_sweeps;
         a.t0 = t0;
         a.rec_stride = rec ? rec : 1;
-        a.min_stride = c->track_min ? c->track_min_stride : 1;
         a.strace = rec ? c->strace.p : nullptr;
         a.emin = want_min ? c->emin.p : nullptr;
-        a.argmin = c->argmin.p;
         a.best = (want_min && want_state) ? c->best.p : nullptr;
 #ifdef NLMC_STAMPS
         HIP_TRY(c, c->dbg.reserve((size_t)R * 16 * 8 + 96));
@@ -1016,7 +1039,7 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
         if (big) {
             if (c->n_cu == 0) HIP_TRY(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
             per_level = (long long)R * 8 <= c->n_cu;
-            if (const char *e = getenv("NLMC_BIG_PER_LEVEL")) per_level = atoi(e) != 0;
+            if (c->knobs.big_per_level >= 0) per_level = c->knobs.big_per_level != 0;
             if (R > 65535) per_level = false;
         }
         if (big && !per_level) {
@@ -1045,20 +1068,10 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
                 if (per_sweep_out || t == w - 1) hipLaunchKernelGGL(k_big_sweep_end, dim3(R), dim3(1024), 0, c->cur, a, t, c->big_esum.p);
                 HIP_TRY(c, hipGetLastError());
             }
-        } else if (stream_mode)
-            hipLaunchKernelGGL(k_sweep_stream, dim3(R), dim3(nt), lds, c->cur, a);
-        else if (f64 && c->f64_pack16 && c->has_diag)
-            hipLaunchKernelGGL((k_sweep_philox<double, true, true>), dim3(R), dim3(nt), lds, c->cur, a);
-        else if (f64 && c->f64_pack16)
-            hipLaunchKernelGGL((k_sweep_philox<double, false, true>), dim3(R), dim3(nt), lds, c->cur, a);
-        else if (f64 && c->has_diag)
-            hipLaunchKernelGGL((k_sweep_philox<double, true>), dim3(R), dim3(nt), lds, c->cur, a);
-        else if (f64)
-            hipLaunchKernelGGL((k_sweep_philox<double, false>), dim3(R), dim3(nt), lds, c->cur, a);
-        else if (c->has_diag)
-            hipLaunchKernelGGL((k_sweep_philox<float, true>), dim3(R), dim3(nt), lds, c->cur, a);
-        else
-            hipLaunchKernelGGL((k_sweep_philox<float, false>), dim3(R), dim3(nt), lds, c->cur, a);
+        } else {
+            void *kargs[] = {&a};
+            HIP_TRY(c, hipLaunchKernel(kfun, dim3(R), dim3(nt), kargs, lds, c->cur));
+        }
         HIP_TRY(c, hipGetLastError());
         if (e2) { HIP_TRY(c, hipEventRecord(e2, c->cur)); c->launches_timed++; }
         c->launches_sweep++;
@@ -1202,7 +1215,8 @@ int nlmc_create(nlmc_ctx **out, int device, void *hip_stream, int n, int64_t nnz
     c->stream = reinterpret_cast<hipStream_t>(hip_stream);
     c->cur = c->stream;
     c->n = n;
-    c->big = n > NLMC_LDS_N || getenv("NLMC_FORCE_BIG") != nullptr;      // (the knob: tests compare the two sets of kernels at one size)
+    c->knobs = read_knobs();
+    c->big = n > NLMC_LDS_N || c->knobs.force_big;
     c->n_pad = (n + 15) / 16 * 16;
     c->nnz = nnz;
     c->n_chains = n_chains;
@@ -1282,13 +1296,9 @@ int nlmc_create(nlmc_ctx **out, int device, void *hip_stream, int n, int64_t nnz
         if (std::ldexp((double)e32[e].q, -qs) != vals[e]) exact_q = false;
         if (e32[e].q != 1 && e32[e].q != -1) pm1 = false;
     }
-    c->compact16 = fits16 && !getenv("NLMC_NO_COMPACT");
-    c->f64_pack16 = fits16 && exact_q && n <= 65535 && !getenv("NLMC_NO_PACK64");
-    c->sign8 = c->compact16 && pm1 && nnz > 0 && !getenv("NLMC_NO_SIGNFMT");
-    c->knob_no_warm = getenv("NLMC_NO_WARM") != nullptr;
-    c->knob_no_prio = getenv("NLMC_FUSED_NOPRIO") != nullptr;
-    c->knob_no_dbuf = getenv("NLMC_NO_DBUF") != nullptr;
-    if (const char *e = getenv("NLMC_DBG_FLAGS")) c->knob_dbg_flags = atoi(e);
+    c->compact16 = fits16 && !c->knobs.no_compact;
+    c->f64_pack16 = fits16 && exact_q && n <= 65535 && !c->knobs.no_pack64;
+    c->sign8 = c->compact16 && pm1 && nnz > 0 && !c->knobs.no_signfmt;
     bool exact_h = true;
     for (int k = 0; k < n; ++k) {
         hq[k] = (int32_t)rq(h[k], qs);
@@ -1298,7 +1308,6 @@ int nlmc_create(nlmc_ctx **out, int device, void *hip_stream, int n, int64_t nnz
         c->xmax = (int)std::min<int64_t>(std::max<int64_t>(c->xmax, row), INT_MAX);
     }
     c->f64_exact = exact_q && exact_h;
-    if (const char *e = getenv("NLMC_F64_TIE_MASK")) c->knob_tie_mask = (unsigned)strtoul(e, nullptr, 0);
 
     // +16 entries of padding behind the row arrays: fixed-width row windows are read unconditionally (never used past the row end)
     const size_t R = (size_t)std::max(n_chains, 1), npad = (size_t)c->n_pad, nz = (size_t)nnz + 16;
@@ -1350,11 +1359,11 @@ void nlmc_destroy(nlmc_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream); else (void)hipDeviceSynchronize();
 #ifdef NLMC_STAMPS
-    if (const char *fn = getenv("NLMC_STAMP_FILE")) {      // diagnostic build: dump the last launch's per-wave cycle sums
+    if (!c->knobs.stamp_file.empty()) {      // diagnostic build: dump the last launch's per-wave cycle sums
         if (c->dbg.p) {
             std::vector<long long> hbuf((size_t)c->n_chains * 16 * 8 + 96);
             if (hipMemcpy(hbuf.data(), c->dbg.p, hbuf.size() * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess) {
-                if (FILE *f = fopen(fn, "wb")) { fwrite(hbuf.data(), sizeof(long long), hbuf.size(), f); fclose(f); }
+                if (FILE *f = fopen(c->knobs.stamp_file.c_str(), "wb")) { fwrite(hbuf.data(), sizeof(long long), hbuf.size(), f); fclose(f); }
             }
         }
     }
@@ -1551,7 +1560,7 @@ int nlmc_sweep_stream(nlmc_ctx *c, int n_sweeps, const int32_t *perm, const doub
                                c->u_raw.p + sh, c->keys.p + sh, c->ustream.p + sh, c->stream_bad.p);
         }
     } else {
-        { int rc = ensure_lds(c, 8, reinterpret_cast<const void *>(k_stream_scatter), (size_t)n * 4); if (rc) return rc; }
+        { int rc = ensure_lds(c, reinterpret_cast<const void *>(k_stream_scatter), (size_t)n * 4); if (rc) return rc; }
         hipLaunchKernelGGL(k_stream_scatter, dim3((unsigned)tot), dim3(256), (size_t)n * 4, c->stream, n, c->perm_raw.p, c->u_raw.p, c->keys.p,
                            c->ustream.p, c->stream_bad.p);
     }
@@ -1605,18 +1614,7 @@ int nlmc_sweep_philox(nlmc_ctx *c, int precision, int order_mode, int n_sweeps, 
         tcs = chain_stride ? T * 2 : 0;
         tss = sweep_stride ? 2 : 0;
     } else {
-        // ladder table re-uploaded only when temp_x changed since the last upload (no host sync on the hot path)
-        if (!c->pt_tab_valid || c->pt_tab_temp_x != c->temp_x) {
-            std::vector<double> tab((size_t)c->ladder_len * 2);
-            for (int r = 0; r < c->ladder_len; ++r) {
-                tab[2 * r + 0] = -2.0 * LOG2E * c->beta_list[r];
-                tab[2 * r + 1] = -2.0 * LOG2E * (c->beta_list[r] / c->temp_x);
-            }
-            HIP_TRY(c, hipMemcpyAsync(c->pt_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, c->cur));
-            HIP_TRY(c, hipStreamSynchronize(c->cur));
-            c->pt_tab_valid = true;
-            c->pt_tab_temp_x = c->temp_x;
-        }
+        { int rc = upload_ladder_tab(c, c->cur); if (rc) return rc; }
         tab_dev = c->pt_tab.p;
         tcs = 2; tss = 0;
         use_slots = true;
@@ -1712,8 +1710,8 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
     a.g = c->g;
     a.T = T;
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.sweep0 = sweep0;
-    P.workers = fused_workers(fused_block(c->n));
-    P.gen0 = fused_gen0(fused_block(c->n));
+    P.workers = fused_workers(c, fused_block(c));
+    P.gen0 = fused_gen0(c, fused_block(c));
     a.level_cap = P.workers * 64;
     a.pstride = P.pstride;
     a.tab_words = c->n_pad;
@@ -1721,7 +1719,7 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
     a.fmt = fused_addr_format(c) ? NLMC_FMT_ADDR : c->compact16 ? NLMC_FMT_COMPACT : NLMC_FMT_WIDE;
     a.k_zero = c->n_pad + 8;
     a.neg_off = c->n_pad + 16;
-    a.bank_aware = (with_val || getenv("NLMC_NO_BANK_AWARE")) ? 0 : 1;    // (the fp64 sum runs in row order)
+    a.bank_aware = (with_val || c->knobs.no_bank_aware) ? 0 : 1;    // (the fp64 sum runs in row order)
     a.val = with_val ? P.val.p : nullptr;
     P.fmt = a.fmt;
     P.has_val = with_val;
@@ -1729,8 +1727,8 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
     a.hi_max = P.himax.p; a.send = P.send.p; a.npos = P.npos.p;
     const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
     const size_t lds = (size_t)n * 8 + n4 * 2 + n4 + n4 * 2 + 2 * (size_t)(NLMC_LCAP + 2) * 4 + 16;
-    { int rc = ensure_lds(c, 16, reinterpret_cast<const void *>(k_levelize_fused), lds); if (rc) return rc; }
-    const bool fz_diag = getenv("NLMC_FZ_STATS") != nullptr;     // diagnostic: phase cycle counts of window 0 on stderr
+    { int rc = ensure_lds(c, reinterpret_cast<const void *>(k_levelize_fused), lds); if (rc) return rc; }
+    const bool fz_diag = c->knobs.fz_stats;     // diagnostic: phase cycle counts of window 0 on stderr
     if (fz_diag) { HIP_TRY(c, c->fz_stats.reserve(W * 8)); a.stats = c->fz_stats.p; }
     // planning time counts as levelize time of the accumulating timer (nlmc_timing_total): an event triple whose
     // sweep part is empty
@@ -1765,8 +1763,11 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
 int nlmc_fused_modes(nlmc_ctx *c, int window)
 {
     if (!c) return 0;
-    return (fused_supported(c, window) ? 1 : 0) | (fused_f64_any(c, window) ? 2 : 0);
+    auto can = [&](int precision) { return fused_route(c, precision, NLMC_ORDER_SHARED, false, false, -1, window, Via::sweeps) != NOT_FUSED; };
+    return (can(NLMC_F32) ? 1 : 0) | (can(NLMC_F64) ? 2 : 0);
 }
+
+int nlmc_last_sweep_fused(const nlmc_ctx *c) { return c && c->stat_fused_window >= 0 ? 1 : 0; }
 
 int nlmc_probe_level_round(nlmc_ctx *c, int waves, int conflict_free, int rounds, int n_workgroups, double *out_ns_per_round)
 {
@@ -2353,74 +2354,76 @@ int nlmc_apt_swap_collective(nlmc_ctx *c, uint32_t round, uint64_t seed, int n_p
     return apt_launch_swap(c, round, seed, n_pairs, out_pairs, out_accepted);
 }
 
+// The checks nlmc_pt_rounds_fused (via rounds) and nlmc_pt_rounds_deferred (via deferred) share, in their order.  NLMC_OK with the
+// plan slot and the arithmetic of the rounds in fslot / arith, fslot = -1 when there is nothing to do.
+int rounds_check(nlmc_ctx *c, Via via, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs,
+                 int &fslot, int &arith)
+{
+    const bool d = via == Via::deferred;
+    const std::string name = d ? "nlmc_pt_rounds_deferred: " : "nlmc_pt_rounds_fused: ";
+    fslot = -1;
+    if (n_rounds < 0 || T < 1 || (precision != NLMC_F32 && precision != NLMC_F64) || n_pairs < 0)
+        return fail(c, NLMC_ERR_ARG, name + "bad argument");
+    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, name + "call nlmc_pt_init first");
+    if (n_rounds == 0 || c->n_chains == 0) return NLMC_OK;
+    const int L = c->ladder_len;
+    auto no = [&](const char *why) { return fail(c, NLMC_ERR_UNSUPPORTED, name + why); };
+    if (d ? c->knobs.no_deferred : c->knobs.no_persistent) return no(d ? "switched off (NLMC_NO_DEFERRED)" : "switched off (NLMC_NO_PERSISTENT)");
+    if (c->chain_base % L != 0 || c->n_chains % L != 0) return no("the context's block cuts a ladder (the swap needs other contexts' energies)");
+    if (c->comm || (c->apt_R > 0 && c->apt_world > 1)) return no("the context takes part in a collective swap round");
+    if (c->has_flags || c->subset != 0 || c->cur != c->stream || (d && c->track_min))
+        return no(d ? "phase flags, a chain subset or a tracked minimum are in force" : "phase flags or a chain subset are in force");
+    if (d && n_pairs < 1) return no("no swap pairs");
+    if (n_pairs > std::max(0, L - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
+    const int k = fused_plan_for(c, sweep0, n_rounds * T, seed);
+    if (k < 0 || c->fz[k].T != T) return no("no fused-window plan of one window per round covers these sweeps");
+    arith = fused_route(c, precision, NLMC_ORDER_SHARED, false, false, k, T, via);
+    if (arith == NOT_FUSED) return no("the fp64 mode does not run on fused windows for this instance");
+    if (n_pairs > 0 && !(c->pt_plan_valid && c->pt_plan_seed == seed && c->pt_plan_npairs == n_pairs && round0 >= c->pt_plan_round0 &&
+                         (uint64_t)round0 + (uint64_t)n_rounds <= (uint64_t)c->pt_plan_round0 + (uint64_t)c->pt_plan_rounds))
+        return no("the pair selections of these rounds are not planned (nlmc_pt_plan)");
+    fslot = k;
+    return NLMC_OK;
+}
+
 // n_rounds rounds (sweeps_per_round sweeps at the ladder temperatures + the swap round) in ONE cooperative launch (k_rounds_fused).
 int nlmc_pt_rounds_fused(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
                          int n_pairs)
 {
     if (!c) return NLMC_ERR_ARG;
-    if (n_rounds < 0 || sweeps_per_round < 1 || (precision != NLMC_F32 && precision != NLMC_F64) || n_pairs < 0)
-        return fail(c, NLMC_ERR_ARG, "nlmc_pt_rounds_fused: bad argument");
-    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, "nlmc_pt_rounds_fused: call nlmc_pt_init first");
-    if (n_rounds == 0 || c->n_chains == 0) return NLMC_OK;
-    const int L = c->ladder_len, T = sweeps_per_round;
-    auto no = [&](const char *why) { return fail(c, NLMC_ERR_UNSUPPORTED, std::string("nlmc_pt_rounds_fused: ") + why); };
-    if (getenv("NLMC_NO_PERSISTENT")) return no("switched off (NLMC_NO_PERSISTENT)");
-    if (c->chain_base % L != 0 || c->n_chains % L != 0) return no("the context's block cuts a ladder (the swap needs other contexts' energies)");
-    if (c->comm || (c->apt_R > 0 && c->apt_world > 1)) return no("the context takes part in a collective swap round");
-    if (c->has_flags || c->subset != 0 || c->cur != c->stream) return no("phase flags or a chain subset are in force");
-    if (n_pairs > std::max(0, L - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
-    const int fslot = fused_plan_for(c, sweep0, n_rounds * T, seed);
-    if (fslot < 0 || c->fz[fslot].T != T) return no("no fused-window plan of one window per round covers these sweeps");
-    if (precision == NLMC_F64 && !fused_f64_supported(c, T)) return no("the fp64 mode does not run on fused windows for this instance");
-    if (n_pairs > 0 && !(c->pt_plan_valid && c->pt_plan_seed == seed && c->pt_plan_npairs == n_pairs && round0 >= c->pt_plan_round0 &&
-                         (uint64_t)round0 + (uint64_t)n_rounds <= (uint64_t)c->pt_plan_round0 + (uint64_t)c->pt_plan_rounds))
-        return no("the pair selections of these rounds are not planned (nlmc_pt_plan)");
+    int fslot = -1, arith = NOT_FUSED;
+    { int rc = rounds_check(c, Via::rounds, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs, fslot, arith); if (rc || fslot < 0) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
+    const int L = c->ladder_len, T = sweeps_per_round;
     const nlmc_ctx::FusedPlan &P = c->fz[fslot];
-    const bool f64 = precision == NLMC_F64;
-    const int kt = f64 ? 2 * c->xmax + 1 : 0;
+    const int kt = arith == ARITH_F64 ? 2 * c->xmax + 1 : 0;
     const FusedLds Lds = fused_lds(c->n, c->n_pad, false, false, P.fmt == NLMC_FMT_ADDR, kt);
-#define NLMC_KR(D, F64_) {reinterpret_cast<const void *>(k_rounds_fused<D, NLMC_FMT_WIDE, F64_>), reinterpret_cast<const void *>(k_rounds_fused<D, NLMC_FMT_COMPACT, F64_>), \
-                          reinterpret_cast<const void *>(k_rounds_fused<D, NLMC_FMT_ADDR, F64_>)}
-    static const void *const table[2][2][3] = {{NLMC_KR(false, false), NLMC_KR(false, true)}, {NLMC_KR(true, false), NLMC_KR(true, true)}};
-#undef NLMC_KR
-    const void *kfun = table[c->has_diag][f64][P.fmt];
-    { int rc = ensure_lds(c, 60 + ((c->has_diag ? 2 : 0) + (f64 ? 1 : 0)) * 3 + P.fmt, kfun, Lds.total); if (rc) return rc; }
-    const int nt = fused_block(c->n);
+    const void *kfun = rounds_kernel(c->has_diag, P.fmt, arith);
+    { int rc = ensure_lds(c, kfun, Lds.total); if (rc) return rc; }
+    const int nt = fused_block(c);
     // every workgroup must be resident at once (they wait for each other): asked of the runtime, which also refuses the launch
     int per_cu = 0, n_cu = 0;
     HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfun, nt, Lds.total));
     HIP_TRY(c, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
-    if ((long long)per_cu * n_cu < c->n_chains) return no("more chains than workgroups the device holds at once");
+    if ((long long)per_cu * n_cu < c->n_chains)
+        return fail(c, NLMC_ERR_UNSUPPORTED, "nlmc_pt_rounds_fused: more chains than workgroups the device holds at once");
     const int w0 = (int)((sweep0 - P.sweep0) / (uint32_t)T), nl = c->n_chains_global / L;
     const size_t G = (size_t)c->n_chains_global, PS = (size_t)P.pstride;
     HIP_TRY(c, c->rounds_ebuf.reserve(2 * G));
     HIP_TRY(c, c->rounds_bar.reserve(1));
     HIP_TRY(c, hipMemsetAsync(c->rounds_bar.p, 0, sizeof(unsigned), c->stream));
-    if (!c->pt_tab_valid || c->pt_tab_temp_x != c->temp_x) {
-        std::vector<double> tab((size_t)L * 2);
-        for (int r = 0; r < L; ++r) { tab[2 * r] = -2.0 * LOG2E * c->beta_list[r]; tab[2 * r + 1] = -2.0 * LOG2E * (c->beta_list[r] / c->temp_x); }
-        HIP_TRY(c, hipMemcpyAsync(c->pt_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->pt_tab_valid = true; c->pt_tab_temp_x = c->temp_x;
-    }
-    SweepArgs a{};
-    a.g = c->g; a.chain_base = c->chain_base; a.spins = c->spins.p; a.temp_x = c->temp_x;
+    { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
+    SweepArgs a = sweep_args(c, sweep0, T, seed, c->pt_tab.p, 2, 0, true);
     a.fz_pstride = P.pstride; a.fz_fmt = P.fmt;
-    a.f_workers = P.workers; a.f_gen0 = P.gen0; a.f_gen_prio = c->knob_no_prio ? 0 : 1;
+    a.f_workers = P.workers; a.f_gen0 = P.gen0; a.f_gen_prio = c->knobs.no_prio ? 0 : 1;
 #ifdef NLMC_DEBUG_KNOBS
-    a.dbg_flags = c->knob_dbg_flags;
+    a.dbg_flags = c->knobs.dbg_flags;
 #endif
-    a.n_sweeps = T; a.sweep0 = sweep0; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-    a.tab = c->pt_tab.p; a.tab_cs = 2; a.tab_ss = 0; a.slot_of_chain = c->slot_of_chain.p;
-    a.efix = c->efix.p; a.escale = c->escale; a.eshift = c->escale - c->qs; a.qinv = std::ldexp(1.0f, -c->qs);
-    a.trace_sweeps = T; a.rec_stride = 1; a.min_stride = 1; a.argmin = c->argmin.p;
+    a.trace_sweeps = T; a.rec_stride = 1;
     a.lds_neg_off = Lds.neg_off; a.lds_flags_off = Lds.flags_off; a.lds_u_off = Lds.u_off; a.lds_u_stride = Lds.u_bytes; a.lds_red_off = Lds.red_off;
-    a.lds_snap_off = Lds.snap_off; a.lds_kt_off = Lds.kt_off; a.f64_xmax = c->xmax; a.f64_tie_mask = c->knob_tie_mask;
-    a.qinv64 = std::ldexp(1.0, -c->qs);
-    a.rng_stride = c->rng_stride; a.rng_base = c->rng_base; a.rng_ladder_len = std::max(1, L);
+    a.lds_snap_off = Lds.snap_off; a.lds_kt_off = Lds.kt_off; a.f64_xmax = c->xmax; a.f64_tie_mask = c->knobs.tie_mask;
     RoundsArgs q{};
-    q.n_rounds = n_rounds; q.n_windows_avail = c->knob_no_warm ? n_rounds : P.windows - w0;
+    q.n_rounds = n_rounds; q.n_windows_avail = c->knobs.no_warm ? n_rounds : P.windows - w0;
     q.loff = P.loff.p + (size_t)w0 * (NLMC_LCAP + 1); q.nlev = P.nlev.p + w0; q.himax = P.himax.p + w0; q.send = P.send.p + (size_t)w0 * T;
     q.npos = P.npos.p + w0; q.head = P.head.p + (size_t)w0 * PS; q.ell = P.ell.p + (size_t)w0 * PS * NLMC_FZ_W;
     q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = nl; q.round0 = round0;
@@ -2475,36 +2478,15 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
                             int n_pairs)
 {
     if (!c) return NLMC_ERR_ARG;
-    if (n_rounds < 0 || sweeps_per_round < 1 || (precision != NLMC_F32 && precision != NLMC_F64) || n_pairs < 0)
-        return fail(c, NLMC_ERR_ARG, "nlmc_pt_rounds_deferred: bad argument");
-    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, "nlmc_pt_rounds_deferred: call nlmc_pt_init first");
-    if (n_rounds == 0 || c->n_chains == 0) return NLMC_OK;
-    const int L = c->ladder_len, T = sweeps_per_round;
-    auto no = [&](const char *why) { return fail(c, NLMC_ERR_UNSUPPORTED, std::string("nlmc_pt_rounds_deferred: ") + why); };
-    if (getenv("NLMC_NO_DEFERRED")) return no("switched off (NLMC_NO_DEFERRED)");
-    if (c->chain_base % L != 0 || c->n_chains % L != 0) return no("the context's block cuts a ladder (the swap needs other contexts' energies)");
-    if (c->comm || (c->apt_R > 0 && c->apt_world > 1)) return no("the context takes part in a collective swap round");
-    if (c->has_flags || c->subset != 0 || c->cur != c->stream || c->track_min) return no("phase flags, a chain subset or a tracked minimum are in force");
-    if (n_pairs < 1 || n_pairs > std::max(0, L - 1)) return n_pairs < 1 ? no("no swap pairs") : fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
-    const int fslot = fused_plan_for(c, sweep0, n_rounds * T, seed);
-    if (fslot < 0 || c->fz[fslot].T != T) return no("no fused-window plan of one window per round covers these sweeps");
-    if (precision == NLMC_F64 && !fused_f64_supported(c, T) && !(fused_f64_real_supported(c, T) && c->fz[fslot].has_val))
-        return no("the fp64 mode does not run on fused windows for this instance");
-    if (!(c->pt_plan_valid && c->pt_plan_seed == seed && c->pt_plan_npairs == n_pairs && round0 >= c->pt_plan_round0 &&
-          (uint64_t)round0 + (uint64_t)n_rounds <= (uint64_t)c->pt_plan_round0 + (uint64_t)c->pt_plan_rounds))
-        return no("the pair selections of these rounds are not planned (nlmc_pt_plan)");
+    int fslot = -1, arith = NOT_FUSED;
+    { int rc = rounds_check(c, Via::deferred, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs, fslot, arith); if (rc || fslot < 0) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
+    const int L = c->ladder_len, T = sweeps_per_round;
     const nlmc_ctx::FusedPlan &P = c->fz[fslot];
     const int w0 = (int)((sweep0 - P.sweep0) / (uint32_t)T), nl = c->n_chains_global / L;
     const size_t G = (size_t)c->n_chains_global;
     HIP_TRY(c, c->rounds_ebuf.reserve(2 * G));
-    if (!c->pt_tab_valid || c->pt_tab_temp_x != c->temp_x) {
-        std::vector<double> tab((size_t)L * 2);
-        for (int r = 0; r < L; ++r) { tab[2 * r] = -2.0 * LOG2E * c->beta_list[r]; tab[2 * r + 1] = -2.0 * LOG2E * (c->beta_list[r] / c->temp_x); }
-        HIP_TRY(c, hipMemcpyAsync(c->pt_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->pt_tab_valid = true; c->pt_tab_temp_x = c->temp_x;
-    }
+    { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
     if (!c->ev_accumulate) c->ev_used = 0;
     c->ev_call_start = c->ev_used;
     c->launches_sweep = 0;
@@ -2528,7 +2510,7 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
         // (this launch publishes its chains' final energies for the next one: rows of the local chains inside the global vector)
         double *sink = c->rounds_ebuf.p + (size_t)(r & 1) * G + c->chain_base;
         int rc = run_fused(c, fslot, w0 + r, sweep0 + (uint32_t)(r * T), seed, c->pt_tab.p, 2, 0, true, false, false, false, false, 0, 0, T,
-                           precision == NLMC_F64, &d, sink);
+                           arith, &d, sink);
         if (rc) return rc;
     }
     c->sub_dirty = true;
@@ -2613,7 +2595,7 @@ static int icm_launch_components(nlmc_ctx *c, const int32_t *pairs_dev, int n_pa
         a.adj = reinterpret_cast<const uint4 *>(c->fz_adj.p);
     }
     const size_t lds = (size_t)c->n * 4 + (((size_t)c->n + 1) & ~(size_t)1) * 2 + 16;
-    { int rc = ensure_lds(c, 1, reinterpret_cast<const void *>(k_icm_components), lds); if (rc) return rc; }
+    { int rc = ensure_lds(c, reinterpret_cast<const void *>(k_icm_components), lds); if (rc) return rc; }
     hipLaunchKernelGGL(k_icm_components, dim3(n_pairs), dim3(c->n >= 4096 ? 1024 : 256), lds, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     return NLMC_OK;
@@ -2649,7 +2631,7 @@ static int icm_launch_round(nlmc_ctx *c, const int32_t *pairs_dev, int n_pairs, 
     a.lds_sa_off = (int)cur; cur += (size_t)c->n_pad;
     a.lds_sb_off = (int)cur; cur += (size_t)c->n_pad;
     const size_t lds = cur + 16;
-    { int rc = ensure_lds(c, 21, reinterpret_cast<const void *>(k_icm_round), lds); if (rc) return rc; }
+    { int rc = ensure_lds(c, reinterpret_cast<const void *>(k_icm_round), lds); if (rc) return rc; }
     hipLaunchKernelGGL(k_icm_round, dim3(n_pairs), dim3(c->n >= 4096 ? 1024 : 256), lds, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     return NLMC_OK;
@@ -2877,21 +2859,21 @@ static int lbp_launch(nlmc_ctx *c, int n_problems, int n_lambdas, double beta, d
     HIP_TRY(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
     int group = 1;
     while (group < 8 && (long long)n_problems * group * 2 <= std::min(32, cus) && n / (group * 2) >= 1024) group *= 2;
-    if (const char *e = getenv("NLMC_LBP_GROUP")) { const int v = atoi(e); if (v >= 1 && v <= 8 && (long long)n_problems * v <= cus) group = v; }
+    if (const int v = c->knobs.lbp_group; v >= 1 && v <= 8 && (long long)n_problems * v <= cus) group = v;
     if (single_workgroup) group = 1;
     a.group = group;
-    if (const char *e = getenv("NLMC_LBP_POLL_BUDGET")) a.poll_budget = atoi(e);      // (test knob: provoke the timeout path)
+    a.poll_budget = c->knobs.lbp_poll_budget;      // (test knob: provoke the timeout path)
     HIP_TRY(c, c->lbp_bar.reserve(P));
     HIP_TRY(c, c->lbp_part.reserve(P * 2 * (size_t)group * 4));
     HIP_TRY(c, hipMemsetAsync(c->lbp_bar.p, 0, sizeof(unsigned int) * P, c->cur));
     a.bar = c->lbp_bar.p; a.part = c->lbp_part.p;
     // small instances: messages in LDS, a thread's edges in registers (k_lbp_lds; same bits): 8 waves x 12 edges per thread, two
     // messages in lock step (other shapes: see the kernel's header)
-    if (group == 1 && n <= 2048 && nnz <= 6144 && !getenv("NLMC_LBP_GLOBAL")) {
+    if (group == 1 && n <= 2048 && nnz <= 6144 && !c->knobs.lbp_global) {
         const size_t lds_small = ((size_t)2 * (6144 + 1) + 2048 + 1 + 64) * sizeof(double);
         const void *kf = c->has_diag ? reinterpret_cast<const void *>(k_lbp_lds<512, 12, 4, true, 2>)
                                      : reinterpret_cast<const void *>(k_lbp_lds<512, 12, 4, false, 2>);
-        { int rc = ensure_lds(c, 17 + (c->has_diag ? 1 : 0), kf, lds_small); if (rc) return rc; }
+        { int rc = ensure_lds(c, kf, lds_small); if (rc) return rc; }
         void *kargs[] = {&a};
         HIP_TRY(c, hipLaunchKernel(kf, dim3(n_problems), dim3(512), kargs, lds_small, c->cur));
         return NLMC_OK;

@@ -74,8 +74,7 @@ class Engine:
         self.ladder_len = 0
         self._ahead = None
         self.fused_f64_real = False
-        self._flags_on = False           # phase flags in force (set_flags / set_phase): a per-call property of the fp64 windows
-        self._flags_fit = None           # (lazy) _f64_flags_fit
+        self._flags_on = False           # phase flags in force (set_flags / set_phase)
         self.energy_scale = int(self._L.nlmc_energy_scale(self._ctx))
         self.field_scale = int(self._L.nlmc_field_scale(self._ctx))      # qs of the "f32" path: Jq = rint(J 2^qs)
 
@@ -231,36 +230,9 @@ class Engine:
         self._ck(self._L.nlmc_set_fused_f64_real(self._ctx, 1 if on else 0))
         self.fused_f64_real = bool(on)
 
-    def _f64_flags_fit(self):
-        """Whether fp64 calls with phase flags in force run on the fused windows of this instance: csrc/nlmc.hip:
-        fused_f64_flags_fit restated (the integer-threshold variant keeps a second K table for the scaled rows; past the LDS
-        budget such calls run sweep by sweep -- same bits)."""
-        if self._flags_fit is None:
-            qs, inst = self.field_scale, self.inst
-            jq, hq = np.rint(np.ldexp(inst.data, qs)), np.rint(np.ldexp(inst.h, qs))
-            exact = np.array_equal(np.ldexp(jq, -qs), inst.data) and np.array_equal(np.ldexp(hq, -qs), inst.h)
-            if not exact:
-                self._flags_fit = True               # real-valued variant: no tables
-            else:
-                rows = np.repeat(np.arange(self.n), np.diff(inst.indptr))
-                xmax = int(np.max(np.abs(hq) + np.bincount(rows, weights=np.abs(jq), minlength=self.n)))
-                n_pad = (self.n + 15) // 16 * 16
-                lds = (3 * (n_pad + 16) + 15) // 16 * 16 + 12 * n_pad + 32 + 16 * (2 * xmax + 1)   # fused_lds(.., flags, neg, 2 K tables)
-                self._flags_fit = lds <= 156 * 1024
-        return self._flags_fit
-
-    def _fused_call(self, precision, window, beta, n_sweeps):
-        """Whether a sweep call on planned fused windows of `window` sweeps runs on them (run_sweeps, csrc/nlmc.hip): the "f32"
-        mode always; the fp64 mode where fused_modes says so, with one temperature per chain, and with phase flags in force only
-        where their layout fits (_f64_flags_fit)."""
-        if precision == "f32":
-            return True
-        if precision not in self.fused_modes(window):
-            return False
-        b = None if beta is None else np.asarray(beta)
-        if b is not None and b.ndim == 2 and n_sweeps > 1 and not (b == b[:, :1]).all():
-            return False                             # a temperature per sweep (the anneal): sweep by sweep
-        return not self._flags_on or self._f64_flags_fit()
+    def _last_fused(self):
+        """Whether every launch of the most recent sweep call ran on fused windows (nlmc_last_sweep_fused)."""
+        return bool(self._L.nlmc_last_sweep_fused(self._ctx))
 
     def sweep_philox_windows(self, n_sweeps, seed, sweep0=0, beta=None, window=None, budget_bytes=None, record_stride=0,
                              want_energy=False, want_min=False, want_state=False, want_recorded_energy=False, precision="f32"):
@@ -283,22 +255,22 @@ class Engine:
             if not (a._fused_from <= ii < a._fused_to):  # planned together with those of the launches that follow
                 a._plan(ii, True)
             if a._fused_from <= ii < a._fused_to:
-                self.fused_last_call = self._fused_call(precision, a.window, beta, S)
                 o = self.sweep_philox(S, seed, sweep0=sweep0, beta=beta, record_stride=record_stride, want_energy=want_energy,
                                       want_min=want_min, want_state=want_state, precision=precision)
+                self.fused_last_call = self._last_fused()
                 if rec_e:
                     o["energy_recorded"] = self.energy_of_recorded(o["spins"].shape[1])
                 return o
         if not T or S % T or S == 0:
-            self.fused_last_call = False
             o = self.sweep_philox(S, seed, sweep0=sweep0, beta=beta, record_stride=record_stride, want_energy=want_energy,
                                   want_min=want_min, want_state=want_state, precision=precision)
+            self.fused_last_call = S > 0 and self._last_fused()
             if rec_e and S > 0:
                 o["energy_recorded"] = self.energy_of_recorded(o["spins"].shape[1])
             return o
         per_piece = sweeps_per_plan_piece(self.fused_plan_bytes(T), S, T, budget, record_stride)
         b = None if beta is None else np.asarray(beta, dtype=np.float64)
-        outs, fused = [], True
+        outs, fused, ran_fused = [], True, True
         if a is not None:                    # this call plans into the slot the announced run's windows live in: they are gone
             a._fused_from = a._fused_to = 0
             self.plan_slot(a.slot)
@@ -309,9 +281,10 @@ class Engine:
             outs.append(self.sweep_philox(t1 - t0, seed, sweep0=sweep0 + t0, beta=b if (b is None or b.ndim < 2) else b[:, t0:t1],
                                           record_stride=record_stride, want_energy=want_energy, want_min=want_min,
                                           want_state=want_state, precision=precision))
+            ran_fused = ran_fused and self._last_fused()
             if rec_e:
                 outs[-1]["energy_recorded"] = self.energy_of_recorded(outs[-1]["spins"].shape[1])
-        self.fused_last_call = fused and self._fused_call(precision, T, beta, S)
+        self.fused_last_call = ran_fused
         o = outs[0] if len(outs) == 1 else _stitch_outputs(outs, per_piece, record_stride, want_energy, want_min, want_state)
         if rec_e and len(outs) > 1:
             o["energy_recorded"] = np.concatenate([p["energy_recorded"] for p in outs], axis=1)

@@ -100,24 +100,27 @@ def test_fused_with_swaps_and_sharded_contexts(product):
     assert np.array_equal(one_f[0], np.concatenate([lo[0], hi[0]]))
 
 
-def test_fused_plan_declines_what_it_cannot_run(product, monkeypatch):
+def test_fused_plan_declines_what_it_cannot_run_knobs_at_create(product, monkeypatch):
     """Tiny instance (n < 256), window of 2: nothing planned, calls take the plain path; per-chain orders and f64
-    ignore a fused plan; calls with per-sweep outputs run on it (snapshot slots in LDS, or in a global ring for large n)."""
+    ignore a fused plan; calls with per-sweep outputs run on it (snapshot slots in LDS, or in a global ring for large n).
+    NLMC_NO_FUSED_OUT holds for the engines created while it is set: one engine with it, one without, the same plan."""
     J, h = make_instance(200, seed=3)
     with product.Engine(J, h, 2) as eng:
         assert eng.plan_philox_fused(0, 4, 10, SEED) == 0
     N, T = 8000, 5
     J, h = make_instance(N, seed=31)
+    monkeypatch.setenv("NLMC_NO_FUSED_OUT", "1")             # (read when an engine is created)
     with product.Engine(J, h, 2) as eng:
         assert eng.plan_philox_fused(0, 2, 2, SEED) == 0
         assert eng.plan_philox_fused(0, 2, T, SEED) == 2
         eng.set_spins(init_spins(2, N))
-        monkeypatch.setenv("NLMC_NO_FUSED_OUT", "1")
         o = eng.sweep_philox(T, SEED, sweep0=0, beta=1.0, want_energy=True, want_min=True)     # sweep by sweep
         st = eng.last_schedule_stats()
         assert o["energy"].shape == (2, T) and st["orders"] == T and st["levels"] / T > 15
         e_plain = eng.energy()
-        monkeypatch.delenv("NLMC_NO_FUSED_OUT")
+    monkeypatch.delenv("NLMC_NO_FUSED_OUT")
+    with product.Engine(J, h, 2) as eng:
+        assert eng.plan_philox_fused(0, 2, T, SEED) == 2
         eng.set_spins(init_spins(2, N))
         o2 = eng.sweep_philox(T, SEED, sweep0=0, beta=1.0, want_energy=True, want_min=True)    # fused, with outputs
         assert eng.last_schedule_stats()["levels"] / T < st["levels"] / T

@@ -167,7 +167,8 @@ def test_lds_resident_kernel_equals_the_global_memory_kernel(product, N, P, monk
     sat = float(np.tanh(19.06)) - EPS
     with product.Engine(inst, None, 1) as eng:
         a = eng.lbp_convexified(ms, eps, lams, 2.5, EPS, 100, sat, want_all=True)
-        monkeypatch.setenv("NLMC_LBP_GLOBAL", "1")
+    monkeypatch.setenv("NLMC_LBP_GLOBAL", "1")                # (read when an engine is created)
+    with product.Engine(inst, None, 1) as eng:
         b = eng.lbp_convexified(ms, eps, lams, 2.5, EPS, 100, sat, want_all=True)
     for k in ("mag", "n_lambdas", "status"):
         assert np.array_equal(a[k], b[k]), k
@@ -191,10 +192,11 @@ def test_group_barrier_timeout_falls_back_to_one_workgroup_per_problem(product, 
     ms = low_energy_states(J, h, 1, seed=2, sweeps=40).astype(np.float64)
     lams = product.lbp.lambda_list(3.0, 0.5, 0.7)
     sat = float(np.tanh(19.06)) - EPS
+    monkeypatch.setenv("NLMC_LBP_GROUP", "4")                 # (knobs are read when an engine is created)
     with product.Engine(inst, None, 1) as eng:
-        monkeypatch.setenv("NLMC_LBP_GROUP", "4")
         a = eng.lbp_convexified(ms, eps, lams, 2.5, EPS, 60, sat)
-        monkeypatch.setenv("NLMC_LBP_POLL_BUDGET", "1")
+    monkeypatch.setenv("NLMC_LBP_POLL_BUDGET", "1")
+    with product.Engine(inst, None, 1) as eng:
         b = eng.lbp_convexified(ms, eps, lams, 2.5, EPS, 60, sat)
     assert a["status"][0] == 0 and b["status"][0] == 0
     assert np.array_equal(a["mag"], b["mag"]) and np.array_equal(a["n_lambdas"], b["n_lambdas"])
