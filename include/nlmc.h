@@ -144,8 +144,11 @@ int nlmc_plan_philox_fused(nlmc_ctx *ctx, uint32_t sweep0, int n_windows, int wi
  * is an exact multiple of 2^-qs (+-J, integer and dyadic instances) with max_k (sum|Jq| + |hq|) <= 4095: its field is then the
  * exact integer X times 2^-qs, z = -2 log2(e) beta x takes one value per X, and the test fma(u, 2^z, u) < 1 of the fp64 spec is
  * monotone in the 53-bit integer of u -- one exact integer threshold per (chain, X), built in the kernel's prologue by bisection on
- * the spec's own test.  A plan is shared by both precisions; an fp64 call runs on it when the call has one temperature per chain
- * (otherwise: sweep by sweep).  Phase flags are a property of the call, not of this answer: with flags in force the scaled rows take
+ * the spec's own test.  A plan is shared by both precisions.  An fp64 call with a temperature per sweep (an anneal) and no phase
+ * flags in force runs on it too: the thresholds of a sweep sit in a ring of three tables, one per threshold slot, each rebuilt at
+ * its next sweep's temperature, when the three tables fit in LDS and 8 (2 max_k (sum|Jq| + |hq|) + 1) <= n (the rebuilding stays
+ * small next to a sweep).  With flags in force, and on real-valued instances (nlmc_set_fused_f64_real: measured slower there than
+ * sweep by sweep), such a call runs sweep by sweep.  Phase flags are a property of the call, not of this answer: with flags in force the scaled rows take
  * a second threshold table at cb1, frozen rows keep their spin; where the two tables and the flags do not fit in LDS (large max_k
  * sum |Jq| + |hq| at large n) such a call runs sweep by sweep.  Bit-identical to the sweep-by-sweep fp64 kernel either way.  The
  * answer comes from the same rule the sweep and round calls follow; whether a given call ran on fused windows: nlmc_last_sweep_fused. */
@@ -158,8 +161,8 @@ int nlmc_last_sweep_fused(const nlmc_ctx *ctx);
  * it is on carry an fp64 value plane beside the entry planes, in row order; the kernel is update_spin<double> operation for
  * operation (fp64 field summed with fma in CSR order, z = cb x, fma(u, 2^z, u) < 1 decided from the 27 high bits of u where they
  * decide, from all 53 otherwise), bit-identical to the sweep-by-sweep fp64 kernel.  nlmc_fused_modes then reports bit 1 for such
- * instances; nlmc_sweep_philox(NLMC_F64) runs on it (one temperature per chain; phase flags in force or not: z = cb1 x on scaled
- * rows, frozen rows unchanged) and so does nlmc_pt_rounds_deferred(NLMC_F64) (no phase flags); nlmc_pt_rounds_fused does not.  NLMC_NO_FUSED64 switches it off.  Changing the setting drops the current fused plans. */
+ * instances; nlmc_sweep_philox(NLMC_F64) runs on it (one temperature per chain, phase flags in force or not: z = cb1 x on scaled
+ * rows, frozen rows unchanged; a call with a temperature per sweep stays sweep by sweep) and so does nlmc_pt_rounds_deferred(NLMC_F64) (no phase flags); nlmc_pt_rounds_fused does not.  NLMC_NO_FUSED64 switches it off.  Changing the setting drops the current fused plans. */
 int nlmc_set_fused_f64_real(nlmc_ctx *ctx, int on);
 /* Only allocates the plan buffers for up to n_windows windows of `window` sweeps (a later nlmc_plan_philox_fused of at
  * most that size then allocates nothing).  Drops the current fused plan. */

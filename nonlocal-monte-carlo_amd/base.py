@@ -141,8 +141,8 @@ class SweepMixin:
         # chain samples the Boltzmann law of (Jq, hq) 2^-qs with |Jq 2^-qs - J| <= 2^-(qs+1), nothing lost for +-J / integer
         # instances), on fused windows planned piece by piece within a memory budget where the instance qualifies, sweep by
         # sweep otherwise (same bits).  NMC(precision="f64"): the reference's arithmetic (fp64 field, 53-bit uniform) instead, on
-        # fused windows where fused_modes says so (phases with their flags included; the anneal, a temperature per sweep, sweep by
-        # sweep).  Smaller instances: fp64 fields.  o["energy_recorded"] holds the fp64 energies of the
+        # fused windows where fused_modes says so (phases with their flags included, and the anneal with its temperature per sweep on
+        # dyadic instances: no flags are in force there; on real-valued instances the anneal runs sweep by sweep).  Smaller instances: fp64 fields.  o["energy_recorded"] holds the fp64 energies of the
         # recorded configurations, computed on the device copy of the trace -- what the reference's list comprehension
         # (NMC/nmc.py:386-387) would give for them; NMC_subroutine's argmin hand-off (NMC/nmc.py:394-395) uses THEM whenever every
         # sweep was recorded (M_skip == 1) and the kernel's tracked minimum (exact integers of the quantised model in the "f32"

@@ -599,12 +599,16 @@ enum class Via { sweeps, deferred, rounds };
 
 // The one rule for whether a call runs on fused windows, and on which arithmetic: NOT_FUSED or ARITH_*.  `slot`: the plan slot whose
 // windows of T sweeps cover the call (fused_plan_for), or -1 to ask whether such windows could carry the precision at all
-// (nlmc_fused_modes).  `sweep_temps`, `flags`: the call has a temperature per sweep, phase flags in force.
+// (nlmc_fused_modes).  `sweep_temps`, `flags`: the call has a temperature per sweep, phase flags in force (both together: sweep by
+// sweep in the fp64 mode).
 int fused_route(const nlmc_ctx *c, int precision, int order_mode, bool sweep_temps, bool flags, int slot, int T, Via via)
 {
     if (order_mode != NLMC_ORDER_SHARED || !fused_supported(c, T)) return NOT_FUSED;
     if (precision == NLMC_F32) return ARITH_F32;
-    if (sweep_temps || c->knobs.no_fused64) return NOT_FUSED;         // the fp64 mode: one temperature per chain
+    if (c->knobs.no_fused64) return NOT_FUSED;
+    // the fp64 mode.  A temperature per sweep (an anneal) with phase flags in force stays sweep by sweep; without flags the
+    // integer-threshold variant takes it (fused_levels<.., SWT>), the real-valued one does not (below)
+    if (sweep_temps && flags) return NOT_FUSED;
     if (c->f64_exact) {
         // exact dyadic couplings and fields (the field is an integer): a per-chain threshold table per value of the field in LDS beside
         // the rest; with phase flags a second one (scaled rows), counted at its worst (negated copy of the spins in), so that the
@@ -612,11 +616,18 @@ int fused_route(const nlmc_ctx *c, int precision, int order_mode, bool sweep_tem
         if (c->xmax > 4095 || fused_lds(c->n, c->n_pad, false, false, fused_addr_format(c), 2 * c->xmax + 1).total > (size_t)156 * 1024)
             return NOT_FUSED;
         if (flags && fused_lds(c->n, c->n_pad, true, false, true, 2 * (2 * c->xmax + 1)).total > (size_t)156 * 1024) return NOT_FUSED;
+        // a temperature per sweep: a ring of three tables, one per threshold slot, counted like the two above (no flags); and the
+        // 2 xmax + 1 entries a sweep rebuilds stay below an eighth of its n updates (at most a handful per producing thread: the
+        // workgroup has about 3 n / 32 of them).  Otherwise the call runs sweep by sweep.
+        if (sweep_temps && (8 * (2 * c->xmax + 1) > c->n ||
+                            fused_lds(c->n, c->n_pad, false, false, true, 3 * (2 * c->xmax + 1)).total > (size_t)156 * 1024))
+            return NOT_FUSED;
         return ARITH_F64;
     }
     // real couplings or fields: opt-in (nlmc_set_fused_f64_real), plans with the fp64 value plane, no tables (the f32 mode's LDS);
-    // k_rounds_fused has no such variant
-    if (!c->f64_real || via == Via::rounds || (slot >= 0 && !c->fz[slot].has_val)) return NOT_FUSED;
+    // k_rounds_fused has no such variant.  One temperature per chain only: with a temperature per sweep the real-valued output variant
+    // was measured at 0.69-0.74x of the sweep-by-sweep kernel (anneals of 10^3 sweeps, DESIGN.md section 2: measured and rejected)
+    if (!c->f64_real || sweep_temps || via == Via::rounds || (slot >= 0 && !c->fz[slot].has_val)) return NOT_FUSED;
     return ARITH_R64;
 }
 
@@ -707,7 +718,8 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
     const bool real = arith == ARITH_R64;
     if (real && !P.has_val) return fail(c, NLMC_ERR_STATE, "run_fused: the plan has no fp64 value plane");
     // per-sweep outputs: three snapshot slots in LDS when they fit beside the threshold tables, in global memory otherwise
-    const int kt = arith == ARITH_F64 ? (c->has_flags ? 2 : 1) * (2 * c->xmax + 1) : 0;     // (phase flags: K0 and K1)
+    // (phase flags: K0 and K1; a temperature per sweep: one table per threshold slot)
+    const int kt = arith == ARITH_F64 ? (c->has_flags ? 2 : tab_ss != 0 ? 3 : 1) * (2 * c->xmax + 1) : 0;
     const bool snap_lds = outs && fused_lds(c->n, c->n_pad, c->has_flags, true, P.fmt == NLMC_FMT_ADDR, kt).total <= (size_t)150 * 1024;
     const FusedLds L = fused_lds(c->n, c->n_pad, c->has_flags, snap_lds, P.fmt == NLMC_FMT_ADDR, kt);
     if (outs && !snap_lds) HIP_TRY(c, c->snap_g.reserve((size_t)R * (3 * (size_t)c->n_pad + 16)));

@@ -1656,7 +1656,7 @@ __device__ __forceinline__ float4 thresholds4(const u32x4 &r)
 // spread evenly over that range of levels: integer multiplies are slow on this chip and a level lasts as long as its
 // slowest wave.  The state is a set of LOCAL variables of the function that runs the level loop (a struct handed
 // around by reference ended up in scratch memory: two global-memory round trips per level).
-struct FusedGenParams { uint32_t gc; int gtid, gnt, nblk, nj, Tn; };
+struct FusedGenParams { uint32_t gc; int gtid, gnt, nblk, nj, Tn; int row; };   // row: the chain's row of the temperature table
 // What changes from one planned window to the next (everything else of a launch is in SweepArgs): k_sweep_fused runs one window,
 // k_rounds_fused a run of consecutive ones.
 struct FusedWin {
@@ -1704,6 +1704,7 @@ __device__ __forceinline__ double quad_move_f64(double v)
    through the persistent kernel's argument pointer is not hoisted out of a condition -- 27 instructions and a scalar-memory
    wait per stage) */
 #define NLMC_GEN_STATE int g_u = 2, g_slot = 2, g_w0 = 0, g_wend = 0, g_wlen = 1, g_acc = 0, g_sidx = 0; u32x4 g_r{0u, 0u, 0u, 0u}; \
+    bool g_kpend = false;                                                                                               \
     const uint32_t g_seed_lo = a.seed_lo, g_seed_hi = a.seed_hi, g_sweep0 = W.sweep0; const int g_u_off = a.lds_u_off, g_u_stride = a.lds_u_stride; \
     const int32_t *const g_fsend = W.fsend;
 /* steps per call: Philox rounds 0-4 | rounds 5-9 | four logits + store  (fp64 mode: rounds 0-4 | rounds 5-9 + store of the four
@@ -1713,6 +1714,7 @@ __device__ __forceinline__ double quad_move_f64(double v)
     {                                                                                                                   \
         typedef const int32_t __attribute__((address_space(4))) *const_i32_;                                            \
         g_sidx = 0; g_acc = 0;                                                                                          \
+        g_kpend = g_swt && g_u < gp.Tn;                                                                                 \
         if (g_u < gp.Tn) {                                                                                              \
             const const_i32_ send_ = (const_i32_)(uintptr_t)g_fsend;                                                    \
             g_w0 = g_u >= 3 ? __builtin_amdgcn_readfirstlane(send_[g_u - 3]) : -1;                                      \
@@ -1744,8 +1746,25 @@ __device__ __forceinline__ double quad_move_f64(double v)
     }
 /* the NLMC_GEN_NSTEP * nj steps of a lane are spread EVENLY over the levels of the production window (an accumulator in
    the manner of a line-drawing algorithm): a level lasts as long as its slowest wave */
+/* g_swt (the fp64 mode's integer thresholds with a temperature per sweep): the K table of sweep g_u at that sweep's coefficient,
+   into the ring slot its uniforms go to, in the FIRST level of the production window -- the slot's previous sweep g_u - 3 ended in
+   the level before, and the Philox steps rarely fall on that level.  Entry i of the table is made by producing thread i, i + gnt,
+   ... with the arithmetic of the window's prologue, which makes the tables of the first two sweeps. */
+#define NLMC_GEN_KT(a, gp)                                                                                              \
+    {                                                                                                                   \
+        typedef unsigned __attribute__((address_space(3))) *lds_u32k_;                                                  \
+        const int xm_ = a.f64_xmax, ne_ = 2 * xm_ + 1;                                                                  \
+        const double cb_ = a.tab[(size_t)gp.row * a.tab_cs + (size_t)g_u * a.tab_ss];       /* (g_u < Tn: g_kpend) */  \
+        const lds_u32k_ kt_ = (lds_u32k_)(uintptr_t)(unsigned)(a.lds_kt_off + 4 * g_slot * ne_);                        \
+        for (int i_ = gp.gtid; i_ < ne_; i_ += gp.gnt) {                                                                \
+            const unsigned long long K_ = accept_count_spec(cb_ * ((double)(i_ - xm_) * a.qinv64));                     \
+            kt_[i_] = (unsigned)(K_ >> 26);                                                                             \
+            kt_[3 * ne_ + i_] = (unsigned)(K_ & 0x3FFFFFFull);                                                          \
+        }                                                                                                               \
+    }
 #define NLMC_GEN(a, gp, l)                                                                                              \
     if (!(NLMC_GEN_DBG_OFF_COND) && (l) > g_w0) {                                                                       \
+        if (g_swt && g_kpend) { NLMC_GEN_KT(a, gp) g_kpend = false; }                                                   \
         g_acc += NLMC_GEN_NSTEP * gp.nj;                                                                                \
         while (g_acc >= g_wlen) { g_acc -= g_wlen; if (g_sidx < NLMC_GEN_NSTEP * gp.nj) NLMC_GEN_STEP(a, gp) }          \
         if (__builtin_expect((l) == g_wend, 0)) {                                                                       \
@@ -1769,12 +1788,19 @@ __device__ __forceinline__ double quad_move_f64(double v)
 // FLAGS with F64 (NMC phases in the fp64 mode, oracle/nlo.c: nlo_sweeps_philox(use_f64=1, flags)): a frozen row (flag 2 or 3) keeps
 // its spin and adds no energy; a scaled row (flag 1) takes cb_run[2t+1].  The integer-threshold variant reads a second K table, built
 // at cb1 beside the first one (Khi0 | Khi1 | Klo0 | Klo1); the real-valued one takes z = cb1 x.
-template <bool DIAG, bool FLAGS, bool PAIR, bool GEN, int FMT, bool OUT = false, bool F64 = false, bool R64 = false>
+//
+// SWT (OUT, F64, no FLAGS, no R64): the fp64 mode's integer thresholds with a temperature per sweep (tab_ss != 0: an anneal).  A
+// chunk may mix the two live sweeps, so the threshold is picked per item like the f32 coefficients cqo / cqn: an update reads the K
+// table of its item's slot in a ring of three (Khi[3] | Klo[3], built at each sweep's cb: the first two by the window's prologue, the
+// others by NLMC_GEN_KT), in the rare exact path too.  The real-valued variant has no such loop: its anneal measured slower than sweep
+// by sweep and runs there (fused_route).
+template <bool DIAG, bool FLAGS, bool PAIR, bool GEN, int FMT, bool OUT = false, bool F64 = false, bool R64 = false, bool SWT = false>
 __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin &W, unsigned char *lds_raw, int wv, int lane, int nl, float cq0,
                                              float cq1, long long &e_loc, const FusedGenParams gp, double cb64 = 0.0, double cb64_1 = 0.0)
 {
-    constexpr bool g_f64 = F64;
+    constexpr bool g_f64 = F64, g_swt = SWT;
     static_assert(!R64 || F64, "the real-valued fp64 variant rides on the fp64 uniform tables");
+    static_assert(!SWT || (OUT && F64 && !FLAGS && !R64), "a temperature per sweep in the fp64 mode: integer thresholds, output variant, no phase flags");
     NLMC_GEN_STATE
     NLMC_GEN_ARM(a, gp)
     typedef const int32_t __attribute__((address_space(4))) *const_i32o;
@@ -1810,7 +1836,10 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
     // (k_ne4 bytes further), and the low words follow all high words (k_lo bytes from a Khi entry to its Klo entry)
     unsigned v_kt0 = (unsigned)(a.lds_kt_off + 4 * a.f64_xmax), v_tie = a.f64_tie_mask;
     if (F64) asm volatile("" : "+v"(v_kt0), "+v"(v_tie));
-    const unsigned k_ne4 = 4u * (unsigned)(2 * a.f64_xmax + 1), k_lo = FLAGS ? 2u * k_ne4 : k_ne4;
+    const unsigned k_ne4 = 4u * (unsigned)(2 * a.f64_xmax + 1), k_lo = SWT ? 3u * k_ne4 : FLAGS ? 2u * k_ne4 : k_ne4;
+    // SWT: LDS address of Khi[X = 0] in the ring slot of the older / the newer live sweep
+    const unsigned k_base = (unsigned)(a.lds_kt_off + 4 * a.f64_xmax);
+    unsigned k_old = k_base, k_new = k_base + k_ne4;
     // real-valued fp64 variant: 2^escale (energy deltas of fixed_delta_slow), every update to the exact path (tie mask 0)
     const double v_esc = __longlong_as_double((long long)(1023 + a.escale) << 52);
     const bool r_all_exact = a.f64_tie_mask == 0u;
@@ -2042,7 +2071,8 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
         bool up64 = false;
         if (F64 && !R64) {
             const unsigned hk = __float_as_uint(wk);
-            const unsigned kaddr = ((unsigned)X << 2) + v_kt0 + ((FLAGS && f == 1u) ? k_ne4 : 0u);     // (scaled row: K1)
+            const unsigned kaddr = SWT ? ((unsigned)X << 2) + ((((unsigned)hx >> 16) - o_lo < (unsigned)o_npad) ? k_old : k_new)   // (the item's slot)
+                                       : ((unsigned)X << 2) + v_kt0 + ((FLAGS && f == 1u) ? k_ne4 : 0u);         // (scaled row: K1)
 #ifdef NLMC_DEBUG_KNOBS
             // 16384: timing experiment -- no dependent table read behind the field sum (wrong results)
             const unsigned kh = (a.dbg_flags & 16384) ? (unsigned)(X * 3000000 + 0x4000000) : *(lds_u32)(uintptr_t)kaddr;
@@ -2134,6 +2164,7 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
         o_end = o_t < a.n_sweeps ? ((const_i32o)(uintptr_t)W.fsend)[o_t] : 0x7FFFFFFF;                                   \
         cqo0 = cqn0; cqo1 = cqn1;                                                                                       \
         cqn0 = NLMC_OCQ(o_t + 1, 0); cqn1 = NLMC_OCQ(o_t + 1, 1);                                                       \
+        if (SWT) { k_old = k_new; k_new = k_base + (unsigned)((o_t + 1) % 3) * k_ne4; }                                 \
     }
 
     // Order inside a level: update first, THEN loads.  The vector-memory path of the CU is the scarcest resource of
@@ -2229,6 +2260,10 @@ template <bool DIAG, bool FLAGS, bool OUT, int FMT, bool F64, bool R64 = false>
 __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin &W, unsigned char *lds_raw, int row, uint32_t gc, long long &e_loc)
 {
     constexpr bool g_f64 = F64;
+    // a temperature per sweep in the fp64 mode (fused_levels<.., SWT>, its ring of K tables): integer thresholds, the output variant
+    // without phase flags
+    constexpr bool can_swt = OUT && F64 && !FLAGS && !R64;
+    const bool g_swt = can_swt && a.tab_ss != 0, swt = g_swt;
     const int n = a.g.n, tid = threadIdx.x, nt = blockDim.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     float *ur = reinterpret_cast<float *>(lds_raw + a.lds_u_off);
@@ -2258,15 +2293,18 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
         // K(X) for every field value a row can reach, at this chain's temperature: z = cb (X 2^-qs) as in update_spin<double>.
         // The trailing lanes of the workgroup take it (they have one Philox call less than the others above).  With FLAGS a
         // second table K1 at cb1 (the scaled rows): Khi0 | Khi1 | Klo0 | Klo1.
-        const int ne = 2 * a.f64_xmax + 1, nk = FLAGS ? 2 : 1;
+        // A temperature per sweep (g_swt; no FLAGS): a ring of three tables Khi[3] | Klo[3], one per threshold slot, each at the cb
+        // of the sweep that holds the slot -- here those of the window's first two sweeps, the others in the level loop (NLMC_GEN_KT).
+        const int ne = 2 * a.f64_xmax + 1, nk = FLAGS ? 2 : g_swt ? min(2, Tn) : 1, nslot = g_swt ? 3 : nk;
+        const int jstride = g_swt ? a.tab_ss : 1;
         unsigned *kt = reinterpret_cast<unsigned *>(lds_raw + a.lds_kt_off);
         for (int i = nt - 1 - tid; i < nk * ne; i += nt) {
             const int j = i >= ne ? 1 : 0, x = i - j * ne;
-            const double cb = a.tab[(size_t)row * a.tab_cs + j];
+            const double cb = a.tab[(size_t)row * a.tab_cs + (size_t)j * jstride];
             const double xf = (double)(x - a.f64_xmax) * a.qinv64;
             const unsigned long long K = accept_count_spec(cb * xf);
             kt[i] = (unsigned)(K >> 26);
-            kt[nk * ne + i] = (unsigned)(K & 0x3FFFFFFull);
+            kt[nslot * ne + i] = (unsigned)(K & 0x3FFFFFFull);
         }
     }
     __syncthreads();
@@ -2275,7 +2313,7 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
     // calls per sweep of THIS wave: block b = (tid - g0) + call * gnt must lie below nblk for at least one of its lanes
     // (wave-uniform; the waves at the end of the producing range do one call less when gnt does not divide nblk)
     const int gwave0 = __builtin_amdgcn_readfirstlane((tid - g0) & ~63);
-    const FusedGenParams gp{gc, tid - g0, gnt, nblk, max(0, (nblk - gwave0 + gnt - 1) / gnt), Tn};
+    const FusedGenParams gp{gc, tid - g0, gnt, nblk, max(0, (nblk - gwave0 + gnt - 1) / gnt), Tn, row};
     const bool is_gen = tid >= g0;
     // The producing waves are the youngest of their SIMDs and would get the issue slots the older worker waves leave
     // over (measured: a 150-instruction call stretched to ~3000 cycles while the workers waited at the barrier).
@@ -2283,9 +2321,18 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
     if (wv < a.f_workers) {
         const bool role_long = wv < W.hi_max;           // chunks that may hold lane PAIRS (rows longer than 8 entries) come first
         const int variant = (role_long ? 2 : 0) + (is_gen ? 1 : 0);
-#define NLMC_FL(P, G) fused_levels<DIAG, FLAGS, P, G, FMT, OUT, F64, R64>(a, W, lds_raw, wv, lane, nl, cq0, cq1, e_loc, gp, cb64, cb64_1)
-        switch (variant) { case 0: NLMC_FL(false, false); break; case 1: NLMC_FL(false, true); break;
-                           case 2: NLMC_FL(true, false); break; default: NLMC_FL(true, true); break; }
+#define NLMC_FL(P, G, S) fused_levels<DIAG, FLAGS, P, G, FMT, OUT, F64, R64, S>(a, W, lds_raw, wv, lane, nl, cq0, cq1, e_loc, gp, cb64, cb64_1)
+        bool done = false;
+        if constexpr (can_swt) {        // (a level loop of its own: the one of calls with one temperature per chain stays as it is)
+            if (swt) {
+                switch (variant) { case 0: NLMC_FL(false, false, true); break; case 1: NLMC_FL(false, true, true); break;
+                                   case 2: NLMC_FL(true, false, true); break; default: NLMC_FL(true, true, true); break; }
+                done = true;
+            }
+        }
+        if (!done)
+            switch (variant) { case 0: NLMC_FL(false, false, false); break; case 1: NLMC_FL(false, true, false); break;
+                               case 2: NLMC_FL(true, false, false); break; default: NLMC_FL(true, true, false); break; }
 #undef NLMC_FL
     } else {
         // Waves without schedule items: their share of the thresholds, and they pull the NEXT window's schedule towards

@@ -242,7 +242,8 @@ class Engine:
         window outside what the fused kernels take) run sweep by sweep -- same bits.  Outputs are stitched together exactly
         as one call would return them (trace, energies, first argmin).  want_recorded_energy: o["energy_recorded"] = fp64
         energies of the recorded configurations [rows, n_recorded], computed on the device copy of each piece's trace.
-        precision: "f32" or "f64" (the fp64 mode takes the fused windows where fused_modes says so, sweep by sweep otherwise)."""
+        precision: "f32" or "f64" (the fp64 mode takes the fused windows where fused_modes says so -- with an [R, S] table, a
+        temperature per sweep, when no phase flags are in force and the instance is dyadic -- and runs sweep by sweep otherwise; fused_last_call tells)."""
         S = int(n_sweeps)
         T = fused_window(S) if window is None else int(window)
         budget = self.FUSED_PLAN_BUDGET if budget_bytes is None else int(budget_bytes)

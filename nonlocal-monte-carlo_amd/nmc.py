@@ -18,7 +18,8 @@ class NMC(Common):
         """`precision` (additive keyword, rng="philox" only): "f32" (default) -- at N >= 256 the device-RNG sweeps use the
         throughput mode's fixed-point couplings and logistic thresholds; "f64" -- the reference's arithmetic (fp64 field, 53-bit
         uniform) for MCMC(), the anneal and every NMC phase of run() / NMC_subroutine() / run_restarts(), on fused windows for
-        real couplings too (Engine.set_fused_f64_real)."""
+        real couplings too (Engine.set_fused_f64_real); the anneal, a temperature per sweep, on fused windows for dyadic instances
+        (+-J, integer) and sweep by sweep for real-valued ones."""
         if precision not in ("f32", "f64"):
             raise ValueError("precision must be 'f32' or 'f64'")
         super().__init__(J, h, rng=rng, seed=seed, device=device, lbp=lbp)
