@@ -56,6 +56,8 @@ def lib():
         L.nlo_exp2_f32.argtypes = [ctypes.c_float]
         L.nlo_exp2_f64.restype = ctypes.c_double
         L.nlo_exp2_f64.argtypes = [ctypes.c_double]
+        L.nlo_accept_count_f64.restype = ctypes.c_uint64
+        L.nlo_accept_count_f64.argtypes = [ctypes.c_double]
         L.nlo_field_scale.restype = ctypes.c_int
         L.nlo_field_scale.argtypes = [ctypes.c_int, _i32p, _f64p, _f64p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
         L.nlo_threshold_f32.restype = ctypes.c_float
@@ -151,6 +153,16 @@ def field_scale(csr, h):
 def threshold(r):
     """W(r) ~= log2((1-u)/u), u = (r + 1/2) / 2^32: the logistic threshold of the "f32" throughput mode."""
     return float(lib().nlo_threshold_f32(int(r) & 0xFFFFFFFF))
+
+
+def exp2_f64(z):
+    """2^z of the fp64 mode (exp2_spec_f64: clamped to [-1000, 1000], degree-13 Horner)."""
+    return float(lib().nlo_exp2_f64(float(z)))
+
+
+def accept_count_f64(z):
+    """Number K of the 2^53 uniforms u = m 2^-53 with fma(u, 2^z, u) < 1: the fp64 mode sets s' = +1 with probability K 2^-53."""
+    return int(lib().nlo_accept_count_f64(float(z)))
 
 
 def threshold_count(z, r0=0, r1=1 << 32, stride=1):

@@ -20,7 +20,9 @@
  *                       field, logistic threshold drawn from 32 random bits; "f64": fp64 field, base-2 logistic test
  *                       on a 53-bit uniform).  The HIP kernels run a level-parallel schedule that must reproduce it
  *                       bit for bit.  Its LAW is tied to the reference by tests/test_law_cpu.py (exhaustive check of
- *                       the threshold distribution) and by the reference-derived statistics under tests/golden/.
+ *                       the threshold distribution, the fp64 acceptance count against exact arithmetic, calibration of
+ *                       its traces against the heat-bath law), by tests/test_gpu_law.py (the same calibration of every
+ *                       sweep route's traces) and by the reference-derived statistics under tests/golden/.
  */
 #include <math.h>
 #include <stdint.h>
@@ -187,6 +189,22 @@ static inline double exp2_spec_f64(double z)
 
 float nlo_exp2_f32(float z) { return exp2_spec_f32(z); }
 double nlo_exp2_f64(double z) { return exp2_spec_f64(z); }
+
+/* Number K of the 2^53 uniforms u = m / 2^53 that the fp64 mode accepts at z: fma(u, exp2_spec(z), u) < 1 is decreasing in m,
+ * so K is the first m that fails; found by plain bisection on the test itself (53 halvings of [0, 2^53], no bracket estimate).
+ * tests/test_law_cpu.py compares it with the closed form ceil((2^53 - 1/2) / (1 + E)). */
+uint64_t nlo_accept_count_f64(double z)
+{
+    const double ee = exp2_spec_f64(z);
+    uint64_t lo = 0, hi = (uint64_t)1 << 53;  /* m = lo is accepted (u = 0), m = hi is past the lattice */
+    for (int i = 0; i < 53; ++i) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        const double u = (double)mid / 9007199254740992.0;
+        if (fma(u, ee, u) < 1.0) lo = mid;
+        else hi = mid;
+    }
+    return hi;
+}
 
 /* ------------------------------------------------------------------------------------------------ */
 /* "f32" throughput mode: fixed-point couplings and the logistic threshold                            */
