@@ -258,25 +258,34 @@ int nlmc_pt_swap_philox_collective(nlmc_ctx *ctx, uint32_t round, uint64_t seed,
  * seed and n_pairs are left with the parallel acceptance test.  Results are identical with or without a plan. */
 int nlmc_pt_plan(nlmc_ctx *ctx, uint32_t round0, int n_rounds, uint64_t seed, int n_pairs);
 /* n_rounds whole rounds -- sweeps_per_round sweeps of every chain at its ladder temperature, then the swap round of
- * nlmc_pt_swap_philox -- in ONE cooperative launch (k_rounds_fused): the chains stay in LDS from round to round, between two
- * rounds every chain publishes its tracked energy, all workgroups of the launch meet once (bounded wait), and the two chains of a
- * selected pair each evaluate the identical decision.  Bit-identical to nlmc_sweep_philox(beta = NULL) + nlmc_pt_swap_philox round
- * by round (the rounds' decisions go to the device-side swap log when one is open); what a launch per round pays again and again
- * (kernel launches, spins HBM -> LDS -> HBM) is paid once per call.  Needs: a fused-window plan of ONE window per round covering
- * sweeps [sweep0, sweep0 + n_rounds sweeps_per_round) (nlmc_plan_philox_fused, window == sweeps_per_round), the pair selections of
- * rounds [round0, round0 + n_rounds) planned (nlmc_pt_plan, same seed and n_pairs), a context of whole ladders without a
- * communicator, no phase flags / chain subset, one workgroup per chain resident at once (n_chains <= CUs for large n).
- * NLMC_ERR_UNSUPPORTED (nothing was run) when a condition is not met: the caller runs the rounds one by one.  Asynchronous: a grid
- * wait that times out is reported by nlmc_pt_check / nlmc_pt_log_read (NLMC_ERR_HIP). */
+ * nlmc_pt_swap_philox -- in cooperative launches of k_rounds_fused (one per 1024 rounds): the chains stay in LDS from round to
+ * round; between two rounds every chain publishes its tracked energy in a record of (round, ladder, slot), a chain whose slot is in
+ * a selected pair waits for the partner slot's record of the same round (bounded wait) and both take the identical decision, a
+ * chain in no pair waits for nobody; the slot maps are written at the end of a launch.  Bit-identical to nlmc_sweep_philox(beta =
+ * NULL) + nlmc_pt_swap_philox round by round (the rounds' decisions go to the device-side swap log when one is open); what a launch
+ * per round pays again and again (kernel launches, spins HBM -> LDS -> HBM, the random tables of a round's first two sweeps, the
+ * fp64 mode's threshold tables of a chain that kept its slot) is paid once per launch.  Needs: a fused-window plan of ONE window per
+ * round covering sweeps [sweep0, sweep0 + n_rounds sweeps_per_round) (nlmc_plan_philox_fused, window == sweeps_per_round), the pair
+ * selections of rounds [round0, round0 + n_rounds) planned (nlmc_pt_plan, same seed and n_pairs), a context of whole ladders without
+ * a communicator, no phase flags / chain subset, one workgroup per chain resident at once (n_chains <= CUs for large n).
+ * NLMC_ERR_UNSUPPORTED (nothing was run) when a condition is not met: the caller runs the rounds one by one.  Asynchronous: a wait
+ * that times out is reported by nlmc_pt_check / nlmc_pt_log_read (NLMC_ERR_HIP). */
 int nlmc_pt_rounds_fused(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0,
                          uint64_t seed, int n_pairs);
-/* The same n_rounds rounds as n_rounds sweep launches + ONE swap launch: the sweep launch of round i decides the swap of round i - 1
- * in its prologue (every chain looks up its pair, reads its partner's energy as the previous launch published it, takes k_pt_swap's
- * decision and updates its own entries of the slot maps; wave 0 does it while the other waves load the spins), the last round's
- * swap is the ordinary kernel.  Same conditions and the same NLMC_ERR_UNSUPPORTED convention as nlmc_pt_rounds_fused (n_pairs >= 1);
- * bit-identical to nlmc_sweep_philox + nlmc_pt_swap_philox round by round, one kernel launch per round less. */
+/* The same n_rounds rounds on the route that fits the context (n_pairs >= 1, no tracked minimum; otherwise nlmc_pt_rounds_fused's
+ * conditions and NLMC_ERR_UNSUPPORTED convention, residency apart).  Where k_rounds_fused can hold all chains at once the rounds run
+ * inside its launches as above (NLMC_NO_PERSISTENT=1 at nlmc_create switches that off).  Otherwise n_rounds sweep launches + ONE
+ * swap launch: the sweep launch of round i decides the swap of round i - 1 in its prologue (every chain looks up its pair, reads its
+ * partner's energy as the previous launch published it, takes k_pt_swap's decision and updates its own entries of the slot maps;
+ * wave 0 does it while the other waves load the spins), the last round's swap is the ordinary kernel.  Bit-identical to
+ * nlmc_sweep_philox + nlmc_pt_swap_philox round by round on either route. */
 int nlmc_pt_rounds_deferred(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0,
                             uint64_t seed, int n_pairs);
+/* The route the most recent nlmc_pt_rounds_fused / nlmc_pt_rounds_deferred call that ran took: NLMC_ROUNDS_IN_LAUNCH (the rounds
+ * inside k_rounds_fused launches), NLMC_ROUNDS_LAUNCH_PER_ROUND, or 0 (no such call yet). */
+#define NLMC_ROUNDS_IN_LAUNCH 1
+#define NLMC_ROUNDS_LAUNCH_PER_ROUND 2
+int nlmc_pt_rounds_route(nlmc_ctx *ctx);
 /* Device-side swap log of rounds [round0, round0 + n_rounds): rounds of nlmc_pt_swap_philox(_host) called WITHOUT host
  * output pointers keep their pairs and decisions on the device; nlmc_pt_log_read copies the whole log in one go
  * (out_pairs [n_rounds][n_ladders][n_pairs][2], -1 where a round did not run; out_accepted [n_rounds][n_ladders][n_pairs])

@@ -73,7 +73,7 @@ struct Knobs {
     bool no_bank_aware = false;      // NLMC_NO_BANK_AWARE: the fused planner does not place items by LDS bank
     bool fz_stats = false;           // NLMC_FZ_STATS: the fused planner prints the phase cycle counts of window 0 on stderr
     unsigned tie_mask = 0xFFFFFFFFu; // NLMC_F64_TIE_MASK: high-word mask of the fp64 fused kernels' exact-path test (test knob)
-    bool no_persistent = false;      // NLMC_NO_PERSISTENT: nlmc_pt_rounds_fused refuses
+    bool no_persistent = false;      // NLMC_NO_PERSISTENT: nlmc_pt_rounds_fused refuses, nlmc_pt_rounds_deferred launches per round
     bool no_deferred = false;        // NLMC_NO_DEFERRED: nlmc_pt_rounds_deferred refuses
     int lbp_group = 0;               // NLMC_LBP_GROUP: workgroups per loopy-BP problem (1..8; 0: by size)
     int lbp_poll_budget = 0;         // NLMC_LBP_POLL_BUDGET: polls of the loopy-BP group barrier (0: the default; test knob)
@@ -300,10 +300,15 @@ struct nlmc_ctx {
     DevBuf<long long> apt_e_all;                     // [world][K][ladder_len]
     DevBuf<int8_t> apt_send, apt_recv;               // [2][K][n_pad]
     DevBuf<int32_t> apt_bd;                          // [2][K]
-    DevBuf<double> rounds_ebuf;                      // k_rounds_fused: [2][n_chains_global] published energies
-    DevBuf<unsigned> rounds_bar;                     // its arrival counter
+    DevBuf<double> rounds_ebuf;                      // nlmc_pt_rounds_deferred: [2][n_chains_global] published energies
+    DevBuf<unsigned long long> rounds_rec;           // k_rounds_fused: [rounds of a launch][n_chains_global] energies by slot
+    int rounds_route = 0;                            // nlmc_pt_rounds_route
+    const void *rounds_res_kfun = nullptr;           // the last residency question (rounds_resident) and its answer
+    size_t rounds_res_lds = 0;
+    int rounds_res_nt = 0;
+    bool rounds_res_yes = false;
     DevBuf<unsigned char> rounds_args;               // its argument structs (read through constant-memory pointers), 2 slots
-    std::vector<unsigned char> rounds_args_host[2];  // ... as uploaded (kept until the next call of the same slot)
+    std::vector<unsigned char> rounds_args_host[2];  // ... as uploaded (pageable memory: staged by hipMemcpyAsync before it returns)
     int rounds_args_slot = 0;
     void *comm = nullptr;              // RCCL communicator of the sharded tempering (nlmc_comm_init): the per-round all-gather of
     int comm_world = 0, comm_rank = 0; // the energies is issued by the library on the kernels' own stream
@@ -1399,7 +1404,7 @@ void nlmc_destroy(nlmc_ctx *c)
     c->lbp_bar.release(); c->lbp_part.release();
     c->lbp_hm.release(); c->lbp_tot.release(); c->lbp_mag.release(); c->lbp_mag_all.release();
     c->pt_tab.release(); c->pt_beta.release(); c->pt_energies_all.release();
-    c->rounds_ebuf.release(); c->rounds_bar.release(); c->rounds_args.release(); c->seed_snap.release();
+    c->rounds_ebuf.release(); c->rounds_rec.release(); c->rounds_args.release(); c->seed_snap.release();
     c->apt_beta.release(); c->apt_e_all.release(); c->apt_send.release(); c->apt_recv.release(); c->apt_bd.release();
     c->slot_of_chain.release(); c->chain_of_slot.release(); c->pt_pairs.release(); c->pt_status.release();
     c->pt_acc.release(); c->pt_log_acc.release(); c->pt_log_pairs.release(); c->pt_plan_pairs.release(); c->pt_plan_ok.release(); c->icm_label.release(); c->icm_info.release(); c->icm_pairs.release();
@@ -2398,7 +2403,118 @@ int rounds_check(nlmc_ctx *c, Via via, int precision, int n_rounds, int T, uint3
     return NLMC_OK;
 }
 
-// n_rounds rounds (sweeps_per_round sweeps at the ladder temperatures + the swap round) in ONE cooperative launch (k_rounds_fused).
+// Can k_rounds_fused run this context's chains (all workgroups resident at once: they wait for each other)?  NLMC_OK with the answer
+// in `yes`.  Asked of the runtime, which also refuses such a launch.
+// The answer is kept per (kernel, block, LDS): the number of chains of a context does not change.
+static int rounds_resident(nlmc_ctx *c, const void *kfun, int nt, size_t lds, bool &yes)
+{
+    if (c->rounds_res_kfun != kfun || c->rounds_res_nt != nt || c->rounds_res_lds != lds) {
+        int per_cu = 0, n_cu = 0;
+        HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfun, nt, lds));
+        HIP_TRY(c, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+        c->rounds_res_kfun = kfun; c->rounds_res_nt = nt; c->rounds_res_lds = lds;
+        c->rounds_res_yes = (long long)per_cu * n_cu >= c->n_chains;
+    }
+    yes = c->rounds_res_yes;
+    return NLMC_OK;
+}
+
+// n_rounds rounds (T sweeps at the ladder temperatures + the swap round) in cooperative launches of k_rounds_fused, at most
+// NLMC_ROUNDS_PER_LAUNCH rounds each (the rows of the record array).  The checks of rounds_check have passed.  `resident` = false
+// (and nothing queued) when the device does not hold all the chains' workgroups at once.
+static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs,
+                            bool &resident)
+{
+    const int L = c->ladder_len;
+    const nlmc_ctx::FusedPlan &P = c->fz[fslot];
+    const int kt = arith == ARITH_F64 ? 2 * c->xmax + 1 : 0;
+    const FusedLds Lds = fused_lds(c->n, c->n_pad, false, false, P.fmt == NLMC_FMT_ADDR, kt);
+    const void *kfun = rounds_kernel(c->has_diag, P.fmt, arith);
+    if (!kfun) return fail(c, NLMC_ERR_STATE, "k_rounds_fused: no kernel for this arithmetic");
+    { int rc = ensure_lds(c, kfun, Lds.total); if (rc) return rc; }
+    const int nt = fused_block(c);
+    { int rc = rounds_resident(c, kfun, nt, Lds.total, resident); if (rc || !resident) return rc; }
+    const int nl = c->n_chains_global / L;
+    const size_t G = (size_t)c->n_chains_global, PS = (size_t)P.pstride;
+    HIP_TRY(c, c->rounds_rec.reserve((size_t)std::min(n_rounds, NLMC_ROUNDS_PER_LAUNCH) * G));
+    { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
+    const bool log = c->pt_log_on && c->pt_log_npairs == n_pairs && n_pairs > 0 && round0 >= c->pt_log_round0 &&
+                     (uint64_t)round0 + (uint64_t)n_rounds <= (uint64_t)c->pt_log_round0 + (uint64_t)c->pt_log_rounds;
+    // the two argument structs travel through device memory (k_rounds_fused reads them through laundered constant-memory pointers);
+    // two device slots written in stream order, so that a launch still running never sees the next one's arguments.  The host
+    // copies are pageable memory: hipMemcpyAsync has staged such a source when it returns, so a slot's host buffer may be filled
+    // again by the chunk after next of the same call.
+    const size_t a_bytes = (sizeof(SweepArgs) + 255) & ~(size_t)255, slot_bytes = a_bytes + ((sizeof(RoundsArgs) + 255) & ~(size_t)255);
+    HIP_TRY(c, c->rounds_args.reserve(2 * slot_bytes));
+    for (int at = 0; at < n_rounds; at += NLMC_ROUNDS_PER_LAUNCH) {
+        const int k = std::min(NLMC_ROUNDS_PER_LAUNCH, n_rounds - at);
+        const uint32_t s0 = sweep0 + (uint32_t)at * (uint32_t)T, r0 = round0 + (uint32_t)at;
+        const int w0 = (int)((s0 - P.sweep0) / (uint32_t)T);
+        // no record yet: all ones, a NaN that no energy equals (0.0 is a legal energy)
+        HIP_TRY(c, hipMemsetAsync(c->rounds_rec.p, 0xFF, sizeof(unsigned long long) * (size_t)k * G, c->stream));
+        SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
+        a.fz_pstride = P.pstride; a.fz_fmt = P.fmt;
+        a.f_workers = P.workers; a.f_gen0 = P.gen0; a.f_gen_prio = c->knobs.no_prio ? 0 : 1;
+#ifdef NLMC_DEBUG_KNOBS
+        a.dbg_flags = c->knobs.dbg_flags;
+#endif
+        a.trace_sweeps = T; a.rec_stride = 1;
+        a.lds_neg_off = Lds.neg_off; a.lds_flags_off = Lds.flags_off; a.lds_u_off = Lds.u_off; a.lds_u_stride = Lds.u_bytes; a.lds_red_off = Lds.red_off;
+        a.lds_snap_off = Lds.snap_off; a.lds_kt_off = Lds.kt_off; a.f64_xmax = c->xmax; a.f64_tie_mask = c->knobs.tie_mask;
+#ifdef NLMC_STAMPS
+        HIP_TRY(c, c->dbg.reserve((size_t)c->n_chains * 16 * 8 + 96));
+        HIP_TRY(c, hipMemsetAsync(c->dbg.p, 0, ((size_t)c->n_chains * 16 * 8 + 96) * sizeof(long long), c->stream));
+        a.dbg = c->dbg.p;
+#endif
+        RoundsArgs q{};
+        q.n_rounds = k; q.n_windows_avail = c->knobs.no_warm ? k : P.windows - w0;
+        q.loff = P.loff.p + (size_t)w0 * (NLMC_LCAP + 1); q.nlev = P.nlev.p + w0; q.himax = P.himax.p + w0; q.send = P.send.p + (size_t)w0 * T;
+        q.npos = P.npos.p + w0; q.head = P.head.p + (size_t)w0 * PS; q.ell = P.ell.p + (size_t)w0 * PS * NLMC_FZ_W;
+        q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = nl; q.round0 = r0;
+        q.plan_pairs = n_pairs > 0 ? c->pt_plan_pairs.p + (size_t)(r0 - c->pt_plan_round0) * nl * n_pairs * 2 : nullptr;
+        q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
+        q.rec = c->rounds_rec.p; q.status = c->pt_status.p;
+        q.timeout_ticks = 100000000ll * 20;                   // 20 s of the 100 MHz wall clock
+        if (log) {
+            const size_t r = r0 - c->pt_log_round0;
+            q.log_pairs = c->pt_log_pairs.p + r * (size_t)nl * n_pairs * 2;
+            q.log_acc = c->pt_log_acc.p + r * (size_t)nl * n_pairs;
+        }
+        // events around the launch while timings accumulate: its time counts for its k rounds
+        const bool timed = c->ev_accumulate;
+        hipEvent_t e0 = nullptr, e2 = nullptr;
+        if (timed) {
+            e0 = next_event(c);
+            hipEvent_t e1 = next_event(c);
+            e2 = next_event(c);
+            if (!e0 || !e1 || !e2) return fail(c, NLMC_ERR_HIP, "hipEventCreate failed");
+            tag_triple(c, 1);
+            HIP_TRY(c, hipEventRecord(e0, c->stream));
+        }
+        const int as = c->rounds_args_slot ^= 1;
+        std::vector<unsigned char> &hb = c->rounds_args_host[as];
+        hb.assign(slot_bytes, 0);
+        std::memcpy(hb.data(), &a, sizeof(SweepArgs));
+        std::memcpy(hb.data() + a_bytes, &q, sizeof(RoundsArgs));
+        unsigned char *dargs = c->rounds_args.p + (size_t)as * slot_bytes;
+        HIP_TRY(c, hipMemcpyAsync(dargs, hb.data(), slot_bytes, hipMemcpyHostToDevice, c->stream));
+        const SweepArgs *ap_dev = reinterpret_cast<const SweepArgs *>(dargs);
+        const RoundsArgs *qp_dev = reinterpret_cast<const RoundsArgs *>(dargs + a_bytes);
+        void *kargs[] = {&ap_dev, &qp_dev};
+        HIP_TRY(c, hipLaunchCooperativeKernel(kfun, dim3(c->n_chains), dim3(nt), kargs, (unsigned)Lds.total, c->stream));
+        HIP_TRY(c, hipGetLastError());
+        if (timed) { HIP_TRY(c, hipEventRecord(e2, c->stream)); c->launches_timed += k; }
+        c->launches_sweep += k;
+        c->launches_total += k;
+        c->stat_fused_window = w0 + k - 1;
+    }
+    c->stat_fused_slot = fslot;
+    c->sub_dirty = true;
+    c->rounds_route = NLMC_ROUNDS_IN_LAUNCH;
+    return NLMC_OK;
+}
+
+// n_rounds rounds in cooperative launches of k_rounds_fused, whatever nlmc_pt_rounds_deferred would choose.
 int nlmc_pt_rounds_fused(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
                          int n_pairs)
 {
@@ -2406,85 +2522,16 @@ int nlmc_pt_rounds_fused(nlmc_ctx *c, int precision, int n_rounds, int sweeps_pe
     int fslot = -1, arith = NOT_FUSED;
     { int rc = rounds_check(c, Via::rounds, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs, fslot, arith); if (rc || fslot < 0) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
-    const int L = c->ladder_len, T = sweeps_per_round;
-    const nlmc_ctx::FusedPlan &P = c->fz[fslot];
-    const int kt = arith == ARITH_F64 ? 2 * c->xmax + 1 : 0;
-    const FusedLds Lds = fused_lds(c->n, c->n_pad, false, false, P.fmt == NLMC_FMT_ADDR, kt);
-    const void *kfun = rounds_kernel(c->has_diag, P.fmt, arith);
-    { int rc = ensure_lds(c, kfun, Lds.total); if (rc) return rc; }
-    const int nt = fused_block(c);
-    // every workgroup must be resident at once (they wait for each other): asked of the runtime, which also refuses the launch
-    int per_cu = 0, n_cu = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfun, nt, Lds.total));
-    HIP_TRY(c, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
-    if ((long long)per_cu * n_cu < c->n_chains)
+    bool resident = false;
+    int rc = rounds_in_launch(c, fslot, arith, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs, resident);
+    if (rc == NLMC_OK && !resident)
         return fail(c, NLMC_ERR_UNSUPPORTED, "nlmc_pt_rounds_fused: more chains than workgroups the device holds at once");
-    const int w0 = (int)((sweep0 - P.sweep0) / (uint32_t)T), nl = c->n_chains_global / L;
-    const size_t G = (size_t)c->n_chains_global, PS = (size_t)P.pstride;
-    HIP_TRY(c, c->rounds_ebuf.reserve(2 * G));
-    HIP_TRY(c, c->rounds_bar.reserve(1));
-    HIP_TRY(c, hipMemsetAsync(c->rounds_bar.p, 0, sizeof(unsigned), c->stream));
-    { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
-    SweepArgs a = sweep_args(c, sweep0, T, seed, c->pt_tab.p, 2, 0, true);
-    a.fz_pstride = P.pstride; a.fz_fmt = P.fmt;
-    a.f_workers = P.workers; a.f_gen0 = P.gen0; a.f_gen_prio = c->knobs.no_prio ? 0 : 1;
-#ifdef NLMC_DEBUG_KNOBS
-    a.dbg_flags = c->knobs.dbg_flags;
-#endif
-    a.trace_sweeps = T; a.rec_stride = 1;
-    a.lds_neg_off = Lds.neg_off; a.lds_flags_off = Lds.flags_off; a.lds_u_off = Lds.u_off; a.lds_u_stride = Lds.u_bytes; a.lds_red_off = Lds.red_off;
-    a.lds_snap_off = Lds.snap_off; a.lds_kt_off = Lds.kt_off; a.f64_xmax = c->xmax; a.f64_tie_mask = c->knobs.tie_mask;
-    RoundsArgs q{};
-    q.n_rounds = n_rounds; q.n_windows_avail = c->knobs.no_warm ? n_rounds : P.windows - w0;
-    q.loff = P.loff.p + (size_t)w0 * (NLMC_LCAP + 1); q.nlev = P.nlev.p + w0; q.himax = P.himax.p + w0; q.send = P.send.p + (size_t)w0 * T;
-    q.npos = P.npos.p + w0; q.head = P.head.p + (size_t)w0 * PS; q.ell = P.ell.p + (size_t)w0 * PS * NLMC_FZ_W;
-    q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = nl; q.round0 = round0;
-    q.plan_pairs = n_pairs > 0 ? c->pt_plan_pairs.p + (size_t)(round0 - c->pt_plan_round0) * nl * n_pairs * 2 : nullptr;
-    q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
-    q.ebuf = c->rounds_ebuf.p; q.bar = c->rounds_bar.p; q.status = c->pt_status.p;
-    q.timeout_ticks = 100000000ll * 20;                   // 20 s of the 100 MHz wall clock
-    if (c->pt_log_on && c->pt_log_npairs == n_pairs && n_pairs > 0 && round0 >= c->pt_log_round0 &&
-        (uint64_t)round0 + (uint64_t)n_rounds <= (uint64_t)c->pt_log_round0 + (uint64_t)c->pt_log_rounds) {
-        const size_t r = round0 - c->pt_log_round0;
-        q.log_pairs = c->pt_log_pairs.p + r * (size_t)nl * n_pairs * 2;
-        q.log_acc = c->pt_log_acc.p + r * (size_t)nl * n_pairs;
-    }
-    const bool timed = c->ev_accumulate;
-    hipEvent_t e0 = nullptr, e2 = nullptr;
-    if (timed) {
-        e0 = next_event(c);
-        hipEvent_t e1 = next_event(c);
-        e2 = next_event(c);
-        if (!e0 || !e1 || !e2) return fail(c, NLMC_ERR_HIP, "hipEventCreate failed");
-        tag_triple(c, 1);
-        HIP_TRY(c, hipEventRecord(e0, c->stream));
-    }
-    // the two argument structs travel through device memory (k_rounds_fused reads them through laundered constant-memory pointers);
-    // two slots, so that a launch still running never sees the next one's arguments
-    const size_t a_bytes = (sizeof(SweepArgs) + 255) & ~(size_t)255, slot_bytes = a_bytes + ((sizeof(RoundsArgs) + 255) & ~(size_t)255);
-    HIP_TRY(c, c->rounds_args.reserve(2 * slot_bytes));
-    const int as = c->rounds_args_slot ^= 1;
-    std::vector<unsigned char> &hb = c->rounds_args_host[as];
-    hb.assign(slot_bytes, 0);
-    std::memcpy(hb.data(), &a, sizeof(SweepArgs));
-    std::memcpy(hb.data() + a_bytes, &q, sizeof(RoundsArgs));
-    unsigned char *dargs = c->rounds_args.p + (size_t)as * slot_bytes;
-    HIP_TRY(c, hipMemcpyAsync(dargs, hb.data(), slot_bytes, hipMemcpyHostToDevice, c->stream));
-    const SweepArgs *ap_dev = reinterpret_cast<const SweepArgs *>(dargs);
-    const RoundsArgs *qp_dev = reinterpret_cast<const RoundsArgs *>(dargs + a_bytes);
-    void *kargs[] = {&ap_dev, &qp_dev};
-    HIP_TRY(c, hipLaunchCooperativeKernel(kfun, dim3(c->n_chains), dim3(nt), kargs, (unsigned)Lds.total, c->stream));
-    HIP_TRY(c, hipGetLastError());
-    if (timed) { HIP_TRY(c, hipEventRecord(e2, c->stream)); c->launches_timed += n_rounds; }
-    c->launches_sweep += n_rounds;
-    c->launches_total += n_rounds;
-    c->stat_fused_window = w0 + n_rounds - 1;
-    c->stat_fused_slot = fslot;
-    c->sub_dirty = true;
-    return NLMC_OK;
+    return rc;
 }
 
-// n_rounds rounds as n_rounds sweep launches + ONE swap launch: launch i decides the swap of round i - 1 in its prologue
+// n_rounds rounds of a context that owns whole ladders.  Where k_rounds_fused qualifies (nlmc_pt_rounds_fused's conditions, the
+// residency of all workgroups among them; NLMC_NO_PERSISTENT switches it off) the rounds run inside its launches, every swap
+// included.  Otherwise n_rounds sweep launches + ONE swap launch: launch i decides the swap of round i - 1 in its prologue
 // (k_sweep_fused<.., DEFER>), the last round's swap is the ordinary k_pt_swap.
 int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
                             int n_pairs)
@@ -2494,14 +2541,19 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
     { int rc = rounds_check(c, Via::deferred, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs, fslot, arith); if (rc || fslot < 0) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
     const int L = c->ladder_len, T = sweeps_per_round;
+    if (!c->ev_accumulate) c->ev_used = 0;
+    c->ev_call_start = c->ev_used;
+    c->launches_sweep = 0;
+    if (!c->knobs.no_persistent && arith != ARITH_R64) {       // (k_rounds_fused has no real-valued variant)
+        bool resident = false;
+        int rc = rounds_in_launch(c, fslot, arith, n_rounds, T, sweep0, round0, seed, n_pairs, resident);
+        if (rc || resident) return rc;
+    }
     const nlmc_ctx::FusedPlan &P = c->fz[fslot];
     const int w0 = (int)((sweep0 - P.sweep0) / (uint32_t)T), nl = c->n_chains_global / L;
     const size_t G = (size_t)c->n_chains_global;
     HIP_TRY(c, c->rounds_ebuf.reserve(2 * G));
     { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
-    if (!c->ev_accumulate) c->ev_used = 0;
-    c->ev_call_start = c->ev_used;
-    c->launches_sweep = 0;
     const bool log = c->pt_log_on && c->pt_log_npairs == n_pairs && round0 >= c->pt_log_round0 &&
                      (uint64_t)round0 + (uint64_t)n_rounds <= (uint64_t)c->pt_log_round0 + (uint64_t)c->pt_log_rounds;
     for (int r = 0; r < n_rounds; ++r) {
@@ -2526,9 +2578,12 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
         if (rc) return rc;
     }
     c->sub_dirty = true;
+    c->rounds_route = NLMC_ROUNDS_LAUNCH_PER_ROUND;
     // the last round's swap: the ordinary kernel on the tracked energies
     return nlmc_pt_swap_philox(c, round0 + (uint32_t)(n_rounds - 1), seed, n_pairs, nullptr, nullptr, nullptr);
 }
+
+int nlmc_pt_rounds_route(nlmc_ctx *c) { return c ? c->rounds_route : 0; }
 
 int nlmc_pt_log_begin(nlmc_ctx *c, uint32_t round0, int n_rounds, int n_pairs)
 {
@@ -2570,7 +2625,7 @@ int nlmc_pt_check(nlmc_ctx *c)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (st != 0) {
         HIP_TRY(c, hipMemsetAsync(c->pt_status.p, 0, sizeof(int32_t), c->stream));
-        if (st == 3) return fail(c, NLMC_ERR_HIP, "nlmc_pt_rounds_fused: the workgroups of a launch lost each other (grid wait timed out); the chains' states are not valid");
+        if (st == 3) return fail(c, NLMC_ERR_HIP, "k_rounds_fused: a chain waited for its swap partner's energy in vain (timed out); the chains' states are not valid");
         return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
     }
     return NLMC_OK;

@@ -2256,8 +2256,12 @@ __device__ __forceinline__ void fused_state_load(const SweepArgs &a, unsigned ch
 
 // One planned window on the chain whose state sits in LDS: threshold tables of its first two sweeps (+ the fp64 mode's K tables at
 // the chain's temperature `row`), then the level loop.  Energy deltas of this thread come back in e_loc (plain variant).
+// k_rounds_fused only: have_tables / have_kt -- the first two tables / the K tables are in LDS already (made in the previous round's
+// tail / kept from a round on the same slot); gen_ahead = 2 -- the producers go on to the two sweeps behind the window, whose tables
+// end up in ring slots T mod 3 and (T + 1) mod 3 (needs T >= 3: their production windows are those of sweeps T - 3 .. T - 1).
 template <bool DIAG, bool FLAGS, bool OUT, int FMT, bool F64, bool R64 = false>
-__device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin &W, unsigned char *lds_raw, int row, uint32_t gc, long long &e_loc)
+__device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin &W, unsigned char *lds_raw, int row, uint32_t gc, long long &e_loc,
+                                             bool have_tables = false, bool have_kt = false, int gen_ahead = 0)
 {
     constexpr bool g_f64 = F64;
     // a temperature per sweep in the fp64 mode (fused_levels<.., SWT>, its ring of K tables): integer thresholds, the output variant
@@ -2279,9 +2283,9 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
 #ifdef NLMC_DEBUG_KNOBS
     // (timing experiments that switch the in-loop production off or down: every table holds valid words, so that stale entries
     // do not send the fp64 mode into its exact path)
-    for (int t = 0; t < ((a.dbg_flags & 1) ? 3 : min(2, Tn)) NLMC_DBG_NOPROLOGUE; ++t) {
+    for (int t = 0; t < ((a.dbg_flags & 1) ? 3 : have_tables ? 0 : min(2, Tn)) NLMC_DBG_NOPROLOGUE; ++t) {
 #else
-    for (int t = 0; t < min(2, Tn) NLMC_DBG_NOPROLOGUE; ++t) {
+    for (int t = 0; t < (have_tables ? 0 : min(2, Tn)) NLMC_DBG_NOPROLOGUE; ++t) {
 #endif
         float *tab_t = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(ur) + (size_t)t * a.lds_u_stride);
         if (F64) fill_uniform_words(reinterpret_cast<unsigned *>(tab_t), n, W.sweep0 + (uint32_t)t, gc, a.seed_lo, a.seed_hi, tid, nt);
@@ -2289,7 +2293,7 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
     }
     // (R64: z = cb x in the update itself, no tables; cb1 for the scaled rows of a phase)
     const double cb64 = R64 ? a.tab[(size_t)row * a.tab_cs] : 0.0, cb64_1 = (R64 && FLAGS) ? a.tab[(size_t)row * a.tab_cs + 1] : 0.0;
-    if (F64 && !R64) {
+    if (F64 && !R64 && !have_kt) {
         // K(X) for every field value a row can reach, at this chain's temperature: z = cb (X 2^-qs) as in update_spin<double>.
         // The trailing lanes of the workgroup take it (they have one Philox call less than the others above).  With FLAGS a
         // second table K1 at cb1 (the scaled rows): Khi0 | Khi1 | Klo0 | Klo1.
@@ -2313,7 +2317,7 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
     // calls per sweep of THIS wave: block b = (tid - g0) + call * gnt must lie below nblk for at least one of its lanes
     // (wave-uniform; the waves at the end of the producing range do one call less when gnt does not divide nblk)
     const int gwave0 = __builtin_amdgcn_readfirstlane((tid - g0) & ~63);
-    const FusedGenParams gp{gc, tid - g0, gnt, nblk, max(0, (nblk - gwave0 + gnt - 1) / gnt), Tn, row};
+    const FusedGenParams gp{gc, tid - g0, gnt, nblk, max(0, (nblk - gwave0 + gnt - 1) / gnt), Tn + gen_ahead, row};
     const bool is_gen = tid >= g0;
     // The producing waves are the youngest of their SIMDs and would get the issue slots the older worker waves leave
     // over (measured: a 150-instruction call stretched to ~3000 cycles while the workers waited at the barrier).
@@ -2419,41 +2423,44 @@ __device__ __forceinline__ void fused_state_store(const SweepArgs &a, unsigned c
 // of 2^-qs.  The fp64 field of the spec is then the exact integer X times 2^-qs whatever the order of the sum, z = cb x takes
 // one value per X, and the spec's test fma(u, 2^z, u) < 1 is a threshold on the 53-bit integer of u (accept_count_spec): the
 // update is the fixed-point one with `k_u < K[X]` in place of `z < W(r)`.  Same bits as the sweep-by-sweep fp64 kernel.
-// The swap step of one chain (k_rounds_fused after its grid-wide meeting, k_sweep_fused<.., DEFER> in its prologue): wave 0, `slot` =
-// the chain's slot before the swap, Ed / e_all = its own / everybody's energy after the round's sweeps.  Returns the slot after it.
-template <bool ATOMIC>
-__device__ __forceinline__ int pt_swap_step_of_chain(int slot, uint32_t gc, int lane, int L, int n_pairs, int n_ladders, uint32_t round,
-                                                     const int32_t *sel_round, const double *beta, int32_t *slot_of_chain, int32_t *chain_of_slot,
-                                                     double Ed, const double *e_all, int32_t *log_pairs, uint8_t *log_acc, uint32_t seed_lo,
-                                                     uint32_t seed_hi)
+// The swap step of one chain, in pieces (k_rounds_fused between two rounds, k_sweep_fused<.., DEFER> in its prologue; wave 0).
+// The selected pair that `slot` belongs to: its index in fp and its lower slot in fi, or fp = -1.  `sel`: the ladder's selection.
+__device__ __forceinline__ void pt_pair_of_slot(const int32_t *sel, int n_pairs, int slot, int lane, int &fp, int &fi)
 {
-    (void)n_ladders;
-    const int g = (int)gc / L;
-    const int32_t *sel = sel_round + (size_t)g * n_pairs * 2;
-    int fp = -1, fi = 0, out = slot;
-    for (int p0 = 0; p0 < n_pairs; p0 += 64) {             // the pair this chain's slot belongs to, if any: one lane per selected pair
+    fp = -1; fi = 0;
+    for (int p0 = 0; p0 < n_pairs; p0 += 64) {             // one lane per selected pair
         const int p = p0 + lane;
         const int i = p < n_pairs ? sel[2 * p] : -5;
         const unsigned long long m = __ballot(i == slot || i + 1 == slot);
         if (m) { const int src = __ffsll((long long)m) - 1; fp = p0 + src; fi = __shfl(i, src, 64); break; }
     }
-    if (fp >= 0) {                                         // (every lane of the wave computes it: the result is wave-uniform)
+}
+// k_pt_swap's decision for pair fp = slots (i, i + 1) of ladder g, seen from the chain on `slot` with energy Ed and its partner's Ep:
+// both chains of the pair compute the same one (every lane of the wave does: the result is wave-uniform).
+__device__ __forceinline__ bool pt_swap_decide(int fp, int i, int slot, double Ed, double Ep, const double *beta, uint32_t round, int g,
+                                               uint32_t seed_lo, uint32_t seed_hi)
+{
+    const double Ea = slot == i ? Ed : Ep, Eb = slot == i ? Ep : Ed;
+    const double dE = Eb - Ea, dB = beta[i + 1] - beta[i];
+    const u32x4 rr = philox4x32_10((uint32_t)fp, round, (uint32_t)g, NLMC_TAG_SWAP, seed_lo, seed_hi);
+    const double u = uniform_from(rr, 0.0);
+    const double z = (dB * dE) * 1.4426950408889634;
+    return u < exp2_spec(z);
+}
+// The whole step on the slot maps of the previous launch: `slot` = the chain's slot before the swap, Ed / e_all = its own /
+// everybody's energy after the round's sweeps.  Returns the slot after it.
+__device__ __forceinline__ int pt_swap_step_of_chain(int slot, uint32_t gc, int lane, int L, int n_pairs, uint32_t round,
+                                                     const int32_t *sel_round, const double *beta, int32_t *slot_of_chain, int32_t *chain_of_slot,
+                                                     double Ed, const double *e_all, int32_t *log_pairs, uint8_t *log_acc, uint32_t seed_lo,
+                                                     uint32_t seed_hi)
+{
+    const int g = (int)gc / L;
+    int fp, fi, out = slot;
+    pt_pair_of_slot(sel_round + (size_t)g * n_pairs * 2, n_pairs, slot, lane, fp, fi);
+    if (fp >= 0) {
         const int i = fi, ps = slot == i ? i + 1 : i;
-        int partner;
-        double Ep;
-        if (ATOMIC) {
-            partner = __hip_atomic_load(&chain_of_slot[(size_t)g * L + ps], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            Ep = __hip_atomic_load(&e_all[partner], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            partner = chain_of_slot[(size_t)g * L + ps];
-            Ep = e_all[partner];
-        }
-        const double Ea = slot == i ? Ed : Ep, Eb = slot == i ? Ep : Ed;
-        const double dE = Eb - Ea, dB = beta[i + 1] - beta[i];
-        const u32x4 rr = philox4x32_10((uint32_t)fp, round, (uint32_t)g, NLMC_TAG_SWAP, seed_lo, seed_hi);
-        const double u = uniform_from(rr, 0.0);
-        const double z = (dB * dE) * 1.4426950408889634;
-        const bool acc = u < exp2_spec(z);
+        const int partner = chain_of_slot[(size_t)g * L + ps];
+        const bool acc = pt_swap_decide(fp, i, slot, Ed, e_all[partner], beta, round, g, seed_lo, seed_hi);
         if (lane == 0) {
             if (slot == i && log_pairs) {                  // the chain on the lower slot keeps the round's log entry
                 const size_t at = (size_t)g * n_pairs + fp;
@@ -2461,13 +2468,8 @@ __device__ __forceinline__ int pt_swap_step_of_chain(int slot, uint32_t gc, int 
                 log_acc[at] = acc ? 1 : 0;
             }
             if (acc) {
-                if (ATOMIC) {
-                    __hip_atomic_store(&slot_of_chain[gc], ps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&chain_of_slot[(size_t)g * L + ps], (int)gc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    slot_of_chain[gc] = ps;
-                    chain_of_slot[(size_t)g * L + ps] = (int)gc;
-                }
+                slot_of_chain[gc] = ps;
+                chain_of_slot[(size_t)g * L + ps] = (int)gc;
             }
         }
         if (acc) out = ps;
@@ -2493,7 +2495,7 @@ __global__ __launch_bounds__(1024) void k_sweep_fused(SweepArgs a)
     int row = a.slot_of_chain ? a.slot_of_chain[gc_chain] : c;
     int new_row = row;
     if (DEFER && a.defer.n_pairs > 0 && threadIdx.x < 64)          // wave 0, while the other waves load the spins
-        new_row = pt_swap_step_of_chain<false>(row, gc_chain, (int)threadIdx.x, a.defer.ladder_len, a.defer.n_pairs, a.defer.n_ladders, a.defer.round,
+        new_row = pt_swap_step_of_chain(row, gc_chain, (int)threadIdx.x, a.defer.ladder_len, a.defer.n_pairs, a.defer.round,
                                                a.defer.plan_pairs, a.defer.beta, a.defer.slot_of_chain, a.defer.chain_of_slot,
                                                a.defer.e_prev[gc_chain], a.defer.e_prev, a.defer.log_pairs, a.defer.log_acc, a.seed_lo, a.seed_hi);
 #ifdef NLMC_STAMPS
@@ -2523,13 +2525,18 @@ __global__ __launch_bounds__(1024) void k_sweep_fused(SweepArgs a)
 // A context that owns whole ladders needs nothing from outside between two rounds: the chains stay in LDS, a round's swap
 // decision needs only the energies of the two chains of a pair.  k_rounds_fused runs n_rounds consecutive planned windows (one
 // window = the sweeps of one round) and, between them, the swap round of k_pt_swap -- same selection (planned), same Philox keys,
-// same arithmetic, same label exchange -- with ONE grid-wide arrive-and-wait per round: every chain publishes its tracked energy
-// (double-buffered by round parity), waits until all chains of the launch have, then the two chains of a selected pair each
-// evaluate the identical decision and each updates its OWN entries of the slot maps (chain_of_slot[new slot] is written by the
-// chain that moves there and read, before that, only by the same chain).  What a launch per round pays again and again -- kernel
-// launch, spins HBM -> LDS -> HBM, the swap kernel's launch -- is paid once per chunk of rounds.  Launched cooperatively (all
-// workgroups resident); the wait is bounded all the same (status 3 on a timeout, every workgroup leaves).  Bit-identical to
+// same arithmetic, same label exchange -- with a PAIRWISE hand-off: after the sweeps of launch-local round r a chain publishes its
+// tracked energy in rec[r][ladder * L + slot] (one 8-byte agent-scope store: the data is the flag), and a chain whose slot is in a
+// selected pair polls the partner SLOT's record of the same round; a chain in no pair waits for nobody.  The array has a row per
+// round of the launch and is filled with 0xFF bytes (a NaN no energy equals; 0.0 is a legal energy) before it: nothing is overwritten
+// inside a launch, so chains may drift apart by any number of rounds and nobody acknowledges anything.  Both chains of a pair take
+// the identical decision and each updates its own slot, which lives in LDS; the slot maps are written once, at the end of the
+// launch.  A record of round r depends on records of earlier rounds only and all workgroups are resident (cooperative launch), so
+// nobody waits for ever; the wait is bounded all the same (status 3 on a timeout, every workgroup leaves).  What a launch per round
+// pays again and again -- kernel launch, spins HBM -> LDS -> HBM, the uniform tables of the first two sweeps (made in the previous
+// round's tail here), the K tables of a chain whose slot did not change -- is paid once per chunk of rounds.  Bit-identical to
 // k_sweep_fused + k_pt_swap round by round.
+#define NLMC_ROUNDS_PER_LAUNCH 1024     // rows of the record array; longer calls are split by the host
 struct RoundsArgs {
     int n_rounds, n_windows_avail;   // rounds of this launch; planned windows from the first one on (>= n_rounds: the one behind the last is warmed)
     const int32_t *loff, *nlev, *himax, *send, *npos;      // plan arrays AT the first window; window r lies r strides further
@@ -2540,37 +2547,43 @@ struct RoundsArgs {
     const int32_t *plan_pairs;       // [n_rounds][n_ladders][n_pairs][2] at round0
     const double *beta;              // [ladder_len]
     int32_t *slot_of_chain, *chain_of_slot;
-    double *ebuf;                    // [2][n_chains_global]
+    unsigned long long *rec;         // [n_rounds][n_chains_global] published energies by SLOT, all-ones = not yet
     int32_t *log_pairs;              // [n_rounds][n_ladders][n_pairs][2] at round0, or nullptr
     uint8_t *log_acc;
-    unsigned *bar;                   // arrival counter, zero at launch
-    int32_t *status;                 // sticky pt status: 3 = the grid wait timed out
+    int32_t *status;                 // sticky pt status: 3 = a wait for a partner timed out
     long long timeout_ticks;         // of the 100 MHz wall clock
 };
 
-// (no static LDS in these kernels: the spins sit at LDS offset 0; `flag` is a word of the reduction scratch)
-// Everything the workgroups tell each other -- energies, slot maps, the counter -- is written and read by THREAD 0 with agent-scope
-// atomics (coherent across the XCDs' L2s by themselves): no fence.  A __threadfence() here would write back and INVALIDATE the L2
-// of every XCD once per wave and round -- and with it the window schedules every level streams from L2 (measured: 236 instead of
-// 117 us per round).
-__device__ __forceinline__ bool grid_arrive_and_wait(unsigned *bar, unsigned target, int32_t *status, long long t_end, volatile int *flag)
+// (no static LDS in these kernels: the spins sit at LDS offset 0; the words the waves share are in the reduction scratch)
+// What the workgroups tell each other -- one energy per chain and round -- is written and read by THREAD 0 with agent-scope atomics
+// (coherent across the XCDs' L2s by themselves): no fence.  A __threadfence() here would write back and INVALIDATE the L2 of every
+// XCD once per wave and round -- and with it the window schedules every level streams from L2 (measured: 236 instead of 117 us per
+// round).
+// (global-address-space pointers: the hand-off words are never reached through flat accesses)
+typedef unsigned long long __attribute__((address_space(1))) *rounds_rec_gptr;
+typedef int32_t __attribute__((address_space(1))) *rounds_status_gptr;
+// Lane 0 waits for the partner slot's record; false (and status 3) when it did not come in time or another chain gave up.
+__device__ __forceinline__ bool rounds_wait_record(rounds_rec_gptr rec, rounds_status_gptr status, long long timeout_ticks, int lane, double &Ep)
 {
-    if (threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this thread's published stores have been acknowledged
-        __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int good = 1;
-        while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 3 || (long long)wall_clock64() > t_end) {
-                __hip_atomic_store(status, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                good = 0;
-                break;
+    unsigned long long v = ~0ull;
+    if (lane == 0) {
+        v = __hip_atomic_load(rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (v == ~0ull) {
+            const long long t_end = (long long)wall_clock64() + timeout_ticks;
+            for (unsigned spin = 1;; ++spin) {
+                __builtin_amdgcn_s_sleep(1);
+                v = __hip_atomic_load(rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (v != ~0ull) break;
+                if ((spin & 63u) == 0u && (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 3 || (long long)wall_clock64() > t_end)) {
+                    __hip_atomic_store(status, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    break;
+                }
             }
-            __builtin_amdgcn_s_sleep(2);
         }
-        *flag = good;
     }
-    __syncthreads();
-    return *flag != 0;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    Ep = __hiloint2double((int)hi, (int)lo);
+    return !(lo == 0xFFFFFFFFu && hi == 0xFFFFFFFFu);
 }
 
 // The arguments come through POINTERS into constant memory, laundered once per round: as by-value kernel arguments the window
@@ -2586,16 +2599,20 @@ __global__ __launch_bounds__(1024) void k_rounds_fused(const SweepArgs *ap_g, co
     if ((unsigned)reinterpret_cast<size_t>(lds_raw) != 0u) __builtin_trap();
     const sweep_args_cptr ap = (sweep_args_cptr)(uintptr_t)ap_g;
     const rounds_args_cptr qp = (rounds_args_cptr)(uintptr_t)qp_g;
-    // State that lives from round to round sits in LDS (reduction scratch: [0] = {slot, barrier flag}, [1] = tracked energy, [3] =
-    // energy sum of the round), NOT in registers: the level loop has no scalar register to spare (every value kept alive across it is
-    // one more spill or reload inside it).
+    // State that lives from round to round sits in LDS (reduction scratch: [0] = {slot, 1 while nothing timed out}, [1] = tracked
+    // energy, [2] = {slot the K tables were built for, 1 when the first two uniform tables of the coming round are in place}, [3] =
+    // energy sum of the round), NOT in registers: the level loop has no scalar register to spare (every value kept alive across it
+    // is one more spill or reload inside it).
     {
         const SweepArgs &a0 = *(const SweepArgs *)ap;
         fused_state_load<false>(a0, lds_raw, (int)blockIdx.x);
         long long *red0 = reinterpret_cast<long long *>(lds_raw + a0.lds_red_off);
         if (threadIdx.x == 0) {
-            reinterpret_cast<volatile int *>(red0)[0] = a0.slot_of_chain[a0.chain_base + (int)blockIdx.x];
+            volatile int *sh0 = reinterpret_cast<volatile int *>(red0);
+            sh0[0] = a0.slot_of_chain[a0.chain_base + (int)blockIdx.x];
+            sh0[1] = 1;
             red0[1] = a0.efix[blockIdx.x];
+            sh0[4] = -1; sh0[5] = 0;
         }
         __syncthreads();
     }
@@ -2608,8 +2625,15 @@ __global__ __launch_bounds__(1024) void k_rounds_fused(const SweepArgs *ap_g, co
         const RoundsArgs &q = *(const RoundsArgs *)q_r;
         long long *red = reinterpret_cast<long long *>(lds_raw + a.lds_red_off);
         volatile int *sh = reinterpret_cast<volatile int *>(red);
+        // the uniform tables of the NEXT round's first two sweeps are made in this round's last two sweeps, when the producers would
+        // have nothing to do: sweeps T and T + 1 of the window, in the production windows (send[T-3], send[T-2]] and (send[T-2],
+        // send[T-1]], into ring slots T mod 3 and (T + 1) mod 3 -- the global sweep index runs on from window to window.  Only when
+        // the chain's RNG key does not follow its slot (the swap between the rounds would change it).
+        // (A fused window has at least three sweeps, so those production windows exist.)
+        const bool carry = r + 1 < n_rounds && a.rng_stride == 0;
         {
             const int c = (int)blockIdx.x, slot = sh[0];
+            const bool keep_kt = __builtin_amdgcn_readfirstlane(sh[4]) == __builtin_amdgcn_readfirstlane(slot), carried = __builtin_amdgcn_readfirstlane(sh[5]) != 0;
             const size_t PS = (size_t)a.fz_pstride;
             const bool has_next = r + 1 < q.n_windows_avail && q.nlev[r + 1] > 0;
             const FusedWin W{q.loff + (size_t)r * (NLMC_LCAP + 1), q.send + (size_t)r * a.n_sweeps, q.ell + (size_t)r * PS * NLMC_FZ_W, q.head + (size_t)r * PS,
@@ -2617,46 +2641,87 @@ __global__ __launch_bounds__(1024) void k_rounds_fused(const SweepArgs *ap_g, co
                              has_next ? q.npos[r + 1] : 0, q.nlev[r], q.himax[r], a.sweep0 + (uint32_t)(r * a.n_sweeps)};
             const uint32_t gcr = a.rng_stride ? (uint32_t)((c / a.rng_ladder_len) * a.rng_stride + a.rng_base + slot) : (uint32_t)(a.chain_base + c);
             long long e_loc = 0;
-            fused_window<DIAG, false, false, FMT, F64>(a, W, lds_raw, slot, gcr, e_loc);
+#ifdef NLMC_STAMPS
+            const long long st_round = (long long)__builtin_readcyclecounter();
+#endif
+            fused_window<DIAG, false, false, FMT, F64>(a, W, lds_raw, slot, gcr, e_loc, carried, keep_kt, carry ? 2 : 0);
+#ifdef NLMC_STAMPS
+            // the level loop left this round's per-wave sums in words 4-6: those of the launch's last but one round (carried tables in,
+            // tables of the next round made) move to words 0-2; words 3 / 7: prologue + level loop of that / of the last round
+            if (a.dbg && (threadIdx.x & 63) == 0) {
+                long long *d = a.dbg + ((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 8;
+                const long long cyc = (long long)__builtin_readcyclecounter() - st_round;
+                if (r == n_rounds - 2) { d[0] = d[4]; d[1] = d[5]; d[2] = d[6]; d[3] = cyc; }
+                d[7] = cyc;
+            }
+#endif
             const long long w = wave_sum_i64(e_loc);
             if ((threadIdx.x & 63) == 0 && w != 0) atomicAdd(reinterpret_cast<unsigned long long *>(&red[3]), (unsigned long long)w);
             __syncthreads();
         }
-        // ---- the swap round: thread 0 publishes, everybody meets, wave 0 decides
+        // ---- the swap round: thread 0 publishes, wave 0 of a chain in a selected pair waits for its partner's record and decides
         const int tid = threadIdx.x, lane = tid & 63;
         const uint32_t gc = (uint32_t)(a.chain_base + (int)blockIdx.x);
         const int L = q.ladder_len, g = (int)gc / L;
         const size_t G = (size_t)q.n_ladders * L;
-        double *eb = q.ebuf + (size_t)(r & 1) * G;
+        const rounds_rec_gptr rec = (rounds_rec_gptr)(uintptr_t)(q.rec + (size_t)r * G + (size_t)g * L);   // this round's records of the chain's ladder, by slot
+        int slot = 0;
         double Ed = 0.0;
         if (tid < 64) {
+            slot = sh[0];                        // (wave 0 alone reads it here and, below, writes it)
             const long long E = red[1] + red[3];
             Ed = (double)E * __longlong_as_double((long long)(1023 - a.escale) << 52);
-            if (tid == 0) __hip_atomic_store(&eb[gc], Ed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) {
+                __hip_atomic_store(&rec[slot], (unsigned long long)__double_as_longlong(Ed), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                red[1] = E; red[3] = 0;          // (the sum is next added to at the end of a whole window from here)
+                sh[4] = slot;                    // the K tables in LDS are this slot's
+                sh[5] = carry ? 1 : 0;
+            }
         }
-        const long long t_end = (long long)wall_clock64() + q.timeout_ticks;       // (bounded per round)
+        if (carry) {
+            // the two tables to ring slots 0 and 1, where a window expects those of its first two sweeps; the copy whose target is
+            // the other one's source comes second (T mod 3 == 0: they are in place)
+            const int m = a.n_sweeps % 3, nv = a.lds_u_stride / 16;
+            int4 *u0 = reinterpret_cast<int4 *>(lds_raw + a.lds_u_off), *u1 = u0 + nv, *u2 = u1 + nv;
+            if (m == 1) {
+                for (int i = tid; i < nv; i += (int)blockDim.x) u0[i] = u1[i];
+                __syncthreads();
+                for (int i = tid; i < nv; i += (int)blockDim.x) u1[i] = u2[i];
+            } else if (m == 2) {
+                for (int i = tid; i < nv; i += (int)blockDim.x) u1[i] = u0[i];
+                __syncthreads();
+                for (int i = tid; i < nv; i += (int)blockDim.x) u0[i] = u2[i];
+            }
+        }
 #ifdef NLMC_DEBUG_KNOBS
-        const bool ok = (a.dbg_flags & 4096) ? true : grid_arrive_and_wait(q.bar, (unsigned)(r + 1) * gridDim.x, q.status, t_end, sh + 1);   // 4096: timing experiment, nobody waits (wrong results)
+        if (tid < 64 && q.n_pairs > 0 && !(a.dbg_flags & 8192)) {     // 8192: timing experiment, no swap step (wrong results)
 #else
-        const bool ok = grid_arrive_and_wait(q.bar, (unsigned)(r + 1) * gridDim.x, q.status, t_end, sh + 1);
+        if (tid < 64 && q.n_pairs > 0) {
 #endif
-        if (tid == 0) { red[1] += red[3]; red[3] = 0; }          // (wave 0 has read both; the sum is next added to a whole window from here)
-        if (!ok) break;
-#ifdef NLMC_DEBUG_KNOBS
-        if (tid < 64 && !(a.dbg_flags & 8192)) {     // 8192: timing experiment, no swap step
-#else
-        if (tid < 64) {
-#endif
-            const int slot = sh[0];
-            const int ns = pt_swap_step_of_chain<true>(slot, gc, lane, L, q.n_pairs, q.n_ladders, q.round0 + (uint32_t)r,
-                                                       q.plan_pairs + (size_t)r * q.n_ladders * q.n_pairs * 2, q.beta, q.slot_of_chain, q.chain_of_slot, Ed, eb,
-                                                       q.log_pairs ? q.log_pairs + (size_t)r * q.n_ladders * q.n_pairs * 2 : nullptr,
-                                                       q.log_acc ? q.log_acc + (size_t)r * q.n_ladders * q.n_pairs : nullptr, a.seed_lo, a.seed_hi);
-            if (lane == 0 && ns != slot) sh[0] = ns;
+            int fp, fi;
+            pt_pair_of_slot(q.plan_pairs + ((size_t)r * q.n_ladders + g) * q.n_pairs * 2, q.n_pairs, slot, lane, fp, fi);
+            if (fp >= 0) {
+                const int ps = slot == fi ? fi + 1 : fi;
+                double Ep;
+                if (!rounds_wait_record(rec + ps, (rounds_status_gptr)(uintptr_t)q.status, q.timeout_ticks, lane, Ep)) {
+                    if (lane == 0) sh[1] = 0;
+                } else {
+                    const bool acc = pt_swap_decide(fp, fi, slot, Ed, Ep, q.beta, q.round0 + (uint32_t)r, g, a.seed_lo, a.seed_hi);
+                    if (lane == 0) {
+                        if (slot == fi && q.log_pairs) {           // the chain on the lower slot keeps the round's log entry
+                            const size_t at = ((size_t)r * q.n_ladders + g) * q.n_pairs + fp;
+                            q.log_pairs[2 * at] = fi; q.log_pairs[2 * at + 1] = fi + 1;
+                            q.log_acc[at] = acc ? 1 : 0;
+                        }
+                        if (acc) sh[0] = ps;
+                    }
+                }
+            }
         }
         __syncthreads();
+        if (sh[1] == 0) break;
     }
-    // state out: spins, tracked energy
+    // state out: spins, tracked energy, the chain's entries of the slot maps
     {
         const int n_pad = ap->g.n_pad, nt = blockDim.x, tid = threadIdx.x, c = (int)blockIdx.x;
         const long long *red = reinterpret_cast<const long long *>(lds_raw + ap->lds_red_off);
@@ -2664,7 +2729,12 @@ __global__ __launch_bounds__(1024) void k_rounds_fused(const SweepArgs *ap_g, co
         int4 *dst = reinterpret_cast<int4 *>(ap->spins + (size_t)c * n_pad);
         const int4 *src = reinterpret_cast<const int4 *>(lds_raw);
         for (int i = tid; i < n_pad / 16; i += nt) dst[i] = src[i];
-        if (tid == 0) ap->efix[c] = red[1];
+        if (tid == 0) {
+            const int gc = ap->chain_base + c, L = qp->ladder_len, slot = reinterpret_cast<const volatile int *>(red)[0];
+            ap->efix[c] = red[1];
+            qp->slot_of_chain[gc] = slot;
+            qp->chain_of_slot[(size_t)(gc / L) * L + slot] = gc;
+        }
     }
 }
 

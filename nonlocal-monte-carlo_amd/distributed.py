@@ -156,18 +156,22 @@ class ShardedTempering:
         return log
 
     def run_rounds(self, n_rounds, n_sweeps, persistent=None):
-        """`n_rounds` rounds of `n_sweeps` sweeps + one swap round each.  `persistent` (default: the environment variable
-        NLMC_PERSISTENT): a context that owns whole ladders and needs no collective runs a planned chunk of rounds per launch
-        (k_rounds_fused: the chains stay in LDS between the rounds, one grid-wide meeting per round; include/nlmc.h:
-        nlmc_pt_rounds_fused) -- same bits as round() called n_rounds times, which is what everything else falls back to.  Off by
-        default: measured at the bench shape it costs what a launch per round costs (117.3 vs 117.6 us per round: what it saves in
-        launches and spin I/O the grid-wide meeting and the per-round bookkeeping take back)."""
+        """`n_rounds` rounds of `n_sweeps` sweeps + one swap round each -- same bits as round() called n_rounds times, which is what
+        everything that does not qualify falls back to.  A context that owns whole ladders and needs no collective hands a planned
+        chunk of rounds to the engine at a time (pt_rounds_deferred; NLMC_NO_DEFERRED switches that off), which runs them inside
+        launches of k_rounds_fused where the device holds all chains at once: the chains stay in LDS between the rounds, a chain
+        publishes its energy per round and waits for its swap partner's alone, the next round's first two uniform tables are made in
+        this round's tail (include/nlmc.h: nlmc_pt_rounds_deferred; measured at the bench shape: 109.6 against 113.9 us per round,
+        DESIGN.md section 5).  Otherwise, or with NLMC_NO_PERSISTENT=1 when the engine is created, the engine runs a sweep launch per
+        round that decides the previous round's swap in its prologue; eng.last_rounds_route() tells which.  `persistent` (default: the
+        environment variable NLMC_PERSISTENT) asks for k_rounds_fused by name (pt_rounds_fused: a refusal instead of the launch per
+        round) and counts the rounds in persistent_rounds instead of deferred_rounds."""
         done = 0
         pl = getattr(self, "_planner", None)
         if persistent is None:
             persistent = bool(os.environ.get("NLMC_PERSISTENT"))
-        # default where it applies (one process, whole ladders, fused windows of one round): a sweep launch decides the PREVIOUS
-        # round's swap in its prologue (nlmc_pt_rounds_deferred: one launch per round instead of two; NLMC_NO_DEFERRED switches it off)
+        # default where it applies (one process, whole ladders, fused windows of one round): nlmc_pt_rounds_deferred, which runs the
+        # chunk in launch or, failing that, as sweep launches that decide the PREVIOUS round's swap in their prologue
         eligible = (pl is not None and self._lt is None and not self.collective and self.n_pairs > 0 and pl.window == n_sweeps == pl.S
                     and hasattr(self.eng, "pt_rounds_fused") and not getattr(self, "_persistent_refused", False))
         can = eligible

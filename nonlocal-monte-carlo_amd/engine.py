@@ -447,7 +447,7 @@ class Engine:
         self._ck(self._L.nlmc_pt_plan(self._ctx, int(round0), int(n_rounds), int(seed), int(n_pairs)))
 
     def pt_rounds_fused(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
-        """n_rounds whole rounds (sweeps + swap round) in one cooperative launch (include/nlmc.h: nlmc_pt_rounds_fused).  True when the
+        """n_rounds whole rounds (sweeps + swap round) inside cooperative launches (include/nlmc.h: nlmc_pt_rounds_fused).  True when the
         rounds were queued, False when the context / plans do not qualify (nothing was run: drive the rounds one by one)."""
         prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
         rc = self._L.nlmc_pt_rounds_fused(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
@@ -459,8 +459,9 @@ class Engine:
         return True
 
     def pt_rounds_deferred(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
-        """n_rounds rounds as n_rounds sweep launches (each decides the previous round's swap in its prologue) + one swap launch
-        (include/nlmc.h: nlmc_pt_rounds_deferred).  True when queued, False when the context / plans do not qualify."""
+        """n_rounds rounds on the route that fits (include/nlmc.h: nlmc_pt_rounds_deferred): inside k_rounds_fused launches where all
+        chains are resident at once, otherwise n_rounds sweep launches (each decides the previous round's swap in its prologue) + one
+        swap launch; last_rounds_route() tells which.  True when queued, False when the context / plans do not qualify."""
         prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
         rc = self._L.nlmc_pt_rounds_deferred(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
                                              int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs))
@@ -469,6 +470,11 @@ class Engine:
             return False
         self._ck(rc)
         return True
+
+    def last_rounds_route(self):
+        """The route the last pt_rounds_fused / pt_rounds_deferred call that ran took: "in launch" (the rounds inside k_rounds_fused
+        launches), "launch per round", or None before any such call (include/nlmc.h: nlmc_pt_rounds_route)."""
+        return {1: "in launch", 2: "launch per round"}.get(self._L.nlmc_pt_rounds_route(self._ctx))
 
     def pt_log_begin(self, round0, n_rounds, n_pairs):
         """Keep the swap log of the next rounds on the device (rounds called with want_log=False)."""

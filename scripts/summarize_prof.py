@@ -15,6 +15,10 @@ import sys
 from collections import defaultdict
 
 KERNELS = ("k_sweep_fused", "k_rounds_fused", "k_sweep_philox")     # dominant kernel: the first of these that appears in the trace
+# A launch of k_rounds_fused holds a planned chunk of rounds (bench.py: PLAN_CHUNK_ROUNDS = 256, which divides the 512 rounds per step
+# of the profiled run); its counters are divided by that, so that "per launch" stays what bench.py's static figures mean by it: one
+# round = 256 chains x 1e4 spins x 10 sweeps.
+ROUNDS_PER_LAUNCH = {"k_rounds_fused": int(os.environ.get("NLMC_PROF_ROUNDS_PER_LAUNCH", "256"))}
 
 
 def find(d, suffix):
@@ -33,7 +37,7 @@ def counters(d):
         if kernel in row["Kernel_Name"]:
             acc[row["Counter_Name"]] += float(row["Counter_Value"])
             n[row["Counter_Name"]] += 1
-    out = {k: (n[k], acc[k] / n[k]) for k in acc}
+    out = {k: (n[k], acc[k] / n[k] / ROUNDS_PER_LAUNCH.get(kernel, 1)) for k in acc}
     out["__kernel__"] = kernel
     return out
 
