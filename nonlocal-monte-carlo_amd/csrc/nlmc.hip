@@ -246,6 +246,13 @@ struct nlmc_ctx {
         DevBuf<double> val;           // [windows][NLMC_FZ_VAL_WORDS * pstride] (has_val only)
         DevBuf<int32_t> loff, nlev, himax, send;
         void release() { npos.release(); head.release(); ell.release(); val.release(); loff.release(); nlev.release(); himax.release(); send.release(); }
+        struct Arrays { const int32_t *loff, *nlev, *himax, *send, *npos; const int2 *head; const EdgeQ *ell; const double *val; };
+        Arrays at(int w) const        // the plan arrays at window w (val: nullptr without the value plane)
+        {
+            const size_t W = (size_t)w, PS = (size_t)pstride;
+            return {loff.p + W * (NLMC_LCAP + 1), nlev.p + W, himax.p + W, send.p + W * T, npos.p + W, head.p + W * PS, ell.p + W * PS * NLMC_FZ_W,
+                    has_val ? val.p + W * NLMC_FZ_VAL_WORDS * PS : nullptr};
+        }
     };
     FusedPlan fz[2];
     int fz_slot = 0;                  // slot the planning entry points write to
@@ -262,15 +269,25 @@ struct nlmc_ctx {
     std::vector<double> beta_list;
     DevBuf<double> pt_tab, pt_beta, pt_energies_all;
     DevBuf<int32_t> slot_of_chain, chain_of_slot, pt_pairs, pt_status, pt_plan_pairs, pt_plan_ok;
-    bool pt_plan_valid = false;
-    uint32_t pt_plan_round0 = 0;
-    int pt_plan_rounds = 0, pt_plan_npairs = 0;
-    uint64_t pt_plan_seed = 0;
+    // A window of consecutive swap rounds that has one row per round in device buffers: the planned pair selections (nlmc_pt_plan)
+    // and the device-side swap log (nlmc_pt_log_begin; it has no seed).
+    struct RoundWindow {
+        bool on = false;
+        uint32_t round0 = 0;
+        int rounds = 0, npairs = 0;
+        uint64_t seed = 0;
+        // Rounds [r0, r0 + n) lie inside the window, with its pairs per round and seed.  In 64 bits: the single-round launchers used
+        // to ask `round < round0 + (uint32_t)rounds`, which wraps; the two forms agree whenever round0 + rounds <= 2^32, which is
+        // every window the library's callers make.
+        bool covers(uint32_t r0, int n, int n_pairs, uint64_t sd = 0) const
+        {
+            return on && seed == sd && npairs == n_pairs && r0 >= round0 && (uint64_t)r0 + (uint64_t)n <= (uint64_t)round0 + (uint64_t)rounds;
+        }
+        size_t row(uint32_t r) const { return (size_t)(r - round0); }       // of a round covers() said yes to
+    };
+    RoundWindow pt_plan, pt_log;
     DevBuf<uint8_t> pt_acc, pt_log_acc;
     DevBuf<int32_t> pt_log_pairs;
-    bool pt_log_on = false;
-    uint32_t pt_log_round0 = 0;
-    int pt_log_rounds = 0, pt_log_npairs = 0;
     std::vector<uint8_t> stage_in, stage_out;      // padded host staging for row copies
     // ICM
     DevBuf<int32_t> icm_label, icm_info, icm_pairs;
@@ -338,16 +355,6 @@ int rows_to_device(nlmc_ctx *c, void *dst_dev, const void *src_host, int rows);
 int rows_to_host_begin(nlmc_ctx *c, const void *src_dev, int rows);               // async copy into c->stage
 void rows_to_host_finish(nlmc_ctx *c, void *dst_host, int rows);                  // after the stream was synchronised
 
-void tag_triple(nlmc_ctx *c, uint8_t kind)     // call right after taking the three events of a triple
-{
-    const size_t t = c->ev_used / 3 - 1;
-    if (c->ev_kind.size() <= t) c->ev_kind.resize(t + 1, 0);
-    c->ev_kind[t] = kind;
-}
-
-// elapsed (levelize, sweep) milliseconds of triple t
-int triple_ms(nlmc_ctx *c, size_t t, float &lev, float &sw);
-
 hipEvent_t next_event(nlmc_ctx *c)
 {
     if (c->ev_used == c->events.size()) {
@@ -358,6 +365,35 @@ hipEvent_t next_event(nlmc_ctx *c)
     return c->events[c->ev_used++];
 }
 
+// An event triple of kind `kind` (ev_kind) around work on one stream.  The launchers open one only while timings accumulate
+// (nlmc_timing_reset); span_mid / span_end of a span that was never begun do nothing.  A span takes its three events even where the
+// middle one is never recorded: triple_ms indexes by threes.
+struct TimerSpan { hipEvent_t mid = nullptr, end = nullptr; hipStream_t st = nullptr; };
+
+int span_begin(nlmc_ctx *c, TimerSpan &s, uint8_t kind, hipStream_t st)
+{
+    hipEvent_t e0 = next_event(c);
+    s.mid = next_event(c); s.end = next_event(c); s.st = st;
+    if (!e0 || !s.mid || !s.end) return fail(c, NLMC_ERR_HIP, "hipEventCreate failed");
+    const size_t t = c->ev_used / 3 - 1;
+    if (c->ev_kind.size() <= t) c->ev_kind.resize(t + 1, 0);
+    c->ev_kind[t] = kind;
+    HIP_TRY(c, hipEventRecord(e0, st));
+    return NLMC_OK;
+}
+
+int span_mid(nlmc_ctx *c, const TimerSpan &s) { if (s.mid) HIP_TRY(c, hipEventRecord(s.mid, s.st)); return NLMC_OK; }
+int span_end(nlmc_ctx *c, const TimerSpan &s) { if (s.end) HIP_TRY(c, hipEventRecord(s.end, s.st)); return NLMC_OK; }
+
+// opens a sweep call for nlmc_last_timing: its events and launches count from here
+void begin_sweep_call(nlmc_ctx *c)
+{
+    if (!c->ev_accumulate) c->ev_used = 0;
+    c->ev_call_start = c->ev_used;
+    c->launches_sweep = 0;
+}
+
+// elapsed (levelize, sweep) milliseconds of triple t
 int triple_ms(nlmc_ctx *c, size_t t, float &lev, float &sw)
 {
     const size_t i = 3 * t;
@@ -544,9 +580,8 @@ int fused_workers(const nlmc_ctx *c, int nt)
 // flags (+16) | 3 threshold tables of n_pad words | (per-sweep outputs only) 3 snapshot slots of n_pad bytes | reduction
 // scratch
 struct FusedLds { int neg_off, flags_off, u_off, u_bytes, snap_off, red_off, kt_off; size_t total; };
-FusedLds fused_lds(int n, int n_pad, bool has_flags, bool with_out, bool with_neg, int kt_entries = 0)
+FusedLds fused_lds(int n_pad, bool has_flags, bool with_out, bool with_neg, int kt_entries = 0)
 {
-    (void)n;
     FusedLds L{};
     L.neg_off = with_neg ? n_pad + 16 : 0;
     L.flags_off = (n_pad + 16) * (with_neg ? 2 : 1);
@@ -563,11 +598,32 @@ FusedLds fused_lds(int n, int n_pad, bool has_flags, bool with_out, bool with_ne
     return L;
 }
 
+// LDS of the sweep-by-sweep kernels: spins | flags | uniforms of one sweep (philox) | level offsets (philox) | reduction scratch
+struct StepLds { int flags_off, u_off, u_bytes, loff_off, red_off; bool dbuf; size_t total; };
+StepLds step_lds(const nlmc_ctx *c, bool stream_mode, bool f64)
+{
+    StepLds L{};
+    L.flags_off = c->n_pad;
+    int cur = c->n_pad * (c->has_flags ? 2 : 1);
+    cur = (cur + 15) / 16 * 16;
+    L.u_off = cur;
+    L.u_bytes = stream_mode ? 0 : ((c->n + 3) / 4 * 4 * (f64 ? 8 : 4) + 15) / 16 * 16;
+    // second copy of the per-sweep uniforms / level offsets when it fits: lets the idle waves prepare sweep t+1 while
+    // wave 0 runs the narrow tail of sweep t
+    L.dbuf = !stream_mode && (size_t)cur + 2 * (size_t)L.u_bytes + 2 * NLMC_LCAP * 4 + 32 <= (size_t)150 * 1024 && !c->knobs.no_dbuf;
+    cur += L.u_bytes * (L.dbuf ? 2 : 1);
+    L.loff_off = cur;
+    cur += NLMC_LCAP * 4 * (L.dbuf ? 2 : 1);               // (stream mode: one copy, the level offsets of the running sweep)
+    L.red_off = cur;
+    L.total = (size_t)cur + 16;
+    return L;
+}
+
 // the address format needs the negated copy of the spins next to everything else (flags counted in: they may be switched
 // on after planning)
 bool fused_addr_format(const nlmc_ctx *c)
 {
-    return c->sign8 && 2 * (c->n_pad + 16) <= 0xFFFF && fused_lds(c->n, c->n_pad, true, false, true).total <= (size_t)150 * 1024;
+    return c->sign8 && 2 * (c->n_pad + 16) <= 0xFFFF && fused_lds(c->n_pad, true, false, true).total <= (size_t)150 * 1024;
 }
 
 // schedule positions reserved per window: one per update, two for a row longer than NLMC_FZ_W entries (n_long of them),
@@ -591,8 +647,7 @@ bool fused_supported(const nlmc_ctx *c, int T)
     if (c->n < 256 || c->n > NLMC_FZ_SPT * 1024 || c->max_deg > 0x3FFF || T < 3 || T > NLMC_FUSED_TMAX) return false;
     if ((size_t)T * ((size_t)c->n + c->n_long) > ((size_t)1 << 22)) return false;   // 32-bit buffer offsets of the packed planes
     if (c->n_pad + 16 > 0x3FFF) return false;                          // spin address in 14 bits of the item head
-    (void)T;
-    const FusedLds L = fused_lds(c->n, c->n_pad, true, false, false);
+    const FusedLds L = fused_lds(c->n_pad, true, false, false);
     if (3 * L.u_bytes / 4 > 0xFFFF) return false;                      // threshold word index in 16 bits
     return L.total <= (size_t)150 * 1024;
 }
@@ -618,14 +673,14 @@ int fused_route(const nlmc_ctx *c, int precision, int order_mode, bool sweep_tem
         // exact dyadic couplings and fields (the field is an integer): a per-chain threshold table per value of the field in LDS beside
         // the rest; with phase flags a second one (scaled rows), counted at its worst (negated copy of the spins in), so that the
         // answer depends on n and xmax alone -- otherwise the call runs sweep by sweep
-        if (c->xmax > 4095 || fused_lds(c->n, c->n_pad, false, false, fused_addr_format(c), 2 * c->xmax + 1).total > (size_t)156 * 1024)
+        if (c->xmax > 4095 || fused_lds(c->n_pad, false, false, fused_addr_format(c), 2 * c->xmax + 1).total > (size_t)156 * 1024)
             return NOT_FUSED;
-        if (flags && fused_lds(c->n, c->n_pad, true, false, true, 2 * (2 * c->xmax + 1)).total > (size_t)156 * 1024) return NOT_FUSED;
+        if (flags && fused_lds(c->n_pad, true, false, true, 2 * (2 * c->xmax + 1)).total > (size_t)156 * 1024) return NOT_FUSED;
         // a temperature per sweep: a ring of three tables, one per threshold slot, counted like the two above (no flags); and the
         // 2 xmax + 1 entries a sweep rebuilds stay below an eighth of its n updates (at most a handful per producing thread: the
         // workgroup has about 3 n / 32 of them).  Otherwise the call runs sweep by sweep.
         if (sweep_temps && (8 * (2 * c->xmax + 1) > c->n ||
-                            fused_lds(c->n, c->n_pad, false, false, true, 3 * (2 * c->xmax + 1)).total > (size_t)156 * 1024))
+                            fused_lds(c->n_pad, false, false, true, 3 * (2 * c->xmax + 1)).total > (size_t)156 * 1024))
             return NOT_FUSED;
         return ARITH_F64;
     }
@@ -701,6 +756,30 @@ SweepArgs sweep_args(const nlmc_ctx *c, uint32_t sweep0, int n_sweeps, uint64_t 
     return a;
 }
 
+// What the two launchers on fused windows (run_fused, rounds_in_launch) set alike: the plan's layout and wave roles, the LDS carve-up
+// of the launch, the range of the integer field.
+void fused_args(const nlmc_ctx *c, const nlmc_ctx::FusedPlan &P, const FusedLds &L, SweepArgs &a)
+{
+    a.fz_pstride = P.pstride; a.fz_fmt = P.fmt;
+    a.f_workers = P.workers; a.f_gen0 = P.gen0; a.f_gen_prio = c->knobs.no_prio ? 0 : 1;
+#ifdef NLMC_DEBUG_KNOBS
+    a.dbg_flags = c->knobs.dbg_flags;
+#endif
+    a.lds_neg_off = L.neg_off; a.lds_flags_off = L.flags_off; a.lds_u_off = L.u_off; a.lds_u_stride = L.u_bytes; a.lds_red_off = L.red_off;
+    a.lds_snap_off = L.snap_off; a.lds_kt_off = L.kt_off; a.f64_xmax = c->xmax; a.f64_tie_mask = c->knobs.tie_mask;
+}
+
+// NLMC_STAMPS builds: the per-wave cycle sums of a launch of `rows` workgroups go to c->dbg, cleared on the launch's stream
+int stamps_arm([[maybe_unused]] nlmc_ctx *c, [[maybe_unused]] SweepArgs &a, [[maybe_unused]] int rows, [[maybe_unused]] hipStream_t st)
+{
+#ifdef NLMC_STAMPS
+    HIP_TRY(c, c->dbg.reserve((size_t)rows * 16 * 8 + 96));
+    HIP_TRY(c, hipMemsetAsync(c->dbg.p, 0, ((size_t)rows * 16 * 8 + 96) * sizeof(long long), st));
+    a.dbg = c->dbg.p;
+#endif
+    return NLMC_OK;
+}
+
 struct SweepOut {
     int record_stride;
     int8_t *out_spins;
@@ -719,14 +798,13 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
 {
     const nlmc_ctx::FusedPlan &P = c->fz[slot];
     const int R = c->sub_count(), T = P.T;
-    const size_t PS = (size_t)P.pstride;
     const bool real = arith == ARITH_R64;
     if (real && !P.has_val) return fail(c, NLMC_ERR_STATE, "run_fused: the plan has no fp64 value plane");
     // per-sweep outputs: three snapshot slots in LDS when they fit beside the threshold tables, in global memory otherwise
     // (phase flags: K0 and K1; a temperature per sweep: one table per threshold slot)
     const int kt = arith == ARITH_F64 ? (c->has_flags ? 2 : tab_ss != 0 ? 3 : 1) * (2 * c->xmax + 1) : 0;
-    const bool snap_lds = outs && fused_lds(c->n, c->n_pad, c->has_flags, true, P.fmt == NLMC_FMT_ADDR, kt).total <= (size_t)150 * 1024;
-    const FusedLds L = fused_lds(c->n, c->n_pad, c->has_flags, snap_lds, P.fmt == NLMC_FMT_ADDR, kt);
+    const bool snap_lds = outs && fused_lds(c->n_pad, c->has_flags, true, P.fmt == NLMC_FMT_ADDR, kt).total <= (size_t)150 * 1024;
+    const FusedLds L = fused_lds(c->n_pad, c->has_flags, snap_lds, P.fmt == NLMC_FMT_ADDR, kt);
     if (outs && !snap_lds) HIP_TRY(c, c->snap_g.reserve((size_t)R * (3 * (size_t)c->n_pad + 16)));
     const void *kfun = fused_kernel(c->has_diag, c->has_flags, outs, P.fmt, arith, defer != nullptr);
     if (!kfun) return fail(c, NLMC_ERR_STATE, "run_fused: no kernel for this combination (deferred swap with phase flags / outputs)");
@@ -734,35 +812,18 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
     // events around the launch (two stream commands) only while timings accumulate (nlmc_timing_reset): every launch or
     // every ev_every-th one.  An event record costs ~2.5 us of stream time: none on the plain product path.
     const bool timed = c->ev_accumulate && (c->ev_every <= 1 || c->launches_total % c->ev_every == 0);
-    hipEvent_t e0 = nullptr, e2 = nullptr;
-    if (timed) {
-        e0 = next_event(c);
-        hipEvent_t e1 = next_event(c);
-        e2 = next_event(c);
-        if (!e0 || !e1 || !e2) return fail(c, NLMC_ERR_HIP, "hipEventCreate failed");
-        tag_triple(c, 1);
-        HIP_TRY(c, hipEventRecord(e0, c->cur));
-    }
+    TimerSpan ts;
+    if (timed) { int rc = span_begin(c, ts, 1, c->cur); if (rc) return rc; }
     SweepArgs a = sweep_args(c, sweep0, T, seed, tab_dev, tab_cs, tab_ss, use_slots);
-    a.lvl_off = P.loff.p + (size_t)w * (NLMC_LCAP + 1);
-    a.nlev = P.nlev.p + w;
-    a.hi_max = P.himax.p + w;
-    a.ell32 = P.ell.p + (size_t)w * PS * NLMC_FZ_W;
-    a.head32 = P.head.p + (size_t)w * PS;
-    a.fsend = P.send.p + (size_t)w * T;
-    a.fz_pstride = P.pstride;
-    a.fz_fmt = P.fmt;
+    fused_args(c, P, L, a);
+    const nlmc_ctx::FusedPlan::Arrays A = P.at(w);
+    a.lvl_off = A.loff; a.nlev = A.nlev; a.hi_max = A.himax; a.fsend = A.send;
+    a.ell32 = A.ell; a.head32 = A.head;
     if (w + 1 < P.windows && P.nlev_host[(size_t)w + 1] > 0 && !c->knobs.no_warm) {
-        a.warm_head = P.head.p + (size_t)(w + 1) * PS;
-        a.warm_ell = P.ell.p + (size_t)(w + 1) * PS * NLMC_FZ_W;
+        a.warm_head = P.at(w + 1).head;
+        a.warm_ell = P.at(w + 1).ell;
         a.fz_npos_next = P.npos_host[(size_t)w + 1];
     }
-    a.f_workers = P.workers;
-    a.f_gen0 = P.gen0;
-    a.f_gen_prio = c->knobs.no_prio ? 0 : 1;
-#ifdef NLMC_DEBUG_KNOBS
-    a.dbg_flags = c->knobs.dbg_flags;
-#endif
     a.energy_sink = sink_override ? sink_override : c->energy_sink;
     if (defer) a.defer = *defer;
     a.trace_sweeps = outs ? n_total : T;
@@ -774,23 +835,14 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
         a.emin = want_min ? c->emin.p : nullptr;
         a.best = (want_min && want_state) ? c->best.p : nullptr;
     }
-    a.lds_neg_off = L.neg_off;
-    a.lds_flags_off = L.flags_off; a.lds_u_off = L.u_off; a.lds_u_stride = L.u_bytes; a.lds_red_off = L.red_off;
-    a.lds_snap_off = L.snap_off;
     a.snap_g = (outs && !snap_lds) ? c->snap_g.p : nullptr;
-    a.lds_kt_off = L.kt_off;
-    a.f64_xmax = c->xmax;
-    a.f64_tie_mask = c->knobs.tie_mask;
-    a.fz_val = real ? P.val.p + (size_t)w * NLMC_FZ_VAL_WORDS * PS : nullptr;
-#ifdef NLMC_STAMPS
-    HIP_TRY(c, c->dbg.reserve((size_t)R * 16 * 8 + 96));
-    HIP_TRY(c, hipMemsetAsync(c->dbg.p, 0, ((size_t)R * 16 * 8 + 96) * sizeof(long long), c->cur));
-    a.dbg = c->dbg.p;
-#endif
+    a.fz_val = real ? A.val : nullptr;
+    { int rc = stamps_arm(c, a, R, c->cur); if (rc) return rc; }
     void *kargs[] = {&a};
     HIP_TRY(c, hipLaunchKernel(kfun, dim3(R), dim3(fused_block(c)), kargs, L.total, c->cur));
     HIP_TRY(c, hipGetLastError());
-    if (timed) { HIP_TRY(c, hipEventRecord(e2, c->cur)); c->launches_timed++; }
+    { int rc = span_end(c, ts); if (rc) return rc; }
+    if (timed) c->launches_timed++;
     c->launches_sweep++;
     c->launches_total++;
     c->stat_fused_window = w;
@@ -902,15 +954,149 @@ bool sweeps_big(const nlmc_ctx *c, bool stream_mode, bool f64)
     return 2 * (size_t)c->n_pad + 32 + u_bytes + (size_t)NLMC_LCAP * 4 + 32 > (size_t)158 * 1024;
 }
 
+// The kernels for chains too long for LDS (csrc/nlmc_big.h), by arithmetic: the whole window in one launch, or one level per launch
+const void *big_kernel(bool per_level, bool stream_mode, bool f64)
+{
+    static const void *const table[2][3] = {
+        {reinterpret_cast<const void *>(k_sweep_big<NLMC_BIG_STREAM>), reinterpret_cast<const void *>(k_sweep_big<NLMC_BIG_F64>), reinterpret_cast<const void *>(k_sweep_big<NLMC_BIG_F32>)},
+        {reinterpret_cast<const void *>(k_big_level<NLMC_BIG_STREAM>), reinterpret_cast<const void *>(k_big_level<NLMC_BIG_F64>), reinterpret_cast<const void *>(k_big_level<NLMC_BIG_F32>)}};
+    return table[per_level ? 1 : 0][stream_mode ? 0 : f64 ? 1 : 2];
+}
+
+// The sweep-by-sweep half of run_sweeps: windows of sweeps -> levelize (or the cached plan) -> the sweep kernel, one launch per window
+// (chains too long for LDS: per window or per level).  The outputs stay in the context's device buffers.
+int run_sweeps_stepwise(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int n_sweeps, uint32_t sweep0, uint64_t seed,
+                        const double *tab_dev, int tab_cs, int tab_ss, bool use_slots, const uint32_t *keys_dev, const double *ustream_dev,
+                        bool want_energy, bool want_min, bool want_state, int rec)
+{
+    const int R = c->sub_count(), n = c->n;
+    // (its schedule buffers are shared with whatever the main stream is sweeping)
+    if (c->cur != c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const int per_chain = (stream_mode || order_mode == NLMC_ORDER_PER_CHAIN) ? 1 : 0;
+    if (per_chain && c->subset != 0) return fail(c, NLMC_ERR_UNSUPPORTED, "chain subsets run shared-order philox sweeps only");
+    // plan cache hit?
+    const bool f64 = stream_mode || precision == NLMC_F64;
+    const bool big = sweeps_big(c, stream_mode, f64);      // spins stay in global memory (csrc/nlmc_big.h)
+    const int ell_mode = big ? -1 : stream_mode ? 0 : (f64 ? 2 : 1);
+    const bool cached = !stream_mode && c->plan_valid && c->plan_mode == order_mode && c->plan_seed == seed && c->plan_big == big &&
+                        c->plan_precision == precision && !per_chain && sweep0 >= c->plan_sweep0 &&
+                        (uint64_t)sweep0 + (uint64_t)n_sweeps <= (uint64_t)c->plan_sweep0 + (uint64_t)c->plan_count;
+    // window size: keep the schedule scratch under ~256 MiB
+    const size_t per_sweep_orders = per_chain ? (size_t)R : 1;
+    const size_t item_bytes = big ? 8 + 12 : ell_mode == 1 ? 8 + 8 + 8 * NLMC_ELL_W32 : (ell_mode == 2 ? 8 + 8 + 12 * NLMC_ELL_W : 8);
+    const size_t bytes_per_sweep = per_sweep_orders * ((size_t)n * item_bytes + (size_t)(n + 1) * 4 + 4);
+    int W = n_sweeps;
+    if (!cached) {
+        // stream mode indexes its uniforms/keys by (chain, sweep) over the WHOLE call -> single window there
+        if (!stream_mode) W = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_sweeps, ((size_t)256 << 20) / bytes_per_sweep));
+        const size_t orders = per_sweep_orders * (size_t)W;
+        if (big) HIP_TRY(c, c->scratch.reserve_big(orders, (size_t)n, !stream_mode));
+        else HIP_TRY(c, c->scratch.reserve(orders, (size_t)n, ell_mode));
+    }
+
+    const int nt = big ? 1024 : sweep_block_for(c, !stream_mode && f64, !stream_mode && !f64 && c->has_diag);
+    const StepLds L = step_lds(c, stream_mode, f64);
+    const void *kfun = sweep_kernel(stream_mode, f64, c->has_diag, f64 && c->f64_pack16);
+    if (!big) { int rc = ensure_lds(c, kfun, L.total); if (rc) return rc; }
+    // chains too long for LDS (csrc/nlmc_big.h): enough of them to fill the chip -> one workgroup per chain for the whole
+    // window (its spins stay in that CU's L1 from level to level); few -> one launch per level over all chains, so that a
+    // single chain of a million spins still uses every CU (NLMC_BIG_PER_LEVEL = 0 / 1: test knob)
+    bool per_level = false;
+    const void *kbig = nullptr;
+    if (big) {
+        if (c->n_cu == 0) HIP_TRY(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+        per_level = (long long)R * 8 <= c->n_cu;
+        if (c->knobs.big_per_level >= 0) per_level = c->knobs.big_per_level != 0;
+        if (R > 65535) per_level = false;
+        kbig = big_kernel(per_level, stream_mode, f64);
+    }
+
+    for (int t0 = 0; t0 < n_sweeps; t0 += W) {
+        const int w = std::min(W, n_sweeps - t0);
+        const nlmc_ctx::Sched &sc = cached ? c->plan : c->scratch;
+        size_t o0 = 0;
+        TimerSpan ts;
+        if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->cur); if (rc) return rc; }
+        if (cached) {
+            o0 = (size_t)(sweep0 - c->plan_sweep0) + t0;
+        } else {
+            const int n_orders = (int)per_sweep_orders * w;
+            int rc = run_levelize(c, n_orders, keys_dev, per_chain, w, sweep0 + (uint32_t)t0, seed, c->scratch, ell_mode);
+            if (rc) return rc;
+            c->stats_nlev_ptr = c->scratch.nlev.p;
+            c->stats_nlev_count = n_orders;
+            c->stats_pending = true;
+        }
+        { int rc = span_mid(c, ts); if (rc) return rc; }
+
+        SweepArgs a = sweep_args(c, sweep0 + (uint32_t)t0, w, seed, tab_dev + (size_t)t0 * tab_ss, tab_cs, tab_ss, use_slots);
+        a.ord2 = sc.order.p + o0 * n;
+        a.lvl_off = sc.lvl_off.p + o0 * (size_t)(n + 1);
+        a.nlev = sc.nlev.p + o0;
+        a.hi_max = sc.hi_max.p + o0;
+        if (ell_mode == 1) { a.ell32 = sc.ell32.p + o0 * (size_t)n * NLMC_ELL_W32; a.head32 = sc.head32.p + o0 * n; }
+        if (ell_mode == 2) {
+            a.ellc64 = sc.ellc64.p + o0 * (size_t)n * NLMC_ELL_W;
+            a.ellv64 = sc.ellv64.p + o0 * (size_t)n * NLMC_ELL_W;
+            a.headh64 = sc.headh64.p + o0 * n;
+        }
+        a.per_chain = per_chain;
+        a.ustream = ustream_dev;
+        a.energy_sink = c->energy_sink;
+        a.etrace = want_energy ? c->etrace.p : nullptr;
+        a.trace_sweeps = n_sweeps;
+        a.t0 = t0;
+        a.rec_stride = rec ? rec : 1;
+        a.strace = rec ? c->strace.p : nullptr;
+        a.emin = want_min ? c->emin.p : nullptr;
+        a.best = (want_min && want_state) ? c->best.p : nullptr;
+        { int rc = stamps_arm(c, a, R, c->cur); if (rc) return rc; }
+        a.lds_u_stride = L.dbuf ? L.u_bytes : 0;
+        a.lds_loff_stride = L.dbuf ? NLMC_LCAP * 4 : 0;
+        a.lds_flags_off = L.flags_off; a.lds_u_off = L.u_off; a.lds_loff_off = L.loff_off; a.lds_red_off = L.red_off;
+        void *kargs[] = {&a};
+        if (big && !per_level) {
+            HIP_TRY(c, hipLaunchKernel(kbig, dim3(R), dim3(1024), kargs, 0, c->cur));
+        } else if (big) {
+            // the numbers of levels come back first
+            const size_t n_ord = per_sweep_orders * (size_t)w;
+            std::vector<int32_t> nlev_h(n_ord);
+            HIP_TRY(c, hipMemcpyAsync(nlev_h.data(), a.nlev, sizeof(int32_t) * n_ord, hipMemcpyDeviceToHost, c->cur));
+            HIP_TRY(c, hipStreamSynchronize(c->cur));
+            HIP_TRY(c, c->big_esum.reserve((size_t)R));
+            HIP_TRY(c, hipMemsetAsync(c->big_esum.p, 0, sizeof(long long) * (size_t)R, c->cur));
+            const bool per_sweep_out = a.etrace || a.emin || a.strace;
+            const unsigned gx = (unsigned)std::max(1, std::min(256, (n / 16 + 255) / 256));
+            for (int t = 0; t < w; ++t) {
+                int nl = 0;
+                if (per_chain) for (size_t q = 0; q < per_sweep_orders; ++q) nl = std::max(nl, nlev_h[q * (size_t)w + t]);
+                else nl = nlev_h[(size_t)t];
+                for (int l = 0; l < nl; ++l) {
+                    void *largs[] = {&a, &t, &l, &c->big_esum.p};
+                    HIP_TRY(c, hipLaunchKernel(kbig, dim3(gx, R), dim3(256), largs, 0, c->cur));
+                }
+                if (per_sweep_out || t == w - 1) hipLaunchKernelGGL(k_big_sweep_end, dim3(R), dim3(1024), 0, c->cur, a, t, c->big_esum.p);
+                HIP_TRY(c, hipGetLastError());
+            }
+        } else {
+            HIP_TRY(c, hipLaunchKernel(kfun, dim3(R), dim3(nt), kargs, L.total, c->cur));
+        }
+        HIP_TRY(c, hipGetLastError());
+        { int rc = span_end(c, ts); if (rc) return rc; }
+        if (c->ev_accumulate) c->launches_timed++;
+        c->launches_sweep++;
+        c->launches_total++;
+    }
+    return NLMC_OK;
+}
+
 // Shared driver: windows of sweeps -> (levelize) -> k_sweep.  `stream_mode` selects the kernel flavour.
 int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int n_sweeps, uint32_t sweep0,
                uint64_t seed, const double *tab_dev, int tab_cs, int tab_ss, bool use_slots, const uint32_t *keys_dev,
                const double *ustream_dev, const SweepOut &o)
 {
     const int R = c->sub_count(), n = c->n;
-    if (!c->ev_accumulate) c->ev_used = 0;
-    c->ev_call_start = c->ev_used;
-    c->launches_sweep = 0;
+    begin_sweep_call(c);
     c->stat_orders = 0;
     c->stat_levels = 0;
     c->stats_pending = false;
@@ -951,156 +1137,13 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
                                use_slots, outs, o.out_energy != nullptr, want_min, want_state, rec, outs ? j * P.T : 0, n_sweeps, arith);
             if (rc) return rc;
         }
-        return read_sweep_outputs(c, o, n_sweeps, rec, n_rec);
+    } else {
+        int rc = run_sweeps_stepwise(c, stream_mode, precision, order_mode, n_sweeps, sweep0, seed, tab_dev, tab_cs, tab_ss, use_slots, keys_dev,
+                                     ustream_dev, o.out_energy != nullptr, want_min, want_state, rec);
+        if (rc) return rc;
     }
-
-    // (sweep-by-sweep path from here on: its schedule buffers are shared with whatever the main stream is sweeping)
-    if (c->cur != c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const int per_chain = (stream_mode || order_mode == NLMC_ORDER_PER_CHAIN) ? 1 : 0;
-    if (per_chain && c->subset != 0) return fail(c, NLMC_ERR_UNSUPPORTED, "chain subsets run shared-order philox sweeps only");
-    // plan cache hit?
-    const bool f64 = stream_mode || precision == NLMC_F64;
-    const bool big = sweeps_big(c, stream_mode, f64);      // spins stay in global memory (csrc/nlmc_big.h)
-    const int ell_mode = big ? -1 : stream_mode ? 0 : (f64 ? 2 : 1);
-    const bool cached = !stream_mode && c->plan_valid && c->plan_mode == order_mode && c->plan_seed == seed && c->plan_big == big &&
-                        c->plan_precision == precision && !per_chain && sweep0 >= c->plan_sweep0 &&
-                        (uint64_t)sweep0 + (uint64_t)n_sweeps <= (uint64_t)c->plan_sweep0 + (uint64_t)c->plan_count;
-    // window size: keep the schedule scratch under ~256 MiB
-    const size_t per_sweep_orders = per_chain ? (size_t)R : 1;
-    const size_t item_bytes = big ? 8 + 12 : ell_mode == 1 ? 8 + 8 + 8 * NLMC_ELL_W32 : (ell_mode == 2 ? 8 + 8 + 12 * NLMC_ELL_W : 8);
-    const size_t bytes_per_sweep = per_sweep_orders * ((size_t)n * item_bytes + (size_t)(n + 1) * 4 + 4);
-    int W = n_sweeps;
-    if (!cached) {
-        // stream mode indexes its uniforms/keys by (chain, sweep) over the WHOLE call -> single window there
-        if (!stream_mode) W = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_sweeps, ((size_t)256 << 20) / bytes_per_sweep));
-        const size_t orders = per_sweep_orders * (size_t)W;
-        if (big) HIP_TRY(c, c->scratch.reserve_big(orders, (size_t)n, !stream_mode));
-        else HIP_TRY(c, c->scratch.reserve(orders, (size_t)n, ell_mode));
-    }
-
-    const int nt = big ? 1024 : sweep_block_for(c, !stream_mode && f64, !stream_mode && !f64 && c->has_diag);
-    // LDS carve-up: spins | flags | uniforms of one sweep (philox) | level offsets (philox) | reduction scratch
-    const int lds_flags_off = c->n_pad;
-    int cur = c->n_pad * (c->has_flags ? 2 : 1);
-    cur = (cur + 15) / 16 * 16;
-    const int lds_u_off = cur;
-    const int u_bytes = stream_mode ? 0 : ((f64 ? ((n + 3) / 4 * 4) * 8 : ((n + 3) / 4 * 4) * 4) + 15) / 16 * 16;
-    // second copy of the per-sweep uniforms / level offsets when it fits: lets the idle waves prepare sweep t+1 while
-    // wave 0 runs the narrow tail of sweep t
-    const bool dbuf = !stream_mode && (size_t)cur + 2 * (size_t)u_bytes + 2 * NLMC_LCAP * 4 + 32 <= (size_t)150 * 1024 &&
-                      !c->knobs.no_dbuf;
-    cur += u_bytes * (dbuf ? 2 : 1);
-    const int lds_loff_off = cur;
-    cur += NLMC_LCAP * 4 * (dbuf ? 2 : 1);               // (stream mode: one copy, the level offsets of the running sweep)
-    const int lds_red_off = cur;
-    const size_t lds = (size_t)cur + 16;
-    const void *kfun = sweep_kernel(stream_mode, f64, c->has_diag, f64 && c->f64_pack16);
-    if (!big) { int rc = ensure_lds(c, kfun, lds); if (rc) return rc; }
-
-    for (int t0 = 0; t0 < n_sweeps; t0 += W) {
-        const int w = std::min(W, n_sweeps - t0);
-        const nlmc_ctx::Sched &sc = cached ? c->plan : c->scratch;
-        size_t o0 = 0;
-        hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-        if (c->ev_accumulate) {
-            e0 = next_event(c); e1 = next_event(c); e2 = next_event(c);
-            if (!e0 || !e1 || !e2) return fail(c, NLMC_ERR_HIP, "hipEventCreate failed");
-            tag_triple(c, 0);
-            HIP_TRY(c, hipEventRecord(e0, c->cur));
-        }
-        if (cached) {
-            o0 = (size_t)(sweep0 - c->plan_sweep0) + t0;
-        } else {
-            const int n_orders = (int)per_sweep_orders * w;
-            int rc = run_levelize(c, n_orders, keys_dev, per_chain, w, sweep0 + (uint32_t)t0, seed, c->scratch, ell_mode);
-            if (rc) return rc;
-            c->stats_nlev_ptr = c->scratch.nlev.p;
-            c->stats_nlev_count = n_orders;
-            c->stats_pending = true;
-        }
-        if (e1) HIP_TRY(c, hipEventRecord(e1, c->cur));
-
-        SweepArgs a = sweep_args(c, sweep0 + (uint32_t)t0, w, seed, tab_dev + (size_t)t0 * tab_ss, tab_cs, tab_ss, use_slots);
-        a.ord2 = sc.order.p + o0 * n;
-        a.lvl_off = sc.lvl_off.p + o0 * (size_t)(n + 1);
-        a.nlev = sc.nlev.p + o0;
-        a.hi_max = sc.hi_max.p + o0;
-        if (ell_mode == 1) { a.ell32 = sc.ell32.p + o0 * (size_t)n * NLMC_ELL_W32; a.head32 = sc.head32.p + o0 * n; }
-        if (ell_mode == 2) {
-            a.ellc64 = sc.ellc64.p + o0 * (size_t)n * NLMC_ELL_W;
-            a.ellv64 = sc.ellv64.p + o0 * (size_t)n * NLMC_ELL_W;
-            a.headh64 = sc.headh64.p + o0 * n;
-        }
-        a.per_chain = per_chain;
-        a.ustream = ustream_dev;
-        a.energy_sink = c->energy_sink;
-        a.etrace = o.out_energy ? c->etrace.p : nullptr;
-        a.trace_sweeps = n_sweeps;
-        a.t0 = t0;
-        a.rec_stride = rec ? rec : 1;
-        a.strace = rec ? c->strace.p : nullptr;
-        a.emin = want_min ? c->emin.p : nullptr;
-        a.best = (want_min && want_state) ? c->best.p : nullptr;
-#ifdef NLMC_STAMPS
-        HIP_TRY(c, c->dbg.reserve((size_t)R * 16 * 8 + 96));
-        HIP_TRY(c, hipMemsetAsync(c->dbg.p, 0, ((size_t)R * 16 * 8 + 96) * sizeof(long long), c->cur));
-        a.dbg = c->dbg.p;
-#endif
-        a.lds_u_stride = dbuf ? u_bytes : 0;
-        a.lds_loff_stride = dbuf ? NLMC_LCAP * 4 : 0;
-        a.lds_flags_off = lds_flags_off; a.lds_u_off = lds_u_off; a.lds_loff_off = lds_loff_off; a.lds_red_off = lds_red_off;
-        // chains too long for LDS (csrc/nlmc_big.h): enough of them to fill the chip -> one workgroup per chain for the whole
-        // window (its spins stay in that CU's L1 from level to level); few -> one launch per level over all chains, so that a
-        // single chain of a million spins still uses every CU (NLMC_BIG_PER_LEVEL = 0 / 1: test knob)
-        bool per_level = false;
-        if (big) {
-            if (c->n_cu == 0) HIP_TRY(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
-            per_level = (long long)R * 8 <= c->n_cu;
-            if (c->knobs.big_per_level >= 0) per_level = c->knobs.big_per_level != 0;
-            if (R > 65535) per_level = false;
-        }
-        if (big && !per_level) {
-            if (stream_mode) hipLaunchKernelGGL(k_sweep_big<NLMC_BIG_STREAM>, dim3(R), dim3(1024), 0, c->cur, a);
-            else if (f64) hipLaunchKernelGGL(k_sweep_big<NLMC_BIG_F64>, dim3(R), dim3(1024), 0, c->cur, a);
-            else hipLaunchKernelGGL(k_sweep_big<NLMC_BIG_F32>, dim3(R), dim3(1024), 0, c->cur, a);
-        } else if (big) {
-            // the numbers of levels come back first
-            const size_t n_ord = per_sweep_orders * (size_t)w;
-            std::vector<int32_t> nlev_h(n_ord);
-            HIP_TRY(c, hipMemcpyAsync(nlev_h.data(), a.nlev, sizeof(int32_t) * n_ord, hipMemcpyDeviceToHost, c->cur));
-            HIP_TRY(c, hipStreamSynchronize(c->cur));
-            HIP_TRY(c, c->big_esum.reserve((size_t)R));
-            HIP_TRY(c, hipMemsetAsync(c->big_esum.p, 0, sizeof(long long) * (size_t)R, c->cur));
-            const bool per_sweep_out = a.etrace || a.emin || a.strace;
-            const unsigned gx = (unsigned)std::max(1, std::min(256, (n / 16 + 255) / 256));
-            for (int t = 0; t < w; ++t) {
-                int nl = 0;
-                if (per_chain) for (size_t q = 0; q < per_sweep_orders; ++q) nl = std::max(nl, nlev_h[q * (size_t)w + t]);
-                else nl = nlev_h[(size_t)t];
-                for (int l = 0; l < nl; ++l) {
-                    if (stream_mode) hipLaunchKernelGGL(k_big_level<NLMC_BIG_STREAM>, dim3(gx, R), dim3(256), 0, c->cur, a, t, l, c->big_esum.p);
-                    else if (f64) hipLaunchKernelGGL(k_big_level<NLMC_BIG_F64>, dim3(gx, R), dim3(256), 0, c->cur, a, t, l, c->big_esum.p);
-                    else hipLaunchKernelGGL(k_big_level<NLMC_BIG_F32>, dim3(gx, R), dim3(256), 0, c->cur, a, t, l, c->big_esum.p);
-                }
-                if (per_sweep_out || t == w - 1) hipLaunchKernelGGL(k_big_sweep_end, dim3(R), dim3(1024), 0, c->cur, a, t, c->big_esum.p);
-                HIP_TRY(c, hipGetLastError());
-            }
-        } else {
-            void *kargs[] = {&a};
-            HIP_TRY(c, hipLaunchKernel(kfun, dim3(R), dim3(nt), kargs, lds, c->cur));
-        }
-        HIP_TRY(c, hipGetLastError());
-        if (e2) { HIP_TRY(c, hipEventRecord(e2, c->cur)); c->launches_timed++; }
-        c->launches_sweep++;
-        c->launches_total++;
-    }
-
     return read_sweep_outputs(c, o, n_sweeps, rec, n_rec);
 }
-
-}  // namespace
-
-namespace {
 
 // ---- RCCL, bound at run time (dlopen): a process that never shards a ladder over GPUs needs no librccl -----------------
 // The library the process already holds (PyTorch ships one under the same soname) is reused.
@@ -1176,6 +1219,40 @@ void rows_to_host_finish(nlmc_ctx *c, void *dst_host, int rows)
 {
     const size_t n = (size_t)c->n, np = (size_t)c->n_pad;
     for (int r = 0; r < rows; ++r) std::memcpy((uint8_t *)dst_host + r * n, c->stage_out.data() + r * np, n);
+}
+
+// threads of a swap workgroup: one lane per selected pair when the selection is planned (the in-kernel selection is written for ONE wave)
+int swap_block(bool planned, int n_pairs) { return std::max(64, planned ? std::min(256, (n_pairs + 63) / 64 * 64) : 64); }
+
+// Where one swap round (k_pt_swap, k_apt_swap; `rows` ladders wide) writes its pairs and decisions and finds its planned selection: the
+// round's rows of the device-side log (read back once: nlmc_pt_log_read) unless the caller wants them on the host now, of the plan
+template <typename Args> void swap_window_rows(nlmc_ctx *c, Args &a, uint32_t round, uint64_t seed, int n_pairs, size_t rows, bool to_host)
+{
+    if (c->pt_log.covers(round, 1, n_pairs) && !to_host) {
+        a.out_pairs = c->pt_log_pairs.p + c->pt_log.row(round) * rows * n_pairs * 2;
+        a.out_acc = c->pt_log_acc.p + c->pt_log.row(round) * rows * n_pairs;
+    }
+    if (c->pt_plan.covers(round, 1, n_pairs, seed)) {
+        a.plan_pairs = c->pt_plan_pairs.p + c->pt_plan.row(round) * rows * n_pairs * 2;
+        a.plan_ok = c->pt_plan_ok.p + c->pt_plan.row(round) * rows;
+    }
+}
+
+// The tail of a swap launch whose caller asked for the pairs or the decisions of its `rows` ladders: they come back with the status word,
+// and a selection that ran out of pairs is reported (and the status cleared).
+int swap_read_back(nlmc_ctx *c, int rows, int n_pairs, int32_t *out_pairs, uint8_t *out_accepted)
+{
+    if (!out_pairs && !out_accepted) return NLMC_OK;
+    int32_t st = 0;
+    if (out_pairs) HIP_TRY(c, hipMemcpyAsync(out_pairs, c->pt_pairs.p, sizeof(int32_t) * (size_t)rows * n_pairs * 2, hipMemcpyDeviceToHost, c->stream));
+    if (out_accepted) HIP_TRY(c, hipMemcpyAsync(out_accepted, c->pt_acc.p, (size_t)rows * n_pairs, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&st, c->pt_status.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (st != 0) {
+        HIP_TRY(c, hipMemsetAsync(c->pt_status.p, 0, sizeof(int32_t), c->stream));
+        return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
+    }
+    return NLMC_OK;
 }
 
 }  // namespace
@@ -1653,16 +1730,11 @@ int nlmc_plan_philox(nlmc_ctx *c, int precision, int order_mode, uint32_t sweep0
     const int ell_mode = big ? -1 : precision == NLMC_F64 ? 2 : 1;
     if (big) HIP_TRY(c, c->plan.reserve_big((size_t)n_sweeps, (size_t)c->n, true));
     else HIP_TRY(c, c->plan.reserve((size_t)n_sweeps, (size_t)c->n, ell_mode));
-    hipEvent_t pe0 = nullptr, pe1 = nullptr, pe2 = nullptr;      // planning time -> levelize time of nlmc_timing_total
-    if (c->ev_accumulate) {
-        pe0 = next_event(c); pe1 = next_event(c); pe2 = next_event(c);
-        if (!pe0 || !pe1 || !pe2) return fail(c, NLMC_ERR_HIP, "hipEventCreate failed");
-        tag_triple(c, 2);
-        HIP_TRY(c, hipEventRecord(pe0, c->stream));
-    }
+    TimerSpan ts;                                                // planning time -> levelize time of nlmc_timing_total
+    if (c->ev_accumulate) { int rc = span_begin(c, ts, 2, c->stream); if (rc) return rc; }
     int rc = run_levelize(c, n_sweeps, nullptr, 0, n_sweeps, sweep0, seed, c->plan, ell_mode);
     if (rc) return rc;
-    if (pe0) HIP_TRY(c, hipEventRecord(pe2, c->stream));
+    if ((rc = span_end(c, ts)) != NLMC_OK) return rc;
     c->plan_valid = true;
     c->plan_big = big;
     c->plan_mode = order_mode;
@@ -1749,16 +1821,11 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
     if (fz_diag) { HIP_TRY(c, c->fz_stats.reserve(W * 8)); a.stats = c->fz_stats.p; }
     // planning time counts as levelize time of the accumulating timer (nlmc_timing_total): an event triple whose
     // sweep part is empty
-    hipEvent_t pe0 = nullptr, pe1 = nullptr, pe2 = nullptr;
-    if (c->ev_accumulate) {
-        pe0 = next_event(c); pe1 = next_event(c); pe2 = next_event(c);
-        if (!pe0 || !pe1 || !pe2) return fail(c, NLMC_ERR_HIP, "hipEventCreate failed");
-        tag_triple(c, 2);
-        HIP_TRY(c, hipEventRecord(pe0, c->stream));
-    }
+    TimerSpan ts;
+    if (c->ev_accumulate) { int rc = span_begin(c, ts, 2, c->stream); if (rc) return rc; }
     hipLaunchKernelGGL(k_levelize_fused, dim3(n_windows), dim3(1024), lds, c->stream, a);
     HIP_TRY(c, hipGetLastError());
-    if (pe0) HIP_TRY(c, hipEventRecord(pe2, c->stream));
+    { int rc = span_end(c, ts); if (rc) return rc; }
     P.nlev_host.assign(W, 0);
     P.npos_host.assign(W, 0);
     HIP_TRY(c, hipMemcpyAsync(P.nlev_host.data(), P.nlev.p, sizeof(int32_t) * W, hipMemcpyDeviceToHost, c->stream));
@@ -1909,7 +1976,7 @@ int nlmc_pt_init(nlmc_ctx *c, int ladder_len, const double *beta_list)
     c->ladder_len = ladder_len;
     c->subset = 0; c->n_marked_local = 0; c->sub_dirty = true;
     c->pt_tab_valid = false;
-    c->pt_plan_valid = false;
+    c->pt_plan.on = false;
     c->beta_list.assign(beta_list, beta_list + ladder_len);
     const int G = c->n_chains_global;
     HIP_TRY(c, c->pt_tab.reserve((size_t)ladder_len * 2));
@@ -1939,7 +2006,7 @@ int nlmc_pt_plan(nlmc_ctx *c, uint32_t round0, int n_rounds, uint64_t seed, int 
     if (n_rounds < 0 || n_pairs < 0 || n_pairs > std::max(0, L - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
     if (L > 4096) return fail(c, NLMC_ERR_UNSUPPORTED, "nlmc_pt_plan: ladder_len > 4096");
     HIP_TRY(c, hipSetDevice(c->device));
-    c->pt_plan_valid = false;
+    c->pt_plan.on = false;
     if (n_rounds == 0 || n_pairs == 0) return NLMC_OK;
     HIP_TRY(c, c->pt_plan_pairs.reserve((size_t)n_rounds * nl * n_pairs * 2));
     HIP_TRY(c, c->pt_plan_ok.reserve((size_t)n_rounds * nl));
@@ -1956,8 +2023,8 @@ int nlmc_pt_plan(nlmc_ctx *c, uint32_t round0, int n_rounds, uint64_t seed, int 
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int32_t v : ok)
         if (!v) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
-    c->pt_plan_valid = true;
-    c->pt_plan_round0 = round0; c->pt_plan_rounds = n_rounds; c->pt_plan_npairs = n_pairs; c->pt_plan_seed = seed;
+    c->pt_plan.on = true;
+    c->pt_plan.round0 = round0; c->pt_plan.rounds = n_rounds; c->pt_plan.npairs = n_pairs; c->pt_plan.seed = seed;
     return NLMC_OK;
 }
 
@@ -2034,39 +2101,15 @@ int nlmc_pt_swap_philox(nlmc_ctx *c, uint32_t round, uint64_t seed, int n_pairs,
     a.ladder0 = energies_all_dev ? 0 : c->chain_base / L;
     a.chain_base = c->chain_base;
     const int n_decide = energies_all_dev ? nl : c->n_chains / L;            // ladders this launch decides
-    if (c->pt_log_on && c->pt_log_npairs == n_pairs && round >= c->pt_log_round0 &&
-        round < c->pt_log_round0 + (uint32_t)c->pt_log_rounds && !out_pairs && !out_accepted) {
-        const size_t r = round - c->pt_log_round0;       // device-side log: read back once (nlmc_pt_log_read)
-        a.out_pairs = c->pt_log_pairs.p + r * (size_t)nl * n_pairs * 2;
-        a.out_acc = c->pt_log_acc.p + r * (size_t)nl * n_pairs;
-    }
-    if (c->pt_plan_valid && c->pt_plan_seed == seed && c->pt_plan_npairs == n_pairs && round >= c->pt_plan_round0 &&
-        round < c->pt_plan_round0 + (uint32_t)c->pt_plan_rounds) {
-        const size_t r = round - c->pt_plan_round0;
-        a.plan_pairs = c->pt_plan_pairs.p + r * (size_t)nl * n_pairs * 2;
-        a.plan_ok = c->pt_plan_ok.p + r * (size_t)nl;
-    }
-    // one lane per selected pair when the selection is planned (the in-kernel selection is written for ONE wave)
-    const int swap_nt = a.plan_pairs ? std::min(256, (n_pairs + 63) / 64 * 64) : 64;
+    swap_window_rows(c, a, round, seed, n_pairs, (size_t)nl, out_pairs || out_accepted);
     c->sub_dirty = true;
     if ((out_pairs || out_accepted) && n_decide < nl) {          // rows of the ladders other contexts decide: "no pair"
         HIP_TRY(c, hipMemsetAsync(c->pt_pairs.p, 0xFF, sizeof(int32_t) * (size_t)nl * n_pairs * 2, c->stream));
         HIP_TRY(c, hipMemsetAsync(c->pt_acc.p, 0, (size_t)nl * n_pairs, c->stream));
     }
-    hipLaunchKernelGGL(k_pt_swap, dim3(n_decide), dim3(std::max(64, swap_nt)), 0, c->stream, a);
+    hipLaunchKernelGGL(k_pt_swap, dim3(n_decide), dim3(swap_block(a.plan_pairs != nullptr, n_pairs)), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
-    if (out_pairs || out_accepted) {
-        int32_t st = 0;
-        if (out_pairs) HIP_TRY(c, hipMemcpyAsync(out_pairs, c->pt_pairs.p, sizeof(int32_t) * (size_t)nl * n_pairs * 2, hipMemcpyDeviceToHost, c->stream));
-        if (out_accepted) HIP_TRY(c, hipMemcpyAsync(out_accepted, c->pt_acc.p, (size_t)nl * n_pairs, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(&st, c->pt_status.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (st != 0) {
-            HIP_TRY(c, hipMemsetAsync(c->pt_status.p, 0, sizeof(int32_t), c->stream));
-            return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
-        }
-    }
-    return NLMC_OK;
+    return swap_read_back(c, nl, n_pairs, out_pairs, out_accepted);
 }
 
 int nlmc_pt_swap_philox_host(nlmc_ctx *c, uint32_t round, uint64_t seed, int n_pairs, const double *energies_all_host,
@@ -2199,7 +2242,7 @@ int nlmc_apt_shard(nlmc_ctx *c, int R_global, int world, int rank, const double 
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->apt_R = R_global; c->apt_world = world; c->apt_rank = rank;
     c->rng_stride = R_global; c->rng_base = rank * L;
-    c->pt_plan_valid = false;                        // (a selection planned over the local ladder is not this mode's)
+    c->pt_plan.on = false;                           // (a selection planned over the local ladder is not this mode's)
     return NLMC_OK;
 }
 
@@ -2235,21 +2278,9 @@ static int apt_launch_swap(nlmc_ctx *c, uint32_t round, uint64_t seed, int n_pai
     a.beta = c->apt_beta.p; a.e_all = c->apt_e_all.p; a.escale = c->escale;
     a.slot_of_chain = c->slot_of_chain.p; a.chain_of_slot = c->chain_of_slot.p;
     a.out_pairs = c->pt_pairs.p; a.out_acc = c->pt_acc.p; a.status = c->pt_status.p; a.bd = c->apt_bd.p;
-    if (c->pt_log_on && c->pt_log_npairs == n_pairs && round >= c->pt_log_round0 &&
-        round < c->pt_log_round0 + (uint32_t)c->pt_log_rounds && !out_pairs && !out_accepted) {
-        const size_t r = round - c->pt_log_round0;
-        a.out_pairs = c->pt_log_pairs.p + r * (size_t)K * n_pairs * 2;
-        a.out_acc = c->pt_log_acc.p + r * (size_t)K * n_pairs;
-    }
-    if (c->pt_plan_valid && c->pt_plan_seed == seed && c->pt_plan_npairs == n_pairs && round >= c->pt_plan_round0 &&
-        round < c->pt_plan_round0 + (uint32_t)c->pt_plan_rounds) {
-        const size_t r = round - c->pt_plan_round0;
-        a.plan_pairs = c->pt_plan_pairs.p + r * (size_t)K * n_pairs * 2;
-        a.plan_ok = c->pt_plan_ok.p + r * (size_t)K;
-    }
-    const int swap_nt = a.plan_pairs ? std::min(256, (n_pairs + 63) / 64 * 64) : 64;
+    swap_window_rows(c, a, round, seed, n_pairs, (size_t)K, out_pairs || out_accepted);
     c->sub_dirty = true;
-    hipLaunchKernelGGL(k_apt_swap, dim3(K), dim3(std::max(64, swap_nt)), 0, c->stream, a);
+    hipLaunchKernelGGL(k_apt_swap, dim3(K), dim3(swap_block(a.plan_pairs != nullptr, n_pairs)), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     if (c->apt_world > 1) {
         AptAdoptArgs d{};
@@ -2259,18 +2290,7 @@ static int apt_launch_swap(nlmc_ctx *c, uint32_t round, uint64_t seed, int n_pai
         hipLaunchKernelGGL(k_apt_adopt, dim3(2 * K), dim3(256), 0, c->stream, d);
         HIP_TRY(c, hipGetLastError());
     }
-    if (out_pairs || out_accepted) {
-        int32_t st = 0;
-        if (out_pairs) HIP_TRY(c, hipMemcpyAsync(out_pairs, c->pt_pairs.p, sizeof(int32_t) * (size_t)K * n_pairs * 2, hipMemcpyDeviceToHost, c->stream));
-        if (out_accepted) HIP_TRY(c, hipMemcpyAsync(out_accepted, c->pt_acc.p, (size_t)K * n_pairs, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(&st, c->pt_status.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (st != 0) {
-            HIP_TRY(c, hipMemsetAsync(c->pt_status.p, 0, sizeof(int32_t), c->stream));
-            return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
-        }
-    }
-    return NLMC_OK;
+    return swap_read_back(c, K, n_pairs, out_pairs, out_accepted);
 }
 
 static int apt_check_pairs(nlmc_ctx *c, int n_pairs)
@@ -2396,8 +2416,7 @@ int rounds_check(nlmc_ctx *c, Via via, int precision, int n_rounds, int T, uint3
     if (k < 0 || c->fz[k].T != T) return no("no fused-window plan of one window per round covers these sweeps");
     arith = fused_route(c, precision, NLMC_ORDER_SHARED, false, false, k, T, via);
     if (arith == NOT_FUSED) return no("the fp64 mode does not run on fused windows for this instance");
-    if (n_pairs > 0 && !(c->pt_plan_valid && c->pt_plan_seed == seed && c->pt_plan_npairs == n_pairs && round0 >= c->pt_plan_round0 &&
-                         (uint64_t)round0 + (uint64_t)n_rounds <= (uint64_t)c->pt_plan_round0 + (uint64_t)c->pt_plan_rounds))
+    if (n_pairs > 0 && !c->pt_plan.covers(round0, n_rounds, n_pairs, seed))
         return no("the pair selections of these rounds are not planned (nlmc_pt_plan)");
     fslot = k;
     return NLMC_OK;
@@ -2428,18 +2447,17 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
     const int L = c->ladder_len;
     const nlmc_ctx::FusedPlan &P = c->fz[fslot];
     const int kt = arith == ARITH_F64 ? 2 * c->xmax + 1 : 0;
-    const FusedLds Lds = fused_lds(c->n, c->n_pad, false, false, P.fmt == NLMC_FMT_ADDR, kt);
+    const FusedLds Lds = fused_lds(c->n_pad, false, false, P.fmt == NLMC_FMT_ADDR, kt);
     const void *kfun = rounds_kernel(c->has_diag, P.fmt, arith);
     if (!kfun) return fail(c, NLMC_ERR_STATE, "k_rounds_fused: no kernel for this arithmetic");
     { int rc = ensure_lds(c, kfun, Lds.total); if (rc) return rc; }
     const int nt = fused_block(c);
     { int rc = rounds_resident(c, kfun, nt, Lds.total, resident); if (rc || !resident) return rc; }
     const int nl = c->n_chains_global / L;
-    const size_t G = (size_t)c->n_chains_global, PS = (size_t)P.pstride;
+    const size_t G = (size_t)c->n_chains_global;
     HIP_TRY(c, c->rounds_rec.reserve((size_t)std::min(n_rounds, NLMC_ROUNDS_PER_LAUNCH) * G));
     { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
-    const bool log = c->pt_log_on && c->pt_log_npairs == n_pairs && n_pairs > 0 && round0 >= c->pt_log_round0 &&
-                     (uint64_t)round0 + (uint64_t)n_rounds <= (uint64_t)c->pt_log_round0 + (uint64_t)c->pt_log_rounds;
+    const bool log = n_pairs > 0 && c->pt_log.covers(round0, n_rounds, n_pairs);
     // the two argument structs travel through device memory (k_rounds_fused reads them through laundered constant-memory pointers);
     // two device slots written in stream order, so that a launch still running never sees the next one's arguments.  The host
     // copies are pageable memory: hipMemcpyAsync has staged such a source when it returns, so a slot's host buffer may be filled
@@ -2453,44 +2471,26 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
         // no record yet: all ones, a NaN that no energy equals (0.0 is a legal energy)
         HIP_TRY(c, hipMemsetAsync(c->rounds_rec.p, 0xFF, sizeof(unsigned long long) * (size_t)k * G, c->stream));
         SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
-        a.fz_pstride = P.pstride; a.fz_fmt = P.fmt;
-        a.f_workers = P.workers; a.f_gen0 = P.gen0; a.f_gen_prio = c->knobs.no_prio ? 0 : 1;
-#ifdef NLMC_DEBUG_KNOBS
-        a.dbg_flags = c->knobs.dbg_flags;
-#endif
+        fused_args(c, P, Lds, a);
         a.trace_sweeps = T; a.rec_stride = 1;
-        a.lds_neg_off = Lds.neg_off; a.lds_flags_off = Lds.flags_off; a.lds_u_off = Lds.u_off; a.lds_u_stride = Lds.u_bytes; a.lds_red_off = Lds.red_off;
-        a.lds_snap_off = Lds.snap_off; a.lds_kt_off = Lds.kt_off; a.f64_xmax = c->xmax; a.f64_tie_mask = c->knobs.tie_mask;
-#ifdef NLMC_STAMPS
-        HIP_TRY(c, c->dbg.reserve((size_t)c->n_chains * 16 * 8 + 96));
-        HIP_TRY(c, hipMemsetAsync(c->dbg.p, 0, ((size_t)c->n_chains * 16 * 8 + 96) * sizeof(long long), c->stream));
-        a.dbg = c->dbg.p;
-#endif
+        { int rc = stamps_arm(c, a, c->n_chains, c->stream); if (rc) return rc; }
         RoundsArgs q{};
         q.n_rounds = k; q.n_windows_avail = c->knobs.no_warm ? k : P.windows - w0;
-        q.loff = P.loff.p + (size_t)w0 * (NLMC_LCAP + 1); q.nlev = P.nlev.p + w0; q.himax = P.himax.p + w0; q.send = P.send.p + (size_t)w0 * T;
-        q.npos = P.npos.p + w0; q.head = P.head.p + (size_t)w0 * PS; q.ell = P.ell.p + (size_t)w0 * PS * NLMC_FZ_W;
+        const nlmc_ctx::FusedPlan::Arrays A = P.at(w0);
+        q.loff = A.loff; q.nlev = A.nlev; q.himax = A.himax; q.send = A.send; q.npos = A.npos; q.head = A.head; q.ell = A.ell;
         q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = nl; q.round0 = r0;
-        q.plan_pairs = n_pairs > 0 ? c->pt_plan_pairs.p + (size_t)(r0 - c->pt_plan_round0) * nl * n_pairs * 2 : nullptr;
+        q.plan_pairs = n_pairs > 0 ? c->pt_plan_pairs.p + c->pt_plan.row(r0) * nl * n_pairs * 2 : nullptr;
         q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
         q.rec = c->rounds_rec.p; q.status = c->pt_status.p;
         q.timeout_ticks = 100000000ll * 20;                   // 20 s of the 100 MHz wall clock
         if (log) {
-            const size_t r = r0 - c->pt_log_round0;
+            const size_t r = c->pt_log.row(r0);
             q.log_pairs = c->pt_log_pairs.p + r * (size_t)nl * n_pairs * 2;
             q.log_acc = c->pt_log_acc.p + r * (size_t)nl * n_pairs;
         }
         // events around the launch while timings accumulate: its time counts for its k rounds
-        const bool timed = c->ev_accumulate;
-        hipEvent_t e0 = nullptr, e2 = nullptr;
-        if (timed) {
-            e0 = next_event(c);
-            hipEvent_t e1 = next_event(c);
-            e2 = next_event(c);
-            if (!e0 || !e1 || !e2) return fail(c, NLMC_ERR_HIP, "hipEventCreate failed");
-            tag_triple(c, 1);
-            HIP_TRY(c, hipEventRecord(e0, c->stream));
-        }
+        TimerSpan ts;
+        if (c->ev_accumulate) { int rc = span_begin(c, ts, 1, c->stream); if (rc) return rc; }
         const int as = c->rounds_args_slot ^= 1;
         std::vector<unsigned char> &hb = c->rounds_args_host[as];
         hb.assign(slot_bytes, 0);
@@ -2503,7 +2503,8 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
         void *kargs[] = {&ap_dev, &qp_dev};
         HIP_TRY(c, hipLaunchCooperativeKernel(kfun, dim3(c->n_chains), dim3(nt), kargs, (unsigned)Lds.total, c->stream));
         HIP_TRY(c, hipGetLastError());
-        if (timed) { HIP_TRY(c, hipEventRecord(e2, c->stream)); c->launches_timed += k; }
+        { int rc = span_end(c, ts); if (rc) return rc; }
+        if (c->ev_accumulate) c->launches_timed += k;
         c->launches_sweep += k;
         c->launches_total += k;
         c->stat_fused_window = w0 + k - 1;
@@ -2541,9 +2542,7 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
     { int rc = rounds_check(c, Via::deferred, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs, fslot, arith); if (rc || fslot < 0) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
     const int L = c->ladder_len, T = sweeps_per_round;
-    if (!c->ev_accumulate) c->ev_used = 0;
-    c->ev_call_start = c->ev_used;
-    c->launches_sweep = 0;
+    begin_sweep_call(c);
     if (!c->knobs.no_persistent && arith != ARITH_R64) {       // (k_rounds_fused has no real-valued variant)
         bool resident = false;
         int rc = rounds_in_launch(c, fslot, arith, n_rounds, T, sweep0, round0, seed, n_pairs, resident);
@@ -2554,8 +2553,7 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
     const size_t G = (size_t)c->n_chains_global;
     HIP_TRY(c, c->rounds_ebuf.reserve(2 * G));
     { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
-    const bool log = c->pt_log_on && c->pt_log_npairs == n_pairs && round0 >= c->pt_log_round0 &&
-                     (uint64_t)round0 + (uint64_t)n_rounds <= (uint64_t)c->pt_log_round0 + (uint64_t)c->pt_log_rounds;
+    const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
     for (int r = 0; r < n_rounds; ++r) {
         DeferSwap d{};
         d.ladder_len = L; d.n_ladders = nl; d.beta = c->pt_beta.p;
@@ -2563,10 +2561,10 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
         if (r > 0) {                          // the swap of round round0 + r - 1, on the energies the previous launch published
             const uint32_t rr = round0 + (uint32_t)(r - 1);
             d.n_pairs = n_pairs; d.round = rr;
-            d.plan_pairs = c->pt_plan_pairs.p + (size_t)(rr - c->pt_plan_round0) * nl * n_pairs * 2;
+            d.plan_pairs = c->pt_plan_pairs.p + c->pt_plan.row(rr) * nl * n_pairs * 2;
             d.e_prev = c->rounds_ebuf.p + (size_t)((r - 1) & 1) * G;
             if (log) {
-                const size_t lr = rr - c->pt_log_round0;
+                const size_t lr = c->pt_log.row(rr);
                 d.log_pairs = c->pt_log_pairs.p + lr * (size_t)nl * n_pairs * 2;
                 d.log_acc = c->pt_log_acc.p + lr * (size_t)nl * n_pairs;
             }
@@ -2592,23 +2590,23 @@ int nlmc_pt_log_begin(nlmc_ctx *c, uint32_t round0, int n_rounds, int n_pairs)
     if (n_rounds < 0 || n_pairs < 0) return fail(c, NLMC_ERR_ARG, "nlmc_pt_log_begin: bad argument");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t nl = (size_t)(c->n_chains_global / c->ladder_len), tot = (size_t)n_rounds * nl * (size_t)n_pairs;
-    c->pt_log_on = false;
+    c->pt_log.on = false;
     if (tot == 0) return NLMC_OK;
     HIP_TRY(c, c->pt_log_pairs.reserve(tot * 2));
     HIP_TRY(c, c->pt_log_acc.reserve(tot));
     HIP_TRY(c, hipMemsetAsync(c->pt_log_pairs.p, 0xFF, sizeof(int32_t) * tot * 2, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->pt_log_acc.p, 0, tot, c->stream));
-    c->pt_log_on = true;
-    c->pt_log_round0 = round0; c->pt_log_rounds = n_rounds; c->pt_log_npairs = n_pairs;
+    c->pt_log.on = true;
+    c->pt_log.round0 = round0; c->pt_log.rounds = n_rounds; c->pt_log.npairs = n_pairs;
     return NLMC_OK;
 }
 
 int nlmc_pt_log_read(nlmc_ctx *c, int32_t *out_pairs, uint8_t *out_accepted)
 {
     if (!c || !out_pairs || !out_accepted) return fail(c, NLMC_ERR_ARG, "nlmc_pt_log_read: NULL argument");
-    if (!c->pt_log_on) return fail(c, NLMC_ERR_STATE, "nlmc_pt_log_read: no log was begun");
+    if (!c->pt_log.on) return fail(c, NLMC_ERR_STATE, "nlmc_pt_log_read: no log was begun");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t nl = (size_t)(c->n_chains_global / c->ladder_len), tot = (size_t)c->pt_log_rounds * nl * (size_t)c->pt_log_npairs;
+    const size_t nl = (size_t)(c->n_chains_global / c->ladder_len), tot = (size_t)c->pt_log.rounds * nl * (size_t)c->pt_log.npairs;
     HIP_TRY(c, hipMemcpyAsync(out_pairs, c->pt_log_pairs.p, sizeof(int32_t) * tot * 2, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(out_accepted, c->pt_log_acc.p, tot, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
