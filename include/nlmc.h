@@ -137,7 +137,9 @@ int nlmc_plan_philox(nlmc_ctx *ctx, int precision, int order_mode, uint32_t swee
  * sweep0 (a whole number of planned windows) runs on it -- with per-sweep outputs or a temperature per sweep when the
  * snapshot slots of that variant fit in LDS; every other call takes the sweep-by-sweep path.  Results are bit-identical either way.  out_planned: number of windows that got a
  * fused schedule (0 when the instance does not qualify: n < 256 or n > 11264,
- * window < 3 or > 64, or the three threshold tables do not fit in LDS next to the spins). */
+ * window < 3 or > 64, or the three threshold tables do not fit in LDS next to the spins; a window is also left out when its
+ * schedule is deeper than 1023 levels or when, in one of its sweeps, a spin has more than 255 neighbours that come before it in the
+ * order -- a hub row: the levelizer counts them in eight bits). */
 int nlmc_plan_philox_fused(nlmc_ctx *ctx, uint32_t sweep0, int n_windows, int window, uint64_t seed, int32_t *out_planned);
 /* Which precisions may run on fused windows of `window` sweeps on this context: bit 0 = NLMC_F32, bit 1 = NLMC_F64.  The fp64
  * mode (the reference's arithmetic, NMC/nmc.py:86-87: fp64 field, 53-bit uniform) qualifies when every coupling AND every field
