@@ -164,7 +164,9 @@ int nlmc_last_sweep_fused(const nlmc_ctx *ctx);
  * operation (fp64 field summed with fma in CSR order, z = cb x, fma(u, 2^z, u) < 1 decided from the 27 high bits of u where they
  * decide, from all 53 otherwise), bit-identical to the sweep-by-sweep fp64 kernel.  nlmc_fused_modes then reports bit 1 for such
  * instances; nlmc_sweep_philox(NLMC_F64) runs on it (one temperature per chain, phase flags in force or not: z = cb1 x on scaled
- * rows, frozen rows unchanged; a call with a temperature per sweep stays sweep by sweep) and so does nlmc_pt_rounds_deferred(NLMC_F64) (no phase flags); nlmc_pt_rounds_fused does not.  NLMC_NO_FUSED64 switches it off.  Changing the setting drops the current fused plans. */
+ * rows, frozen rows unchanged; a call with a temperature per sweep stays sweep by sweep), and so do nlmc_pt_rounds_deferred(NLMC_F64)
+ * and nlmc_pt_rounds_fused(NLMC_F64) (no phase flags; the real-valued variant of k_rounds_fused reads the windows' value planes).
+ * NLMC_NO_FUSED64 switches it off.  Changing the setting drops the current fused plans. */
 int nlmc_set_fused_f64_real(nlmc_ctx *ctx, int on);
 /* Only allocates the plan buffers for up to n_windows windows of `window` sweeps (a later nlmc_plan_philox_fused of at
  * most that size then allocates nothing).  Drops the current fused plan. */
@@ -269,14 +271,20 @@ int nlmc_pt_plan(nlmc_ctx *ctx, uint32_t round0, int n_rounds, uint64_t seed, in
  * fp64 mode's threshold tables of a chain that kept its slot) is paid once per launch.  Needs: a fused-window plan of ONE window per
  * round covering sweeps [sweep0, sweep0 + n_rounds sweeps_per_round) (nlmc_plan_philox_fused, window == sweeps_per_round), the pair
  * selections of rounds [round0, round0 + n_rounds) planned (nlmc_pt_plan, same seed and n_pairs), a context of whole ladders without
- * a communicator, no phase flags / chain subset, one workgroup per chain resident at once (n_chains <= CUs for large n).
+ * a communicator, no phase flags / chain subset, one workgroup per chain resident at once (n_chains <= CUs for large n).  All three
+ * arithmetics: fixed point, the fp64 mode's integer thresholds (dyadic instances) and, with nlmc_set_fused_f64_real on and plans made
+ * since, the fp64 mode on real couplings and fields (no K tables: the launch's LDS is the fixed-point mode's; without the option such
+ * an instance is refused: the fp64 mode does not run on fused windows for it).
  * NLMC_ERR_UNSUPPORTED (nothing was run) when a condition is not met: the caller runs the rounds one by one.  Asynchronous: a wait
  * that times out is reported by nlmc_pt_check / nlmc_pt_log_read (NLMC_ERR_HIP). */
 int nlmc_pt_rounds_fused(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0,
                          uint64_t seed, int n_pairs);
 /* The same n_rounds rounds on the route that fits the context (n_pairs >= 1, no tracked minimum; otherwise nlmc_pt_rounds_fused's
  * conditions and NLMC_ERR_UNSUPPORTED convention, residency apart).  Where k_rounds_fused can hold all chains at once the rounds run
- * inside its launches as above (NLMC_NO_PERSISTENT=1 at nlmc_create switches that off).  Otherwise n_rounds sweep launches + ONE
+ * inside its launches as above (NLMC_NO_PERSISTENT=1 at nlmc_create switches that off) -- except for real-valued fp64 instances
+ * (nlmc_set_fused_f64_real), which keep a launch per round here by default: the in-launch route is taken by default only where it was measured faster beyond the
+ * run-to-run spread, and for the real-valued variant that measurement is still open; nlmc_pt_rounds_fused reaches the
+ * kernel.  Otherwise n_rounds sweep launches + ONE
  * swap launch: the sweep launch of round i decides the swap of round i - 1 in its prologue (every chain looks up its pair, reads its
  * partner's energy as the previous launch published it, takes k_pt_swap's decision and updates its own entries of the slot maps;
  * wave 0 does it while the other waves load the spins), the last round's swap is the ordinary kernel.  Bit-identical to

@@ -684,10 +684,10 @@ int fused_route(const nlmc_ctx *c, int precision, int order_mode, bool sweep_tem
             return NOT_FUSED;
         return ARITH_F64;
     }
-    // real couplings or fields: opt-in (nlmc_set_fused_f64_real), plans with the fp64 value plane, no tables (the f32 mode's LDS);
-    // k_rounds_fused has no such variant.  One temperature per chain only: with a temperature per sweep the real-valued output variant
+    // real couplings or fields: opt-in (nlmc_set_fused_f64_real), plans with the fp64 value plane, no tables (the f32 mode's LDS),
+    // on all three launchers.  One temperature per chain only: with a temperature per sweep the real-valued output variant
     // was measured at 0.69-0.74x of the sweep-by-sweep kernel (anneals of 10^3 sweeps, DESIGN.md section 2: measured and rejected)
-    if (!c->f64_real || sweep_temps || via == Via::rounds || (slot >= 0 && !c->fz[slot].has_val)) return NOT_FUSED;
+    if (!c->f64_real || sweep_temps || (slot >= 0 && !c->fz[slot].has_val)) return NOT_FUSED;
     return ARITH_R64;
 }
 
@@ -709,14 +709,13 @@ const void *fused_kernel(bool diag, bool flags, bool outs, int fmt, int arith, b
     return kernel_at<FusedKernel>(key, std::make_index_sequence<144>{});
 }
 
-// k_rounds_fused<DIAG, FMT, F64> by {diag, fmt, arith}: 12 kernels, none real-valued
+// k_rounds_fused<DIAG, FMT, F64, R64> by {diag, fmt, arith}: 18 kernels
 template <int K> struct RoundsKernel {
     static constexpr bool diag = K & 1;
     static constexpr int fmt = K / 2 % 3, arith = K / 6;
     static const void *get()
     {
-        if constexpr (arith == ARITH_R64) return nullptr;
-        else return reinterpret_cast<const void *>(k_rounds_fused<diag, fmt, arith == ARITH_F64>);
+        return reinterpret_cast<const void *>(k_rounds_fused<diag, fmt, arith != ARITH_F32, arith == ARITH_R64>);
     }
 };
 const void *rounds_kernel(bool diag, int fmt, int arith)
@@ -2446,7 +2445,9 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
 {
     const int L = c->ladder_len;
     const nlmc_ctx::FusedPlan &P = c->fz[fslot];
-    const int kt = arith == ARITH_F64 ? 2 * c->xmax + 1 : 0;
+    const bool real = arith == ARITH_R64;
+    if (real && !P.has_val) return fail(c, NLMC_ERR_STATE, "k_rounds_fused: the plan has no fp64 value plane");
+    const int kt = arith == ARITH_F64 ? 2 * c->xmax + 1 : 0;          // (the real-valued variant has no K tables: the f32 mode's LDS)
     const FusedLds Lds = fused_lds(c->n_pad, false, false, P.fmt == NLMC_FMT_ADDR, kt);
     const void *kfun = rounds_kernel(c->has_diag, P.fmt, arith);
     if (!kfun) return fail(c, NLMC_ERR_STATE, "k_rounds_fused: no kernel for this arithmetic");
@@ -2478,6 +2479,7 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
         q.n_rounds = k; q.n_windows_avail = c->knobs.no_warm ? k : P.windows - w0;
         const nlmc_ctx::FusedPlan::Arrays A = P.at(w0);
         q.loff = A.loff; q.nlev = A.nlev; q.himax = A.himax; q.send = A.send; q.npos = A.npos; q.head = A.head; q.ell = A.ell;
+        q.val = real ? A.val : nullptr;
         q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = nl; q.round0 = r0;
         q.plan_pairs = n_pairs > 0 ? c->pt_plan_pairs.p + c->pt_plan.row(r0) * nl * n_pairs * 2 : nullptr;
         q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
@@ -2530,6 +2532,11 @@ int nlmc_pt_rounds_fused(nlmc_ctx *c, int precision, int n_rounds, int sweeps_pe
     return rc;
 }
 
+// Whether nlmc_pt_rounds_deferred takes k_rounds_fused for real-valued fp64 instances too.  The rule: only when
+// its median time per round is below the launch-per-round one by more than the run-to-run spread at both shapes of
+// scripts/f64_real_throughput.py; not shown so far, so such calls keep a launch per round and nlmc_pt_rounds_fused reaches the kernel.
+constexpr bool ROUNDS_REAL_IN_LAUNCH = false;
+
 // n_rounds rounds of a context that owns whole ladders.  Where k_rounds_fused qualifies (nlmc_pt_rounds_fused's conditions, the
 // residency of all workgroups among them; NLMC_NO_PERSISTENT switches it off) the rounds run inside its launches, every swap
 // included.  Otherwise n_rounds sweep launches + ONE swap launch: launch i decides the swap of round i - 1 in its prologue
@@ -2543,7 +2550,7 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
     HIP_TRY(c, hipSetDevice(c->device));
     const int L = c->ladder_len, T = sweeps_per_round;
     begin_sweep_call(c);
-    if (!c->knobs.no_persistent && arith != ARITH_R64) {       // (k_rounds_fused has no real-valued variant)
+    if (!c->knobs.no_persistent && (arith != ARITH_R64 || ROUNDS_REAL_IN_LAUNCH)) {
         bool resident = false;
         int rc = rounds_in_launch(c, fslot, arith, n_rounds, T, sweep0, round0, seed, n_pairs, resident);
         if (rc || resident) return rc;

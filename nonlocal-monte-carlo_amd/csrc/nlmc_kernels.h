@@ -2542,6 +2542,7 @@ struct RoundsArgs {
     const int32_t *loff, *nlev, *himax, *send, *npos;      // plan arrays AT the first window; window r lies r strides further
     const int2 *head;
     const EdgeQ *ell;
+    const double *val;               // the real-valued variant's fp64 value plane AT the first window (NLMC_FZ_VAL_WORDS * pstride doubles per window), or nullptr
     int ladder_len, n_pairs, n_ladders;
     uint32_t round0;
     const int32_t *plan_pairs;       // [n_rounds][n_ladders][n_pairs][2] at round0
@@ -2592,7 +2593,10 @@ __device__ __forceinline__ bool rounds_wait_record(rounds_rec_gptr rec, rounds_s
 typedef const SweepArgs __attribute__((address_space(4))) *sweep_args_cptr;
 typedef const RoundsArgs __attribute__((address_space(4))) *rounds_args_cptr;
 
-template <bool DIAG, int FMT, bool F64>
+// R64 (with F64): the real-valued fp64 variant (k_sweep_fused<.., R64>) on the windows' value plane.  It has no K tables (the launch's
+// LDS is the f32 mode's, kt = 0): keep_kt and the slot remembered in sh[4] then decide nothing.  Its uniform tables are the fp64 mode's
+// high words, so the carry of the next round's first two tables is the same.
+template <bool DIAG, int FMT, bool F64, bool R64 = false>
 __global__ __launch_bounds__(1024) void k_rounds_fused(const SweepArgs *ap_g, const RoundsArgs *qp_g)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -2638,13 +2642,14 @@ __global__ __launch_bounds__(1024) void k_rounds_fused(const SweepArgs *ap_g, co
             const bool has_next = r + 1 < q.n_windows_avail && q.nlev[r + 1] > 0;
             const FusedWin W{q.loff + (size_t)r * (NLMC_LCAP + 1), q.send + (size_t)r * a.n_sweeps, q.ell + (size_t)r * PS * NLMC_FZ_W, q.head + (size_t)r * PS,
                              has_next ? q.head + (size_t)(r + 1) * PS : nullptr, has_next ? q.ell + (size_t)(r + 1) * PS * NLMC_FZ_W : nullptr,
-                             has_next ? q.npos[r + 1] : 0, q.nlev[r], q.himax[r], a.sweep0 + (uint32_t)(r * a.n_sweeps)};
+                             has_next ? q.npos[r + 1] : 0, q.nlev[r], q.himax[r], a.sweep0 + (uint32_t)(r * a.n_sweeps),
+                             R64 ? q.val + (size_t)r * NLMC_FZ_VAL_WORDS * PS : nullptr};
             const uint32_t gcr = a.rng_stride ? (uint32_t)((c / a.rng_ladder_len) * a.rng_stride + a.rng_base + slot) : (uint32_t)(a.chain_base + c);
             long long e_loc = 0;
 #ifdef NLMC_STAMPS
             const long long st_round = (long long)__builtin_readcyclecounter();
 #endif
-            fused_window<DIAG, false, false, FMT, F64>(a, W, lds_raw, slot, gcr, e_loc, carried, keep_kt, carry ? 2 : 0);
+            fused_window<DIAG, false, false, FMT, F64, R64>(a, W, lds_raw, slot, gcr, e_loc, carried, keep_kt, carry ? 2 : 0);
 #ifdef NLMC_STAMPS
             // the level loop left this round's per-wave sums in words 4-6: those of the launch's last but one round (carried tables in,
             // tables of the next round made) move to words 0-2; words 3 / 7: prologue + level loop of that / of the last round

@@ -376,6 +376,64 @@ class LocalTempering:
         self.rounds_done += 1
         return outs
 
+    def run_rounds(self, n_rounds, n_sweeps):
+        """`n_rounds` rounds of `n_sweeps` sweeps + one swap round each, without outputs -- same bits as round(n_sweeps) called
+        n_rounds times, which is what everything that does not qualify falls back to.  ShardedTempering.run_rounds' rule: no NMC
+        slots, swap pairs, every context owns whole ladders, one fused window per round, an engine with pt_rounds_deferred,
+        NLMC_NO_DEFERRED unset.  Every context is handed the rest of its planned chunk at a time (the engine picks the route:
+        Engine.pt_rounds_deferred); the calls are asynchronous, so all contexts have their chunk queued before any of them is
+        waited for.  A context whose engine refuses is not asked again and runs its rounds one by one from then on (whole ladders:
+        the contexts never meet).  Counters: deferred_rounds (rounds every context took in batched calls), deferred_calls, and
+        rounds_routes (per context: last_rounds_route() after its last batched call, or None)."""
+        n_rounds, n_sweeps = int(n_rounds), int(n_sweeps)
+        pls = self._planners
+        if not hasattr(self, "rounds_routes"):
+            self.deferred_rounds, self.deferred_calls = 0, 0
+            self.rounds_routes = [None] * len(self.engs)
+            self._rounds_refused = [False] * len(self.engs)
+        eligible = bool(not self.nmc and self.n_pairs > 0 and self.whole_ladders and pls
+                        and not os.environ.get("NLMC_NO_DEFERRED")
+                        and all(pl.window == n_sweeps == pl.S for pl in pls)
+                        and all(hasattr(e, "pt_rounds_deferred") for e in self.engs))
+        done = 0
+        while done < n_rounds:
+            ii = self.rounds_done - (self._planner_round0 if pls else 0)
+            if not eligible or not (0 <= ii < pls[0].R) or all(self._rounds_refused):
+                self.round(n_sweeps)
+                done += 1
+                continue
+            # this chunk's schedules and pair selections, for the contexts that are still asked (the same chunk for all of them)
+            k = n_rounds - done
+            for j, pl in enumerate(pls):
+                if self._rounds_refused[j]:
+                    continue
+                if not (pl._fused_from <= ii < pl._fused_to):
+                    pl._plan(ii, True)
+                if pl._fused_from <= ii < pl._fused_to:
+                    k = min(k, pl._fused_to - ii)
+                else:
+                    self._rounds_refused[j] = True           # (the instance does not take fused windows after all)
+            if all(self._rounds_refused):
+                continue
+            one_by_one = []
+            for j, e in enumerate(self.engs):
+                if not self._rounds_refused[j] and e.pt_rounds_deferred(k, n_sweeps, self.seed, self.sweeps_done, self.rounds_done,
+                                                                        self.n_pairs, precision=self.precision):
+                    self.rounds_routes[j] = e.last_rounds_route() if hasattr(e, "last_rounds_route") else None
+                    self.deferred_calls += 1
+                else:
+                    self._rounds_refused[j] = True           # stop asking; the reason is in e.rounds_fused_refusal
+                    one_by_one.append(j)
+            for j in one_by_one:                             # the same k rounds of a context that was refused: round()'s two calls
+                for r in range(k):
+                    pls[j].sweep(ii + r)
+                    self.engs[j].pt_swap_philox(self.rounds_done + r, self.seed, self.n_pairs, want_log=False)
+            if not one_by_one:
+                self.deferred_rounds += k
+            self.sweeps_done += k * n_sweeps
+            self.rounds_done += k
+            done += k
+
     def slots(self):
         if len(self.engs) == 1 or not self.whole_ladders:
             return self.engs[0].pt_slots()

@@ -226,7 +226,8 @@ class Engine:
     def set_fused_f64_real(self, on=True):
         """Opt-in: the fp64 mode runs on fused windows for real couplings and fields too (include/nlmc.h:
         nlmc_set_fused_f64_real) -- same bits as sweep by sweep.  Plans made while it is on carry an fp64 value plane (72 more
-        bytes per schedule position).  Changing the setting drops the current fused plans."""
+        bytes per schedule position).  sweep_philox, pt_rounds_deferred and pt_rounds_fused all take such instances then.  Changing
+        the setting drops the current fused plans."""
         self._ck(self._L.nlmc_set_fused_f64_real(self._ctx, 1 if on else 0))
         self.fused_f64_real = bool(on)
 
@@ -447,8 +448,10 @@ class Engine:
         self._ck(self._L.nlmc_pt_plan(self._ctx, int(round0), int(n_rounds), int(seed), int(n_pairs)))
 
     def pt_rounds_fused(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
-        """n_rounds whole rounds (sweeps + swap round) inside cooperative launches (include/nlmc.h: nlmc_pt_rounds_fused).  True when the
-        rounds were queued, False when the context / plans do not qualify (nothing was run: drive the rounds one by one)."""
+        """n_rounds whole rounds (sweeps + swap round) inside cooperative launches (include/nlmc.h: nlmc_pt_rounds_fused), in any of the
+        three arithmetics: "f32", "f64" on dyadic instances, "f64" on real-valued ones with set_fused_f64_real on.  True when the
+        rounds were queued, False when the context / plans do not qualify (nothing was run: drive the rounds one by one; the reason
+        is in rounds_fused_refusal)."""
         prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
         rc = self._L.nlmc_pt_rounds_fused(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
                                           int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs))
@@ -461,7 +464,9 @@ class Engine:
     def pt_rounds_deferred(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
         """n_rounds rounds on the route that fits (include/nlmc.h: nlmc_pt_rounds_deferred): inside k_rounds_fused launches where all
         chains are resident at once, otherwise n_rounds sweep launches (each decides the previous round's swap in its prologue) + one
-        swap launch; last_rounds_route() tells which.  True when queued, False when the context / plans do not qualify."""
+        swap launch; last_rounds_route() tells which.  Real-valued "f64" instances (set_fused_f64_real) keep the launch per round
+        by default (include/nlmc.h says why); pt_rounds_fused asks for their k_rounds_fused variant by name.  True when queued, False
+        when the context / plans do not qualify.  What LocalTempering.run_rounds and ShardedTempering.run_rounds call."""
         prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
         rc = self._L.nlmc_pt_rounds_deferred(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
                                              int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs))

@@ -390,13 +390,17 @@ class NPT(Common):
                 lt.log_begin(rounds)
             k = self.num_sweeps_read_per_swap
             last, e_last, E_cols, slots_last = None, None, None, np.arange(G, dtype=np.int32) % R
-            for ii in range(rounds):
-                is_last = ii == rounds - 1
-                if is_last:
-                    slots_last = lt.slots()
-                if not is_last:
-                    lt.round(S)
-                elif return_trace is not None:
+            # rounds 0 .. rounds - 2 need no output: LocalTempering hands them to the engine a planned chunk at a time (run_rounds:
+            # k_rounds_fused where the contexts qualify, round by round otherwise -- same bits); the last round is a call of its own
+            if rounds > 1:
+                if hasattr(lt, "run_rounds"):
+                    lt.run_rounds(rounds - 1, S)
+                else:                                    # (a ladder cut across ranks: one all-gather per round)
+                    for ii in range(rounds - 1):
+                        lt.round(S)
+            for ii in range(max(0, rounds - 1), rounds):
+                slots_last = lt.slots()
+                if return_trace is not None:
                     outs = lt.round(S, record_stride=1, energy_columns=min(k, S) if (0 < k and S > 0) else 0)
                     if nmc:
                         last, E_cols = self._assemble_mixed(lt, outs, S, N, min(k, S) if (0 < k and S > 0) else 0, "spins")
