@@ -137,9 +137,16 @@ int nlmc_plan_philox(nlmc_ctx *ctx, int precision, int order_mode, uint32_t swee
  * sweep0 (a whole number of planned windows) runs on it -- with per-sweep outputs or a temperature per sweep when the
  * snapshot slots of that variant fit in LDS; every other call takes the sweep-by-sweep path.  Results are bit-identical either way.  out_planned: number of windows that got a
  * fused schedule (0 when the instance does not qualify: n < 256 or n > 11264,
- * window < 3 or > 64, or the three threshold tables do not fit in LDS next to the spins; a window is also left out when its
+ * window < 3 or > 64, or the three threshold tables do not fit in LDS next to the spins and the flags -- 14 bytes per spin, n rounded
+ * up to a multiple of 16, plus 64 within 150 KB: that bound bites first, the largest n that gets a fused schedule is 10960, and
+ * 11264 is only what the planner itself could hold; a window is also left out when its
  * schedule is deeper than 1023 levels or when, in one of its sweeps, a spin has more than 255 neighbours that come before it in the
- * order -- a hub row: the levelizer counts them in eight bits). */
+ * order -- a hub row: the levelizer counts them in eight bits).
+ * A level holds at most 64 positions per worker wave of the sweep workgroup.  An update whose earliest level is full goes to the
+ * next level with room (level fill; NLMC_NO_LEVEL_FILL=1, read at nlmc_create: every update keeps its earliest level and a wider
+ * level is cut into consecutive levels of that width instead, which moves everything behind it one level back).  Which updates
+ * are moved depends on the order in which the planner's threads reach a level, so two plans of the same window may differ by a
+ * level or two in depth, as they always could in the positions inside a level; the sweeps' results depend on neither. */
 int nlmc_plan_philox_fused(nlmc_ctx *ctx, uint32_t sweep0, int n_windows, int window, uint64_t seed, int32_t *out_planned);
 /* Which precisions may run on fused windows of `window` sweeps on this context: bit 0 = NLMC_F32, bit 1 = NLMC_F64.  The fp64
  * mode (the reference's arithmetic, NMC/nmc.py:86-87: fp64 field, 53-bit uniform) qualifies when every coupling AND every field

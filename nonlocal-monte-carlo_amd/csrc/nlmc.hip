@@ -71,6 +71,7 @@ struct Knobs {
     bool no_dbuf = false;            // NLMC_NO_DBUF: sweep-by-sweep kernels keep one copy of the per-sweep uniforms in LDS
     int big_per_level = -1;          // NLMC_BIG_PER_LEVEL: long chains run one launch per level (1) / per window (0); -1: by count
     bool no_bank_aware = false;      // NLMC_NO_BANK_AWARE: the fused planner does not place items by LDS bank
+    bool no_level_fill = false;      // NLMC_NO_LEVEL_FILL: the fused planner gives every update its earliest level and splits full levels
     bool fz_stats = false;           // NLMC_FZ_STATS: the fused planner prints the phase cycle counts of window 0 on stderr
     unsigned tie_mask = 0xFFFFFFFFu; // NLMC_F64_TIE_MASK: high-word mask of the fp64 fused kernels' exact-path test (test knob)
     bool no_persistent = false;      // NLMC_NO_PERSISTENT: nlmc_pt_rounds_fused refuses, nlmc_pt_rounds_deferred launches per round
@@ -95,7 +96,7 @@ Knobs read_knobs()
     k.no_fused = on("NLMC_NO_FUSED"); k.no_fused64 = on("NLMC_NO_FUSED64"); k.no_fused_out = on("NLMC_NO_FUSED_OUT");
     k.no_warm = on("NLMC_NO_WARM"); k.no_prio = on("NLMC_FUSED_NOPRIO"); k.no_dbuf = on("NLMC_NO_DBUF");
     k.big_per_level = on("NLMC_BIG_PER_LEVEL") ? num("NLMC_BIG_PER_LEVEL", 0) != 0 : -1;
-    k.no_bank_aware = on("NLMC_NO_BANK_AWARE"); k.fz_stats = on("NLMC_FZ_STATS");
+    k.no_bank_aware = on("NLMC_NO_BANK_AWARE"); k.no_level_fill = on("NLMC_NO_LEVEL_FILL"); k.fz_stats = on("NLMC_FZ_STATS");
     if (const char *s = getenv("NLMC_F64_TIE_MASK")) k.tie_mask = (unsigned)strtoul(s, nullptr, 0);
     k.no_persistent = on("NLMC_NO_PERSISTENT"); k.no_deferred = on("NLMC_NO_DEFERRED");
     k.lbp_group = num("NLMC_LBP_GROUP", 0); k.lbp_poll_budget = num("NLMC_LBP_POLL_BUDGET", 0); k.lbp_global = on("NLMC_LBP_GLOBAL");
@@ -1801,6 +1802,7 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
     P.workers = fused_workers(c, fused_block(c));
     P.gen0 = fused_gen0(c, fused_block(c));
     a.level_cap = P.workers * 64;
+    a.level_fill = c->knobs.no_level_fill ? 0 : 1;
     a.pstride = P.pstride;
     a.tab_words = c->n_pad;
     a.k_dummy = c->n_pad;

@@ -244,6 +244,8 @@ struct FusedLevelizeArgs {
     int T;                    // sweeps per window
     uint32_t seed_lo, seed_hi, sweep0;     // window w covers sweeps sweep0 + w T ... + T - 1 (shared order, group 0)
     int level_cap;            // 64 x worker waves of k_sweep_fused
+    int level_fill;           // 1: an update whose level is full (level_cap positions) takes the next one with room; 0: every update
+                              // gets its earliest level and wider levels are split when published (NLMC_NO_LEVEL_FILL)
     int pstride;              // schedule positions reserved per window (multiple of 64, >= T n + 64 NLMC_LCAP)
     int tab_words;            // 4-byte words per threshold table of k_sweep_fused (its LDS stride / 4)
     int k_dummy;              // LDS address of the scratch spin that dummy (padding) items update: n_pad
@@ -290,6 +292,12 @@ __global__ void k_fused_adjacency(int n, const int32_t *rowptr, const int32_t *c
 // precede it; (2) topological passes: a spin with cnt == 0 is final at level m + 1 and pushes that level to its later
 // neighbours (LDS atomicMax on m, then decrement of their cnt) -- every edge is handled once per sweep, a pass costs a
 // look at the thread's own <= NLMC_FZ_SPT counters plus the pushes of the spins that became final.
+// Level fill (FusedLevelizeArgs::level_fill): a level holds level_cap positions.  A spin that becomes final claims its
+// positions at level m + 1 and, where that level is full, at the next one with room; the level that accepts the claim is
+// the one it is stored at and pushes on.  Every constraint above reads "at least one level after X" and X always pushes the
+// level it really got, so a later level is always legal.  Which updates are turned away depends on the order in which the
+// claims reach the LDS, so two plans of one window may differ in their level count by a level or two -- as the positions
+// inside a level always did; the results of the sweeps do not depend on either.
 // LDS: key u32[n] | m u32[n] | g u16[n] | cnt u8[n] | queue u16[n] | hist u32[LCAP + 2] | histL u32[LCAP + 2]
 #define NLMC_FZ_SPT 11         // spins per thread: n <= 11 * 1024
 __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
@@ -365,14 +373,29 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
                 const int k = (int)queue[idx];
                 const int re = a.g.rowptr[k + 1], rs = a.g.rowptr[k];
                 const uint4 a0 = a.adj[2 * k], a1 = a.adj[2 * k + 1];
-                const int lv = min((int)mx[k] + 1, 65535);
+                int lv = min((int)mx[k] + 1, 65535);
+                if (lv <= NLMC_LCAP) {
+                    // hist[lv]: positions taken in the low half, long rows among them in the high half -- one atomic per claim.
+                    const uint32_t npos = re - rs > NLMC_FZ_W ? 2u : 1u, inc = npos | ((npos - 1u) << 16);
+                    if (a.level_fill) {
+                        // Capacity claim, add and undo: the add takes the positions, and where that runs over the cap the same
+                        // amount is taken back and the update tries the next level.  The low half is never below the successful
+                        // claims, so a level is never overfilled; between a failed add and its undo a level may look fuller than
+                        // it is and turn away a claim it had room for (a later level is always legal).  At most 1024 claims of 2
+                        // positions are in flight: the low half cannot carry into the high one.
+                        for (;;) {
+                            const uint32_t old = atomicAdd(&hist[lv], inc);
+                            if ((old & 0xFFFFu) + npos <= (uint32_t)a.level_cap) break;
+                            atomicSub(&hist[lv], inc);
+                            if (++lv > NLMC_LCAP) break;       // deeper than the sweep kernels' level list: the window fails below
+                        }
+                    } else {
+                        atomicAdd(&hist[lv], inc);
+                    }
+                }
                 g[k] = (uint16_t)lv;
                 glv[(size_t)t * n + k] = (uint16_t)lv;
                 lmax = max(lmax, lv);
-                if (lv <= NLMC_LCAP) {
-                    atomicAdd(&hist[lv], 1u);
-                    if (re - rs > 8) atomicAdd(&histL[lv], 1u);
-                }
                 const uint32_t kk = key[k];
                 const uint32_t aw[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
                 uint32_t kj[NLMC_FZ_ADJ];
@@ -414,8 +437,12 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
     // partly filled wave (no per-lane validity: a wave either holds a chunk of a level or it does not).  A row longer
     // than NLMC_FZ_W entries takes TWO neighbouring positions (an even / odd lane pair: entries 0-7 and 8-15, the two
     // partial fields are added with one cross-lane move), so that every wave of a level does the same amount of work;
-    // the pairs come first in their level.  Levels wider than level_cap positions (a multiple of 64) are split.
-    // off[] counts chunks; hist[lv] becomes the level's first position, histL[lv] (was: its number of long rows) the
+    // the pairs come first in their level.  With level_fill no level is wider than level_cap positions (a multiple of 64: the
+    // claims of the passes above see to it), so the loop over p below publishes every level once; without it a wider level
+    // is split there into consecutive sub-levels of level_cap positions (any subset of an independent set is independent),
+    // and the split stays as the guard of the invariant.  send[] is strictly increasing in t either way: update (t + 1, k)
+    // waits for (t, k), so sh_lmax[t + 1] > sh_lmax[t], and the walk over t_next meets every sweep's last level in turn.
+    // off[] counts chunks; hist[lv] (was: positions | long rows << 16) becomes the level's first position, histL[lv] the
     // position behind its last real item.
     if (tid == 0) {
         const int L = sh_lmax[T - 1];
@@ -423,7 +450,7 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
         int m = 0, run = 0, t_next = 0, himax = 0;
         if (!sh_fail) {
             for (int lv = 1; lv <= L; ++lv) {
-                const int cl = (int)histL[lv], width = (int)hist[lv] + cl;
+                const int cl = (int)(hist[lv] >> 16), width = (int)(hist[lv] & 0xFFFFu);
                 hist[lv] = (uint32_t)run;
                 himax = max(himax, (2 * cl + 63) >> 6);
                 histL[lv] = (uint32_t)(run + width);

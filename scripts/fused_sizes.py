@@ -1,4 +1,5 @@
-"""Fused-window vs sweep-by-sweep schedule across instance sizes (same bits, us per launch)."""
+"""Fused-window vs sweep-by-sweep schedule across instance sizes (same bits, us per launch).  SIZES="N:R,N:R,..." replaces the
+default list of (spins, chains); NLMC_NO_LEVEL_FILL=1 in the environment gives the schedule without level fill."""
 import os, sys
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -7,7 +8,10 @@ from conftest import load_product
 from helpers import make_instance, init_spins
 P = load_product()
 T, W = 10, int(os.environ.get("W", 20))
-for N, R in ((300, 1024), (1000, 256), (1000, 1024), (1600, 512), (2048, 512), (4096, 256), (7000, 256), (10000, 256)):
+SIZES = ((300, 1024), (1000, 256), (1000, 1024), (1600, 512), (2048, 512), (4096, 256), (7000, 256), (10000, 256))
+if os.environ.get("SIZES"):
+    SIZES = tuple(tuple(int(v) for v in s.split(":")) for s in os.environ["SIZES"].split(","))
+for N, R in SIZES:
     J, h = make_instance(N, seed=5)
     inst = P.Instance(J, h)
     res = {}
