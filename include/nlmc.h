@@ -122,10 +122,33 @@ int nlmc_sweep_stream(nlmc_ctx *ctx, int n_sweeps, const int32_t *perm, const do
  * (global index sweep0 + t) visits spins in ascending order of philox(k, t, group, ORDER) and spin k of chain c
  * draws one word of philox(k>>2, t, c, UNIFORM) (f32: 32 bits -> logistic threshold; f64: its high 27 bits + the high 26 bits of the same word of philox(k>>2, t, c, UNIFORM_LO) -> 53-bit uniform); results are a pure function of (seed, global chain id, sweep index, spin) and
  * therefore independent of how chains are sharded over GPUs.
- *   beta : as above, or NULL to take each chain's beta from the PT ladder (nlmc_pt_init). */
+ *   beta : as above, or NULL to take each chain's beta from the PT ladder (nlmc_pt_init).
+ * Three routes compute a call, with the same bits: sweep by sweep (a level schedule per order, one workgroup per chain), fused
+ * windows (nlmc_plan_philox_fused; n >= 256) and, for chains of at most NLMC_LANE_N spins, one chain per lane
+ * (nlmc_set_lane_sweeps).  nlmc_last_sweep_route tells which one the most recent call took. */
 int nlmc_sweep_philox(nlmc_ctx *ctx, int precision, int order_mode, int n_sweeps, uint32_t sweep0, uint64_t seed,
                       const double *beta, int chain_stride, int sweep_stride, int record_stride, int8_t *out_spins,
                       double *out_energy, double *out_min_energy, int32_t *out_argmin, int8_t *out_argmin_state);
+
+/* Chain-per-lane sweeps (csrc/nlmc_lanes.h): a wave runs 64 chains, one per lane, through the same sequential sweep in lock step, the
+ * spins transposed in LDS -- no level schedule, no barrier.  Made for many chains of a short or dense instance (complete graphs of
+ * 8..40 spins, Chimera-128: below the fused windows' floor, and one spin per level on a complete graph), where a workgroup per chain
+ * leaves most of a compute unit idle.  mode: 0 off (the default); 1 auto -- nlmc_sweep_philox calls with n < 256 over at least
+ * NLMC_LANE_AUTO_ROWS rows (chains of the call) take it; 2 force -- every nlmc_sweep_philox call with n <= NLMC_LANE_N takes it
+ * (longer chains run as before: never an error).  Everything nlmc_sweep_philox accepts runs there: both precisions, both order
+ * modes, phase flags, a temperature per sweep, ladder temperatures, chain subsets (shared order), the running minimum, every
+ * output.  Results are bit-identical to the other routes.  nlmc_last_sweep_fused is 0 after such a call, nlmc_last_schedule_stats
+ * reports the visiting orders built and 0 levels, the timings count the order kernel as the levelize half. */
+#define NLMC_LANE_N 1024
+/* Rows from which `auto` takes the lane route.  A measured constant: the smallest row count from which the
+ * route is at least 1.2 times the sweep-by-sweep route on every instance of the measured grid in both precisions; 2147483647
+ * (never) while no row count qualifies. */
+#define NLMC_LANE_AUTO_ROWS 2147483647
+int nlmc_set_lane_sweeps(nlmc_ctx *ctx, int mode);
+/* Route of the most recent nlmc_sweep_philox call: NLMC_ROUTE_NONE before any, a call whose launches mixed routes reports
+ * NLMC_ROUTE_STEPWISE. */
+enum { NLMC_ROUTE_NONE = 0, NLMC_ROUTE_STEPWISE = 1, NLMC_ROUTE_FUSED = 2, NLMC_ROUTE_LANES = 3 };
+int nlmc_last_sweep_route(const nlmc_ctx *ctx);
 
 /* Optional: build and cache the level schedules of sweeps [sweep0, sweep0+n_sweeps) ahead of time (shared-order
  * philox mode).  Later nlmc_sweep_philox calls inside that range with the same seed and precision skip their

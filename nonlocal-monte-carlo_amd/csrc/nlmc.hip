@@ -7,6 +7,7 @@
 #include "nlmc_nmc.h"
 #include "nlmc_probe.h"
 #include "nlmc_big.h"
+#include "nlmc_lanes.h"
 #include "nlmc_host.h"
 
 #include <dlfcn.h>
@@ -79,6 +80,9 @@ struct Knobs {
     int lbp_group = 0;               // NLMC_LBP_GROUP: workgroups per loopy-BP problem (1..8; 0: by size)
     int lbp_poll_budget = 0;         // NLMC_LBP_POLL_BUDGET: polls of the loopy-BP group barrier (0: the default; test knob)
     bool lbp_global = false;         // NLMC_LBP_GLOBAL: loopy BP never takes the LDS-resident kernel
+    size_t lane_scratch = (size_t)256 << 20;   // NLMC_LANE_SCRATCH: bytes of visiting orders one window of chain-per-lane sweeps may hold (test knob)
+    int lane_rng = -1;               // NLMC_LANE_RNG: chain-per-lane sweeps make the Philox call per update (0) / keep a table per sweep in LDS
+                                     // where it fits (1); -1: the default
     int dbg_flags = 0;               // NLMC_DBG_FLAGS: timing experiments of NLMC_DEBUG_KNOBS builds
     std::string stamp_file;          // NLMC_STAMP_FILE: NLMC_STAMPS builds dump the last launch's per-wave cycle sums here
 };
@@ -100,6 +104,8 @@ Knobs read_knobs()
     if (const char *s = getenv("NLMC_F64_TIE_MASK")) k.tie_mask = (unsigned)strtoul(s, nullptr, 0);
     k.no_persistent = on("NLMC_NO_PERSISTENT"); k.no_deferred = on("NLMC_NO_DEFERRED");
     k.lbp_group = num("NLMC_LBP_GROUP", 0); k.lbp_poll_budget = num("NLMC_LBP_POLL_BUDGET", 0); k.lbp_global = on("NLMC_LBP_GLOBAL");
+    if (const char *s = getenv("NLMC_LANE_SCRATCH")) k.lane_scratch = std::max<size_t>(1, (size_t)strtoull(s, nullptr, 0));
+    k.lane_rng = on("NLMC_LANE_RNG") ? (num("NLMC_LANE_RNG", 0) != 0) : -1;
     k.dbg_flags = num("NLMC_DBG_FLAGS", 0);
     if (const char *s = getenv("NLMC_STAMP_FILE")) k.stamp_file = s;
     return k;
@@ -174,6 +180,11 @@ struct nlmc_ctx {
     DevBuf<uint8_t> cmask_scratch; // chains too long for LDS: the two membership arrays of k_cluster_mask per problem
     DevBuf<int32_t> big_flag;     // ... "changed" words of the levelizer's relaxation passes
     DevBuf<long long> big_esum;   // ... energy deltas of the running sweep per block row
+    // chain-per-lane sweeps (csrc/nlmc_lanes.h)
+    int lane_mode = 0;            // nlmc_set_lane_sweeps: 0 off, 1 auto, 2 force
+    int last_route = 0;           // nlmc_last_sweep_route: NLMC_ROUTE_* of the most recent sweep call
+    int64_t stat_lane_orders = 0; // visiting orders the most recent sweep call built for the lane kernels
+    DevBuf<uint16_t> lane_perm;   // [orders of a window][n]
     DevBuf<int32_t> nmc_status;   // sticky: a backbone inference diverged at its first lambda
     DevBuf<double> nmc_thr;       // thresholds of the cluster growth
     std::vector<double> nmc_thr_host, tab_host, lbp_eps_host, lbp_lams_host;   // contents of the device copies (uploads skipped when unchanged)
@@ -1090,6 +1101,92 @@ int run_sweeps_stepwise(nlmc_ctx *c, bool stream_mode, int precision, int order_
     return NLMC_OK;
 }
 
+// Whether a philox call over R rows takes the chain-per-lane kernels (nlmc_set_lane_sweeps): forced, whenever the chain fits; auto,
+// below the fused windows' floor from NLMC_LANE_AUTO_ROWS rows on (include/nlmc.h: where the route was measured ahead)
+bool lanes_route(const nlmc_ctx *c, int R)
+{
+    if (c->knobs.force_big || c->n > NLMC_LANE_N) return false;
+    if (c->lane_mode == 2) return true;
+    return c->lane_mode == 1 && c->n < 256 && R >= NLMC_LANE_AUTO_ROWS;
+}
+
+// LDS of k_sweep_lanes: transposed spins | transposed flags | (where it fits) one sweep's random numbers, a word per (spin, lane)
+struct LaneLds { int flags_off, u_off; bool tab; size_t total; };
+LaneLds lane_lds(const nlmc_ctx *c)
+{
+    LaneLds L{};
+    const size_t plane = (size_t)c->n_pad * NLMC_LANE_STRIDE;
+    L.flags_off = (int)plane;
+    const size_t state = plane * (c->has_flags ? 2 : 1), tab = (size_t)((c->n + 3) / 4 * 4) * 256;
+    L.u_off = (int)state;
+    // the table where four waves still share a compute unit (one per SIMD): 40 KB per wave
+    L.tab = c->knobs.lane_rng != 0 && state + tab <= (size_t)40 * 1024;
+    L.total = state + (L.tab ? tab : 0);
+    return L;
+}
+
+const void *lanes_kernel(bool f64, bool per_chain)
+{
+    static const void *const table[2][2] = {
+        {reinterpret_cast<const void *>(k_sweep_lanes<false, false>), reinterpret_cast<const void *>(k_sweep_lanes<false, true>)},
+        {reinterpret_cast<const void *>(k_sweep_lanes<true, false>), reinterpret_cast<const void *>(k_sweep_lanes<true, true>)}};
+    return table[f64 ? 1 : 0][per_chain ? 1 : 0];
+}
+
+// The chain-per-lane half of run_sweeps: windows of sweeps -> k_lane_orders (the "levelize" half of the timings) -> k_sweep_lanes, one
+// launch per window.  Windows are cut against the scratch bound of run_sweeps_stepwise.  The outputs stay in the context's buffers.
+int run_sweeps_lanes(nlmc_ctx *c, int precision, int order_mode, int n_sweeps, uint32_t sweep0, uint64_t seed, const double *tab_dev,
+                     int tab_cs, int tab_ss, bool use_slots, bool want_energy, bool want_min, bool want_state, int rec)
+{
+    const int R = c->sub_count(), n = c->n;
+    if (c->cur != c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the order scratch is shared with the main stream's sweeps)
+    const int per_chain = order_mode == NLMC_ORDER_PER_CHAIN ? 1 : 0;
+    if (per_chain && c->subset != 0) return fail(c, NLMC_ERR_UNSUPPORTED, "chain subsets run shared-order philox sweeps only");
+    const size_t per_sweep_orders = per_chain ? (size_t)R : 1;
+    const size_t bytes_per_sweep = per_sweep_orders * (size_t)n * sizeof(uint16_t);
+    const int W = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_sweeps, c->knobs.lane_scratch / bytes_per_sweep));
+    if (per_sweep_orders * (size_t)W > (size_t)INT_MAX) return fail(c, NLMC_ERR_UNSUPPORTED, "too many per-chain orders in one window");
+    HIP_TRY(c, c->lane_perm.reserve(per_sweep_orders * (size_t)W * (size_t)n));
+    const LaneLds L = lane_lds(c);
+    const void *kfun = lanes_kernel(precision == NLMC_F64, per_chain != 0);
+    { int rc = ensure_lds(c, kfun, L.total); if (rc) return rc; }
+    for (int t0 = 0; t0 < n_sweeps; t0 += W) {
+        const int w = std::min(W, n_sweeps - t0);
+        TimerSpan ts;
+        if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->cur); if (rc) return rc; }
+        LaneOrderArgs oa{};
+        oa.n = n; oa.n_sweeps = w; oa.per_chain = per_chain; oa.chain_base = c->chain_base;
+        oa.seed_lo = (uint32_t)seed; oa.seed_hi = (uint32_t)(seed >> 32); oa.sweep0 = sweep0 + (uint32_t)t0;
+        oa.perm = c->lane_perm.p;
+        const size_t n_orders = per_sweep_orders * (size_t)w;
+        hipLaunchKernelGGL(k_lane_orders, dim3((unsigned)n_orders), dim3(256), 0, c->cur, oa);
+        HIP_TRY(c, hipGetLastError());
+        c->stat_lane_orders += (int64_t)n_orders;
+        { int rc = span_mid(c, ts); if (rc) return rc; }
+
+        SweepArgs a = sweep_args(c, sweep0 + (uint32_t)t0, w, seed, tab_dev + (size_t)t0 * tab_ss, tab_cs, tab_ss, use_slots);
+        a.per_chain = per_chain;
+        a.energy_sink = c->energy_sink;
+        a.etrace = want_energy ? c->etrace.p : nullptr;
+        a.trace_sweeps = n_sweeps;
+        a.t0 = t0;
+        a.rec_stride = rec ? rec : 1;
+        a.strace = rec ? c->strace.p : nullptr;
+        a.emin = want_min ? c->emin.p : nullptr;
+        a.best = (want_min && want_state) ? c->best.p : nullptr;
+        a.lane_perm = c->lane_perm.p; a.lane_rows = R; a.lane_diag = c->has_diag ? 1 : 0; a.lane_tab = L.tab ? 1 : 0;
+        a.lds_flags_off = L.flags_off; a.lds_u_off = L.u_off;
+        void *kargs[] = {&a};
+        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)((R + 63) / 64)), dim3(64), kargs, L.total, c->cur));
+        HIP_TRY(c, hipGetLastError());
+        { int rc = span_end(c, ts); if (rc) return rc; }
+        if (c->ev_accumulate) c->launches_timed++;
+        c->launches_sweep++;
+        c->launches_total++;
+    }
+    return NLMC_OK;
+}
+
 // Shared driver: windows of sweeps -> (levelize) -> k_sweep.  `stream_mode` selects the kernel flavour.
 int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int n_sweeps, uint32_t sweep0,
                uint64_t seed, const double *tab_dev, int tab_cs, int tab_ss, bool use_slots, const uint32_t *keys_dev,
@@ -1102,6 +1199,7 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
     c->stats_pending = false;
     c->strace_nrec = 0;
     c->strace_rows = 0;
+    c->stat_lane_orders = 0;
     if (R == 0 || n_sweeps == 0) return NLMC_OK;
     { int rc = ensure_subset(c); if (rc) return rc; }
     // running minimum + argmin state: asked for through host outputs, or kept on the device for the hand-off between NMC
@@ -1121,6 +1219,9 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
     const int fslot = fused_plan_for(c, sweep0, n_sweeps, seed);
     int arith = fslot < 0 ? NOT_FUSED : fused_route(c, precision, order_mode, tab_ss != 0, c->has_flags, fslot, c->fz[fslot].T, Via::sweeps);
     if (outs && c->knobs.no_fused_out) arith = NOT_FUSED;
+    const bool lanes = !stream_mode && lanes_route(c, R);        // short chains, one per lane (csrc/nlmc_lanes.h): before the fused windows
+    if (lanes) arith = NOT_FUSED;
+    c->last_route = lanes ? NLMC_ROUTE_LANES : arith != NOT_FUSED ? NLMC_ROUTE_FUSED : NLMC_ROUTE_STEPWISE;
     if (o.out_energy) HIP_TRY(c, c->etrace.reserve((size_t)R * n_sweeps));
     if (rec) HIP_TRY(c, c->strace.reserve((size_t)R * n_rec * n));
     c->strace_nrec = n_rec;
@@ -1137,6 +1238,10 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
                                use_slots, outs, o.out_energy != nullptr, want_min, want_state, rec, outs ? j * P.T : 0, n_sweeps, arith);
             if (rc) return rc;
         }
+    } else if (lanes) {
+        int rc = run_sweeps_lanes(c, precision, order_mode, n_sweeps, sweep0, seed, tab_dev, tab_cs, tab_ss, use_slots, o.out_energy != nullptr,
+                                  want_min, want_state, rec);
+        if (rc) return rc;
     } else {
         int rc = run_sweeps_stepwise(c, stream_mode, precision, order_mode, n_sweeps, sweep0, seed, tab_dev, tab_cs, tab_ss, use_slots, keys_dev,
                                      ustream_dev, o.out_energy != nullptr, want_min, want_state, rec);
@@ -1474,7 +1579,7 @@ void nlmc_destroy(nlmc_ctx *c)
     c->spins.release(); c->best.release(); c->flags.release(); c->efix.release(); c->emin.release(); c->etrace.release();
     c->argmin.release(); c->energy.release(); c->tab.release(); c->ustream.release(); c->etrace_d.release();
     c->keys.release(); c->perm_raw.release(); c->u_raw.release(); c->stream_bad.release(); c->strace.release(); c->cfg.release(); c->snap_g.release(); c->scratch.release(); c->plan.release();
-    c->slot_mark.release(); c->sub_list_buf.release(); c->cmask.release(); c->cmask_scratch.release(); c->big_flag.release(); c->big_esum.release(); c->nmc_status.release(); c->nmc_thr.release();
+    c->slot_mark.release(); c->sub_list_buf.release(); c->cmask.release(); c->cmask_scratch.release(); c->big_flag.release(); c->big_esum.release(); c->lane_perm.release(); c->nmc_status.release(); c->nmc_thr.release();
     c->fz_glv.release(); c->fz_perm.release(); c->fz_adj.release(); c->fz_stats.release(); c->fz[0].release(); c->fz[1].release();
     c->lbp_src.release(); c->lbp_rev.release(); c->lbp_flag.release(); c->lbp_out_i.release(); c->lbp_tJ.release();
     c->lbp_eps.release(); c->lbp_ms.release(); c->lbp_lams.release(); c->lbp_w0.release(); c->lbp_w1.release();
@@ -1854,6 +1959,16 @@ int nlmc_fused_modes(nlmc_ctx *c, int window)
 
 int nlmc_last_sweep_fused(const nlmc_ctx *c) { return c && c->stat_fused_window >= 0 ? 1 : 0; }
 
+int nlmc_set_lane_sweeps(nlmc_ctx *c, int mode)
+{
+    if (!c) return NLMC_ERR_ARG;
+    if (mode < 0 || mode > 2) return fail(c, NLMC_ERR_ARG, "nlmc_set_lane_sweeps: mode must be 0 (off), 1 (auto) or 2 (force)");
+    c->lane_mode = mode;
+    return NLMC_OK;
+}
+
+int nlmc_last_sweep_route(const nlmc_ctx *c) { return c ? c->last_route : NLMC_ROUTE_NONE; }
+
 int nlmc_probe_level_round(nlmc_ctx *c, int waves, int conflict_free, int rounds, int n_workgroups, double *out_ns_per_round)
 {
     if (!c || !out_ns_per_round || waves < 1 || waves > 16 || rounds < 1 || n_workgroups < 1)
@@ -1947,6 +2062,11 @@ int nlmc_last_schedule_stats(nlmc_ctx *c, int64_t *n_orders, int64_t *n_levels)
 {
     if (!c) return NLMC_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
+    if (c->last_route == NLMC_ROUTE_LANES && c->stat_fused_window < 0) {   // chain-per-lane sweeps: visiting orders, no levels
+        if (n_orders) *n_orders = c->stat_lane_orders;
+        if (n_levels) *n_levels = 0;
+        return NLMC_OK;
+    }
     if (c->stat_fused_window >= 0) {       // one merged level list for fz_T sweeps
         if (n_orders) *n_orders = c->fz[c->stat_fused_slot].T;
         if (n_levels) *n_levels = c->fz[c->stat_fused_slot].nlev_host[(size_t)c->stat_fused_window];

@@ -807,6 +807,11 @@ struct SweepArgs {
     int f64_xmax;             // largest |X| any row can reach: max_k (sum |Jq| + |hq|)
     unsigned f64_tie_mask;    // 0xFFFFFFFF; a test knob (NLMC_F64_TIE_MASK) clears low bits so that the rare exact path runs often
     const double *fz_val;     // k_sweep_fused<.., R64>: the window's fp64 value plane (NLMC_FZ_VAL_WORDS doubles per position)
+    // chain-per-lane sweeps (k_sweep_lanes, csrc/nlmc_lanes.h)
+    const uint16_t *lane_perm;    // [orders of the launch][n] spin visited i-th
+    int lane_rows;                // rows (chains) of the call: lane l of block b owns row 64 b + l
+    int lane_diag;                // the instance has diagonal entries (left out of the energy deltas)
+    int lane_tab;                 // 1: a sweep's random numbers sit in an LDS table at lds_u_off, 0: the Philox call is made per update
     int dbg_flags;            // -DNLMC_DEBUG_KNOBS builds only (NLMC_DBG_FLAGS): 1 = no threshold production, 2 = no updates, 4 = no item loads,
                               // 512 / 1024 = bank-conflict-free addresses for the neighbour gather / the spin's own accesses (wrong results)
 };

@@ -75,6 +75,7 @@ class Engine:
         self._ahead = None
         self.fused_f64_real = False
         self._flags_on = False           # phase flags in force (set_flags / set_phase)
+        self.lane_sweeps = "off"         # set_lane_sweeps
         self.energy_scale = int(self._L.nlmc_energy_scale(self._ctx))
         self.field_scale = int(self._L.nlmc_field_scale(self._ctx))      # qs of the "f32" path: Jq = rint(J 2^qs)
 
@@ -231,6 +232,30 @@ class Engine:
         self._ck(self._L.nlmc_set_fused_f64_real(self._ctx, 1 if on else 0))
         self.fused_f64_real = bool(on)
 
+    LANE_MODES = {"off": _abi.LANES_OFF, "auto": _abi.LANES_AUTO, "force": _abi.LANES_FORCE}
+    ROUTES = {_abi.ROUTE_STEPWISE: "stepwise", _abi.ROUTE_FUSED: "fused", _abi.ROUTE_LANES: "lanes"}
+
+    def set_lane_sweeps(self, mode):
+        """Chain-per-lane sweeps for short chains (include/nlmc.h: nlmc_set_lane_sweeps): "off" (the default), "auto" (sweep_philox
+        calls with n < 256 over at least NLMC_LANE_AUTO_ROWS rows), "force" (every sweep_philox call with n <= 1024).  The results
+        are the same bits on every route; last_sweep_route() tells which one a call took."""
+        if mode not in self.LANE_MODES:
+            raise ValueError(f"set_lane_sweeps: mode must be one of {sorted(self.LANE_MODES)}, got {mode!r}")
+        self._ck(self._L.nlmc_set_lane_sweeps(self._ctx, self.LANE_MODES[mode]))
+        self.lane_sweeps = mode
+
+    def last_sweep_route(self):
+        """Route of the most recent sweep_philox call: "stepwise", "fused", "lanes", or None before any (nlmc_last_sweep_route)."""
+        return self.ROUTES.get(int(self._L.nlmc_last_sweep_route(self._ctx)))
+
+    def lanes_take(self, rows=None):
+        """Whether the context routes a sweep_philox call over `rows` rows (default: the selected chains) to the chain-per-lane
+        kernels -- the rule of nlmc_set_lane_sweeps.  Such a call needs no fused-window plan."""
+        if self.lane_sweeps == "force":
+            return self.n <= _abi.LANE_N
+        rows = self.rows() if rows is None else int(rows)
+        return self.lane_sweeps == "auto" and self.n < 256 and rows >= _abi.LANE_AUTO_ROWS
+
     def _last_fused(self):
         """Whether every launch of the most recent sweep call ran on fused windows (nlmc_last_sweep_fused)."""
         return bool(self._L.nlmc_last_sweep_fused(self._ctx))
@@ -249,6 +274,13 @@ class Engine:
         T = fused_window(S) if window is None else int(window)
         budget = self.FUSED_PLAN_BUDGET if budget_bytes is None else int(budget_bytes)
         rec_e = bool(want_recorded_energy and record_stride)
+        if S > 0 and self.lanes_take():         # the context runs this call one chain per lane: no windows to plan
+            o = self.sweep_philox(S, seed, sweep0=sweep0, beta=beta, record_stride=record_stride, want_energy=want_energy,
+                                  want_min=want_min, want_state=want_state, precision=precision)
+            self.fused_last_call = False
+            if rec_e:
+                o["energy_recorded"] = self.energy_of_recorded(o["spins"].shape[1])
+            return o
         a = getattr(self, "_ahead", None)
         if (a is not None and window is None and a.window and S == a.S and int(seed) == a.seed and (int(sweep0) - a.sweep0) % max(1, S) == 0
                 and 0 <= (int(sweep0) - a.sweep0) // max(1, S) < a.R
