@@ -321,10 +321,28 @@ int nlmc_pt_rounds_fused(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_
  * nlmc_sweep_philox + nlmc_pt_swap_philox round by round on either route. */
 int nlmc_pt_rounds_deferred(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0,
                             uint64_t seed, int n_pairs);
-/* The route the most recent nlmc_pt_rounds_fused / nlmc_pt_rounds_deferred call that ran took: NLMC_ROUNDS_IN_LAUNCH (the rounds
- * inside k_rounds_fused launches), NLMC_ROUNDS_LAUNCH_PER_ROUND, or 0 (no such call yet). */
+/* The same n_rounds rounds of short chains in launches of k_rounds_lanes (csrc/nlmc_lane_rounds.h), whatever the lane mode is: a lane
+ * owns a chain as in the chain-per-lane sweeps, a wave holds 64 / ladder_len whole ladders, the spins stay transposed in LDS for the
+ * whole launch, and a swap round stays inside the wave -- lane p of a ladder decides selected pair p from the two energies the wave
+ * shuffles to it, chains keep their lanes and two byte maps in LDS exchange entries.  No wave waits for another one (no barrier, no
+ * atomic, no cooperative launch, no residency condition).  Bit-identical to nlmc_sweep_philox(beta = NULL, shared order) +
+ * nlmc_pt_swap_philox round by round on any route; the rounds' decisions go to the device-side swap log when one covers them.  Needs:
+ * n <= NLMC_LANE_N, ladder_len <= 64, a context of whole ladders without a communicator, no phase flags / chain subset / second stream /
+ * tracked minimum, n_pairs >= 1 with the pair selections of rounds [round0, round0 + n_rounds) planned (nlmc_pt_plan, same seed and
+ * n_pairs); no fused-window plan.  The visiting orders of as many rounds as the order scratch holds are built per launch (a call is
+ * cut into launches of whole rounds; one round's orders must fit).  NLMC_ERR_UNSUPPORTED (nothing was run, the reason in
+ * nlmc_last_error) when a condition is not met.  nlmc_pt_rounds_deferred takes this route first, before it asks for a fused plan,
+ * when nlmc_set_lane_sweeps routes the context's sweeps to the lane kernels (today: mode 2, force) and the conditions hold; with
+ * the lane mode off it behaves as it always did.  nlmc_last_sweep_route is NLMC_ROUTE_LANES after such a call, nlmc_last_schedule_stats
+ * reports the visiting orders built, the timings count the order kernel as the levelize half. */
+int nlmc_pt_rounds_lanes(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0,
+                         uint64_t seed, int n_pairs);
+/* The route the most recent nlmc_pt_rounds_fused / nlmc_pt_rounds_deferred / nlmc_pt_rounds_lanes call that ran took:
+ * NLMC_ROUNDS_IN_LAUNCH (the rounds inside k_rounds_fused launches), NLMC_ROUNDS_LAUNCH_PER_ROUND, NLMC_ROUNDS_LANES (inside
+ * k_rounds_lanes launches), or 0 (no such call yet). */
 #define NLMC_ROUNDS_IN_LAUNCH 1
 #define NLMC_ROUNDS_LAUNCH_PER_ROUND 2
+#define NLMC_ROUNDS_LANES 3
 int nlmc_pt_rounds_route(nlmc_ctx *ctx);
 /* Device-side swap log of rounds [round0, round0 + n_rounds): rounds of nlmc_pt_swap_philox(_host) called WITHOUT host
  * output pointers keep their pairs and decisions on the device; nlmc_pt_log_read copies the whole log in one go

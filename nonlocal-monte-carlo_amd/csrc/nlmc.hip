@@ -8,6 +8,7 @@
 #include "nlmc_probe.h"
 #include "nlmc_big.h"
 #include "nlmc_lanes.h"
+#include "nlmc_lane_rounds.h"
 #include "nlmc_host.h"
 
 #include <dlfcn.h>
@@ -2512,6 +2513,18 @@ int nlmc_apt_swap_collective(nlmc_ctx *c, uint32_t round, uint64_t seed, int n_p
     return apt_launch_swap(c, round, seed, n_pairs, out_pairs, out_accepted);
 }
 
+// Why a context cannot run whole rounds by itself whatever the kernel, or nullptr: what nlmc_pt_rounds_fused, nlmc_pt_rounds_deferred
+// and nlmc_pt_rounds_lanes refuse alike.  `strict` (deferred, lanes): a tracked minimum is refused too.
+const char *rounds_context_refusal(const nlmc_ctx *c, bool strict)
+{
+    const int L = c->ladder_len;
+    if (c->chain_base % L != 0 || c->n_chains % L != 0) return "the context's block cuts a ladder (the swap needs other contexts' energies)";
+    if (c->comm || (c->apt_R > 0 && c->apt_world > 1)) return "the context takes part in a collective swap round";
+    if (c->has_flags || c->subset != 0 || c->cur != c->stream || (strict && c->track_min))
+        return strict ? "phase flags, a chain subset or a tracked minimum are in force" : "phase flags or a chain subset are in force";
+    return nullptr;
+}
+
 // The checks nlmc_pt_rounds_fused (via rounds) and nlmc_pt_rounds_deferred (via deferred) share, in their order.  NLMC_OK with the
 // plan slot and the arithmetic of the rounds in fslot / arith, fslot = -1 when there is nothing to do.
 int rounds_check(nlmc_ctx *c, Via via, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs,
@@ -2527,10 +2540,7 @@ int rounds_check(nlmc_ctx *c, Via via, int precision, int n_rounds, int T, uint3
     const int L = c->ladder_len;
     auto no = [&](const char *why) { return fail(c, NLMC_ERR_UNSUPPORTED, name + why); };
     if (d ? c->knobs.no_deferred : c->knobs.no_persistent) return no(d ? "switched off (NLMC_NO_DEFERRED)" : "switched off (NLMC_NO_PERSISTENT)");
-    if (c->chain_base % L != 0 || c->n_chains % L != 0) return no("the context's block cuts a ladder (the swap needs other contexts' energies)");
-    if (c->comm || (c->apt_R > 0 && c->apt_world > 1)) return no("the context takes part in a collective swap round");
-    if (c->has_flags || c->subset != 0 || c->cur != c->stream || (d && c->track_min))
-        return no(d ? "phase flags, a chain subset or a tracked minimum are in force" : "phase flags or a chain subset are in force");
+    if (const char *why = rounds_context_refusal(c, d)) return no(why);
     if (d && n_pairs < 1) return no("no swap pairs");
     if (n_pairs > std::max(0, L - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
     const int k = fused_plan_for(c, sweep0, n_rounds * T, seed);
@@ -2639,6 +2649,107 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
     return NLMC_OK;
 }
 
+// ---- tempering rounds of short chains: a ladder per wave (k_rounds_lanes, csrc/nlmc_lane_rounds.h) ----------------------------------
+// Why this context cannot run rounds [round0, round0 + n_rounds) in k_rounds_lanes, or nullptr: the checks of rounds_check that do not
+// concern fused plans, the reach of the lane kernels (n <= NLMC_LANE_N) and a ladder inside one wave.  Arguments are checked by the
+// callers.
+const char *rounds_lanes_refusal(const nlmc_ctx *c, int n_rounds, int T, uint32_t round0, uint64_t seed, int n_pairs)
+{
+    if (const char *why = rounds_context_refusal(c, true)) return why;
+    if (n_pairs < 1) return "no swap pairs";
+    if (c->knobs.force_big || c->n > NLMC_LANE_N) return "the chain-per-lane kernels take chains of at most NLMC_LANE_N spins";
+    if (c->ladder_len > 64) return "a ladder of more than 64 temperatures does not fit a wave";
+    if (!c->pt_plan.covers(round0, n_rounds, n_pairs, seed)) return "the pair selections of these rounds are not planned (nlmc_pt_plan)";
+    if ((size_t)T * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
+        return "the visiting orders of one round exceed the order scratch (NLMC_LANE_SCRATCH)";
+    return nullptr;
+}
+
+// n_rounds rounds in launches of k_rounds_lanes, as many whole rounds per launch as the order scratch holds visiting orders for.
+// rounds_lanes_refusal said nullptr.
+int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
+{
+    const int L = c->ladder_len, n = c->n, nl = c->n_chains_global / L, P = 64 / L;
+    const size_t bytes_per_round = (size_t)T * (size_t)n * sizeof(uint16_t);
+    const int K = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_rounds, c->knobs.lane_scratch / bytes_per_round, (size_t)(INT_MAX / 2) / (size_t)T}));
+    begin_sweep_call(c);
+    c->stat_orders = 0; c->stat_levels = 0; c->stats_pending = false;
+    c->stat_fused_window = -1;
+    c->stat_lane_orders = 0;
+    HIP_TRY(c, c->lane_perm.reserve((size_t)K * (size_t)T * (size_t)n));
+    { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
+    LaneLds Lds = lane_lds(c);
+    const int map_off = (int)((Lds.total + 15) & ~(size_t)15);          // lane_of_slot | slot_of_lane, 64 bytes each
+    Lds.total = (size_t)map_off + 128;
+    const void *kfun = precision == NLMC_F64 ? reinterpret_cast<const void *>(k_rounds_lanes<true>)
+                                             : reinterpret_cast<const void *>(k_rounds_lanes<false>);
+    { int rc = ensure_lds(c, kfun, Lds.total); if (rc) return rc; }
+    const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
+    const int ladders = c->n_chains / L;
+    for (int at = 0; at < n_rounds; at += K) {
+        const int k = std::min(K, n_rounds - at);
+        const uint32_t s0 = sweep0 + (uint32_t)at * (uint32_t)T, r0 = round0 + (uint32_t)at;
+        TimerSpan ts;
+        if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->stream); if (rc) return rc; }
+        LaneOrderArgs oa{};
+        oa.n = n; oa.n_sweeps = k * T; oa.per_chain = 0; oa.chain_base = c->chain_base;
+        oa.seed_lo = (uint32_t)seed; oa.seed_hi = (uint32_t)(seed >> 32); oa.sweep0 = s0;
+        oa.perm = c->lane_perm.p;
+        hipLaunchKernelGGL(k_lane_orders, dim3((unsigned)(k * T)), dim3(256), 0, c->stream, oa);
+        HIP_TRY(c, hipGetLastError());
+        c->stat_lane_orders += (int64_t)k * T;
+        { int rc = span_mid(c, ts); if (rc) return rc; }
+
+        SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
+        a.energy_sink = c->energy_sink;
+        a.lane_perm = c->lane_perm.p; a.lane_rows = c->n_chains; a.lane_diag = c->has_diag ? 1 : 0; a.lane_tab = Lds.tab ? 1 : 0;
+        a.lds_u_off = Lds.u_off;
+        LaneRoundsArgs q{};
+        q.n_rounds = k; q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = nl; q.round0 = r0;
+        q.plan_pairs = c->pt_plan_pairs.p + c->pt_plan.row(r0) * (size_t)nl * n_pairs * 2;
+        q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
+        if (log) {
+            const size_t lr = c->pt_log.row(r0);
+            q.log_pairs = c->pt_log_pairs.p + lr * (size_t)nl * n_pairs * 2;
+            q.log_acc = c->pt_log_acc.p + lr * (size_t)nl * n_pairs;
+        }
+        q.lds_map_off = map_off;
+        void *kargs[] = {&a, &q};
+        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)((ladders + P - 1) / P)), dim3(64), kargs, Lds.total, c->stream));
+        HIP_TRY(c, hipGetLastError());
+        { int rc = span_end(c, ts); if (rc) return rc; }
+        if (c->ev_accumulate) c->launches_timed += k;
+        c->launches_sweep += k;
+        c->launches_total += k;
+    }
+    c->sub_dirty = true;
+    c->last_route = NLMC_ROUTE_LANES;
+    c->rounds_route = NLMC_ROUNDS_LANES;
+    return NLMC_OK;
+}
+
+// n_rounds rounds in launches of k_rounds_lanes, whatever the lane mode is and whatever nlmc_pt_rounds_deferred would choose.
+int nlmc_pt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
+                         int n_pairs)
+{
+    if (!c) return NLMC_ERR_ARG;
+    const std::string name = "nlmc_pt_rounds_lanes: ";
+    if (n_rounds < 0 || sweeps_per_round < 1 || (precision != NLMC_F32 && precision != NLMC_F64) || n_pairs < 0)
+        return fail(c, NLMC_ERR_ARG, name + "bad argument");
+    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, name + "call nlmc_pt_init first");
+    if (n_rounds == 0 || c->n_chains == 0) return NLMC_OK;
+    if (n_pairs > std::max(0, c->ladder_len - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
+    if (const char *why = rounds_lanes_refusal(c, n_rounds, sweeps_per_round, round0, seed, n_pairs)) return fail(c, NLMC_ERR_UNSUPPORTED, name + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return rounds_lanes(c, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+}
+
+// Whether nlmc_pt_rounds_deferred takes k_rounds_lanes where the lane mode routes the context's sweeps to the lane kernels.  The rule
+// (that of ROUNDS_REAL_IN_LAUNCH): only if its median time per run is not above that of lane sweeps round by round on the same build
+// by more than the run-to-run spread at any shape of scripts/lane_rounds_throughput.py.  Measured (DESIGN.md section 6,
+// profiles/lane_rounds_throughput.txt): below it at all 48 shapes, 1.02-1.08x at T = 1000 up to 4.7-6.4x at T = 1 on n = 10.
+constexpr bool ROUNDS_LANES_IN_LAUNCH = true;
+
 // n_rounds rounds in cooperative launches of k_rounds_fused, whatever nlmc_pt_rounds_deferred would choose.
 int nlmc_pt_rounds_fused(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
                          int n_pairs)
@@ -2667,6 +2778,13 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
                             int n_pairs)
 {
     if (!c) return NLMC_ERR_ARG;
+    // short chains under the lane mode: the rounds inside k_rounds_lanes, before a fused plan is asked for
+    if (ROUNDS_LANES_IN_LAUNCH && !c->knobs.no_deferred && c->ladder_len > 0 && n_rounds > 0 && c->n_chains > 0 && sweeps_per_round >= 1 &&
+        (precision == NLMC_F32 || precision == NLMC_F64) && n_pairs >= 1 && n_pairs <= c->ladder_len - 1 && lanes_route(c, c->n_chains) &&
+        !rounds_lanes_refusal(c, n_rounds, sweeps_per_round, round0, seed, n_pairs)) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        return rounds_lanes(c, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+    }
     int fslot = -1, arith = NOT_FUSED;
     { int rc = rounds_check(c, Via::deferred, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs, fslot, arith); if (rc || fslot < 0) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));

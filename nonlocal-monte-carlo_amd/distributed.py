@@ -172,7 +172,9 @@ class ShardedTempering:
             persistent = bool(os.environ.get("NLMC_PERSISTENT"))
         # default where it applies (one process, whole ladders, fused windows of one round): nlmc_pt_rounds_deferred, which runs the
         # chunk in launch or, failing that, as sweep launches that decide the PREVIOUS round's swap in their prologue
-        eligible = (pl is not None and self._lt is None and not self.collective and self.n_pairs > 0 and pl.window == n_sweeps == pl.S
+        # (a context whose sweeps run one chain per lane needs no window: pt_rounds_deferred runs its rounds inside k_rounds_lanes)
+        eligible = (pl is not None and self._lt is None and not self.collective and self.n_pairs > 0 and n_sweeps == pl.S
+                    and (pl.window == n_sweeps or (not persistent and pl.lanes()))
                     and hasattr(self.eng, "pt_rounds_fused") and not getattr(self, "_persistent_refused", False))
         can = eligible
         batch = self.eng.pt_rounds_fused if persistent else getattr(self.eng, "pt_rounds_deferred", None)
@@ -235,10 +237,11 @@ class LocalTempering:
     ShardedTempering."""
 
     def __init__(self, inst, beta_list, n_chains_global, seed, n_pairs, device_ids, precision="f32", engine_factory=None,
-                 engines=None, parts=None):
+                 engines=None, parts=None, lane_sweeps="off"):
         """`parts` (optional): the blocks [(chain_base, count)] this process drives instead of an even cut over device_ids -- one
         rank's share under a launcher; `engines`: contexts that exist already (they must have had pt_init; not closed here... they
-        ARE closed by close(): hand over ownership)."""
+        ARE closed by close(): hand over ownership); `lane_sweeps`: Engine.set_lane_sweeps of every engine created here ("off",
+        "auto", "force": short chains one per lane, and run_rounds' chunks inside k_rounds_lanes -- same bits)."""
         self.G, self.seed, self.n_pairs, self.precision = int(n_chains_global), int(seed), int(n_pairs), precision
         devs = list(device_ids)
         self.parts = list(parts) if parts is not None else [block_partition(self.G, len(devs), r) for r in range(len(devs))]
@@ -255,6 +258,8 @@ class LocalTempering:
                 else:
                     e = Engine(inst, None, count, device=int(d), chain_base=base, n_chains_global=self.G,
                                own_stream=len(devs) > 1)
+                if lane_sweeps != "off":
+                    e.set_lane_sweeps(lane_sweeps)
                 e.pt_init(np.asarray(beta_list, dtype=np.float64))
                 self.engs.append(e)
         except Exception:
@@ -379,8 +384,9 @@ class LocalTempering:
     def run_rounds(self, n_rounds, n_sweeps):
         """`n_rounds` rounds of `n_sweeps` sweeps + one swap round each, without outputs -- same bits as round(n_sweeps) called
         n_rounds times, which is what everything that does not qualify falls back to.  ShardedTempering.run_rounds' rule: no NMC
-        slots, swap pairs, every context owns whole ladders, one fused window per round, an engine with pt_rounds_deferred,
-        NLMC_NO_DEFERRED unset.  Every context is handed the rest of its planned chunk at a time (the engine picks the route:
+        slots, swap pairs, every context owns whole ladders, one fused window per round -- or sweeps that run one chain per lane
+        (lane_sweeps: such a chunk needs only its pair selections planned, and the engine runs it inside k_rounds_lanes) -- an engine
+        with pt_rounds_deferred, NLMC_NO_DEFERRED unset.  Every context is handed the rest of its planned chunk at a time (the engine picks the route:
         Engine.pt_rounds_deferred); the calls are asynchronous, so all contexts have their chunk queued before any of them is
         waited for.  A context whose engine refuses is not asked again and runs its rounds one by one from then on (whole ladders:
         the contexts never meet).  Counters: deferred_rounds (rounds every context took in batched calls), deferred_calls, and
@@ -393,7 +399,7 @@ class LocalTempering:
             self._rounds_refused = [False] * len(self.engs)
         eligible = bool(not self.nmc and self.n_pairs > 0 and self.whole_ladders and pls
                         and not os.environ.get("NLMC_NO_DEFERRED")
-                        and all(pl.window == n_sweeps == pl.S for pl in pls)
+                        and all(n_sweeps == pl.S and (pl.window == n_sweeps or pl.lanes()) for pl in pls)
                         and all(hasattr(e, "pt_rounds_deferred") for e in self.engs))
         done = 0
         while done < n_rounds:

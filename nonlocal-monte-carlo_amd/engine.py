@@ -508,10 +508,26 @@ class Engine:
         self._ck(rc)
         return True
 
+    def pt_rounds_lanes(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
+        """n_rounds whole rounds of short chains inside k_rounds_lanes launches, whatever the lane mode is (include/nlmc.h:
+        nlmc_pt_rounds_lanes): a chain per lane, a ladder of at most 64 temperatures inside one wave, n <= 1024, pair selections planned
+        (pt_plan), no fused-window plan.  True when the rounds were queued, False when the context does not qualify (nothing was run;
+        the reason is in rounds_fused_refusal).  pt_rounds_deferred takes this route by itself under set_lane_sweeps("force")."""
+        prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
+        rc = self._L.nlmc_pt_rounds_lanes(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
+                                          int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs))
+        if rc == _abi.ERR_UNSUPPORTED:
+            self.rounds_fused_refusal = _abi.lib().nlmc_last_error(self._ctx).decode()
+            return False
+        self._ck(rc)
+        return True
+
     def last_rounds_route(self):
-        """The route the last pt_rounds_fused / pt_rounds_deferred call that ran took: "in launch" (the rounds inside k_rounds_fused
-        launches), "launch per round", or None before any such call (include/nlmc.h: nlmc_pt_rounds_route)."""
-        return {1: "in launch", 2: "launch per round"}.get(self._L.nlmc_pt_rounds_route(self._ctx))
+        """The route the last pt_rounds_fused / pt_rounds_deferred / pt_rounds_lanes call that ran took: "in launch" (the rounds inside
+        k_rounds_fused launches), "launch per round", "lanes" (inside k_rounds_lanes launches), or None before any such call
+        (include/nlmc.h: nlmc_pt_rounds_route)."""
+        return {_abi.ROUNDS_IN_LAUNCH: "in launch", _abi.ROUNDS_LAUNCH_PER_ROUND: "launch per round",
+                _abi.ROUNDS_LANES: "lanes"}.get(self._L.nlmc_pt_rounds_route(self._ctx))
 
     def pt_log_begin(self, round0, n_rounds, n_pairs):
         """Keep the swap log of the next rounds on the device (rounds called with want_log=False)."""
@@ -779,11 +795,19 @@ class RoundPlanner:
         self._fused_from = self._fused_to = self._plain_from = self._plain_to = 0      # planned round ranges
         self.chunks_planned = 0
 
+    def lanes(self):
+        """Whether the engine runs this planner's sweeps one chain per lane (Engine.lanes_take): such rounds need no level schedule,
+        fused or plain -- a chunk is planned once its pair selections are -- and may go to the engine's batched rounds call."""
+        return hasattr(self.eng, "lanes_take") and bool(self.eng.lanes_take())
+
     def _plan(self, ii, want_fused):
         r0, r1 = ii, min(self.R, ii + self.chunk)
         self.chunks_planned += 1
         if self.pt_pairs > 0 and hasattr(self.eng, "pt_plan"):
             self.eng.pt_plan(self.pt_round0 + r0, r1 - r0, self.seed, self.pt_pairs)
+        if self.lanes():
+            self._fused_from, self._fused_to = self._plain_from, self._plain_to = r0, r1
+            return True
         if want_fused and self.window:
             if hasattr(self.eng, "plan_slot"):
                 self.eng.plan_slot(self.slot)
@@ -802,6 +826,11 @@ class RoundPlanner:
         needs_plain = any(outputs.get(k) for k in ("record_stride", "want_energy", "want_min", "want_state")) and not self.fused_outputs
         if self.S == 0:
             return self.eng.sweep_philox(0, self.seed, sweep0=self.sweep0, beta=self.beta, precision=self.precision, **outputs)
+        if self.lanes():                                     # a chain per lane: nothing to plan but the chunk's pair selections
+            if not (self._fused_from <= ii < self._fused_to):
+                self._plan(ii, True)
+            return self.eng.sweep_philox(self.S, self.seed, sweep0=self.sweep0 + ii * self.S, beta=self.beta, precision=self.precision,
+                                         **outputs)
         if not needs_plain and self.window:
             if not (self._fused_from <= ii < self._fused_to):
                 self._plan(ii, True)

@@ -30,16 +30,24 @@ class NPT(Common):
     """NMC + Adaptive Parallel Tempering (NPT/npt.py:15)."""
     _variant = "npt"
 
-    def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32"):
+    def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32", lanes="off"):
         """`precision` (additive keyword, rng="philox" only): "f32" (default) -- the throughput mode's fixed-point couplings and
         logistic thresholds; "f64" -- the device-resident rounds in the reference's arithmetic (fp64 field, 53-bit uniform), on
-        fused windows for real couplings too (Engine.set_fused_f64_real).  Replicas with doNMC set are not supported with "f64"."""
+        fused windows for real couplings too (Engine.set_fused_f64_real).  Replicas with doNMC set are not supported with "f64".
+        `lanes` (additive keyword, rng="philox" only): "off" (default), "auto" or "force" -- Engine.set_lane_sweeps of the run's
+        engines ("auto" never fires today: its row threshold NLMC_LANE_AUTO_ROWS is 2^31 - 1, so it runs as "off"): short chains (n <= 1024, a ladder of at most 64 temperatures) run one per lane, their rounds inside k_rounds_lanes
+        launches -- same results.  Plain replicas only; a ladder cut across ranks keeps its route."""
         if precision not in ("f32", "f64"):
             raise ValueError("precision must be 'f32' or 'f64'")
+        if lanes not in ("off", "auto", "force"):
+            raise ValueError("lanes must be 'off', 'auto' or 'force'")
         super().__init__(J, h, rng=rng, seed=seed, device=device, lbp=lbp)
         if precision != "f32" and self.rng != "philox":
             raise ValueError("precision applies to rng='philox' (rng='numpy' runs the reference's own arithmetic)")
+        if lanes != "off" and self.rng != "philox":
+            raise ValueError("lanes applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
         self.precision = precision
+        self.lanes = lanes
 
     # ------------------------------------------------------------------------------------------------
     def replica_energy(self, M, num_sweeps):
@@ -114,6 +122,8 @@ class NPT(Common):
         any_nmc = any(bool(v) for v in doNMC)
         if any_nmc and self.precision != "f32":
             raise ValueError("precision='f64' runs plain replicas only: doNMC slots are not supported")
+        if any_nmc and self.lanes != "off":
+            raise ValueError("lanes runs plain replicas only: doNMC slots are not supported")
         # (with NMC replicas and M_skip > 1 the phases' traces and argmin hand-offs are strided on the device; a phase length that M_skip
         # does not divide raises the reference's own shape error on the host-managed path)
         device_resident = self.rng == "philox" and (not any_nmc or (int(M_skip) >= 1 and self.num_sweeps_per_NMC_phase_per_swap % int(M_skip) == 0))
@@ -358,9 +368,10 @@ class NPT(Common):
                 e.set_fused_f64_real(True)
             return e
         if ctx is None:
-            lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, precision=prec)
+            lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, precision=prec, lane_sweeps=self.lanes)
         elif not cut:
-            lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, parts=[(base_, count_)], precision=prec)
+            lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, parts=[(base_, count_)], precision=prec,
+                                lane_sweeps=self.lanes)
         else:
             lt = ShardedAsLocal(ShardedTempering(
                 lambda i, n, b, g: opt_in(Engine(i, None, n, device=lrank_, chain_base=b, n_chains_global=g)), inst, beta_list, G,
