@@ -339,11 +339,32 @@ int nlmc_pt_rounds_lanes(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_
                          uint64_t seed, int n_pairs);
 /* The route the most recent nlmc_pt_rounds_fused / nlmc_pt_rounds_deferred / nlmc_pt_rounds_lanes call that ran took:
  * NLMC_ROUNDS_IN_LAUNCH (the rounds inside k_rounds_fused launches), NLMC_ROUNDS_LAUNCH_PER_ROUND, NLMC_ROUNDS_LANES (inside
- * k_rounds_lanes launches), or 0 (no such call yet). */
+ * k_rounds_lanes launches), NLMC_ROUNDS_APT_LANES (nlmc_apt_rounds_lanes), or 0 (no such call yet). */
 #define NLMC_ROUNDS_IN_LAUNCH 1
 #define NLMC_ROUNDS_LAUNCH_PER_ROUND 2
 #define NLMC_ROUNDS_LANES 3
+#define NLMC_ROUNDS_APT_LANES (NLMC_ROUNDS_LANES + 1) /* 4 */
 int nlmc_pt_rounds_route(nlmc_ctx *ctx);
+/* n_rounds APT rounds of short chains -- sweeps_per_round sweeps at the slot temperatures, the Houdayer step of
+ * nlmc_icm_round_ladders, the swap round of nlmc_pt_swap_philox -- in launches of k_apt_rounds_lanes (csrc/nlmc_lane_apt.h): the whole
+ * system, K = n_chains / ladder_len sub-replica ladders, in ONE workgroup.  A lane owns a chain, wave w holds ladders w P .. w P + P - 1
+ * (P = 64 / ladder_len) transposed in a region of LDS of its own, sweeps and swaps stay inside the wave as in k_rounds_lanes; around the
+ * Houdayer step the waves meet at a barrier, every chain ranks its ladder among the pairing keys of its slot, and a lane owns a PAIR:
+ * components of the disagreement graph by label passes over wave-uniform rows (csrc/nlmc_lane_icm.h, labels in LDS, no atomic), the pick,
+ * the Katzgraber flip or the exchange, and k_icm_round's integer energy deltas.  Round r of the call uses sweeps sweep0 + r
+ * sweeps_per_round .., Houdayer round round0 + r and swap round round0 + r.  Bit-identical to nlmc_sweep_philox(beta = NULL, shared
+ * order) + nlmc_icm_round_ladders + nlmc_pt_swap_philox round by round on any route; swap decisions go to the device-side log when one
+ * covers the rounds.  out_info [n_rounds][ladder_len * (K / 2)][2] = {n_components, picked size} per round and pair ({0, 0} where nothing
+ * disagrees), nullable; reading it back synchronises the stream and reports a component search that did not converge (NLMC_ERR_STATE),
+ * as nlmc_icm_round_ladders does.  Needs nlmc_pt_rounds_lanes' conditions, except that n_pairs = 0 (rounds without swaps) is taken, and:
+ * the context holds the whole system (chain_base = 0, all chains), random numbers are keyed by chain (no nlmc_apt_shard), the system fits
+ * 16 waves (ceil(K / P) <= 16), and spins + maps + labels fit 150 KB of LDS (64 n_pad bytes per wave + 2 n ladder_len (K / 2) bytes of
+ * labels + under 2 KB; the waves' random-number tables share the labels' bytes where they fit too, NLMC_LANE_RNG = 0 leaves them out).
+ * NLMC_ERR_UNSUPPORTED (nothing was run, the reason in nlmc_last_error) otherwise.  Afterwards nlmc_last_sweep_route is
+ * NLMC_ROUTE_LANES, nlmc_pt_rounds_route NLMC_ROUNDS_APT_LANES, nlmc_last_schedule_stats reports the visiting orders built (as many
+ * rounds' orders per launch as the order scratch holds: a call is cut into launches of whole rounds). */
+int nlmc_apt_rounds_lanes(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0,
+                          uint64_t seed, int n_pairs, int katzgraber, int32_t *out_info);
 /* Device-side swap log of rounds [round0, round0 + n_rounds): rounds of nlmc_pt_swap_philox(_host) called WITHOUT host
  * output pointers keep their pairs and decisions on the device; nlmc_pt_log_read copies the whole log in one go
  * (out_pairs [n_rounds][n_ladders][n_pairs][2], -1 where a round did not run; out_accepted [n_rounds][n_ladders][n_pairs])

@@ -25,7 +25,7 @@ LANE_N = 1024                        # include/nlmc.h: NLMC_LANE_N, longest chai
 LANE_AUTO_ROWS = 2147483647          # include/nlmc.h: NLMC_LANE_AUTO_ROWS, rows from which "auto" takes them (2^31 - 1: never)
 LANES_OFF, LANES_AUTO, LANES_FORCE = 0, 1, 2
 ROUTE_NONE, ROUTE_STEPWISE, ROUTE_FUSED, ROUTE_LANES = 0, 1, 2, 3
-ROUNDS_IN_LAUNCH, ROUNDS_LAUNCH_PER_ROUND, ROUNDS_LANES = 1, 2, 3     # include/nlmc.h: nlmc_pt_rounds_route
+ROUNDS_IN_LAUNCH, ROUNDS_LAUNCH_PER_ROUND, ROUNDS_LANES, ROUNDS_APT_LANES = 1, 2, 3, 4     # include/nlmc.h: nlmc_pt_rounds_route
 PHASE_ALL, PHASE_BACKBONE_HOT, PHASE_BACKBONE_FROZEN = 0, 1, 2
 
 EXPORTS = [
@@ -38,6 +38,7 @@ EXPORTS = [
     "nlmc_pt_mark_slots", "nlmc_select_chains", "nlmc_subset_count", "nlmc_get_subset", "nlmc_track_minimum", "nlmc_backbone_seed", "nlmc_adopt_best",
     "nlmc_backbone_clusters", "nlmc_backbone_check", "nlmc_get_cluster_mask", "nlmc_set_phase", "nlmc_plan_slot", "nlmc_overlap_subsets", "nlmc_own_stream", "nlmc_plan_get_levels", "nlmc_probe_level_round", "nlmc_comm_unique_id", "nlmc_comm_init", "nlmc_comm_probe", "nlmc_comm_check", "nlmc_apt_shard", "nlmc_apt_pack", "nlmc_apt_swap_host", "nlmc_apt_swap_collective", "nlmc_apt_selftest_exchange", "nlmc_pt_swap_philox_collective", "nlmc_set_cluster_mask", "nlmc_host_prefault",
     "nlmc_set_fused_f64_real", "nlmc_last_sweep_fused", "nlmc_set_lane_sweeps", "nlmc_last_sweep_route", "nlmc_pt_rounds_lanes",
+    "nlmc_apt_rounds_lanes",
 ]
 
 
@@ -166,6 +167,7 @@ def lib():
                        ("nlmc_pt_rounds_fused", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),
                        ("nlmc_pt_rounds_deferred", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),
                        ("nlmc_pt_rounds_lanes", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),
+                       ("nlmc_apt_rounds_lanes", [_vp, _i, _i, _i, _u32, _u32, _u64, _i, _i, _vp]),
                        ("nlmc_apt_shard", [_vp, _i, _i, _i, _vp]), ("nlmc_apt_pack", [_vp, _vp, _vp, _vp]),
                        ("nlmc_apt_swap_host", [_vp, _u32, _u64, _i, _vp, _vp, _vp, _vp, _vp]),
                        ("nlmc_apt_swap_collective", [_vp, _u32, _u64, _i, _vp, _vp]), ("nlmc_apt_selftest_exchange", [_vp, _vp, _vp])):

@@ -17,6 +17,7 @@ import random as _pyrandom
 
 import numpy as np
 
+from . import engine as _engine
 from . import hostlogic
 from .base import SweepMixin
 from .engine import Engine, RoundPlanner, trace_layout
@@ -26,7 +27,14 @@ class APT_ICM(SweepMixin):
     num_subreplicas = 10      # NPT/apt_ICM.py:177
     useKatzgraber = True      # NPT/apt_ICM.py:178
 
-    def __init__(self, J, h, rng=None, seed=None, device=0):
+    def __init__(self, J, h, rng=None, seed=None, device=0, lanes="off"):
+        """`lanes` (additive keyword, rng="philox" only; run(..., icm_feedback=True) without device_ids, the device-resident route):
+        "off" (default), "auto" or "force" -- Engine.set_lane_sweeps of the run's engine ("auto" never fires today: its row threshold
+        NLMC_LANE_AUTO_ROWS is 2^31 - 1).  Short chains (n <= 1024, at most 64 temperatures) then sweep one per lane; where
+        engine.APT_LANES_IN_LAUNCH says so (today it does not: measured behind), all rounds but the last run inside
+        k_apt_rounds_lanes (Engine.apt_rounds_lanes).  Same bits as "off"."""
+        if lanes not in ("off", "auto", "force"):
+            raise ValueError("lanes must be 'off', 'auto' or 'force'")
         self.J = J
         if isinstance(h, list):
             h = np.array(h)
@@ -34,6 +42,9 @@ class APT_ICM(SweepMixin):
             h = h[:, np.newaxis]                      # NPT/apt_ICM.py:27-34: h kept as an [N,1] column
         self.h = h
         self._init_backend(rng, seed, device)
+        if lanes != "off" and self.rng != "philox":
+            raise ValueError("lanes applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
+        self.lanes = lanes
 
     def _hflat(self):
         return np.asarray(self.h, dtype=np.float64).reshape(-1)
@@ -108,6 +119,8 @@ class APT_ICM(SweepMixin):
         beta_list = np.asarray(beta_list, dtype=np.float64)
         if device_ids is not None and not (self.rng == "philox" and icm_feedback):
             raise ValueError("device_ids needs rng='philox' and icm_feedback=True (the device-resident path)")
+        if self.lanes != "off" and (not icm_feedback or device_ids is not None):
+            raise ValueError("lanes needs icm_feedback=True and no device_ids (the device-resident path of one context)")
         if self.rng == "philox" and icm_feedback and device_ids is not None:
             return self._run_slot_sharded(inst, beta_list, plot, return_trace, list(device_ids))
         if self.rng == "philox" and icm_feedback:
@@ -198,19 +211,24 @@ class APT_ICM(SweepMixin):
                                 for r in range(R)], beta_list)
         return M, Energy
 
-    def _run_device_resident(self, inst, beta_list, plot, return_trace="float64"):
+    def _run_device_resident(self, inst, beta_list, plot, return_trace="float64", engine_factory=Engine):
         """Throughput path (rng="philox", icm_feedback=True): every (sub-replica, replica) chain lives in ONE context,
         laid out sub-replica-major so that each sub-replica's beta ladder is a block of consecutive chains.  Per round:
         batched sweeps at the ladder temperatures -> iso-cluster moves between randomly paired sub-replicas of every
         replica, acting on the CURRENT states (k_icm_components / k_icm_move, picks drawn on the device) -> label-
         exchange swaps decided on the device for every sub-replica ladder.  Configurations never leave HBM until the
-        last round's trace is read out."""
+        last round's trace is read out.  Under a lane mode (`lanes`) whose sweeps the engine routes to the lane kernels, and where
+        engine.APT_LANES_IN_LAUNCH holds, rounds 0 .. rounds - 2 are ONE Engine.apt_rounds_lanes call (the last round keeps its three
+        calls: it records the trace); a refused call leaves every round to the three calls.  `engine_factory`: the engine class
+        (a seam for tests)."""
         R, K, N = self.num_replicas, self.num_subreplicas, inst.n
         S, rounds = self.num_sweeps_MCMC_per_swap, int(self.num_swap_attempts)
         G = K * R                                       # chain id = j * R + slot-holder index
         host_rng = np.random.default_rng(self.seed)      # initial states only
-        eng = Engine(inst, None, G, device=self._cache.device)
+        eng = engine_factory(inst, None, G, device=self._cache.device)
         try:
+            if self.lanes != "off":
+                eng.set_lane_sweeps(self.lanes)
             eng.set_spins((2 * host_rng.integers(0, 2, size=(G, N), dtype=np.int8) - 1).astype(np.int8))
             eng.pt_init(beta_list)
             planner = RoundPlanner(eng, self._sweep_counter, rounds, S, self.seed)
@@ -222,7 +240,14 @@ class APT_ICM(SweepMixin):
             swaps = self.num_swapping_pairs > 0 and rounds > 0
             if swaps:
                 eng.pt_log_begin(0, rounds, self.num_swapping_pairs)      # swap log stays on the device, read once
-            for ii in range(rounds):
+            first = 0
+            if self.lanes != "off" and _engine.APT_LANES_IN_LAUNCH and rounds > 1 and S > 0 and eng.lanes_take():
+                queued, info = eng.apt_rounds_lanes(rounds - 1, S, self.seed, self._sweep_counter, 0, self.num_swapping_pairs,
+                                                    katzgraber=self.useKatzgraber, want_info=True)
+                if queued:
+                    first = rounds - 1
+                    icm_sizes = [info[ii, :, 1].copy() for ii in range(first) if rounds <= 16 or ii % log_every == 0]
+            for ii in range(first, rounds):
                 is_last = ii == rounds - 1
                 if is_last:
                     slots_last = eng.pt_slots()

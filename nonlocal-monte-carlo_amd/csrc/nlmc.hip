@@ -9,6 +9,7 @@
 #include "nlmc_big.h"
 #include "nlmc_lanes.h"
 #include "nlmc_lane_rounds.h"
+#include "nlmc_lane_apt.h"
 #include "nlmc_host.h"
 
 #include <dlfcn.h>
@@ -2653,13 +2654,14 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
 // Why this context cannot run rounds [round0, round0 + n_rounds) in k_rounds_lanes, or nullptr: the checks of rounds_check that do not
 // concern fused plans, the reach of the lane kernels (n <= NLMC_LANE_N) and a ladder inside one wave.  Arguments are checked by the
 // callers.
-const char *rounds_lanes_refusal(const nlmc_ctx *c, int n_rounds, int T, uint32_t round0, uint64_t seed, int n_pairs)
+// `swaps_optional` (the APT rounds, which have their Houdayer step): n_pairs = 0, a round without swaps, is taken.
+const char *rounds_lanes_refusal(const nlmc_ctx *c, int n_rounds, int T, uint32_t round0, uint64_t seed, int n_pairs, bool swaps_optional = false)
 {
     if (const char *why = rounds_context_refusal(c, true)) return why;
-    if (n_pairs < 1) return "no swap pairs";
+    if (n_pairs < 1 && !swaps_optional) return "no swap pairs";
     if (c->knobs.force_big || c->n > NLMC_LANE_N) return "the chain-per-lane kernels take chains of at most NLMC_LANE_N spins";
     if (c->ladder_len > 64) return "a ladder of more than 64 temperatures does not fit a wave";
-    if (!c->pt_plan.covers(round0, n_rounds, n_pairs, seed)) return "the pair selections of these rounds are not planned (nlmc_pt_plan)";
+    if (n_pairs >= 1 && !c->pt_plan.covers(round0, n_rounds, n_pairs, seed)) return "the pair selections of these rounds are not planned (nlmc_pt_plan)";
     if ((size_t)T * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
         return "the visiting orders of one round exceed the order scratch (NLMC_LANE_SCRATCH)";
     return nullptr;
@@ -2749,6 +2751,8 @@ int nlmc_pt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_pe
 // by more than the run-to-run spread at any shape of scripts/lane_rounds_throughput.py.  Measured (DESIGN.md section 6,
 // profiles/lane_rounds_throughput.txt): below it at all 48 shapes, 1.02-1.08x at T = 1000 up to 4.7-6.4x at T = 1 on n = 10.
 constexpr bool ROUNDS_LANES_IN_LAUNCH = true;
+// (APT_LANES_IN_LAUNCH, the same rule for APT_ICM's rounds in k_apt_rounds_lanes, is a constant of engine.py: the class, not this
+// library, chooses between nlmc_apt_rounds_lanes and a call per step.)
 
 // n_rounds rounds in cooperative launches of k_rounds_fused, whatever nlmc_pt_rounds_deferred would choose.
 int nlmc_pt_rounds_fused(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
@@ -3083,6 +3087,118 @@ int nlmc_icm_round_ladders(nlmc_ctx *c, uint32_t round, uint64_t seed, int katzg
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (int p = 0; p < n_pairs; ++p)
             if (out_info[2 * p] < 0) return fail(c, NLMC_ERR_STATE, "icm: the component search did not converge");
+    }
+    return NLMC_OK;
+}
+
+// ---- APT rounds of short chains: one system per workgroup (k_apt_rounds_lanes, csrc/nlmc_lane_apt.h) --------------------------------
+// LDS of k_apt_rounds_lanes for W waves: spins of every wave | slot maps | pair_col | energy deltas | labels, sharing their bytes with
+// the waves' random-number tables where those fit too.  ok = false: the carve-up without the tables exceeds NLMC_APT_LANES_LDS.
+constexpr size_t NLMC_APT_LANES_LDS = (size_t)150 * 1024;
+struct AptLanesLds { size_t wave, map_off, pcol_off, de_off, u_off, tab_wave, total; int lab_stride; bool tab, ok; };
+static AptLanesLds apt_lanes_lds(const nlmc_ctx *c, int K, int L, int W)
+{
+    AptLanesLds A{};
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    A.wave = (size_t)c->n_pad * NLMC_LANE_STRIDE;
+    A.map_off = A.wave * (size_t)W;
+    A.pcol_off = A.map_off + (size_t)W * 128;
+    A.de_off = up16(A.pcol_off + (size_t)L * K * sizeof(uint16_t));
+    A.u_off = up16(A.de_off + (size_t)W * 64 * sizeof(long long));
+    A.lab_stride = (L * (K / 2) + 1) & ~1;
+    const size_t labels = (size_t)c->n * (size_t)A.lab_stride * sizeof(uint16_t);
+    A.tab_wave = (size_t)((c->n + 3) / 4 * 4) * 256;
+    A.ok = A.u_off + labels <= NLMC_APT_LANES_LDS;
+    A.tab = A.ok && c->knobs.lane_rng != 0 && A.u_off + A.tab_wave * (size_t)W <= NLMC_APT_LANES_LDS;
+    A.total = A.u_off + std::max(labels, A.tab ? A.tab_wave * (size_t)W : (size_t)0);
+    return A;
+}
+
+int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
+                          int n_pairs, int katzgraber, int32_t *out_info)
+{
+    if (!c) return NLMC_ERR_ARG;
+    const std::string name = "nlmc_apt_rounds_lanes: ";
+    const int T = sweeps_per_round;
+    if (n_rounds < 0 || T < 1 || (precision != NLMC_F32 && precision != NLMC_F64) || n_pairs < 0)
+        return fail(c, NLMC_ERR_ARG, name + "bad argument");
+    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, name + "call nlmc_pt_init first");
+    if (n_rounds == 0 || c->n_chains == 0) return NLMC_OK;
+    if (n_pairs > std::max(0, c->ladder_len - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
+    auto no = [&](const char *why) { return fail(c, NLMC_ERR_UNSUPPORTED, name + why); };
+    if (c->chain_base != 0 || c->n_chains != c->n_chains_global) return no("the sub-replicas of a temperature must live in one context");
+    if (c->rng_stride != 0) return no("random numbers keyed by temperature slot (nlmc_apt_shard) keep the round-by-round route");
+    if (const char *why = rounds_lanes_refusal(c, n_rounds, T, round0, seed, n_pairs, true)) return no(why);
+    const int L = c->ladder_len, n = c->n, K = c->n_chains_global / L, P = 64 / L, W = (K + P - 1) / P, NP = L * (K / 2);
+    if (W > 16) return no("the system needs more than 16 waves: it does not fit one workgroup");
+    const AptLanesLds A = apt_lanes_lds(c, K, L, W);
+    if (!A.ok) return no("the system's chains and labels exceed one workgroup's LDS (150 KB)");
+    HIP_TRY(c, hipSetDevice(c->device));
+
+    const size_t bytes_per_round = (size_t)T * (size_t)n * sizeof(uint16_t);
+    const int R = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_rounds, c->knobs.lane_scratch / bytes_per_round, (size_t)(INT_MAX / 2) / (size_t)T}));
+    begin_sweep_call(c);
+    c->stat_orders = 0; c->stat_levels = 0; c->stats_pending = false;
+    c->stat_fused_window = -1;
+    c->stat_lane_orders = 0;
+    HIP_TRY(c, c->lane_perm.reserve((size_t)R * (size_t)T * (size_t)n));
+    { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
+    const bool want_info = out_info && NP > 0;
+    if (want_info) HIP_TRY(c, c->icm_info.reserve((size_t)n_rounds * NP * 2));
+    const void *kfun = precision == NLMC_F64 ? reinterpret_cast<const void *>(k_apt_rounds_lanes<true>)
+                                             : reinterpret_cast<const void *>(k_apt_rounds_lanes<false>);
+    { int rc = ensure_lds(c, kfun, A.total); if (rc) return rc; }
+    const bool log = n_pairs > 0 && c->pt_log.covers(round0, n_rounds, n_pairs);
+    for (int at = 0; at < n_rounds; at += R) {
+        const int k = std::min(R, n_rounds - at);
+        const uint32_t s0 = sweep0 + (uint32_t)at * (uint32_t)T, r0 = round0 + (uint32_t)at;
+        TimerSpan ts;
+        if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->stream); if (rc) return rc; }
+        LaneOrderArgs oa{};
+        oa.n = n; oa.n_sweeps = k * T; oa.per_chain = 0; oa.chain_base = 0;
+        oa.seed_lo = (uint32_t)seed; oa.seed_hi = (uint32_t)(seed >> 32); oa.sweep0 = s0;
+        oa.perm = c->lane_perm.p;
+        hipLaunchKernelGGL(k_lane_orders, dim3((unsigned)(k * T)), dim3(256), 0, c->stream, oa);
+        HIP_TRY(c, hipGetLastError());
+        c->stat_lane_orders += (int64_t)k * T;
+        { int rc = span_mid(c, ts); if (rc) return rc; }
+
+        SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
+        a.energy_sink = c->energy_sink;
+        a.lane_perm = c->lane_perm.p; a.lane_rows = c->n_chains; a.lane_diag = c->has_diag ? 1 : 0; a.lane_tab = A.tab ? 1 : 0;
+        a.lds_u_off = (int)A.u_off;
+        LaneRoundsArgs q{};
+        q.n_rounds = k; q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = K; q.round0 = r0;
+        q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
+        if (n_pairs > 0) q.plan_pairs = c->pt_plan_pairs.p + c->pt_plan.row(r0) * (size_t)K * n_pairs * 2;
+        if (log) {
+            const size_t lr = c->pt_log.row(r0);
+            q.log_pairs = c->pt_log_pairs.p + lr * (size_t)K * n_pairs * 2;
+            q.log_acc = c->pt_log_acc.p + lr * (size_t)K * n_pairs;
+        }
+        q.lds_map_off = (int)A.map_off;
+        LaneAptArgs x{};
+        x.n_sub = K; x.n_icm = NP; x.katz = katzgraber ? 1 : 0;
+        x.info = want_info ? c->icm_info.p + (size_t)at * NP * 2 : nullptr;
+        x.lds_wave_bytes = (int)A.wave; x.lds_tab_bytes = (int)A.tab_wave; x.lds_pcol_off = (int)A.pcol_off; x.lds_de_off = (int)A.de_off;
+        x.lds_lab_off = (int)A.u_off; x.lab_stride = A.lab_stride;
+        void *kargs[] = {&a, &q, &x};
+        HIP_TRY(c, hipLaunchKernel(kfun, dim3(1), dim3((unsigned)(64 * W)), kargs, A.total, c->stream));
+        HIP_TRY(c, hipGetLastError());
+        { int rc = span_end(c, ts); if (rc) return rc; }
+        if (c->ev_accumulate) c->launches_timed += k;
+        c->launches_sweep += k;
+        c->launches_total += k;
+    }
+    c->sub_dirty = true;
+    c->last_route = NLMC_ROUTE_LANES;
+    c->rounds_route = NLMC_ROUNDS_APT_LANES;
+    if (want_info) {
+        const size_t cnt = (size_t)n_rounds * NP * 2;
+        HIP_TRY(c, hipMemcpyAsync(out_info, c->icm_info.p, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (size_t p = 0; p < cnt; p += 2)
+            if (out_info[p] < 0) return fail(c, NLMC_ERR_STATE, "icm: the component search did not converge");
     }
     return NLMC_OK;
 }

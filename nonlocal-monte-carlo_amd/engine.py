@@ -522,12 +522,32 @@ class Engine:
         self._ck(rc)
         return True
 
+    def apt_rounds_lanes(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, katzgraber=True, precision="f32",
+                         want_info=False):
+        """n_rounds whole APT rounds of short chains -- sweeps, the Houdayer step of icm_round_ladders, the swap round -- inside
+        k_apt_rounds_lanes launches (include/nlmc.h: nlmc_apt_rounds_lanes): the whole system of K sub-replica ladders in one
+        workgroup, a chain per lane, a Houdayer pair per lane.  n_pairs = 0: rounds without swaps; otherwise the pair selections are
+        planned (pt_plan).  Returns (queued, info): queued False when the context does not qualify (nothing was run; the reason is in
+        rounds_fused_refusal); info [n_rounds, L * (K // 2), 2] = {n_components, picked size} with want_info (a read-back: it
+        synchronises the stream), else None.  Same bits as sweep_philox(beta=None) + icm_round_ladders + pt_swap_philox round by round."""
+        prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
+        R = self.ladder_len
+        K = self.n_chains_global // R if R else 0
+        info = np.zeros((int(n_rounds), R * (K // 2), 2), np.int32) if want_info else None
+        rc = self._L.nlmc_apt_rounds_lanes(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
+                                           int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs), int(bool(katzgraber)), _abi.ptr(info))
+        if rc == _abi.ERR_UNSUPPORTED:
+            self.rounds_fused_refusal = _abi.lib().nlmc_last_error(self._ctx).decode()
+            return False, None
+        self._ck(rc)
+        return True, info
+
     def last_rounds_route(self):
-        """The route the last pt_rounds_fused / pt_rounds_deferred / pt_rounds_lanes call that ran took: "in launch" (the rounds inside
-        k_rounds_fused launches), "launch per round", "lanes" (inside k_rounds_lanes launches), or None before any such call
-        (include/nlmc.h: nlmc_pt_rounds_route)."""
+        """The route the last pt_rounds_fused / pt_rounds_deferred / pt_rounds_lanes / apt_rounds_lanes call that ran took: "in launch"
+        (the rounds inside k_rounds_fused launches), "launch per round", "lanes" (inside k_rounds_lanes launches), "apt lanes" (inside
+        k_apt_rounds_lanes launches), or None before any such call (include/nlmc.h: nlmc_pt_rounds_route)."""
         return {_abi.ROUNDS_IN_LAUNCH: "in launch", _abi.ROUNDS_LAUNCH_PER_ROUND: "launch per round",
-                _abi.ROUNDS_LANES: "lanes"}.get(self._L.nlmc_pt_rounds_route(self._ctx))
+                _abi.ROUNDS_LANES: "lanes", _abi.ROUNDS_APT_LANES: "apt lanes"}.get(self._L.nlmc_pt_rounds_route(self._ctx))
 
     def pt_log_begin(self, round0, n_rounds, n_pairs):
         """Keep the swap log of the next rounds on the device (rounds called with want_log=False)."""
@@ -766,6 +786,14 @@ def fused_window(n_sweeps, lo=3, hi=64):
         if n_sweeps % t == 0:
             return t
     return 0
+
+
+# Whether APT_ICM(lanes=...) hands its rounds to Engine.apt_rounds_lanes where the engine's sweeps go to the lane kernels.  The rule is
+# that of ROUNDS_LANES_IN_LAUNCH (csrc/nlmc.hip): True only if the in-launch median time per run is not above that of lane sweeps
+# round by round on the same build by more than the run-to-run spread at any shape of scripts/apt_lanes_throughput.py.  Measured
+# (profiles/apt_lanes_throughput.txt): above it at 69 of 72 shapes, 1.1-1.2x at T = 1 on n = 10 up to 7-10x on n = 40
+# and Chimera-128.  So the class keeps a call per step, and Engine.apt_rounds_lanes reaches the kernel by name.
+APT_LANES_IN_LAUNCH = False
 
 
 class RoundPlanner:
