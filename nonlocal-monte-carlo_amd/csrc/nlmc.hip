@@ -442,9 +442,11 @@ int sweep_block_for(const nlmc_ctx *c, bool f64_philox, bool f32_diag = false)
 }
 
 // beyond the default dynamic-LDS window a kernel has to opt in (once per kernel and size step)
+constexpr size_t NLMC_LDS_BYTES_MAX = (size_t)158 * 1024;      // dynamic LDS a workgroup may ask for
+
 int ensure_lds(nlmc_ctx *c, const void *func, size_t bytes)
 {
-    if (bytes > (size_t)158 * 1024) return fail(c, NLMC_ERR_UNSUPPORTED, "instance too large for the LDS-resident kernels of this build");
+    if (bytes > NLMC_LDS_BYTES_MAX) return fail(c, NLMC_ERR_UNSUPPORTED, "instance too large for the LDS-resident kernels of this build");
     if (bytes <= (size_t)60 * 1024) return NLMC_OK;
     auto it = std::find_if(c->lds_granted.begin(), c->lds_granted.end(), [&](const auto &e) { return e.first == func; });
     if (it != c->lds_granted.end() && bytes <= it->second) return NLMC_OK;
@@ -2933,7 +2935,15 @@ static int icm_launch_round(nlmc_ctx *c, const int32_t *pairs_dev, int n_pairs, 
     }
     a.round = round; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.katz = katz; a.chain_base = c->chain_base;
     a.efix = c->efix.p; a.energy_sink = c->energy_sink; a.eshift = c->escale - c->qs; a.escale = c->escale;
-    if (c->big) {
+    // k_icm_round keeps labels, candidates and both states in LDS: 8 bytes a spin, which the workgroup's LDS holds up to n =
+    // 20 220 only.  Chains from there to NLMC_LDS_N take the global-memory kernel (same pairing keys, same pick, same integers).
+    size_t cur = (size_t)c->n * 4;
+    a.lds_cand_off = (int)cur; cur += (((size_t)c->n + 7) & ~(size_t)7) * 2;
+    cur = (cur + 15) & ~(size_t)15;
+    a.lds_sa_off = (int)cur; cur += (size_t)c->n_pad;
+    a.lds_sb_off = (int)cur; cur += (size_t)c->n_pad;
+    const size_t lds = cur + 16;
+    if (c->big || lds > NLMC_LDS_BYTES_MAX) {
         if (!pairs_dev && pair_K > 1024) return fail(c, NLMC_ERR_UNSUPPORTED, "icm: more sub-replicas than threads of a workgroup");
         HIP_TRY(c, c->icm_label.reserve((size_t)n_pairs * c->n));
         a.adj = nullptr;
@@ -2941,12 +2951,6 @@ static int icm_launch_round(nlmc_ctx *c, const int32_t *pairs_dev, int n_pairs, 
         HIP_TRY(c, hipGetLastError());
         return NLMC_OK;
     }
-    size_t cur = (size_t)c->n * 4;
-    a.lds_cand_off = (int)cur; cur += (((size_t)c->n + 7) & ~(size_t)7) * 2;
-    cur = (cur + 15) & ~(size_t)15;
-    a.lds_sa_off = (int)cur; cur += (size_t)c->n_pad;
-    a.lds_sb_off = (int)cur; cur += (size_t)c->n_pad;
-    const size_t lds = cur + 16;
     { int rc = ensure_lds(c, reinterpret_cast<const void *>(k_icm_round), lds); if (rc) return rc; }
     hipLaunchKernelGGL(k_icm_round, dim3(n_pairs), dim3(c->n >= 4096 ? 1024 : 256), lds, c->stream, a);
     HIP_TRY(c, hipGetLastError());

@@ -491,7 +491,7 @@ __global__ __launch_bounds__(1024) void k_icm_round_big(IcmRoundArgs a, int32_t 
     for (int k = tid; k < n; k += nt) if (lab[k] != INT_MAX) cnt += (icm_find_halving(lab, k) == k);
     if (cnt) atomicAdd(&nroots, cnt);
     __syncthreads();
-    for (int k = tid; k < n; k += nt) if (lab[k] != INT_MAX) lab[k] = icm_find_halving(lab, k);
+    for (int k = tid; k < n; k += nt) if (lab[k] != INT_MAX) lab[k] = icm_find_readonly(lab, k);      // (no halving stores beside the final labels)
     __syncthreads();
     const int ncomp = nroots;
     if (ncomp <= 0) {

@@ -189,6 +189,16 @@ __device__ __forceinline__ int icm_find_halving(int32_t *lab, int k)
     return cur;
 }
 
+// Root of k without a store.  For the pass that writes the final labels: there a halving store is not harmless -- it holds a grandparent
+// read EARLIER, and landing after another thread's `lab[k] = root` it would put that ancestor back over the root (seen on a path of
+// 24 577 spins labelled in descending order: a handful of spins kept an inner node as label and fell out of the cluster).  Every
+// value a walk can read here is the old parent or the root, both ancestors, so it ends at the root whatever the interleaving.
+__device__ __forceinline__ int icm_find_readonly(const int32_t *lab, int k)
+{
+    int r = k;
+    for (;;) { const int up = lab[r]; if (up == r) return r; r = up; }
+}
+
 __global__ void k_icm_components(IcmArgs a)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -388,7 +398,7 @@ __global__ __launch_bounds__(1024) void k_icm_round(IcmRoundArgs a)
     }
     if (cnt) atomicAdd(&nroots, cnt);
     __syncthreads();
-    for (int idx = tid; idx < nc; idx += nt) { const int k = (int)cand[idx]; lab[k] = icm_find_halving(lab, k); }
+    for (int idx = tid; idx < nc; idx += nt) { const int k = (int)cand[idx]; lab[k] = icm_find_readonly(lab, k); }
     __syncthreads();
     const int ncomp = converged ? nroots : -1;
     if (ncomp <= 0) {                       // nothing to move (identical or opposite... no disagreement), or not converged
