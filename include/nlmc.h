@@ -421,6 +421,39 @@ int nlmc_get_subset(nlmc_ctx *ctx, int32_t *out_chains /*[nlmc_subset_count] loc
 /* on = 0: off; 1: the running minimum looks at every sweep of a call; k > 1: at sweeps 0, k, 2k, ... only -- the reference takes its
  * argmin over the recorded columns M[:, ::M_skip] (NMC/nmc.py:390-395 == NPT/npt.py:434-437). */
 int nlmc_track_minimum(nlmc_ctx *ctx, int on);
+/* ---- run-long best-state record: the lowest-energy configuration every chain visited, and when -------------------------------
+ * nlmc_track_minimum is a per-call minimum (the NMC phase hand-off); NPT.run's read-out looks at the last round only.  This record
+ * lasts from nlmc_best_begin to nlmc_best_end, over any number of calls, and only observes: no call's results change while it is open.
+ * Per local chain: the lowest tracked energy seen (an integer of 2^-nlmc_energy_scale), the stamp of the observation that FIRST reached
+ * it and the chain's spins at that observation, and the stamp of the first observation whose energy was <= target (first passage).
+ * One observation of chain c at stamp s with tracked energy E: E < best (strict) replaces energy, stamp and state; first_hit < 0 and
+ * E <= target sets first_hit = s.  Both compares are made on the energies as nlmc_energy_tracked reports them ((double) integer 2^-scale:
+ * the integer compare while |integer| < 2^53), so a host that keeps its own running minimum over nlmc_energy_tracked sees the same
+ * record; it is a function of the observed (state, energy) pairs and has the same bits on every route.
+ *   nlmc_best_begin(target)  opens or resets the record (energy: none, stamps -1); target = NaN: no first-passage stamp.  The device
+ *                            buffers (8 + 4 + 4 + n bytes per chain) are allocated at the first begin and kept.
+ *   nlmc_best_update(stamp)  one observation of every local chain's CURRENT state (k_best_update: a workgroup per chain on the state
+ *                            arrays, any n), queued on the context's stream, asynchronous.  stamp < 2^31.  Needs all chains selected
+ *                            (NLMC_ERR_UNSUPPORTED under a chain subset).  For drivers that run a round call by call: after the
+ *                            sweeps, before the swap round (APT: again after nlmc_icm_round_ladders, which lowers one partner's energy).
+ *   nlmc_best_read           energies as nlmc_energy_tracked reports them (+inf for a chain never observed), stamps, first-passage
+ *                            stamps (-1: never), states [n_chains][n]; every pointer nullable; one stream synchronisation.  Also after
+ *                            nlmc_best_end.
+ *   nlmc_best_end            closes the record: the routes behave as before; the buffers stay for the next begin and for reads.
+ * While a record is open the rounds entry points observe every chain once per round, stamp = round0 + r, after that round's sweeps and
+ * before its swap decision: nlmc_pt_rounds_fused and the in-launch route of nlmc_pt_rounds_deferred inside k_rounds_fused (wave 0
+ * copies the spins from LDS after the chain's hand-off record is out; instantiations of their own, the kernels without a record are
+ * unchanged), the launch-per-round route of nlmc_pt_rounds_deferred by a k_best_update behind every sweep launch, nlmc_pt_rounds_lanes
+ * inside k_rounds_lanes (a lane compares its own energy, improved lanes' columns are written a chain at a time).  The record lives in
+ * global memory and carries over from launch to launch and from call to call.  nlmc_apt_rounds_lanes returns NLMC_ERR_UNSUPPORTED
+ * (nothing was run) while a record is open: its kernel keeps none.  nlmc_sweep_philox / nlmc_sweep_stream, nlmc_set_spins, nlmc_energy,
+ * the Houdayer and swap entry points do not observe and leave the record alone.  The unit is the round: fused windows overlap a round's
+ * sweeps, there is no consistent state between them. */
+int nlmc_best_begin(nlmc_ctx *ctx, double target);
+int nlmc_best_update(nlmc_ctx *ctx, uint32_t stamp);
+int nlmc_best_read(nlmc_ctx *ctx, double *out_energy /*[n_chains]*/, int32_t *out_stamp /*[n_chains]*/,
+                   int32_t *out_first_hit /*[n_chains]*/, int8_t *out_state /*[n_chains][n]*/);
+int nlmc_best_end(nlmc_ctx *ctx);
 /* mode 1: copy the chains' CURRENT configurations aside; later nlmc_backbone_clusters calls are seeded with that copy instead of the
  * states they find (the m_star of a cycle without a plain phase is the state after the last plain phase, NMC/nmc.py:368-373,433:
  * full_update_frequency != 1).  mode 0: seed with the current states again. */

@@ -95,13 +95,21 @@ class APT_ICM(SweepMixin):
     # ------------------------------------------------------------------------------------------------
     def run(self, beta_list, num_replicas, num_sweeps_MCMC=1000, num_sweeps_read=1000, num_swap_attempts=100,
             num_swapping_pairs=1, use_hash_table=0, num_cores=8, plot=False, icm_feedback=False, return_trace="float64",
-            device_ids=None):
+            device_ids=None, track_best=False, target_energy=None):
         """NPT/apt_ICM.py:145-305.  Returns (M [R*N, S_swap*10], Energy [R]).  `return_trace` (device-resident path only):
         "float64" (the reference's M), "int8" (same layout, 1 byte per entry) or None (M is not materialised).
         `device_ids` (rng="philox", icm_feedback=True; the reference's knob is num_cores, NPT/apt_ICM.py:145-146): the
         temperature ladder is cut into len(device_ids) slot blocks, one context each -- all sub-replicas of a temperature on one
         GPU (distributed.SlotShardedAPT); random numbers are then keyed by (sub-replica, temperature slot), the results do not
-        depend on the number of blocks."""
+        depend on the number of blocks.
+        `track_best` (the device-resident path of one context: rng="philox", icm_feedback=True, no device_ids): every chain's
+        lowest-energy state over all rounds is kept on the device -- two observations per round, after its sweeps and again after its
+        Houdayer step (which lowers one partner's energy), both stamped with the round -- and the run sets self.best_energy [G]
+        (tracked energies), self.best_state [G, N] int8, self.best_round [G], self.first_hit_round [G] (first round at or below
+        `target_energy`; -1: never or no target), G = num_subreplicas * num_replicas by chain id (sub-replica-major).  Such a run
+        does not take Engine.apt_rounds_lanes.  ValueError on the other paths."""
+        if track_best and not (self.rng == "philox" and icm_feedback and device_ids is None):
+            raise ValueError("track_best needs rng='philox', icm_feedback=True and no device_ids (the device-resident path of one context)")
         if return_trace not in ("float64", "int8", None):
             raise ValueError("return_trace must be 'float64', 'int8' or None")
         self.num_replicas = num_replicas
@@ -124,7 +132,7 @@ class APT_ICM(SweepMixin):
         if self.rng == "philox" and icm_feedback and device_ids is not None:
             return self._run_slot_sharded(inst, beta_list, plot, return_trace, list(device_ids))
         if self.rng == "philox" and icm_feedback:
-            return self._run_device_resident(inst, beta_list, plot, return_trace)
+            return self._run_device_resident(inst, beta_list, plot, return_trace, track_best=bool(track_best), target_energy=target_energy)
         numpy_mode = self.rng == "numpy"
         host_rng = None if numpy_mode else np.random.default_rng(self.seed)
         all_pairs = [(i, i + 1) for i in range(1, R)]
@@ -211,7 +219,8 @@ class APT_ICM(SweepMixin):
                                 for r in range(R)], beta_list)
         return M, Energy
 
-    def _run_device_resident(self, inst, beta_list, plot, return_trace="float64", engine_factory=Engine):
+    def _run_device_resident(self, inst, beta_list, plot, return_trace="float64", engine_factory=Engine, track_best=False,
+                             target_energy=None):
         """Throughput path (rng="philox", icm_feedback=True): every (sub-replica, replica) chain lives in ONE context,
         laid out sub-replica-major so that each sub-replica's beta ladder is a block of consecutive chains.  Per round:
         batched sweeps at the ladder temperatures -> iso-cluster moves between randomly paired sub-replicas of every
@@ -241,7 +250,9 @@ class APT_ICM(SweepMixin):
             if swaps:
                 eng.pt_log_begin(0, rounds, self.num_swapping_pairs)      # swap log stays on the device, read once
             first = 0
-            if self.lanes != "off" and _engine.APT_LANES_IN_LAUNCH and rounds > 1 and S > 0 and eng.lanes_take():
+            if track_best:
+                eng.best_begin(target_energy)
+            if not track_best and self.lanes != "off" and _engine.APT_LANES_IN_LAUNCH and rounds > 1 and S > 0 and eng.lanes_take():
                 queued, info = eng.apt_rounds_lanes(rounds - 1, S, self.seed, self._sweep_counter, 0, self.num_swapping_pairs,
                                                     katzgraber=self.useKatzgraber, want_info=True)
                 if queued:
@@ -255,6 +266,8 @@ class APT_ICM(SweepMixin):
                 if is_last and S > 0:
                     last = o["spins"]                                  # [G, S, N] int8
                     E_rec = eng.energy_of_recorded(S)                  # fp64 energies of the trace, from its device copy
+                if track_best:
+                    eng.best_update(ii)
                 # Houdayer: for every temperature slot the K sub-replicas that currently hold it are shuffled and paired
                 # on the device (nlmc_icm_round_ladders); cluster sizes are read back on a sample of the rounds only (a
                 # read-back synchronises the stream; it also reports a component search that did not converge)
@@ -262,6 +275,8 @@ class APT_ICM(SweepMixin):
                 info = eng.icm_round_ladders(ii, self.seed, self.useKatzgraber, want_info=logged)
                 if logged:
                     icm_sizes.append(info[:, 1].copy())
+                if track_best:                                         # the Houdayer step lowers one partner's energy
+                    eng.best_update(ii)
                 if swaps:
                     eng.pt_swap_philox(ii, self.seed, self.num_swapping_pairs, want_log=False)
             acc_log = [eng.pt_log_read()[1]] if swaps else []
@@ -279,6 +294,9 @@ class APT_ICM(SweepMixin):
                 E_blk[slots_last[:, None], cols[:, None] + np.arange(S)[None, :]] = E_rec
                 k = self.num_sweeps_read_per_swap
                 Energy = np.min(E_blk[:, :k], axis=1) if k > 0 else np.min(np.zeros(0))    # np.min of nothing: ValueError
+            if track_best:
+                b = eng.best_read()
+                self.best_energy, self.best_state, self.best_round, self.first_hit_round = b["energy"], b["state"], b["stamp"], b["first_hit"]
             self.final_energies = eng.energy()
             self.final_slots = eng.pt_slots()
             self.swap_accepted = np.concatenate([a.reshape(-1) for a in acc_log]).astype(np.int8) if acc_log else np.zeros(0, np.int8)

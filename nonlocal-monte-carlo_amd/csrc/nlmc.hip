@@ -176,7 +176,14 @@ struct nlmc_ctx {
     const int32_t *sub_list() const { return subset == 0 ? nullptr : subset == 1 ? sub_list_buf.p : sub_list_buf.p + (n_chains - n_marked_local); }
     bool track_min = false;       // sweep calls keep running minimum + argmin state on the device (nlmc_track_minimum)
     int track_min_stride = 1;     // ... over the sweeps 0, stride, 2 stride, ... of a call (the reference's M[:, ::M_skip])
-    DevBuf<int8_t> seed_snap;     // nlmc_backbone_seed: the configurations later backbone inferences are seeded with
+    // run-long best-state record (nlmc_best_begin): allocated at the first begin, kept until the context goes
+    bool best_on = false;
+    double best_target = 0.0;     // NaN: no first-passage stamp
+    DevBuf<long long> rec_efix;   // [n_chains]
+    DevBuf<int32_t> rec_stamp, rec_hit;
+    DevBuf<int8_t> rec_state;     // [n_chains][n_pad]
+    BestRec best_rec() const { return BestRec{rec_efix.p, rec_stamp.p, rec_hit.p, rec_state.p, best_target}; }
+    DevBuf<int8_t> seed_snap;    // nlmc_backbone_seed: the configurations later backbone inferences are seeded with
     bool seed_snap_on = false;
     DevBuf<uint8_t> cmask;        // [n_chains][n_pad] backbone mask of the last inference per chain
     DevBuf<uint8_t> cmask_scratch; // chains too long for LDS: the two membership arrays of k_cluster_mask per problem
@@ -725,18 +732,18 @@ const void *fused_kernel(bool diag, bool flags, bool outs, int fmt, int arith, b
     return kernel_at<FusedKernel>(key, std::make_index_sequence<144>{});
 }
 
-// k_rounds_fused<DIAG, FMT, F64, R64> by {diag, fmt, arith}: 18 kernels
+// k_rounds_fused<DIAG, FMT, F64, R64, BEST> by {diag, fmt, arith, best}: 36 kernels (best: a best-state record is open)
 template <int K> struct RoundsKernel {
-    static constexpr bool diag = K & 1;
-    static constexpr int fmt = K / 2 % 3, arith = K / 6;
+    static constexpr bool diag = K & 1, best = K / 18;
+    static constexpr int fmt = K / 2 % 3, arith = K / 6 % 3;
     static const void *get()
     {
-        return reinterpret_cast<const void *>(k_rounds_fused<diag, fmt, arith != ARITH_F32, arith == ARITH_R64>);
+        return reinterpret_cast<const void *>(k_rounds_fused<diag, fmt, arith != ARITH_F32, arith == ARITH_R64, best>);
     }
 };
-const void *rounds_kernel(bool diag, int fmt, int arith)
+const void *rounds_kernel(bool diag, int fmt, int arith, bool best)
 {
-    return kernel_at<RoundsKernel>(((size_t)arith * 3 + fmt) * 2 + (diag ? 1 : 0), std::make_index_sequence<18>{});
+    return kernel_at<RoundsKernel>((((size_t)best * 3 + arith) * 3 + fmt) * 2 + (diag ? 1 : 0), std::make_index_sequence<36>{});
 }
 
 // the sweep-by-sweep kernels: k_sweep_stream, or k_sweep_philox<float | double, DIAG, PK> by {diag, pk, f64} (PK, the packed 16-bit
@@ -1591,6 +1598,7 @@ void nlmc_destroy(nlmc_ctx *c)
     c->lbp_hm.release(); c->lbp_tot.release(); c->lbp_mag.release(); c->lbp_mag_all.release();
     c->pt_tab.release(); c->pt_beta.release(); c->pt_energies_all.release();
     c->rounds_ebuf.release(); c->rounds_rec.release(); c->rounds_args.release(); c->seed_snap.release();
+    c->rec_efix.release(); c->rec_stamp.release(); c->rec_hit.release(); c->rec_state.release();
     c->apt_beta.release(); c->apt_e_all.release(); c->apt_send.release(); c->apt_recv.release(); c->apt_bd.release();
     c->slot_of_chain.release(); c->chain_of_slot.release(); c->pt_pairs.release(); c->pt_status.release();
     c->pt_acc.release(); c->pt_log_acc.release(); c->pt_log_pairs.release(); c->pt_plan_pairs.release(); c->pt_plan_ok.release(); c->icm_label.release(); c->icm_info.release(); c->icm_pairs.release();
@@ -2516,6 +2524,17 @@ int nlmc_apt_swap_collective(nlmc_ctx *c, uint32_t round, uint64_t seed, int n_p
     return apt_launch_swap(c, round, seed, n_pairs, out_pairs, out_accepted);
 }
 
+// One observation of every local chain for the open best-state record (k_best_update), on the context's stream.
+static int launch_best_update(nlmc_ctx *c, uint32_t stamp)
+{
+    if (c->n_chains == 0) return NLMC_OK;
+    BestArgs a{};
+    a.b = c->best_rec(); a.efix = c->efix.p; a.spins = c->spins.p; a.n_pad = c->n_pad; a.escale = c->escale; a.stamp = (int32_t)stamp;
+    hipLaunchKernelGGL(k_best_update, dim3((unsigned)c->n_chains), dim3(256), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return NLMC_OK;
+}
+
 // Why a context cannot run whole rounds by itself whatever the kernel, or nullptr: what nlmc_pt_rounds_fused, nlmc_pt_rounds_deferred
 // and nlmc_pt_rounds_lanes refuse alike.  `strict` (deferred, lanes): a tracked minimum is refused too.
 const char *rounds_context_refusal(const nlmc_ctx *c, bool strict)
@@ -2584,7 +2603,7 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
     if (real && !P.has_val) return fail(c, NLMC_ERR_STATE, "k_rounds_fused: the plan has no fp64 value plane");
     const int kt = arith == ARITH_F64 ? 2 * c->xmax + 1 : 0;          // (the real-valued variant has no K tables: the f32 mode's LDS)
     const FusedLds Lds = fused_lds(c->n_pad, false, false, P.fmt == NLMC_FMT_ADDR, kt);
-    const void *kfun = rounds_kernel(c->has_diag, P.fmt, arith);
+    const void *kfun = rounds_kernel(c->has_diag, P.fmt, arith, c->best_on);
     if (!kfun) return fail(c, NLMC_ERR_STATE, "k_rounds_fused: no kernel for this arithmetic");
     { int rc = ensure_lds(c, kfun, Lds.total); if (rc) return rc; }
     const int nt = fused_block(c);
@@ -2620,6 +2639,7 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
         q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
         q.rec = c->rounds_rec.p; q.status = c->pt_status.p;
         q.timeout_ticks = 100000000ll * 20;                   // 20 s of the 100 MHz wall clock
+        if (c->best_on) q.best = c->best_rec();               // (the record lives in global memory: it carries over from launch to launch)
         if (log) {
             const size_t r = c->pt_log.row(r0);
             q.log_pairs = c->pt_log_pairs.p + r * (size_t)nl * n_pairs * 2;
@@ -2685,8 +2705,10 @@ int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep
     LaneLds Lds = lane_lds(c);
     const int map_off = (int)((Lds.total + 15) & ~(size_t)15);          // lane_of_slot | slot_of_lane, 64 bytes each
     Lds.total = (size_t)map_off + 128;
-    const void *kfun = precision == NLMC_F64 ? reinterpret_cast<const void *>(k_rounds_lanes<true>)
-                                             : reinterpret_cast<const void *>(k_rounds_lanes<false>);
+    const void *kfun = c->best_on ? (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_rounds_lanes<true, true>)
+                                                           : reinterpret_cast<const void *>(k_rounds_lanes<false, true>))
+                                  : (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_rounds_lanes<true>)
+                                                           : reinterpret_cast<const void *>(k_rounds_lanes<false>));
     { int rc = ensure_lds(c, kfun, Lds.total); if (rc) return rc; }
     const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
     const int ladders = c->n_chains / L;
@@ -2718,6 +2740,7 @@ int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep
             q.log_acc = c->pt_log_acc.p + lr * (size_t)nl * n_pairs;
         }
         q.lds_map_off = map_off;
+        if (c->best_on) q.best = c->best_rec();
         void *kargs[] = {&a, &q};
         HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)((ladders + P - 1) / P)), dim3(64), kargs, Lds.total, c->stream));
         HIP_TRY(c, hipGetLastError());
@@ -2827,6 +2850,9 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
         int rc = run_fused(c, fslot, w0 + r, sweep0 + (uint32_t)(r * T), seed, c->pt_tab.p, 2, 0, true, false, false, false, false, 0, 0, T,
                            arith, &d, sink);
         if (rc) return rc;
+        // an open record observes the round here: a swap is a label exchange, so chain c's spins and tracked energy in the state
+        // arrays after this launch are the state of round r, whatever the next launch's prologue decides about its slot
+        if (c->best_on) { rc = launch_best_update(c, round0 + (uint32_t)r); if (rc) return rc; }
     }
     c->sub_dirty = true;
     c->rounds_route = NLMC_ROUNDS_LAUNCH_PER_ROUND;
@@ -3130,6 +3156,7 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
     if (n_rounds == 0 || c->n_chains == 0) return NLMC_OK;
     if (n_pairs > std::max(0, c->ladder_len - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
     auto no = [&](const char *why) { return fail(c, NLMC_ERR_UNSUPPORTED, name + why); };
+    if (c->best_on) return no("a best-state record is open: k_apt_rounds_lanes keeps none (run the round step by step with nlmc_best_update)");
     if (c->chain_base != 0 || c->n_chains != c->n_chains_global) return no("the sub-replicas of a temperature must live in one context");
     if (c->rng_stride != 0) return no("random numbers keyed by temperature slot (nlmc_apt_shard) keep the round-by-round route");
     if (const char *why = rounds_lanes_refusal(c, n_rounds, T, round0, seed, n_pairs, true)) return no(why);
@@ -3470,6 +3497,68 @@ int nlmc_track_minimum(nlmc_ctx *c, int on)
     if (!c) return NLMC_ERR_ARG;
     c->track_min = on != 0;
     c->track_min_stride = on > 1 ? on : 1;
+    return NLMC_OK;
+}
+
+// ---- run-long best-state record --------------------------------------------------------------------------------------------------
+int nlmc_best_begin(nlmc_ctx *c, double target)
+{
+    if (!c) return NLMC_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t R = (size_t)c->n_chains;
+    HIP_TRY(c, c->rec_efix.reserve(R));
+    HIP_TRY(c, c->rec_stamp.reserve(R));
+    HIP_TRY(c, c->rec_hit.reserve(R));
+    HIP_TRY(c, c->rec_state.reserve(R * (size_t)c->n_pad));
+    c->best_target = target;
+    if (R > 0) {
+        hipLaunchKernelGGL(k_best_init, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, c->stream, c->best_rec(), (int)R);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemsetAsync(c->rec_state.p, 0, R * (size_t)c->n_pad, c->stream));
+    }
+    c->best_on = true;
+    return NLMC_OK;
+}
+
+int nlmc_best_update(nlmc_ctx *c, uint32_t stamp)
+{
+    if (!c) return NLMC_ERR_ARG;
+    if (!c->best_on) return fail(c, NLMC_ERR_STATE, "nlmc_best_update: no record is open (nlmc_best_begin)");
+    if (stamp > (uint32_t)INT32_MAX) return fail(c, NLMC_ERR_ARG, "nlmc_best_update: the stamp does not fit 31 bits");
+    if (c->subset != 0 || c->cur != c->stream)
+        return fail(c, NLMC_ERR_UNSUPPORTED, "nlmc_best_update: a chain subset is selected (an observation takes every local chain: select all chains first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return launch_best_update(c, stamp);
+}
+
+int nlmc_best_read(nlmc_ctx *c, double *out_energy, int32_t *out_stamp, int32_t *out_first_hit, int8_t *out_state)
+{
+    if (!c) return NLMC_ERR_ARG;
+    if (!c->rec_efix.p) return fail(c, NLMC_ERR_STATE, "nlmc_best_read: no record was begun (nlmc_best_begin)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t R = (size_t)c->n_chains;
+    if (R == 0) return NLMC_OK;
+    std::vector<long long> e(out_energy ? R : 0);
+    if (out_energy) HIP_TRY(c, hipMemcpyAsync(e.data(), c->rec_efix.p, sizeof(long long) * R, hipMemcpyDeviceToHost, c->stream));
+    if (out_stamp) HIP_TRY(c, hipMemcpyAsync(out_stamp, c->rec_stamp.p, sizeof(int32_t) * R, hipMemcpyDeviceToHost, c->stream));
+    if (out_first_hit) HIP_TRY(c, hipMemcpyAsync(out_first_hit, c->rec_hit.p, sizeof(int32_t) * R, hipMemcpyDeviceToHost, c->stream));
+    if (out_state) {
+        c->stage_out.resize((size_t)c->n_pad * R);
+        HIP_TRY(c, hipMemcpyAsync(c->stage_out.data(), c->rec_state.p, c->stage_out.size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (out_state) rows_to_host_finish(c, out_state, (int)R);
+    if (out_energy) {
+        const double inv = std::ldexp(1.0, -c->escale);         // nlmc_energy_tracked's conversion; a chain never observed reads +inf
+        for (size_t i = 0; i < R; ++i) out_energy[i] = e[i] == LLONG_MAX ? HUGE_VAL : (double)e[i] * inv;
+    }
+    return NLMC_OK;
+}
+
+int nlmc_best_end(nlmc_ctx *c)
+{
+    if (!c) return NLMC_ERR_ARG;
+    c->best_on = false;
     return NLMC_OK;
 }
 

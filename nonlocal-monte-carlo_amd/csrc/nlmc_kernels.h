@@ -2568,6 +2568,53 @@ __global__ __launch_bounds__(1024) void k_sweep_fused(SweepArgs a)
 // pays again and again -- kernel launch, spins HBM -> LDS -> HBM, the uniform tables of the first two sweeps (made in the previous
 // round's tail here), the K tables of a chain whose slot did not change -- is paid once per chunk of rounds.  Bit-identical to
 // k_sweep_fused + k_pt_swap round by round.
+// ---- run-long best-state record (nlmc_best_begin) ----------------------------------------------------------------------------
+// Per local chain: the lowest tracked energy any observation saw (an integer of 2^-escale, LLONG_MAX before the first one), the stamp
+// of the observation that first reached it with the chain's spins at that moment, and the stamp of the first observation whose energy
+// was at or below the target (-1: none yet; a NaN target is never reached).  An observation compares the energies as
+// nlmc_energy_tracked reports them -- the integers converted to double, which is the integer compare below 2^53 units and merges
+// integers the double cannot tell apart above (escale can reach 2^60 units per unit of energy) -- so a host that drives the rounds call
+// by call and keeps its own running minimum sees the same record, and the record is a function of the observed (state, energy) pairs
+// alone: the same bits whichever kernel observed them.  Observers: k_best_update (any n, reads the state arrays), k_rounds_fused<.., BEST>
+// (spins in LDS, wave 0 between two windows), k_rounds_lanes<.., BEST> (a lane per chain).
+struct BestRec {
+    long long *efix;                 // [n_chains]
+    int32_t *stamp, *first_hit;      // [n_chains]
+    int8_t *state;                   // [n_chains][n_pad]
+    double target;
+};
+
+__global__ void k_best_init(BestRec b, int count)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) { b.efix[i] = 0x7FFFFFFFFFFFFFFFll; b.stamp[i] = -1; b.first_hit[i] = -1; }
+}
+
+// One observation of every local chain's CURRENT state: one workgroup per chain, energy and spins from the state arrays in global
+// memory (so it serves chains of any length, those of csrc/nlmc_big.h included).  Every thread reads the same three words, so the
+// improvement branch is wave-uniform; the barrier keeps thread 0's new record behind every wave's read of the old one.
+struct BestArgs {
+    BestRec b;
+    const long long *efix;           // [n_chains] tracked energies
+    const int8_t *spins;             // [n_chains][n_pad]
+    int n_pad, escale;
+    int32_t stamp;
+};
+__global__ __launch_bounds__(256) void k_best_update(BestArgs a)
+{
+    const int c = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const long long E = a.efix[c], old = a.b.efix[c];
+    const int hit = a.b.first_hit[c];
+    __syncthreads();
+    if (tid == 0 && hit < 0 && (double)E * __longlong_as_double((long long)(1023 - a.escale) << 52) <= a.b.target) a.b.first_hit[c] = a.stamp;
+    if ((double)E < (double)old) {                               // strict: the first attainment is kept
+        const int4 *src = reinterpret_cast<const int4 *>(a.spins + (size_t)c * a.n_pad);
+        int4 *dst = reinterpret_cast<int4 *>(a.b.state + (size_t)c * a.n_pad);
+        for (int i = tid; i < a.n_pad / 16; i += (int)blockDim.x) dst[i] = src[i];
+        if (tid == 0) { a.b.efix[c] = E; a.b.stamp[c] = a.stamp; }
+    }
+}
+
 #define NLMC_ROUNDS_PER_LAUNCH 1024     // rows of the record array; longer calls are split by the host
 struct RoundsArgs {
     int n_rounds, n_windows_avail;   // rounds of this launch; planned windows from the first one on (>= n_rounds: the one behind the last is warmed)
@@ -2585,6 +2632,7 @@ struct RoundsArgs {
     uint8_t *log_acc;
     int32_t *status;                 // sticky pt status: 3 = a wait for a partner timed out
     long long timeout_ticks;         // of the 100 MHz wall clock
+    BestRec best;                    // k_rounds_fused<.., BEST>: the open best-state record (last: the other fields keep their offsets)
 };
 
 // (no static LDS in these kernels: the spins sit at LDS offset 0; the words the waves share are in the reduction scratch)
@@ -2628,7 +2676,10 @@ typedef const RoundsArgs __attribute__((address_space(4))) *rounds_args_cptr;
 // R64 (with F64): the real-valued fp64 variant (k_sweep_fused<.., R64>) on the windows' value plane.  It has no K tables (the launch's
 // LDS is the f32 mode's, kt = 0): keep_kt and the slot remembered in sh[4] then decide nothing.  Its uniform tables are the fp64 mode's
 // high words, so the carry of the next round's first two tables is the same.
-template <bool DIAG, int FMT, bool F64, bool R64 = false>
+// BEST: a best-state record is open (nlmc_best_begin) -- every round is one observation, stamp round0 + r, of the state its sweeps left:
+// after the chain's hand-off record is out (no partner waits for the copy), before the swap step.  A template parameter, not a
+// pointer test: the instantiations without a record are the kernels they were.
+template <bool DIAG, int FMT, bool F64, bool R64 = false, bool BEST = false>
 __global__ __launch_bounds__(1024) void k_rounds_fused(const SweepArgs *ap_g, const RoundsArgs *qp_g)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -2713,6 +2764,23 @@ __global__ __launch_bounds__(1024) void k_rounds_fused(const SweepArgs *ap_g, co
                 red[1] = E; red[3] = 0;          // (the sum is next added to at the end of a whole window from here)
                 sh[4] = slot;                    // the K tables in LDS are this slot's
                 sh[5] = carry ? 1 : 0;
+            }
+            if constexpr (BEST) {
+                // Lane 0 reads the record it alone writes and hands the answer to the wave (E is wave-uniform: one LDS word), wave 0
+                // copies the spins out of LDS 16 bytes a lane.  Nothing writes the spins before the barrier that ends the swap step.
+                const int cb = (int)blockIdx.x, n_pad = a.g.n_pad;
+                const int32_t stamp = (int32_t)(q.round0 + (uint32_t)r);
+                int imp = 0;
+                if (lane == 0) {
+                    imp = (double)E < (double)q.best.efix[cb] ? 1 : 0;
+                    if (q.best.first_hit[cb] < 0 && Ed <= q.best.target) q.best.first_hit[cb] = stamp;
+                }
+                if (__builtin_amdgcn_readfirstlane(imp)) {
+                    const int4 *src = reinterpret_cast<const int4 *>(lds_raw);
+                    int4 *dst = reinterpret_cast<int4 *>(q.best.state + (size_t)cb * n_pad);
+                    for (int i = lane; i < n_pad / 16; i += 64) dst[i] = src[i];
+                    if (lane == 0) { q.best.efix[cb] = E; q.best.stamp[cb] = stamp; }
+                }
             }
         }
         if (carry) {

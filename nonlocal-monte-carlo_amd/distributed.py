@@ -237,11 +237,14 @@ class LocalTempering:
     ShardedTempering."""
 
     def __init__(self, inst, beta_list, n_chains_global, seed, n_pairs, device_ids, precision="f32", engine_factory=None,
-                 engines=None, parts=None, lane_sweeps="off"):
+                 engines=None, parts=None, lane_sweeps="off", track_best=False, target_energy=None):
         """`parts` (optional): the blocks [(chain_base, count)] this process drives instead of an even cut over device_ids -- one
         rank's share under a launcher; `engines`: contexts that exist already (they must have had pt_init; not closed here... they
         ARE closed by close(): hand over ownership); `lane_sweeps`: Engine.set_lane_sweeps of every engine created here ("off",
-        "auto", "force": short chains one per lane, and run_rounds' chunks inside k_rounds_lanes -- same bits)."""
+        "auto", "force": short chains one per lane, and run_rounds' chunks inside k_rounds_lanes -- same bits); `track_best`: every
+        context keeps the record of its chains' lowest-energy states (Engine.best_begin; `target_energy`: the energy whose first
+        passage is stamped, in the engine's units) -- one observation per round, stamp = round index, after the round's sweeps (and
+        NMC cycles) and before its swap; best() reads it.  The record only observes: the trajectory is the same bits."""
         self.G, self.seed, self.n_pairs, self.precision = int(n_chains_global), int(seed), int(n_pairs), precision
         devs = list(device_ids)
         self.parts = list(parts) if parts is not None else [block_partition(self.G, len(devs), r) for r in range(len(devs))]
@@ -269,6 +272,10 @@ class LocalTempering:
         self._planners = None
         self.nmc = None
         self._nmc_planners = None
+        self.track_best = bool(track_best)
+        if self.track_best:
+            for e in self.engs:
+                e.best_begin(target_energy)
 
     def set_spins(self, spins_global):
         for e, (base, count) in zip(self.engs, self.parts):
@@ -338,6 +345,8 @@ class LocalTempering:
             else:
                 o = e.sweep_philox(n_sweeps, self.seed, sweep0=self.sweeps_done, beta=None, precision=self.precision, **outputs)
             if not self.nmc:
+                if self.track_best:
+                    e.best_update(self.rounds_done)
                 outs.append(o)
                 continue
             rec = dict(plain=o, nmc=[])
@@ -366,6 +375,8 @@ class LocalTempering:
             e.track_minimum(False)
             e.set_phase("ALL")
             e.select("all")
+            if self.track_best:                      # (all chains selected again: the NMC chains in the state they carry on)
+                e.best_update(self.rounds_done)
             outs.append(rec)
         self.sweeps_done += n_sweeps
         if self.nmc:
@@ -433,6 +444,8 @@ class LocalTempering:
             for j in one_by_one:                             # the same k rounds of a context that was refused: round()'s two calls
                 for r in range(k):
                     pls[j].sweep(ii + r)
+                    if self.track_best:
+                        self.engs[j].best_update(self.rounds_done + r)
                     self.engs[j].pt_swap_philox(self.rounds_done + r, self.seed, self.n_pairs, want_log=False)
             if not one_by_one:
                 self.deferred_rounds += k
@@ -458,6 +471,16 @@ class LocalTempering:
 
     def gather_spins(self):
         return np.concatenate([e.get_spins() for e in self.engs])
+
+    def best(self, want_state=True):
+        """The contexts' best-state records by global chain id (track_best): dict(energy [G], stamp [G] = round of the first
+        attainment, first_hit [G] = first round at or below target_energy or -1, state [G, n] int8 or None)."""
+        if not self.track_best:
+            raise ValueError("LocalTempering.best: created without track_best")
+        order = np.argsort([base for base, _ in self.parts], kind="stable")
+        recs = [self.engs[j].best_read(want_state=want_state) for j in order]
+        return {k: (np.concatenate([r[k] for r in recs]) if recs[0][k] is not None else None)
+                for k in ("energy", "stamp", "first_hit", "state")}
 
     def check(self):
         if self.n_pairs > 0:

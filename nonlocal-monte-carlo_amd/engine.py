@@ -589,6 +589,30 @@ class Engine:
         """Sweep calls keep the running minimum + argmin state on the device; `stride` > 1: over sweeps 0, stride, 2 stride, ... only."""
         self._ck(self._L.nlmc_track_minimum(self._ctx, (max(1, int(stride)) if on else 0)))
 
+    # -- run-long best-state record (include/nlmc.h: nlmc_best_begin) -------------------------------------------------------
+    def best_begin(self, target=None):
+        """Open (or reset) the record of every chain's lowest-energy state.  target: energy whose first passage is stamped
+        (None: no first-passage stamp).  While it is open pt_rounds_fused / pt_rounds_deferred / pt_rounds_lanes observe every
+        chain once per round (stamp = round index); round-by-round drivers call best_update."""
+        self._ck(self._L.nlmc_best_begin(self._ctx, float("nan") if target is None else float(target)))
+
+    def best_update(self, stamp):
+        """One observation of every local chain's current state (asynchronous; all chains must be selected)."""
+        self._ck(self._L.nlmc_best_update(self._ctx, int(stamp) & 0xFFFFFFFF))
+
+    def best_read(self, want_state=True):
+        """dict(energy [n_chains] as energy_tracked reports (+inf: never observed), stamp [n_chains] of the first attainment,
+        first_hit [n_chains] (-1: the target was never reached), state [n_chains, n] int8 or None)."""
+        e = np.empty(self.n_chains, np.float64)
+        st, fh = np.empty(self.n_chains, np.int32), np.empty(self.n_chains, np.int32)
+        s = np.empty((self.n_chains, self.n), np.int8) if want_state else None
+        self._ck(self._L.nlmc_best_read(self._ctx, _abi.ptr(e), _abi.ptr(st), _abi.ptr(fh), _abi.ptr(s)))
+        return {"energy": e, "stamp": st, "first_hit": fh, "state": s}
+
+    def best_end(self):
+        """Close the record (best_read still returns it); the rounds routes behave as before."""
+        self._ck(self._L.nlmc_best_end(self._ctx))
+
     def backbone_seed(self, snapshot=True):
         """snapshot=True: later backbone_clusters calls are seeded with the configurations as they are NOW; False: with the current ones."""
         self._ck(self._L.nlmc_backbone_seed(self._ctx, 1 if snapshot else 0))

@@ -90,7 +90,8 @@ class NPT(Common):
             num_swapping_pairs=1, num_cycles=10, full_update_frequency=1, M_skip=1, temp_x=20, global_beta=2.5,
             lambda_start=0.5, lambda_end=0.01, lambda_reduction_factor=0.9, threshold_initial=0.999999,
             threshold_cutoff=0.99999, max_iterations=100, tolerance=np.finfo(float).eps, use_hash_table=False,
-            num_cores=8, plot=False, num_restarts=1, device_ids=None, return_trace="float64"):
+            num_cores=8, plot=False, num_restarts=1, device_ids=None, return_trace="float64", track_best=False,
+            target_energy=None):
         """Run the NPT algorithm (NPT/npt.py:535-700).  Returns (M [R*N, S_swap], Energy [R]).
 
         Additive keyword arguments (defaults = the reference's behaviour): `num_restarts` independent ladders advanced
@@ -98,7 +99,14 @@ class NPT(Common):
         -- both for rng="philox" runs (with NMC replicas: M_skip == 1); M and Energy describe restart 0,
         `self.restart_energies` [num_restarts, R] all of them.  `return_trace`: "float64" (reference dtype), "int8", or
         None (M is not built).  Dynamics of the philox mode: 24-bit fixed-point couplings + logistic thresholds (DESIGN.md
-        section 2 states the tolerance); the argmin hand-off between NMC phases uses the energies tracked in that model."""
+        section 2 states the tolerance); the argmin hand-off between NMC phases uses the energies tracked in that model.
+        `track_best` (rng="philox", device-resident path): the run keeps every chain's lowest-energy state over ALL rounds on the
+        device (one observation per round, after its sweeps / NMC cycles and before its swap; Energy looks at the last round only) and
+        sets self.best_energy [G] (tracked energies, normalised units like Energy), self.best_state [G, N] int8, self.best_round
+        [G] (round of the first attainment) and self.first_hit_round [G] (first round at or below `target_energy`, -1: never or no
+        target), G = num_restarts * num_replicas by global chain id (under a launcher with whole ladders per rank: this rank's
+        chains).  The trajectory is the same bits with or without it.  ValueError on the host-managed / rng="numpy" paths and where
+        a launcher cuts a ladder across ranks."""
         self.num_replicas = num_replicas
         self.num_sweeps_MCMC = num_sweeps_MCMC
         self.num_sweeps_read = num_sweeps_read
@@ -132,6 +140,8 @@ class NPT(Common):
                              "reference's own stream order has one ladder in one process")
         if int(num_restarts) < 1:
             raise ValueError("num_restarts must be >= 1")
+        if track_best and not device_resident:
+            raise ValueError("track_best needs the device-resident path: rng='philox' (with NMC replicas: a phase length M_skip divides)")
         if device_resident:
             nmc = None
             if any_nmc:
@@ -139,7 +149,8 @@ class NPT(Common):
                            global_beta=global_beta, lambda_start=lambda_start, lambda_end=lambda_end,
                            lambda_reduction_factor=lambda_reduction_factor, threshold_initial=threshold_initial,
                            threshold_cutoff=threshold_cutoff, max_iterations=max_iterations, tolerance=tolerance, M_skip=int(M_skip))
-            M, Energy = self._run_device_resident(beta_list, int(num_restarts), device_ids, return_trace, nmc)
+            M, Energy = self._run_device_resident(beta_list, int(num_restarts), device_ids, return_trace, nmc,
+                                                  track_best=bool(track_best), target_energy=target_energy)
         else:
             M, Energy = self._run_host_managed(beta_list, num_cycles, full_update_frequency, M_skip, temp_x, global_beta,
                                                lambda_start, lambda_end, lambda_reduction_factor, threshold_initial,
@@ -311,7 +322,8 @@ class NPT(Common):
         return selected
 
     # ------------------------------------------------------------------------------------------------
-    def _run_device_resident(self, beta_list, n_restarts=1, device_ids=None, return_trace="float64", nmc=None):
+    def _run_device_resident(self, beta_list, n_restarts=1, device_ids=None, return_trace="float64", nmc=None, track_best=False,
+                             target_energy=None):
         """Throughput path: all replicas (x restarts) stay on the device(s); label-exchange swaps decided by a kernel; the
         swap log is kept on the device and read once; only the last round's trace comes back (as int8 until the
         reference-shaped float64 M is asked for).  `nmc`: NMC_task parameters when some slots have doNMC set -- those
@@ -342,6 +354,8 @@ class NPT(Common):
             cut = base_ % R != 0 or count_ % R != 0 or (bool(os.environ.get("NLMC_NPT_FORCE_COLLECTIVE")) and not nmc)
             if nmc and cut:
                 raise ValueError("with NMC replicas every ladder must lie on one rank: num_restarts % ranks != 0")
+            if track_best and cut:
+                raise ValueError("track_best needs every ladder on one rank: num_restarts % ranks != 0")
             devs = [lrank_]
         if G % len(devs):
             raise ValueError("num_replicas * num_restarts must be a multiple of len(device_ids)")
@@ -368,10 +382,11 @@ class NPT(Common):
                 e.set_fused_f64_real(True)
             return e
         if ctx is None:
-            lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, precision=prec, lane_sweeps=self.lanes)
+            lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, precision=prec, lane_sweeps=self.lanes,
+                                track_best=track_best, target_energy=target_energy)
         elif not cut:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, parts=[(base_, count_)], precision=prec,
-                                lane_sweeps=self.lanes)
+                                lane_sweeps=self.lanes, track_best=track_best, target_energy=target_energy)
         else:
             lt = ShardedAsLocal(ShardedTempering(
                 lambda i, n, b, g: opt_in(Engine(i, None, n, device=lrank_, chain_base=b, n_chains_global=g)), inst, beta_list, G,
@@ -440,6 +455,9 @@ class NPT(Common):
             self._sweep_counter += rounds * lt.sweeps_per_round(S)
             self._nmc_sweep_counter = lt.nmc_sweeps_done          # (the NMC phases draw from a counter range of their own)
             lt.check()
+            if track_best:
+                b = lt.best()
+                self.best_energy, self.best_state, self.best_round, self.first_hit_round = b["energy"], b["state"], b["stamp"], b["first_hit"]
             Energy = np.zeros(R)
             E_all = np.zeros((n_restarts, R))
             if last is not None and S > 0:
