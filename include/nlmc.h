@@ -347,7 +347,8 @@ int nlmc_pt_rounds_lanes(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_
 int nlmc_pt_rounds_route(nlmc_ctx *ctx);
 /* n_rounds APT rounds of short chains -- sweeps_per_round sweeps at the slot temperatures, the Houdayer step of
  * nlmc_icm_round_ladders, the swap round of nlmc_pt_swap_philox -- in launches of k_apt_rounds_lanes (csrc/nlmc_lane_apt.h): the whole
- * system, K = n_chains / ladder_len sub-replica ladders, in ONE workgroup.  A lane owns a chain, wave w holds ladders w P .. w P + P - 1
+ * system, K = n_chains / ladder_len sub-replica ladders, in ONE workgroup (nlmc_apt_systems(M): M systems of K = n_ladders / M, a
+ * workgroup each, out_info [n_rounds][M][ladder_len * (K / 2)][2]).  A lane owns a chain, wave w holds ladders w P .. w P + P - 1
  * (P = 64 / ladder_len) transposed in a region of LDS of its own, sweeps and swaps stay inside the wave as in k_rounds_lanes; around the
  * Houdayer step the waves meet at a barrier, every chain ranks its ladder among the pairing keys of its slot, and a lane owns a PAIR:
  * components of the disagreement graph by label passes over wave-uniform rows (csrc/nlmc_lane_icm.h, labels in LDS, no atomic), the pick,
@@ -365,6 +366,18 @@ int nlmc_pt_rounds_route(nlmc_ctx *ctx);
  * rounds' orders per launch as the order scratch holds: a call is cut into launches of whole rounds). */
 int nlmc_apt_rounds_lanes(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0,
                           uint64_t seed, int n_pairs, int katzgraber, int32_t *out_info);
+/* A context of n_ladders = M K ladders (nlmc_pt_init) as M = n_systems independent APT systems -- restarts side by side.  System s owns
+ * ladders s K .. s K + K - 1, hence chains s K L .. (s + 1) K L - 1.  Only the Houdayer pairing changes: per system s and slot r the K
+ * ladders of THAT system are ordered by the keys philox(j, round, r, ICM_PAIR), j the global ladder id, ties to the smaller j; ranks 2 i
+ * and 2 i + 1 form pair i, an odd K leaves the last rank out.  Pairs and info rows are listed in the order (system, slot, i): M L (K / 2)
+ * rows where the calls below say ladder_len * (K / 2).  Sweeps, the pick of a pair and the energy deltas stay keyed by global chain ids,
+ * pair selections and swap decisions by global ladder, the visiting order is shared: system 0 has exactly the bits of a one-system
+ * context of K L chains with the same seed, the other systems are independent runs.  nlmc_icm_round_ladders pairs by system on all of
+ * its kernels; nlmc_apt_rounds_lanes launches a workgroup per system (its 16-wave and 150 KB limits are those of ONE system; no
+ * workgroup reads what another writes, so M may exceed the number of compute units).  NLMC_ERR_STATE before nlmc_pt_init; NLMC_ERR_ARG
+ * for n_systems < 1 or n_ladders % n_systems != 0; NLMC_ERR_UNSUPPORTED for n_systems > 1 on a context of nlmc_apt_shard (slot-keyed
+ * random numbers), as nlmc_apt_shard is on a context of several systems.  nlmc_pt_init resets it to 1. */
+int nlmc_apt_systems(nlmc_ctx *ctx, int n_systems);
 /* Device-side swap log of rounds [round0, round0 + n_rounds): rounds of nlmc_pt_swap_philox(_host) called WITHOUT host
  * output pointers keep their pairs and decisions on the device; nlmc_pt_log_read copies the whole log in one go
  * (out_pairs [n_rounds][n_ladders][n_pairs][2], -1 where a round did not run; out_accepted [n_rounds][n_ladders][n_pairs])
@@ -487,7 +500,8 @@ int nlmc_icm_round_philox(nlmc_ctx *ctx, const int32_t *pairs, int n_pairs, uint
  * chains are K = n_chains_global / ladder_len ladders (sub-replicas) of ladder_len temperature slots (nlmc_pt_init);
  * per slot the ladders are shuffled (Philox(ladder, round, slot, ICM_PAIR) keys) and paired, each pair gets one
  * iso-cluster move with a Philox-picked cluster, tracked energies are resynchronised.  No host round trip.
- * out_n_pairs = ladder_len * (K / 2); out_info (nullable) [n_pairs][2] = {n_components, picked size}, slot-major. */
+ * out_n_pairs = ladder_len * (K / 2); out_info (nullable) [n_pairs][2] = {n_components, picked size}, slot-major.
+ * Under nlmc_apt_systems(M): K = n_ladders / M, every system pairs its own ladders, out_n_pairs = M ladder_len (K / 2), system-major. */
 int nlmc_icm_round_ladders(nlmc_ctx *ctx, uint32_t round, uint64_t seed, int katzgraber, int32_t *out_n_pairs,
                            int32_t *out_info /*nullable*/);
 

@@ -95,7 +95,7 @@ class APT_ICM(SweepMixin):
     # ------------------------------------------------------------------------------------------------
     def run(self, beta_list, num_replicas, num_sweeps_MCMC=1000, num_sweeps_read=1000, num_swap_attempts=100,
             num_swapping_pairs=1, use_hash_table=0, num_cores=8, plot=False, icm_feedback=False, return_trace="float64",
-            device_ids=None, track_best=False, target_energy=None):
+            device_ids=None, track_best=False, target_energy=None, num_restarts=1):
         """NPT/apt_ICM.py:145-305.  Returns (M [R*N, S_swap*10], Energy [R]).  `return_trace` (device-resident path only):
         "float64" (the reference's M), "int8" (same layout, 1 byte per entry) or None (M is not materialised).
         `device_ids` (rng="philox", icm_feedback=True; the reference's knob is num_cores, NPT/apt_ICM.py:145-146): the
@@ -107,7 +107,19 @@ class APT_ICM(SweepMixin):
         Houdayer step (which lowers one partner's energy), both stamped with the round -- and the run sets self.best_energy [G]
         (tracked energies), self.best_state [G, N] int8, self.best_round [G], self.first_hit_round [G] (first round at or below
         `target_energy`; -1: never or no target), G = num_subreplicas * num_replicas by chain id (sub-replica-major).  Such a run
-        does not take Engine.apt_rounds_lanes.  ValueError on the other paths."""
+        does not take Engine.apt_rounds_lanes.  ValueError on the other paths.
+        `num_restarts` (additive keyword; rng="philox", icm_feedback=True, no device_ids, else ValueError): that many independent systems
+        of num_subreplicas x num_replicas chains side by side in ONE context (Engine.apt_systems): chain id = (s K + j) R + holder for
+        restart s, sub-replica j.  Restart 0 does not depend on num_restarts: (M, Energy) describe it and are bit-identical to
+        num_restarts=1.  self.restart_energies [num_restarts, R] is Energy of every restart; final_energies, final_slots, swap_accepted,
+        icm_cluster_sizes and the best-record arrays cover all num_restarts K R chains (restart-major); with track_best also
+        self.restart_best_energy [num_restarts] (minimum of the restart's best_energy) and self.restart_first_hit_round [num_restarts]
+        (smallest non-negative first_hit_round of the restart's chains, -1: none)."""
+        if int(num_restarts) != num_restarts or num_restarts < 1:
+            raise ValueError("num_restarts must be an integer >= 1")
+        num_restarts = int(num_restarts)
+        if num_restarts > 1 and not (self.rng == "philox" and icm_feedback and device_ids is None):
+            raise ValueError("num_restarts needs rng='philox', icm_feedback=True and no device_ids (the device-resident path of one context)")
         if track_best and not (self.rng == "philox" and icm_feedback and device_ids is None):
             raise ValueError("track_best needs rng='philox', icm_feedback=True and no device_ids (the device-resident path of one context)")
         if return_trace not in ("float64", "int8", None):
@@ -132,7 +144,8 @@ class APT_ICM(SweepMixin):
         if self.rng == "philox" and icm_feedback and device_ids is not None:
             return self._run_slot_sharded(inst, beta_list, plot, return_trace, list(device_ids))
         if self.rng == "philox" and icm_feedback:
-            return self._run_device_resident(inst, beta_list, plot, return_trace, track_best=bool(track_best), target_energy=target_energy)
+            return self._run_device_resident(inst, beta_list, plot, return_trace, track_best=bool(track_best), target_energy=target_energy,
+                                             num_restarts=num_restarts)
         numpy_mode = self.rng == "numpy"
         host_rng = None if numpy_mode else np.random.default_rng(self.seed)
         all_pairs = [(i, i + 1) for i in range(1, R)]
@@ -220,7 +233,7 @@ class APT_ICM(SweepMixin):
         return M, Energy
 
     def _run_device_resident(self, inst, beta_list, plot, return_trace="float64", engine_factory=Engine, track_best=False,
-                             target_energy=None):
+                             target_energy=None, num_restarts=1):
         """Throughput path (rng="philox", icm_feedback=True): every (sub-replica, replica) chain lives in ONE context,
         laid out sub-replica-major so that each sub-replica's beta ladder is a block of consecutive chains.  Per round:
         batched sweeps at the ladder temperatures -> iso-cluster moves between randomly paired sub-replicas of every
@@ -229,10 +242,13 @@ class APT_ICM(SweepMixin):
         last round's trace is read out.  Under a lane mode (`lanes`) whose sweeps the engine routes to the lane kernels, and where
         engine.APT_LANES_IN_LAUNCH holds, rounds 0 .. rounds - 2 are ONE Engine.apt_rounds_lanes call (the last round keeps its three
         calls: it records the trace); a refused call leaves every round to the three calls.  `engine_factory`: the engine class
-        (a seam for tests)."""
+        (a seam for tests).  `num_restarts` systems share the context (Engine.apt_systems): restart s owns chains s K R .. and its
+        sub-replicas are paired among themselves; the initial states of restart 0 are the first K R rows of the (G, N) draw, whatever
+        num_restarts is."""
         R, K, N = self.num_replicas, self.num_subreplicas, inst.n
         S, rounds = self.num_sweeps_MCMC_per_swap, int(self.num_swap_attempts)
-        G = K * R                                       # chain id = j * R + slot-holder index
+        G1 = K * R                                      # chains of one restart
+        G = num_restarts * G1                           # chain id = (s * K + j) * R + slot-holder index
         host_rng = np.random.default_rng(self.seed)      # initial states only
         eng = engine_factory(inst, None, G, device=self._cache.device)
         try:
@@ -240,6 +256,8 @@ class APT_ICM(SweepMixin):
                 eng.set_lane_sweeps(self.lanes)
             eng.set_spins((2 * host_rng.integers(0, 2, size=(G, N), dtype=np.int8) - 1).astype(np.int8))
             eng.pt_init(beta_list)
+            if num_restarts > 1:
+                eng.apt_systems(num_restarts)
             planner = RoundPlanner(eng, self._sweep_counter, rounds, S, self.seed)
             if self.num_swapping_pairs > 0 and rounds > 0:
                 eng.pt_plan(0, rounds, self.seed, self.num_swapping_pairs)
@@ -286,17 +304,24 @@ class APT_ICM(SweepMixin):
             dt = np.float64 if return_trace != "int8" else np.int8
             M = None if return_trace is None else np.zeros((N * R, S * K), dtype=dt)
             Energy = np.zeros(R)
+            self.restart_energies = np.zeros((num_restarts, R))
             if last is not None:
-                cols = (np.arange(G, dtype=np.int32) // R) * S
-                if return_trace is not None:
-                    M = trace_layout(last, slots_last, R, dt, dst_col=cols, row_len=S * K)
-                E_blk = np.empty((R, K * S))
-                E_blk[slots_last[:, None], cols[:, None] + np.arange(S)[None, :]] = E_rec
+                cols = (np.arange(G1, dtype=np.int32) // R) * S
+                if return_trace is not None:                           # (M, Energy): restart 0
+                    M = trace_layout(np.ascontiguousarray(last[:G1]), slots_last[:G1], R, dt, dst_col=cols, row_len=S * K)
                 k = self.num_sweeps_read_per_swap
-                Energy = np.min(E_blk[:, :k], axis=1) if k > 0 else np.min(np.zeros(0))    # np.min of nothing: ValueError
+                for s in range(num_restarts):
+                    E_blk = np.empty((R, K * S))
+                    E_blk[slots_last[s * G1:(s + 1) * G1, None], cols[:, None] + np.arange(S)[None, :]] = E_rec[s * G1:(s + 1) * G1]
+                    self.restart_energies[s] = np.min(E_blk[:, :k], axis=1) if k > 0 else np.min(np.zeros(0))    # np.min of nothing: ValueError
+                Energy = self.restart_energies[0].copy()
             if track_best:
                 b = eng.best_read()
                 self.best_energy, self.best_state, self.best_round, self.first_hit_round = b["energy"], b["state"], b["stamp"], b["first_hit"]
+                self.restart_best_energy = self.best_energy.reshape(num_restarts, G1).min(axis=1)
+                fh = self.first_hit_round.reshape(num_restarts, G1).astype(np.int64)
+                fh = np.where(fh >= 0, fh, np.iinfo(np.int64).max).min(axis=1)
+                self.restart_first_hit_round = np.where(fh == np.iinfo(np.int64).max, -1, fh).astype(np.int32)
             self.final_energies = eng.energy()
             self.final_slots = eng.pt_slots()
             self.swap_accepted = np.concatenate([a.reshape(-1) for a in acc_log]).astype(np.int8) if acc_log else np.zeros(0, np.int8)

@@ -334,6 +334,7 @@ struct nlmc_ctx {
     // APT run cut into slot blocks over ranks (nlmc_apt_shard, csrc/nlmc_apt.h)
     int apt_R = 0, apt_world = 0, apt_rank = 0;      // global ladder length; 0: not sharded by slot
     int rng_stride = 0, rng_base = 0;                // random numbers keyed by (ladder, global slot): SweepArgs::rng_*
+    int apt_systems = 1;                             // independent APT systems of n_ladders / apt_systems ladders each (nlmc_apt_systems)
     DevBuf<double> apt_beta;                         // [apt_R] the global ladder
     DevBuf<long long> apt_e_all;                     // [world][K][ladder_len]
     DevBuf<int8_t> apt_send, apt_recv;               // [2][K][n_pad]
@@ -2107,6 +2108,7 @@ int nlmc_pt_init(nlmc_ctx *c, int ladder_len, const double *beta_list)
     if (c->n_chains_global % ladder_len != 0) return fail(c, NLMC_ERR_ARG, "nlmc_pt_init: n_chains_global not a multiple of ladder_len");
     HIP_TRY(c, hipSetDevice(c->device));
     c->ladder_len = ladder_len;
+    c->apt_systems = 1;
     c->subset = 0; c->n_marked_local = 0; c->sub_dirty = true;
     c->pt_tab_valid = false;
     c->pt_plan.on = false;
@@ -2356,6 +2358,8 @@ int nlmc_apt_shard(nlmc_ctx *c, int R_global, int world, int rank, const double 
     const int L = c->ladder_len;
     if (world < 1 || rank < 0 || rank >= world || R_global != world * L)
         return fail(c, NLMC_ERR_ARG, "nlmc_apt_shard: R_global must be world x the local ladder length");
+    if (c->apt_systems > 1)
+        return fail(c, NLMC_ERR_UNSUPPORTED, "nlmc_apt_shard: the context is divided into several systems (nlmc_apt_systems): slot-keyed random numbers know one");
     if (c->chain_base != 0 || c->n_chains != c->n_chains_global)
         return fail(c, NLMC_ERR_ARG, "nlmc_apt_shard: the context must be self-contained (K ladders of its own slots: chain_base 0, n_chains_global == n_chains)");
     for (int i = 0; i < L; ++i)
@@ -2376,6 +2380,20 @@ int nlmc_apt_shard(nlmc_ctx *c, int R_global, int world, int rank, const double 
     c->apt_R = R_global; c->apt_world = world; c->apt_rank = rank;
     c->rng_stride = R_global; c->rng_base = rank * L;
     c->pt_plan.on = false;                           // (a selection planned over the local ladder is not this mode's)
+    return NLMC_OK;
+}
+
+// A context of M K ladders as M independent APT systems: system s owns ladders s K .. s K + K - 1 and only its Houdayer pairing changes
+// (nlmc_icm_round_ladders, nlmc_apt_rounds_lanes); everything else is keyed by global chain or ladder ids as before.
+int nlmc_apt_systems(nlmc_ctx *c, int n_systems)
+{
+    if (!c) return NLMC_ERR_ARG;
+    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, "nlmc_apt_systems: call nlmc_pt_init first");
+    if (n_systems < 1 || (c->n_chains_global / c->ladder_len) % n_systems != 0)
+        return fail(c, NLMC_ERR_ARG, "nlmc_apt_systems: n_systems must be at least 1 and divide the number of ladders");
+    if (n_systems > 1 && c->rng_stride != 0)
+        return fail(c, NLMC_ERR_UNSUPPORTED, "nlmc_apt_systems: random numbers keyed by temperature slot (nlmc_apt_shard) know one system");
+    c->apt_systems = n_systems;
     return NLMC_OK;
 }
 
@@ -3094,7 +3112,7 @@ int nlmc_icm_round_ladders(nlmc_ctx *c, uint32_t round, uint64_t seed, int katzg
     if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, "nlmc_icm_round_ladders: nlmc_pt_init first");
     if (c->chain_base != 0 || c->n_chains != c->n_chains_global)
         return fail(c, NLMC_ERR_UNSUPPORTED, "nlmc_icm_round_ladders: the sub-replicas of a temperature must live in one context");
-    const int R = c->ladder_len, K = c->n_chains_global / R, n_pairs = R * (K / 2);
+    const int R = c->ladder_len, M = c->apt_systems, K = c->n_chains_global / R / M, n_pairs = M * R * (K / 2);   // K ladders a system
     if (out_n_pairs) *out_n_pairs = n_pairs;
     if (n_pairs == 0) return NLMC_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -3103,7 +3121,7 @@ int nlmc_icm_round_ladders(nlmc_ctx *c, uint32_t round, uint64_t seed, int katzg
     if (!pair_in_kernel && c->rng_stride) return fail(c, NLMC_ERR_UNSUPPORTED, "nlmc_icm_round_ladders: more sub-replicas than threads with slot-keyed random numbers");
     if (!pair_in_kernel) {
         HIP_TRY(c, c->icm_pairs.reserve((size_t)n_pairs * 2));
-        hipLaunchKernelGGL(k_icm_pair_ladders, dim3((R * K + 63) / 64), dim3(64), 0, c->stream, R, K, round, (uint32_t)seed,
+        hipLaunchKernelGGL(k_icm_pair_ladders, dim3((M * R * K + 63) / 64), dim3(64), 0, c->stream, M, R, K, round, (uint32_t)seed,
                            (uint32_t)(seed >> 32), c->chain_of_slot.p, c->icm_pairs.p);
         HIP_TRY(c, hipGetLastError());
     }
@@ -3121,7 +3139,7 @@ int nlmc_icm_round_ladders(nlmc_ctx *c, uint32_t round, uint64_t seed, int katzg
     return NLMC_OK;
 }
 
-// ---- APT rounds of short chains: one system per workgroup (k_apt_rounds_lanes, csrc/nlmc_lane_apt.h) --------------------------------
+// ---- APT rounds of short chains: one system per workgroup, a workgroup per system (k_apt_rounds_lanes, csrc/nlmc_lane_apt.h) --------
 // LDS of k_apt_rounds_lanes for W waves: spins of every wave | slot maps | pair_col | energy deltas | labels, sharing their bytes with
 // the waves' random-number tables where those fit too.  ok = false: the carve-up without the tables exceeds NLMC_APT_LANES_LDS.
 constexpr size_t NLMC_APT_LANES_LDS = (size_t)150 * 1024;
@@ -3160,7 +3178,8 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
     if (c->chain_base != 0 || c->n_chains != c->n_chains_global) return no("the sub-replicas of a temperature must live in one context");
     if (c->rng_stride != 0) return no("random numbers keyed by temperature slot (nlmc_apt_shard) keep the round-by-round route");
     if (const char *why = rounds_lanes_refusal(c, n_rounds, T, round0, seed, n_pairs, true)) return no(why);
-    const int L = c->ladder_len, n = c->n, K = c->n_chains_global / L, P = 64 / L, W = (K + P - 1) / P, NP = L * (K / 2);
+    // (M systems, nlmc_apt_systems: a workgroup each; K, W, NP and the LDS carve-up are those of ONE system)
+    const int L = c->ladder_len, n = c->n, M = c->apt_systems, K = c->n_chains_global / L / M, P = 64 / L, W = (K + P - 1) / P, NP = L * (K / 2);
     if (W > 16) return no("the system needs more than 16 waves: it does not fit one workgroup");
     const AptLanesLds A = apt_lanes_lds(c, K, L, W);
     if (!A.ok) return no("the system's chains and labels exceed one workgroup's LDS (150 KB)");
@@ -3175,7 +3194,7 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
     HIP_TRY(c, c->lane_perm.reserve((size_t)R * (size_t)T * (size_t)n));
     { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
     const bool want_info = out_info && NP > 0;
-    if (want_info) HIP_TRY(c, c->icm_info.reserve((size_t)n_rounds * NP * 2));
+    if (want_info) HIP_TRY(c, c->icm_info.reserve((size_t)n_rounds * M * NP * 2));
     const void *kfun = precision == NLMC_F64 ? reinterpret_cast<const void *>(k_apt_rounds_lanes<true>)
                                              : reinterpret_cast<const void *>(k_apt_rounds_lanes<false>);
     { int rc = ensure_lds(c, kfun, A.total); if (rc) return rc; }
@@ -3199,22 +3218,23 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
         a.lane_perm = c->lane_perm.p; a.lane_rows = c->n_chains; a.lane_diag = c->has_diag ? 1 : 0; a.lane_tab = A.tab ? 1 : 0;
         a.lds_u_off = (int)A.u_off;
         LaneRoundsArgs q{};
-        q.n_rounds = k; q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = K; q.round0 = r0;
+        const size_t nl = (size_t)M * K;                       // plan and log rows hold every ladder of the context
+        q.n_rounds = k; q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = (int)nl; q.round0 = r0;
         q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
-        if (n_pairs > 0) q.plan_pairs = c->pt_plan_pairs.p + c->pt_plan.row(r0) * (size_t)K * n_pairs * 2;
+        if (n_pairs > 0) q.plan_pairs = c->pt_plan_pairs.p + c->pt_plan.row(r0) * nl * n_pairs * 2;
         if (log) {
             const size_t lr = c->pt_log.row(r0);
-            q.log_pairs = c->pt_log_pairs.p + lr * (size_t)K * n_pairs * 2;
-            q.log_acc = c->pt_log_acc.p + lr * (size_t)K * n_pairs;
+            q.log_pairs = c->pt_log_pairs.p + lr * nl * n_pairs * 2;
+            q.log_acc = c->pt_log_acc.p + lr * nl * n_pairs;
         }
         q.lds_map_off = (int)A.map_off;
         LaneAptArgs x{};
         x.n_sub = K; x.n_icm = NP; x.katz = katzgraber ? 1 : 0;
-        x.info = want_info ? c->icm_info.p + (size_t)at * NP * 2 : nullptr;
+        x.info = want_info ? c->icm_info.p + (size_t)at * M * NP * 2 : nullptr;
         x.lds_wave_bytes = (int)A.wave; x.lds_tab_bytes = (int)A.tab_wave; x.lds_pcol_off = (int)A.pcol_off; x.lds_de_off = (int)A.de_off;
         x.lds_lab_off = (int)A.u_off; x.lab_stride = A.lab_stride;
         void *kargs[] = {&a, &q, &x};
-        HIP_TRY(c, hipLaunchKernel(kfun, dim3(1), dim3((unsigned)(64 * W)), kargs, A.total, c->stream));
+        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)M), dim3((unsigned)(64 * W)), kargs, A.total, c->stream));
         HIP_TRY(c, hipGetLastError());
         { int rc = span_end(c, ts); if (rc) return rc; }
         if (c->ev_accumulate) c->launches_timed += k;
@@ -3225,7 +3245,7 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
     c->last_route = NLMC_ROUTE_LANES;
     c->rounds_route = NLMC_ROUNDS_APT_LANES;
     if (want_info) {
-        const size_t cnt = (size_t)n_rounds * NP * 2;
+        const size_t cnt = (size_t)n_rounds * M * NP * 2;
         HIP_TRY(c, hipMemcpyAsync(out_info, c->icm_info.p, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (size_t p = 0; p < cnt; p += 2)

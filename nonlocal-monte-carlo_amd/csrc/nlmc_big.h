@@ -449,17 +449,18 @@ __global__ __launch_bounds__(1024) void k_icm_round_big(IcmRoundArgs a, int32_t 
     __shared__ int sh_pair[2], sh_lad[2];
     const int n = a.g.n, n_pad = a.g.n_pad, tid = threadIdx.x, nt = blockDim.x, p = blockIdx.x;
     if (!a.pairs) {
-        const int half = a.pair_K / 2, r = p / half, i = p % half;
+        const int half = a.pair_K / 2, r = (p / half) % a.pair_R, i = p % half;
+        const int j0 = p / (a.pair_R * half) * a.pair_K, j = j0 + tid;       // first ladder of the block's system; this thread's ladder
         const uint32_t rg = (uint32_t)(r + a.slot0);
         if (tid < a.pair_K) {
-            const uint32_t kj = philox4x32_10((uint32_t)tid, a.round, rg, NLMC_TAG_ICM_PAIR, a.seed_lo, a.seed_hi).x;
+            const uint32_t kj = philox4x32_10((uint32_t)j, a.round, rg, NLMC_TAG_ICM_PAIR, a.seed_lo, a.seed_hi).x;
             int rank = 0;
-            for (int q = 0; q < a.pair_K; ++q) {
-                if (q == tid) continue;
+            for (int q = j0; q < j0 + a.pair_K; ++q) {
+                if (q == j) continue;
                 const uint32_t kq = philox4x32_10((uint32_t)q, a.round, rg, NLMC_TAG_ICM_PAIR, a.seed_lo, a.seed_hi).x;
-                rank += (kq < kj) || (kq == kj && q < tid);
+                rank += (kq < kj) || (kq == kj && q < j);
             }
-            if (rank == 2 * i || rank == 2 * i + 1) { sh_pair[rank & 1] = a.chain_of_slot[(size_t)tid * a.pair_R + r]; sh_lad[rank & 1] = tid; }
+            if (rank == 2 * i || rank == 2 * i + 1) { sh_pair[rank & 1] = a.chain_of_slot[(size_t)j * a.pair_R + r]; sh_lad[rank & 1] = j; }
         }
         __syncthreads();
     }
@@ -500,7 +501,7 @@ __global__ __launch_bounds__(1024) void k_icm_round_big(IcmRoundArgs a, int32_t 
     }
     uint32_t ida = (uint32_t)(a.chain_base + ca), idb = (uint32_t)(a.chain_base + cb);
     if (a.rng_stride && !a.pairs) {
-        const int rl = p / (a.pair_K / 2);
+        const int rl = p / (a.pair_K / 2) % a.pair_R;
         ida = (uint32_t)(sh_lad[0] * a.rng_stride + a.rng_base + rl);
         idb = (uint32_t)(sh_lad[1] * a.rng_stride + a.rng_base + rl);
     }

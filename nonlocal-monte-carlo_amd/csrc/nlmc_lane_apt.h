@@ -14,7 +14,10 @@
 //              reads registers and writes a table nobody reads before it.)
 //   swaps    : the swap round of k_rounds_lanes, unchanged.
 // Same bits as nlmc_sweep_philox(beta = NULL) + nlmc_icm_round_ladders + nlmc_pt_swap_philox round by round, on any route.  No wave
-// waits on memory written by another workgroup: grid = 1, no poll, no atomic, no cooperative launch, no fence but the barriers.
+// waits on memory written by another workgroup: no poll, no atomic, no cooperative launch, no fence but the barriers.
+// Grid = M systems (nlmc_apt_systems), a workgroup each: workgroup b owns chains b K L .. and ladders b K .., reads and writes only their
+// rows of every array, and ranks only its own K pairing keys.  Random numbers, plan and log rows stay keyed by the GLOBAL chain / ladder
+// id, so workgroup 0 has the bits of a one-system launch.  No residency condition: M may exceed the number of compute units.
 #pragma once
 #include "nlmc_lane_rounds.h"
 #include "nlmc_lane_icm.h"
@@ -24,7 +27,7 @@ struct LaneAptArgs {
     int n_sub;                       // K, sub-replica ladders of the system
     int n_icm;                       // Houdayer pairs per round, L (K / 2): threads 0 .. n_icm - 1 own one each
     int katz;
-    int32_t *info;                   // [n_rounds][n_icm][2] {n_components, picked size} at the launch's first round, or nullptr
+    int32_t *info;                   // [n_rounds][gridDim.x][n_icm][2] {n_components, picked size} at the launch's first round, or nullptr
     int lds_wave_bytes;              // a wave's transposed spins: n_pad * 64
     int lds_tab_bytes;               // a wave's random-number table (SweepArgs::lds_u_off + wave * lds_tab_bytes)
     int lds_pcol_off;                // pair_col[slot][rank], 16-bit columns (wave * 64 + lane)
@@ -46,9 +49,11 @@ __global__ __launch_bounds__(1024) void k_apt_rounds_lanes(SweepArgs a, LaneRoun
     const int nlad = min(P, K - lad0);                                  // its ladders (wave-uniform, >= 1)
     const int row0 = lad0 * L, nrow = nlad * L;
     const bool live = lane < nrow;
-    const int c = live ? row0 + lane : row0;                            // chain (tail lanes: the wave's first, read only)
+    const int sys = blockIdx.x, g0 = sys * K;                           // this workgroup's system and its first ladder
+    const size_t c0 = (size_t)g0 * L;                                   // its first chain: row of spins, efix, sink, slot_of_chain
+    const int c = live ? row0 + lane : row0;                            // chain of the system (tail lanes: the wave's first, read only)
     const int lw = live ? lane / L : 0, base = lw * L;
-    const int g = lad0 + lw;                                            // ladder: Philox key, rows of plan / log / chain_of_slot
+    const int g = g0 + lad0 + lw;                                       // GLOBAL ladder: Philox key, rows of plan / log / chain_of_slot
     unsigned char *lds_w = lds_raw + (size_t)w * x.lds_wave_bytes;      // this wave's region
     int8_t *s = reinterpret_cast<int8_t *>(lds_w);
     uint32_t *rtab = a.lane_tab ? reinterpret_cast<uint32_t *>(lds_raw + a.lds_u_off + (size_t)w * x.lds_tab_bytes) : nullptr;
@@ -59,10 +64,10 @@ __global__ __launch_bounds__(1024) void k_apt_rounds_lanes(SweepArgs a, LaneRoun
 
     // prologue: the rows of the wave's chains, read coalesced, written transposed
     for (int r = 0; r < 64; ++r) {
-        if (r < nrow) lane_column_in(lds_w, stride, r, a.spins + (size_t)(row0 + r) * n_pad, n_pad, lane);
+        if (r < nrow) lane_column_in(lds_w, stride, r, a.spins + (c0 + row0 + r) * n_pad, n_pad, lane);
         else for (int j = lane; j < n_pad; j += 64) lds_w[j * stride + r] = 0;
     }
-    int slot = q.slot_of_chain[c];
+    int slot = q.slot_of_chain[c0 + c];
     lane_of_slot[lane] = (uint8_t)lane;
     slot_of_lane[lane] = (uint8_t)slot;
     dEw[tid] = 0;
@@ -70,11 +75,11 @@ __global__ __launch_bounds__(1024) void k_apt_rounds_lanes(SweepArgs a, LaneRoun
     if (live) lane_of_slot[base + slot] = (uint8_t)lane;
     lane_lds_fence();
 
-    const uint32_t gc = (uint32_t)c;                                    // (the whole system, random numbers keyed by chain)
+    const uint32_t gc = (uint32_t)(c0 + c);                             // (random numbers keyed by the global chain id)
     T cb0 = scale_cb((T)a.tab[(size_t)slot * a.tab_cs], a.qinv);
     const double esc = __longlong_as_double((long long)(1023 + a.escale) << 52);   // 2^escale
     const double inv = __longlong_as_double((long long)(1023 - a.escale) << 52);   // 2^-escale
-    long long E = a.efix[c];
+    long long E = a.efix[c0 + c];
     const bool decides = live && (lane - base) < q.n_pairs;
     const int p = lane - base;
 
@@ -137,7 +142,7 @@ __global__ __launch_bounds__(1024) void k_apt_rounds_lanes(SweepArgs a, LaneRoun
             if (live) {
                 const uint32_t kj = philox4x32_10((uint32_t)g, round, (uint32_t)slot, NLMC_TAG_ICM_PAIR, a.seed_lo, a.seed_hi).x;
                 int rank = 0;                                 // position of this ladder in the shuffled order of its slot
-                for (int j = 0; j < K; ++j) {
+                for (int j = g0; j < g0 + K; ++j) {
                     const uint32_t ki = philox4x32_10((uint32_t)j, round, (uint32_t)slot, NLMC_TAG_ICM_PAIR, a.seed_lo, a.seed_hi).x;
                     rank += (j != g) && ((ki < kj) || (ki == kj && j < g));
                 }
@@ -160,7 +165,7 @@ __global__ __launch_bounds__(1024) void k_apt_rounds_lanes(SweepArgs a, LaneRoun
                 int root = -1, size = 0;
                 if (ncomp > 0) {
                     // component number floor(u ncomp / 2^32) in ascending order of the roots, keyed by the two chain ids (k_icm_round)
-                    const uint32_t ida = (uint32_t)((ca >> 6) * P * L + (ca & 63)), idb = (uint32_t)((cb >> 6) * P * L + (cb & 63));
+                    const uint32_t ida = (uint32_t)c0 + (uint32_t)((ca >> 6) * P * L + (ca & 63)), idb = (uint32_t)c0 + (uint32_t)((cb >> 6) * P * L + (cb & 63));
                     const uint32_t u = philox4x32_10(ida, round, idb, NLMC_TAG_ICM, a.seed_lo, a.seed_hi).x;
                     const int pick = (int)(((unsigned long long)u * (unsigned long long)ncomp) >> 32);
                     int seen = 0;
@@ -197,7 +202,7 @@ __global__ __launch_bounds__(1024) void k_apt_rounds_lanes(SweepArgs a, LaneRoun
                 dEw[ca] = dEa;
                 dEw[cb] = dEb;
                 if (x.info) {
-                    int32_t *o = x.info + ((size_t)r * x.n_icm + tid) * 2;
+                    int32_t *o = x.info + (((size_t)r * gridDim.x + sys) * x.n_icm + tid) * 2;
                     o[0] = ncomp; o[1] = size;
                 }
             }
@@ -237,11 +242,11 @@ __global__ __launch_bounds__(1024) void k_apt_rounds_lanes(SweepArgs a, LaneRoun
         }
     }
     lane_lds_fence();
-    for (int r = 0; r < nrow; ++r) lane_column_out(lds_w, stride, r, a.spins + (size_t)(row0 + r) * n_pad, n_pad, lane);
+    for (int r = 0; r < nrow; ++r) lane_column_out(lds_w, stride, r, a.spins + (c0 + row0 + r) * n_pad, n_pad, lane);
     if (live) {
-        a.efix[c] = E;
-        if (a.energy_sink) a.energy_sink[c] = (double)E * inv;
-        q.slot_of_chain[c] = slot;
-        q.chain_of_slot[(size_t)g * L + slot] = c;
+        a.efix[c0 + c] = E;
+        if (a.energy_sink) a.energy_sink[c0 + c] = (double)E * inv;
+        q.slot_of_chain[c0 + c] = slot;
+        q.chain_of_slot[(size_t)g * L + slot] = (int32_t)(c0 + c);
     }
 }

@@ -282,8 +282,9 @@ struct IcmRoundArgs {
     CsrDev g;
     int8_t *spins;            // [n_chains][n_pad]
     const int32_t *pairs;     // [n_pairs][2] local chain ids, or nullptr: the Houdayer pairing of the APT round is made here --
-    int pair_R, pair_K;       // block p pairs the ladders ranked 2i, 2i+1 among the K ladders of slot r = p / (K/2), i = p % (K/2),
-    const int32_t *chain_of_slot;   // ranks by the keys philox(j, round, r, ICM_PAIR) (k_icm_pair_ladders' law, NPT/apt_ICM.py:216-222)
+    int pair_R, pair_K;       // block p pairs the ladders ranked 2i, 2i+1 among the K ladders of system s = p / (R (K/2)) on slot
+    const int32_t *chain_of_slot;   // r = (p / (K/2)) % R, i = p % (K/2); ranks by the keys philox(j, round, r, ICM_PAIR), j = s K + t the
+                              // GLOBAL ladder (k_icm_pair_ladders' law, NPT/apt_ICM.py:216-222; nlmc_apt_systems: K of ONE system)
     int32_t *info;            // [n_pairs][2]  {n_components (-1: hook rounds did not converge), picked size}
     const uint4 *adj;         // 16-bit adjacency table or nullptr (see IcmArgs)
     uint32_t round, seed_lo, seed_hi;
@@ -308,17 +309,18 @@ __global__ __launch_bounds__(1024) void k_icm_round(IcmRoundArgs a)
     const int n = a.g.n, n_pad = a.g.n_pad, tid = threadIdx.x, nt = blockDim.x, p = blockIdx.x;
     __shared__ int sh_pair[2], sh_lad[2];
     if (!a.pairs) {                        // pairing on the fly (pair_K <= blockDim.x: checked by the host)
-        const int half = a.pair_K / 2, r = p / half, i = p % half;
+        const int half = a.pair_K / 2, r = (p / half) % a.pair_R, i = p % half;
+        const int j0 = p / (a.pair_R * half) * a.pair_K, j = j0 + tid;       // first ladder of the block's system; this thread's ladder
         const uint32_t rg = (uint32_t)(r + a.slot0);
         if (tid < a.pair_K) {
-            const uint32_t kj = philox4x32_10((uint32_t)tid, a.round, rg, 6u /*NLMC_TAG_ICM_PAIR*/, a.seed_lo, a.seed_hi).x;
+            const uint32_t kj = philox4x32_10((uint32_t)j, a.round, rg, 6u /*NLMC_TAG_ICM_PAIR*/, a.seed_lo, a.seed_hi).x;
             int rank = 0;
-            for (int q = 0; q < a.pair_K; ++q) {
-                if (q == tid) continue;
+            for (int q = j0; q < j0 + a.pair_K; ++q) {
+                if (q == j) continue;
                 const uint32_t kq = philox4x32_10((uint32_t)q, a.round, rg, 6u, a.seed_lo, a.seed_hi).x;
-                rank += (kq < kj) || (kq == kj && q < tid);
+                rank += (kq < kj) || (kq == kj && q < j);
             }
-            if (rank == 2 * i || rank == 2 * i + 1) { sh_pair[rank & 1] = a.chain_of_slot[(size_t)tid * a.pair_R + r]; sh_lad[rank & 1] = tid; }
+            if (rank == 2 * i || rank == 2 * i + 1) { sh_pair[rank & 1] = a.chain_of_slot[(size_t)j * a.pair_R + r]; sh_lad[rank & 1] = j; }
         }
         __syncthreads();
     }
@@ -408,7 +410,7 @@ __global__ __launch_bounds__(1024) void k_icm_round(IcmRoundArgs a)
     // pick component number floor(r ncomp / 2^32) in ascending-label order (NPT/apt_ICM.py:232-233)
     uint32_t ida = (uint32_t)(a.chain_base + ca), idb = (uint32_t)(a.chain_base + cb);
     if (a.rng_stride && !a.pairs) {        // keyed by (ladder, global slot): the same pick whichever chains sit on the two places
-        const int rl = p / (a.pair_K / 2);
+        const int rl = p / (a.pair_K / 2) % a.pair_R;
         ida = (uint32_t)(sh_lad[0] * a.rng_stride + a.rng_base + rl);
         idb = (uint32_t)(sh_lad[1] * a.rng_stride + a.rng_base + rl);
     }
@@ -497,20 +499,22 @@ __global__ __launch_bounds__(1024) void k_icm_round(IcmRoundArgs a)
 // are shuffled -- order = sort of the keys philox(j, round, r, ICM_PAIR) -- and paired (sh[0], sh[1]), (sh[2], sh[3]), ...;
 // a pair is written as the two LOCAL chains that currently hold slot r in those ladders.
 #define NLMC_TAG_ICM_PAIR 6u
-__global__ void k_icm_pair_ladders(int R, int K, uint32_t round, uint32_t seed_lo, uint32_t seed_hi,
+// M systems of K ladders each (nlmc_apt_systems): system s shuffles its own ladders s K .. s K + K - 1, keyed by the global ladder id;
+// its pairs follow those of system s - 1.
+__global__ void k_icm_pair_ladders(int M, int R, int K, uint32_t round, uint32_t seed_lo, uint32_t seed_hi,
                                    const int32_t *chain_of_slot, int32_t *pairs)
 {
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;          // one thread per (slot r, ladder j)
-    if (id >= R * K) return;
-    const int r = id / K, j = id % K, half = K / 2;
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;          // one thread per (system s, slot r, ladder j of the system)
+    if (id >= M * R * K) return;
+    const int sr = id / K, s = sr / R, r = sr % R, j0 = s * K, j = j0 + id % K, half = K / 2;
     const uint32_t kj = philox4x32_10((uint32_t)j, round, (uint32_t)r, NLMC_TAG_ICM_PAIR, seed_lo, seed_hi).x;
-    int rank = 0;                              // position of ladder j in the shuffled order of slot r
-    for (int i = 0; i < K; ++i) {
+    int rank = 0;                              // position of ladder j in the shuffled order of slot r of its system
+    for (int i = j0; i < j0 + K; ++i) {
         if (i == j) continue;
         const uint32_t ki = philox4x32_10((uint32_t)i, round, (uint32_t)r, NLMC_TAG_ICM_PAIR, seed_lo, seed_hi).x;
         rank += (ki < kj) || (ki == kj && i < j);
     }
-    if (rank < 2 * half) pairs[((size_t)r * half + rank / 2) * 2 + (rank & 1)] = chain_of_slot[(size_t)j * R + r];
+    if (rank < 2 * half) pairs[((size_t)sr * half + rank / 2) * 2 + (rank & 1)] = chain_of_slot[(size_t)j * R + r];
 }
 
 struct IcmMoveArgs {

@@ -53,6 +53,8 @@ def _beta_table(beta, R, S):
 
 
 class Engine:
+    n_systems = 1            # independent APT systems the ladders are divided into (apt_systems; pt_init resets it)
+
     def __init__(self, J, h, n_chains, device=0, stream=None, chain_base=0, n_chains_global=None, own_stream=False):
         self.inst = J if isinstance(J, Instance) else Instance(J, h)
         if not self.inst.symmetric:
@@ -374,6 +376,7 @@ class Engine:
         b = _abi.as_c(beta_list, np.float64).reshape(-1)
         self._ck(self._L.nlmc_pt_init(self._ctx, b.shape[0], _abi.ptr(b)))
         self.ladder_len = int(b.shape[0])
+        self.n_systems = 1
 
     def pt_slots(self):
         s = np.empty(self.n_chains_global, dtype=np.int32)
@@ -440,6 +443,19 @@ class Engine:
         b = _abi.as_c(beta_global, np.float64).reshape(-1)
         self._ck(self._L.nlmc_apt_shard(self._ctx, b.shape[0], int(world), int(rank), _abi.ptr(b)))
         self.apt_world, self.apt_rank, self.apt_R = int(world), int(rank), int(b.shape[0])
+
+    def apt_systems(self, n_systems):
+        """Divide the context's n_ladders = M K ladders into M = n_systems independent APT systems of K ladders (include/nlmc.h:
+        nlmc_apt_systems): icm_round_ladders and apt_rounds_lanes then pair the ladders of each system among themselves and list
+        their info rows in the order (system, slot, pair); everything else stays keyed by global chain and ladder ids, so system 0
+        has the bits of a one-system context of K L chains.  After pt_init (which resets it to 1); not together with apt_shard."""
+        self._ck(self._L.nlmc_apt_systems(self._ctx, int(n_systems)))
+        self.n_systems = int(n_systems)
+
+    def _icm_rows(self):
+        """Houdayer pairs of one round: M systems x L slots x (K // 2), K the ladders of a system."""
+        R, M = self.ladder_len, self.n_systems
+        return M * R * ((self.n_chains_global // R // M) // 2) if R else 0
 
     def apt_pack(self, want_configs=True):
         """(tracked energies [K, Rw] int64 in units of 2^-energy_scale by (ladder, local slot), configurations on local slot 0
@@ -529,11 +545,10 @@ class Engine:
         workgroup, a chain per lane, a Houdayer pair per lane.  n_pairs = 0: rounds without swaps; otherwise the pair selections are
         planned (pt_plan).  Returns (queued, info): queued False when the context does not qualify (nothing was run; the reason is in
         rounds_fused_refusal); info [n_rounds, L * (K // 2), 2] = {n_components, picked size} with want_info (a read-back: it
-        synchronises the stream), else None.  Same bits as sweep_philox(beta=None) + icm_round_ladders + pt_swap_philox round by round."""
+        synchronises the stream), else None.  Same bits as sweep_philox(beta=None) + icm_round_ladders + pt_swap_philox round by round.
+        Under apt_systems(M): a workgroup per system, K the ladders of one system, info [n_rounds, M * L * (K // 2), 2]."""
         prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
-        R = self.ladder_len
-        K = self.n_chains_global // R if R else 0
-        info = np.zeros((int(n_rounds), R * (K // 2), 2), np.int32) if want_info else None
+        info = np.zeros((int(n_rounds), self._icm_rows(), 2), np.int32) if want_info else None
         rc = self._L.nlmc_apt_rounds_lanes(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
                                            int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs), int(bool(katzgraber)), _abi.ptr(info))
         if rc == _abi.ERR_UNSUPPORTED:
@@ -669,11 +684,10 @@ class Engine:
         return info
 
     def icm_round_ladders(self, round_idx, seed, katzgraber=True, want_info=False):
-        """Houdayer step of one APT round with the pairing decided on the device (include/nlmc.h)."""
+        """Houdayer step of one APT round with the pairing decided on the device (include/nlmc.h); info [M * L * (K // 2), 2] in the
+        order (system, slot, pair) under apt_systems(M), K the ladders of one system."""
         npairs = ctypes.c_int32(0)
-        R = self.ladder_len
-        K = self.n_chains_global // R
-        info = np.zeros((R * (K // 2), 2), np.int32) if want_info else None
+        info = np.zeros((self._icm_rows(), 2), np.int32) if want_info else None
         self._ck(self._L.nlmc_icm_round_ladders(self._ctx, int(round_idx), int(seed), int(bool(katzgraber)),
                                                 ctypes.byref(npairs), _abi.ptr(info)))
         return info
