@@ -169,7 +169,10 @@ int nlmc_plan_philox(nlmc_ctx *ctx, int precision, int order_mode, uint32_t swee
  * next level with room (level fill; NLMC_NO_LEVEL_FILL=1, read at nlmc_create: every update keeps its earliest level and a wider
  * level is cut into consecutive levels of that width instead, which moves everything behind it one level back).  Which updates
  * are moved depends on the order in which the planner's threads reach a level, so two plans of the same window may differ by a
- * level or two in depth, as they always could in the positions inside a level; the sweeps' results depend on neither. */
+ * level or two in depth, as they always could in the positions inside a level; the sweeps' results depend on neither.
+ * A row of up to 8 entries takes one schedule position, one of 9-16 entries two (a lane pair of the sweep kernel), one of 17-32
+ * entries four (a lane quad); only what a row holds beyond 32 entries is read from the CSR arrays while the sweeps run.
+ * NLMC_NO_QUADS=1, read at nlmc_create: two positions for every row beyond 8 entries, the CSR arrays beyond 16 -- same results. */
 int nlmc_plan_philox_fused(nlmc_ctx *ctx, uint32_t sweep0, int n_windows, int window, uint64_t seed, int32_t *out_planned);
 /* Which precisions may run on fused windows of `window` sweeps on this context: bit 0 = NLMC_F32, bit 1 = NLMC_F64.  The fp64
  * mode (the reference's arithmetic, NMC/nmc.py:86-87: fp64 field, 53-bit uniform) qualifies when every coupling AND every field

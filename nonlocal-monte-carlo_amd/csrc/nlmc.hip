@@ -74,6 +74,7 @@ struct Knobs {
     bool no_dbuf = false;            // NLMC_NO_DBUF: sweep-by-sweep kernels keep one copy of the per-sweep uniforms in LDS
     int big_per_level = -1;          // NLMC_BIG_PER_LEVEL: long chains run one launch per level (1) / per window (0); -1: by count
     bool no_bank_aware = false;      // NLMC_NO_BANK_AWARE: the fused planner does not place items by LDS bank
+    bool no_quads = false;           // NLMC_NO_QUADS: a row of more than 16 entries takes a lane pair and its CSR tail, not a lane quad
     bool no_level_fill = false;      // NLMC_NO_LEVEL_FILL: the fused planner gives every update its earliest level and splits full levels
     bool fz_stats = false;           // NLMC_FZ_STATS: the fused planner prints the phase cycle counts of window 0 on stderr
     unsigned tie_mask = 0xFFFFFFFFu; // NLMC_F64_TIE_MASK: high-word mask of the fp64 fused kernels' exact-path test (test knob)
@@ -102,7 +103,7 @@ Knobs read_knobs()
     k.no_fused = on("NLMC_NO_FUSED"); k.no_fused64 = on("NLMC_NO_FUSED64"); k.no_fused_out = on("NLMC_NO_FUSED_OUT");
     k.no_warm = on("NLMC_NO_WARM"); k.no_prio = on("NLMC_FUSED_NOPRIO"); k.no_dbuf = on("NLMC_NO_DBUF");
     k.big_per_level = on("NLMC_BIG_PER_LEVEL") ? num("NLMC_BIG_PER_LEVEL", 0) != 0 : -1;
-    k.no_bank_aware = on("NLMC_NO_BANK_AWARE"); k.no_level_fill = on("NLMC_NO_LEVEL_FILL"); k.fz_stats = on("NLMC_FZ_STATS");
+    k.no_bank_aware = on("NLMC_NO_BANK_AWARE"); k.no_level_fill = on("NLMC_NO_LEVEL_FILL"); k.fz_stats = on("NLMC_FZ_STATS"); k.no_quads = on("NLMC_NO_QUADS");
     if (const char *s = getenv("NLMC_F64_TIE_MASK")) k.tie_mask = (unsigned)strtoul(s, nullptr, 0);
     k.no_persistent = on("NLMC_NO_PERSISTENT"); k.no_deferred = on("NLMC_NO_DEFERRED");
     k.lbp_group = num("NLMC_LBP_GROUP", 0); k.lbp_poll_budget = num("NLMC_LBP_POLL_BUDGET", 0); k.lbp_global = on("NLMC_LBP_GLOBAL");
@@ -248,7 +249,8 @@ struct nlmc_ctx {
     uint64_t plan_seed = 0;
     // fused-window plan (k_levelize_fused / k_sweep_fused)
     int max_deg = 0;
-    int n_long = 0;                    // rows with more than NLMC_FZ_W entries (two schedule positions in a fused plan)
+    int n_long = 0;                    // schedule positions a sweep takes beyond one per row in a fused plan: one for a row of more than
+                                       // NLMC_FZ_W entries (a lane pair), three for one of more than 2 NLMC_FZ_W (a lane quad)
     int stat_fused_window = -1;          // >= 0: the most recent sweep call ran this fused window
     // Two plan slots (nlmc_plan_slot): a replica-exchange round whose marked slots run NMC cycles sweeps its plain chains
     // on windows of one length and its NMC phases on windows of another (NPT/npt.py:577-580).
@@ -650,7 +652,7 @@ bool fused_addr_format(const nlmc_ctx *c)
     return c->sign8 && 2 * (c->n_pad + 16) <= 0xFFFF && fused_lds(c->n_pad, true, false, true).total <= (size_t)150 * 1024;
 }
 
-// schedule positions reserved per window: one per update, two for a row longer than NLMC_FZ_W entries (n_long of them),
+// schedule positions reserved per window: one per update, two or four for a row on a lane pair or quad (n_long more per sweep),
 // plus the padding of every level to a chunk boundary
 int fused_pstride(int n, int n_long, int T) { return (int)((((size_t)T * ((size_t)n + n_long) + 63) / 64 + NLMC_LCAP) * 64); }
 
@@ -783,7 +785,7 @@ SweepArgs sweep_args(const nlmc_ctx *c, uint32_t sweep0, int n_sweeps, uint64_t 
 // of the launch, the range of the integer field.
 void fused_args(const nlmc_ctx *c, const nlmc_ctx::FusedPlan &P, const FusedLds &L, SweepArgs &a)
 {
-    a.fz_pstride = P.pstride; a.fz_fmt = P.fmt;
+    a.fz_pstride = P.pstride; a.fz_fmt = P.fmt; a.fz_qmask = c->knobs.no_quads ? 0xC000 : 0x8000;
     a.f_workers = P.workers; a.f_gen0 = P.gen0; a.f_gen_prio = c->knobs.no_prio ? 0 : 1;
 #ifdef NLMC_DEBUG_KNOBS
     a.dbg_flags = c->knobs.dbg_flags;
@@ -1402,11 +1404,12 @@ int nlmc_create(nlmc_ctx **out, int device, void *hip_stream, int n, int64_t nnz
     if (n > NLMC_MAX_N) return fail(nullptr, NLMC_ERR_UNSUPPORTED, "nlmc_create: n exceeds NLMC_MAX_N");
     if (rowptr[0] != 0 || rowptr[n] != nnz) return fail(nullptr, NLMC_ERR_ARG, "nlmc_create: rowptr[0] != 0 or rowptr[n] != nnz");
     bool diag = false, zero_vals = false;
-    int max_deg = 0, n_long = 0;
+    int max_deg = 0, n_gt8 = 0, n_gt16 = 0;     // rows longer than one / two row windows of a fused plan
     for (int k = 0; k < n; ++k) {
         if (rowptr[k + 1] < rowptr[k]) return fail(nullptr, NLMC_ERR_ARG, "nlmc_create: rowptr not monotone");
         max_deg = std::max(max_deg, (int)(rowptr[k + 1] - rowptr[k]));
-        n_long += (rowptr[k + 1] - rowptr[k]) > NLMC_FZ_W;
+        n_gt8 += (rowptr[k + 1] - rowptr[k]) > NLMC_FZ_W;
+        n_gt16 += (rowptr[k + 1] - rowptr[k]) > 2 * NLMC_FZ_W;
         for (int e = rowptr[k]; e < rowptr[k + 1]; ++e) {
             if (colidx[e] < 0 || colidx[e] >= n) return fail(nullptr, NLMC_ERR_ARG, "nlmc_create: column index out of range");
             if (colidx[e] == k && vals[e] != 0.0) diag = true;
@@ -1436,7 +1439,7 @@ int nlmc_create(nlmc_ctx **out, int device, void *hip_stream, int n, int64_t nnz
     c->has_diag = diag;
     c->has_zero_vals = zero_vals;
     c->max_deg = max_deg;
-    c->n_long = n_long;
+    c->n_long = n_gt8 + (c->knobs.no_quads ? 0 : 2 * n_gt16);
 
     // fixed-point scales.  Energies: integers in units of 2^-escale, |E| <= sum|J|/2 + sum|h|.  Couplings of the "f32"
     // throughput path: Jq = rint(J 2^qs), hq = rint(h 2^qs) with qs the largest exponent such that every |Jq| fits a
@@ -1928,6 +1931,7 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
     a.k_zero = c->n_pad + 8;
     a.neg_off = c->n_pad + 16;
     a.bank_aware = (with_val || c->knobs.no_bank_aware) ? 0 : 1;    // (the fp64 sum runs in row order)
+    a.quads = c->knobs.no_quads ? 0 : 1;
     a.val = with_val ? P.val.p : nullptr;
     P.fmt = a.fmt;
     P.has_val = with_val;

@@ -235,10 +235,16 @@ __global__ void k_levelize(LevelizeArgs a)
 // ------------------------------------------------------------------------------------------------------
 #define NLMC_LCAP 1024          // level offsets of one schedule kept in LDS by the sweep kernels
 #define NLMC_FUSED_TMAX 64
-#define NLMC_FZ_W 8              // row entries per schedule position of a fused plan; longer rows take two positions
+#define NLMC_FZ_W 8              // row entries per schedule position of a fused plan; longer rows take two or four positions
 #define NLMC_FMT_WIDE 0
 #define NLMC_FMT_COMPACT 1
 #define NLMC_FMT_ADDR 2
+// bits 14-15 of an item head: how many lanes the item's row is spread over (NLMC_FZ_W entries per lane)
+#define NLMC_FZ_KIND_SINGLE 0    // up to 8 entries
+#define NLMC_FZ_KIND_PAIR 1      // 9-16 entries on an even / odd lane pair
+#define NLMC_FZ_KIND_QUAD 2      // 17-32 entries on an aligned lane quad
+#define NLMC_FZ_KIND_TAIL 3      // longer than the widest group of the plan -- a quad (32 entries), or a pair (16) under
+                                 // NLMC_NO_QUADS: the rest is read from the CSR arrays inside the level loop
 struct FusedLevelizeArgs {
     CsrDev g;
     int T;                    // sweeps per window
@@ -253,15 +259,18 @@ struct FusedLevelizeArgs {
     int k_zero;               // address format: LDS address of a byte that is always 0 (padding entries point at it)
     int neg_off;              // address format: LDS offset of the negated copy of the spins
     int bank_aware;           // order every item's row entries so that the 32 lanes of a half-wave gather from different LDS banks
-    const uint4 *adj;         // [n][2]: the first 16 neighbours of every spin as 16-bit indices (k_fused_adjacency)
+    int quads;                // 1: a row of more than 16 entries takes an aligned lane QUAD (four positions); 0: a pair plus the CSR
+                              // tail beyond 16 (NLMC_NO_QUADS)
+    const uint4 *adj;        // [n][2]: the first 16 neighbours of every spin as 16-bit indices (k_fused_adjacency)
     uint16_t *glv;            // scratch [n_windows][T][n]: level of update (t, k), 1-based
-    uint32_t *perm;           // scratch [n_windows][pstride]: item id k | t << 16 at its position, ~0 = padding
+    uint32_t *perm;           // scratch [n_windows][pstride]: item id k | t << 16 | part << 30 at its position (part: which eight
+                              // entries of a grouped row), ~0 = padding
     long long *stats;         // diagnostic (NLMC_FZ_STATS): [n_windows][8] cycles keys / init / passes, pass count, place 1 / 2
-    int2 *head;               // [n_windows][pstride]   { k | LONG << 14 | threshold word << 16, hq_k }
+    int2 *head;               // [n_windows][pstride]   { k | kind << 14 | threshold word << 16, hq_k }  (kind: NLMC_FZ_KIND_*)
     EdgeQ *ell;               // [n_windows][NLMC_FZ_W / 2][pstride][2]   row window planes (8 entries per position), position-minor
     int32_t *loff;            // [n_windows][NLMC_LCAP + 1] published level offsets, in chunks of 64 positions
     int32_t *nlev;            // [n_windows] published levels; 0 = deeper than NLMC_LCAP - 1 (caller falls back)
-    int32_t *hi_max;          // [n_windows] leading chunks of a level that may hold PAIRS (rows longer than 8 entries)
+    int32_t *hi_max;          // [n_windows] leading chunks of a level that may hold GROUPS (rows longer than 8 entries: pairs, quads)
     int32_t *send;            // [n_windows][T] published index of the last level that holds an item of sweep t
     int32_t *npos;            // [n_windows] schedule positions in use (multiple of 64)
     double *val;              // nullptr, or [n_windows][NLMC_FZ_VAL_WORDS * pstride] fp64 value plane of the real-valued fp64 variant
@@ -375,14 +384,16 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
                 const uint4 a0 = a.adj[2 * k], a1 = a.adj[2 * k + 1];
                 int lv = min((int)mx[k] + 1, 65535);
                 if (lv <= NLMC_LCAP) {
-                    // hist[lv]: positions taken in the low half, long rows among them in the high half -- one atomic per claim.
-                    const uint32_t npos = re - rs > NLMC_FZ_W ? 2u : 1u, inc = npos | ((npos - 1u) << 16);
+                    // hist[lv]: positions taken in the low half, those of grouped rows (pairs, quads) among them in the high half --
+                    // one atomic per claim of 1, 2 or 4 positions.
+                    const uint32_t npos = (a.quads && re - rs > 2 * NLMC_FZ_W) ? 4u : re - rs > NLMC_FZ_W ? 2u : 1u;
+                    const uint32_t inc = npos | ((npos > 1u ? npos : 0u) << 16);
                     if (a.level_fill) {
                         // Capacity claim, add and undo: the add takes the positions, and where that runs over the cap the same
                         // amount is taken back and the update tries the next level.  The low half is never below the successful
                         // claims, so a level is never overfilled; between a failed add and its undo a level may look fuller than
-                        // it is and turn away a claim it had room for (a later level is always legal).  At most 1024 claims of 2
-                        // positions are in flight: the low half cannot carry into the high one.
+                        // it is and turn away a claim it had room for (a later level is always legal).  At most 1024 claims of 4
+                        // positions are in flight (level_cap + 4096 < 2^16): the low half cannot carry into the high one.
                         for (;;) {
                             const uint32_t old = atomicAdd(&hist[lv], inc);
                             if ((old & 0xFFFFu) + npos <= (uint32_t)a.level_cap) break;
@@ -435,14 +446,17 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
     // publish offsets.  Positions are handed out in CHUNKS of 64 (one wave's items of one level): every level starts on
     // a chunk boundary and its last chunk is padded with dummy items, so that the sweep kernel never deals with a
     // partly filled wave (no per-lane validity: a wave either holds a chunk of a level or it does not).  A row longer
-    // than NLMC_FZ_W entries takes TWO neighbouring positions (an even / odd lane pair: entries 0-7 and 8-15, the two
-    // partial fields are added with one cross-lane move), so that every wave of a level does the same amount of work;
-    // the pairs come first in their level.  With level_fill no level is wider than level_cap positions (a multiple of 64: the
+    // than NLMC_FZ_W entries takes a GROUP of neighbouring positions, so that every wave of a level does the same amount
+    // of work and no row entry is read from the CSR arrays inside the level loop: 9-16 entries an even / odd lane PAIR
+    // (entries 0-7 and 8-15), 17-32 entries an aligned lane QUAD (entries 0-7 ... 24-31 in lanes 4m ... 4m+3); the partial
+    // fields are added with one or two cross-lane moves.  Only what a row holds beyond 32 entries stays in the CSR arrays
+    // (NLMC_NO_QUADS: beyond 16, on a pair).  The quads come first in their level, then the pairs: quad starts are
+    // multiples of 4, pair starts even (a level starts on a multiple of 64).  With level_fill no level is wider than level_cap positions (a multiple of 64: the
     // claims of the passes above see to it), so the loop over p below publishes every level once; without it a wider level
     // is split there into consecutive sub-levels of level_cap positions (any subset of an independent set is independent),
     // and the split stays as the guard of the invariant.  send[] is strictly increasing in t either way: update (t + 1, k)
     // waits for (t, k), so sh_lmax[t + 1] > sh_lmax[t], and the walk over t_next meets every sweep's last level in turn.
-    // off[] counts chunks; hist[lv] (was: positions | long rows << 16) becomes the level's first position, histL[lv] the
+    // off[] counts chunks; hist[lv] (was: positions | grouped positions << 16) becomes the level's first position, histL[lv] the
     // position behind its last real item.
     if (tid == 0) {
         const int L = sh_lmax[T - 1];
@@ -452,7 +466,7 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
             for (int lv = 1; lv <= L; ++lv) {
                 const int cl = (int)(hist[lv] >> 16), width = (int)(hist[lv] & 0xFFFFu);
                 hist[lv] = (uint32_t)run;
-                himax = max(himax, (2 * cl + 63) >> 6);
+                himax = max(himax, (cl + 63) >> 6);
                 histL[lv] = (uint32_t)(run + width);
                 for (int p = 0; p < width; p += a.level_cap) { if (m < NLMC_LCAP) { off[m] = (run + p) >> 6; mx[m] = (uint32_t)((run + p) >> 6); } ++m; }
                 run += (width + 63) & ~63;
@@ -469,8 +483,9 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
     __syncthreads();
     if (sh_nlev == 0) return;
 
-    // placement: the pairs (rows longer than 8 entries) from the front of their level, two positions each, the others
-    // from the back of its real items.  Two steps so that the 40-72 B per position are written with coalesced stores:
+    // placement: the quads (rows longer than 16 entries) from the front of their level, four positions each; behind them
+    // the pairs (9-16 entries), two positions each -- once every quad has its place, hist[lv] is the level's first
+    // position behind its quads; the others from the back of its real items.  Two steps so that the 40-72 B per position are written with coalesced stores:
     // (1) scatter the 4-byte item ids to their positions, (2) position-major: lane p gathers its half of row k(p) (CSR is
     // cache resident) and writes head[p] and the planes [q][p] next to its neighbours' -- a direct scatter of 16-byte
     // pieces ran at a tenth of the bandwidth.
@@ -481,15 +496,28 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
     for (int pos = tid; pos < npos; pos += nt) perm[pos] = 0xFFFFFFFFu;       // padding = dummy items
     __threadfence_block();
     __syncthreads();
+    if (a.quads) {
+        for (int k = tid; k < n; k += nt) {
+            if (a.g.rowptr[k + 1] - a.g.rowptr[k] <= 2 * NLMC_FZ_W) continue;
+            for (int t = 0; t < T; ++t) {
+                const uint32_t id = (uint32_t)k | ((uint32_t)t << 16);
+                const uint32_t pos = atomicAdd(&hist[(int)glv[(size_t)t * n + k]], 4u);     // a multiple of 4
+#pragma unroll
+                for (uint32_t part = 0; part < 4u; ++part) perm[pos + part] = id | (part << 30);
+            }
+        }
+        __syncthreads();
+    }
     for (int t = 0; t < T; ++t) {
         for (int k = tid; k < n; k += nt) {
             const int lv = (int)glv[(size_t)t * n + k];
             const int deg = a.g.rowptr[k + 1] - a.g.rowptr[k];
             const uint32_t id = (uint32_t)k | ((uint32_t)t << 16);
+            if (a.quads && deg > 2 * NLMC_FZ_W) continue;                      // placed above
             if (deg > NLMC_FZ_W) {
                 const uint32_t pos = atomicAdd(&hist[lv], 2u);                 // even: a level starts on a multiple of 64
                 perm[pos] = id;
-                perm[pos + 1] = id | 0x80000000u;                              // second half of the row
+                perm[pos + 1] = id | (1u << 30);                               // second half of the row
             } else {
                 perm[atomicSub(&histL[lv], 1u) - 1u] = id;
             }
@@ -499,9 +527,11 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
     __syncthreads();
     long long p1 = (long long)__builtin_readcyclecounter();
     st[4] = p1 - p0;
-    // head.x = k | LONG << 14 | PAIR << 15 | thr << 16: k = LDS address of the spin, LONG = row longer than two windows
-    // (the rest is read from the CSR arrays by the first lane of the pair), PAIR = this lane holds half of a row, thr =
-    // word index of the update's threshold in the three LDS tables (slot t mod 3); head.y = hq_k (first half only).
+    // head.x = k | kind << 14 | thr << 16: k = LDS address of the spin; kind (NLMC_FZ_KIND_*, the same in every lane of a
+    // group) = a row on one lane / on a lane pair / on a lane quad / on the widest group the plan has, with a tail that the
+    // group's first lane reads from the CSR arrays (the last lane in the real-valued fp64 variant, which sums in row
+    // order); the lane's part of the row is lane & 1 in a pair and lane & 3 in a quad; thr = word index of the update's
+    // threshold in the three LDS tables (slot t mod 3); head.y = hq_k (first lane of a group only).
     // A dummy item updates the scratch spin behind the real ones from an all-zero row: harmless by construction.
     int2 *head = a.head + (size_t)w * PS;
     int4 *ell = reinterpret_cast<int4 *>(a.ell) + (size_t)w * (NLMC_FZ_W / 2) * PS;
@@ -554,26 +584,29 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
             }
             continue;
         }
-        const int second = (int)(it >> 31);
-        const int k = (int)(it & 0xFFFFu), t = (int)((it >> 16) & 0x7FFFu);
+        const int second = (int)(it >> 30);                                     // part of a grouped row: 0 = its first lane
+        const int k = (int)(it & 0xFFFFu), t = (int)((it >> 16) & 0x3FFFu);
         const int rs = rs_cur, deg = deg_cur;
         const int thr = ((t % 3) * a.tab_words + k) << 16;
-        const int e0 = second ? NLMC_FZ_W : 0, left = deg - e0;                 // this lane's entries: e0 .. e0 + 7
+        const int e0 = second * NLMC_FZ_W, left = deg - e0;                     // this lane's entries: e0 .. e0 + 7
+        const int kind = deg <= NLMC_FZ_W ? NLMC_FZ_KIND_SINGLE : deg <= 2 * NLMC_FZ_W ? NLMC_FZ_KIND_PAIR
+                       : (a.quads && deg <= 4 * NLMC_FZ_W) ? NLMC_FZ_KIND_QUAD : NLMC_FZ_KIND_TAIL;
         EdgeQ ed[NLMC_FZ_W];
 #pragma unroll
-        for (int q = 0; q < NLMC_FZ_W; ++q) ed[q] = a.g.edge32[rs + e0 + q];    // unconditional (the array is padded by a
-                                                                                // full window): independent loads
+        for (int q = 0; q < NLMC_FZ_W; ++q) ed[q] = a.g.edge32[rs + e0 + q];    // unconditional (the array is padded by two
+                                                                                // windows; a quad's last lane reads up to 14
+                                                                                // entries past its row): independent loads
         const int hy = second ? 0 : a.g.hq[k];
         if (vplane) {      // (bank_aware is off: entry q of this lane is row entry e0 + q, padding behind the row's end)
             double v[NLMC_FZ_W];
 #pragma unroll
             for (int q = 0; q < NLMC_FZ_W; ++q) {
-                const double j = a.g.val64[rs + e0 + q];          // (the array is padded by a full window, like edge32)
+                const double j = a.g.val64[rs + e0 + q];          // (the array is padded like edge32)
                 v[q] = q < left ? (a.fmt == NLMC_FMT_ADDR ? j * (double)ed[q].q : j) : 0.0;
             }
 #pragma unroll
             for (int q = 0; q < NLMC_FZ_W / 2; ++q) reinterpret_cast<double2 *>(vplane)[(size_t)q * PS + pos] = make_double2(v[2 * q], v[2 * q + 1]);
-            vplane[(size_t)(NLMC_FZ_W) * PS + pos] = a.g.h64[k];   // both lanes of a pair: the field is added after the whole row
+            vplane[(size_t)(NLMC_FZ_W) * PS + pos] = a.g.h64[k];   // every lane of a group: the field is added after the whole row
         }
         if (a.bank_aware) {
             const int nreal = min(max(left, 0), NLMC_FZ_W);
@@ -630,8 +663,7 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
                     pk[q / 2] |= v16 << (16 * (q & 1));
                 }
                 ell[pos] = make_int4((int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]);
-                head[pos] = second ? make_int2(k | 0x8000 | thr, hy)
-                                   : make_int2(k | (deg > 2 * NLMC_FZ_W ? 0x4000 : 0) | (deg > NLMC_FZ_W ? 0x8000 : 0) | thr, hy);
+                head[pos] = make_int2(k | (kind << 14) | thr, hy);
                 continue;
             }
             EdgeQ od[NLMC_FZ_W];
@@ -665,8 +697,7 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
             }
             ell[pos] = make_int4((int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]);
         }
-        head[pos] = second ? make_int2(k | 0x8000 | thr, hy)
-                           : make_int2(k | (deg > 2 * NLMC_FZ_W ? 0x4000 : 0) | (deg > NLMC_FZ_W ? 0x8000 : 0) | thr, hy);
+        head[pos] = make_int2(k | (kind << 14) | thr, hy);
         if (a.fmt == NLMC_FMT_ADDR) continue;
         if (a.fmt == NLMC_FMT_COMPACT) {
             uint32_t pk[NLMC_FZ_W];
@@ -793,6 +824,8 @@ struct SweepArgs {
     int fz_pstride;           // schedule positions reserved per window (plane stride of ell32, length of head32)
     int fz_npos_next;         // positions the NEXT window actually uses (for the warm-up touches)
     int fz_fmt;               // entry format of the plan: NLMC_FMT_WIDE / _COMPACT / _ADDR, see FusedItem
+    int fz_qmask;             // head bits that tell a lane QUAD: (head & fz_qmask) == 0x8000.  0x8000: kinds QUAD and TAIL (a quad with a
+                              // CSR tail); 0xC000: kind QUAD alone -- a plan without quads (NLMC_NO_QUADS), whose TAIL rows sit on pairs
     int lds_neg_off;          // NLMC_FMT_ADDR: LDS offset of the negated copy of the spins (n_pad + 16); 0: none
     int lds_send_off;
     int lds_snap_off;         // k_sweep_fused<.., OUT>: three snapshot slots of n_pad bytes
@@ -1651,10 +1684,16 @@ __global__ __launch_bounds__(sizeof(T) == 8 ? 512 : DIAG ? 768 : 1024) void k_sw
 //                    sum of the gathered bytes (no unpacking, no multiply), every update writes s and -s.
 // The vector-memory path of the CU is what a level's loads queue on (24 instead of 40 bytes per position measured 9 %
 // off the launch), and the update of the address format is 11 instructions shorter.
+// Rows longer than 8 entries take a GROUP of neighbouring positions, eight entries each, in all three formats: an even / odd lane
+// pair (9-16 entries) or an aligned lane quad (17-32); the lanes of a group add their partial fields with one or two DPP moves
+// inside the quad and all take the same decision.  A row entry is read from the CSR arrays inside the level loop only beyond
+// the 32nd (three dependent L2 round trips in one wave while the others wait at the barrier: two rows of 18 entries among the
+// bench instance's 10^4 cost 7 % of a round that way, profiles/long_rows.txt).
 template <int FMT> struct FusedItem {
     static constexpr int NE = NLMC_FZ_W;
     static constexpr int NP = FMT == NLMC_FMT_WIDE ? NE / 2 : FMT == NLMC_FMT_COMPACT ? NE / 4 : NE / 8;
-    nlmc_i2 hd;                   // { k | LONG << 14 | PAIR << 15 | threshold word << 16, hq_k (+ sign-format constant) }
+    nlmc_i2 hd;                   // { k | kind << 14 | threshold word << 16, hq_k }: kind = NLMC_FZ_KIND_* -- the row sits on one lane, a
+                                  // lane pair or a lane quad (hq_k in the group's first lane, 0 in the others)
     nlmc_i4 pk[NP];
     __device__ __forceinline__ int word(int i) const { const int p = i >> 2, j = i & 3; return j == 0 ? pk[p].x : j == 1 ? pk[p].y : j == 2 ? pk[p].z : pk[p].w; }
     // LDS address of the byte entry q gathers (wide / compact: the neighbour's spin)
@@ -1864,6 +1903,9 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
     unsigned v_u_off = (unsigned)a.lds_u_off, v_neg_off = (unsigned)a.lds_neg_off;
     int v_eshift = a.eshift;
     asm volatile("" : "+v"(v_u_off), "+v"(v_neg_off), "+v"(v_eshift));
+    // PAIR: the head bits that tell a lane quad (SweepArgs::fz_qmask)
+    unsigned v_qmask = (unsigned)a.fz_qmask;
+    if (PAIR) asm volatile("" : "+v"(v_qmask));
     // fp64 mode: LDS address of Khi[X = 0] (entry X sits 4 X bytes from it); with FLAGS the scaled rows' table Khi1 follows Khi0
     // (k_ne4 bytes further), and the low words follow all high words (k_lo bytes from a Khi entry to its Klo entry)
     unsigned v_kt0 = (unsigned)(a.lds_kt_off + 4 * a.f64_xmax), v_tie = a.f64_tie_mask;
@@ -1958,24 +2000,36 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
             double xs = 0.0, xd = 0.0;
             part(xs, xd);
             bool second = false;
-            if (PAIR && __builtin_amdgcn_ballot_w64((hx & 0x8000) != 0) != 0ull) {
-                // A row of 9-16 entries on an even / odd lane pair: the odd lane continues the even lane's sums with entries 8-15
-                // (the sum stays in row order; the lane-pair split of the integer field would reassociate it), then takes what is
-                // left of a longer row from the CSR arrays, and hands the row's sums back to the even lane.
-                const bool pair = (hx & 0x8000) != 0;
-                second = pair && (lane & 1);
-                const double ps = quad_move_f64<0xA0>(xs);                 // quad_perm [0,0,2,2]: the even lane's sums
-                const double pd = DIAG ? quad_move_f64<0xA0>(xd) : 0.0;
-                const int hxe = __builtin_amdgcn_mov_dpp(hx, 0xA0, 0xF, 0xF, true);
-                double s2 = ps, d2 = pd;
-                part(s2, d2);
-                if (second) { xs = s2; xd = d2; }
-                const bool tail = second && (hxe & 0x4000) != 0;
+            if (PAIR && __builtin_amdgcn_ballot_w64((hx & 0xC000) != 0) != 0ull) {
+                // A row of 9-16 entries on an even / odd lane pair, one of 17-32 entries on an aligned lane quad: every lane
+                // continues the sums of the lane before it with its own eight entries (the sum stays in row order; the
+                // split of the integer field would reassociate it), the last lane takes what is left of a longer row from
+                // the CSR arrays and hands the row's sums back to the whole group.
+                const bool grouped = (hx & 0xC000) != 0, quad = ((unsigned)hx & v_qmask) == 0x8000u;
+                const int pi = lane & (quad ? 3 : grouped ? 1 : 0), last = quad ? 3 : 1;       // this lane's part of the row
+                second = pi != 0;
+                {
+                    double s2 = quad_move_f64<0xA0>(xs);                   // quad_perm [0,0,2,2]: the sums of part 0
+                    double d2 = DIAG ? quad_move_f64<0xA0>(xd) : 0.0;
+                    part(s2, d2);
+                    if (pi == 1) { xs = s2; xd = d2; }
+                }
+                if (__builtin_amdgcn_ballot_w64(quad) != 0ull) {
+                    double s3 = quad_move_f64<0xD4>(xs);                   // quad_perm [0,1,1,3]: parts 0-1
+                    double d3 = DIAG ? quad_move_f64<0xD4>(xd) : 0.0;
+                    part(s3, d3);
+                    if (pi == 2) { xs = s3; xd = d3; }
+                    double s4 = quad_move_f64<0xA4>(xs);                   // quad_perm [0,1,2,2]: parts 0-2
+                    double d4 = DIAG ? quad_move_f64<0xA4>(xd) : 0.0;
+                    part(s4, d4);
+                    if (pi == 3) { xs = s4; xd = d4; }
+                }
+                const bool tail = (hx & 0xC000) == 0xC000 && pi == last;
                 if (__builtin_amdgcn_ballot_w64(tail) != 0ull) {
                     if (tail) {
                         const int rs = a.g.rowptr[ka], re = a.g.rowptr[ka + 1];
 #pragma clang loop vectorize(disable) unroll(disable)
-                        for (int e = rs + 2 * NLMC_FZ_W; e < re; ++e) {
+                        for (int e = rs + (last + 1) * NLMC_FZ_W; e < re; ++e) {
                             const int j = a.g.col[e];
                             const double v = a.g.val64[e], sv = (double)*(lds_i8)(uintptr_t)(unsigned)j;
                             xs = fma_rn(v, sv, xs);
@@ -1983,9 +2037,10 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
                         }
                     }
                 }
-                const double bs = quad_move_f64<0xF5>(xs);                 // quad_perm [1,1,3,3]: the odd lane's (whole row)
-                const double bd = DIAG ? quad_move_f64<0xF5>(xd) : 0.0;
-                if (pair) { xs = bs; xd = bd; }
+                const double bs = quad_move_f64<0xF5>(xs), bq = quad_move_f64<0xFF>(xs);       // quad_perm [1,1,3,3], [3,3,3,3]:
+                const double bd = DIAG ? quad_move_f64<0xF5>(xd) : 0.0;                        // the last lane's (whole row)
+                const double bdq = DIAG ? quad_move_f64<0xFF>(xd) : 0.0;
+                if (grouped) { xs = quad ? bq : bs; xd = quad ? bdq : bd; }
             }
             const double hk = fv.field();
             const double x_true = DIAG ? ((xs - xd) + hk) : (xs + hk);
@@ -2076,26 +2131,45 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
         int X = X0 + X1;
         bool second = false;
         if (PAIR) {
-            // chunks at the head of a level may hold PAIRS: a row of 9-16 entries on an even / odd lane pair, eight entries
-            // each; both lanes end up with the whole field and take the same decision, the energy counts once.  A row longer
-            // than that: the rest comes from the CSR arrays, in the first lane of the pair.
-            if (__builtin_amdgcn_ballot_w64((hx & 0x4000) != 0) != 0ull) {
-                if (hx & 0x4000) {
-                    const int rs = a.g.rowptr[ka], re = a.g.rowptr[ka + 1];
+            // chunks at the head of a level may hold GROUPS: a row of 9-16 entries on an even / odd lane pair, one of 17-32
+            // entries on an aligned lane quad, eight entries per lane; every lane of a group ends up with the whole field and
+            // takes the same decision, the energy counts once (in the group's first lane).  A row longer than the plan's
+            // widest group: the rest comes from the CSR arrays, in the first lane of the group.
+            // The common chunk holds single rows and pairs only and costs what it did before there were quads: everything
+            // about quads and tails (head bit 15) sits behind one wave-uniform branch that few levels take.
+            const bool grouped = (hx & 0xC000) != 0;
+            second = grouped && (lane & 1);
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64((hx & 0x8000) != 0) != 0ull, 0)) {
+                const bool quad = ((unsigned)hx & v_qmask) == 0x8000u;
+                second = quad ? (lane & 3) != 0 : second;
+                const bool tail = (hx & 0xC000) == 0xC000 && !second;
+                if (__builtin_amdgcn_ballot_w64(tail) != 0ull) {
+                    if (tail) {
+                        const int rs = a.g.rowptr[ka], re = a.g.rowptr[ka + 1];
 #pragma clang loop vectorize(disable) unroll(disable)
-                    for (int e = rs + 2 * NLMC_FZ_W; e < re; ++e) {
-                        const EdgeQ t = a.g.edge32[e];
-                        const int pr = __mul24(t.q, (int)*(lds_i8)(uintptr_t)(unsigned)t.col);
-                        X += pr;
-                        if (DIAG && (unsigned)t.col == ka) Xd += pr;
+                        for (int e = rs + (quad ? 4 : 2) * NLMC_FZ_W; e < re; ++e) {
+                            const EdgeQ t = a.g.edge32[e];
+                            const int pr = __mul24(t.q, (int)*(lds_i8)(uintptr_t)(unsigned)t.col);
+                            X += pr;
+                            if (DIAG && (unsigned)t.col == ka) Xd += pr;
+                        }
                     }
                 }
+                const int Xp = __builtin_amdgcn_mov_dpp(X, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]: the neighbour lane
+                X += grouped ? Xp : 0;
+                const int Xq = __builtin_amdgcn_mov_dpp(X, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]: the quad's other pair
+                X += quad ? Xq : 0;
+                if (DIAG) {
+                    const int Xdp = __builtin_amdgcn_mov_dpp(Xd, 0xB1, 0xF, 0xF, true);
+                    Xd += grouped ? Xdp : 0;
+                    const int Xdq = __builtin_amdgcn_mov_dpp(Xd, 0x4E, 0xF, 0xF, true);
+                    Xd += quad ? Xdq : 0;
+                }
+            } else {
+                const int Xp = __builtin_amdgcn_mov_dpp(X, 0xB1, 0xF, 0xF, true);
+                X += grouped ? Xp : 0;
+                if (DIAG) { const int Xdp = __builtin_amdgcn_mov_dpp(Xd, 0xB1, 0xF, 0xF, true); Xd += grouped ? Xdp : 0; }
             }
-            const bool pair = (hx & 0x8000) != 0;
-            const int Xp = __builtin_amdgcn_mov_dpp(X, 0xB1, 0xF, 0xF, true);       // quad_perm [1,0,3,2]: the neighbour lane
-            X += pair ? Xp : 0;
-            if (DIAG) { const int Xdp = __builtin_amdgcn_mov_dpp(Xd, 0xB1, 0xF, 0xF, true); Xd += pair ? Xdp : 0; }
-            second = pair && (lane & 1);
         }
         // fp64 mode: s' = +1 iff the 53-bit integer of the update's uniform lies below K(X) (accept_count_spec).  The table of
         // the sweep holds the 27 high bits; they decide unless they EQUAL the high word of K(X) (probability 2^-27 per

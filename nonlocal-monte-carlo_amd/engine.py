@@ -223,7 +223,8 @@ class Engine:
     FUSED_PLAN_BUDGET = 1 << 30        # bytes of fused-window plan one sweep_philox_windows piece may hold
 
     def fused_plan_bytes(self, window):
-        return fused_plan_bytes(self.n, int(np.count_nonzero(np.diff(self.inst.indptr) > 8)), window,
+        rows = np.diff(self.inst.indptr)
+        return fused_plan_bytes(self.n, int(np.count_nonzero(rows > 8) + 2 * np.count_nonzero(rows > 16)), window,
                                 value_plane=self.fused_f64_real)
 
     def set_fused_f64_real(self, on=True):
@@ -802,7 +803,8 @@ def device_count():
 def fused_plan_bytes(n, n_long, window, value_plane=False):
     """Upper estimate of the device memory one planned window of `window` sweeps takes (head 8 + row planes <= 64 + item ids
     4 bytes per schedule position, 2 bytes per update of level scratch): what nlmc_plan_philox_fused allocates per window
-    (csrc/nlmc.hip: reserve_fused_plan, fused_pstride).  n_long: rows longer than 8 entries (two positions each).
+    (csrc/nlmc.hip: reserve_fused_plan, fused_pstride).  n_long: positions a sweep takes beyond one per row -- one more for a
+    row longer than 8 entries (a lane pair), three more for one longer than 16 (a lane quad).
     value_plane: plans of the real-valued fp64 variant (Engine.set_fused_f64_real) add 9 doubles per position."""
     pstride = -(-int(window) * (int(n) + int(n_long)) // 64) * 64 + 64 * 1024
     return pstride * (76 + (72 if value_plane else 0)) + int(window) * int(n) * 2 + 8192
