@@ -470,6 +470,36 @@ int nlmc_best_update(nlmc_ctx *ctx, uint32_t stamp);
 int nlmc_best_read(nlmc_ctx *ctx, double *out_energy /*[n_chains]*/, int32_t *out_stamp /*[n_chains]*/,
                    int32_t *out_first_hit /*[n_chains]*/, int8_t *out_state /*[n_chains][n]*/);
 int nlmc_best_end(nlmc_ctx *ctx);
+/* ---- run-long per-round energy log: what energy sat on which temperature in every round ------------------------------------------
+ * The swap log says which swaps happened, the best-state record which state a chain reached; this log keeps, for every round of a window
+ * [round0, round0 + n_rounds) and every local chain, the tracked energy and the temperature slot AS THE SWAP DECISION OF THAT ROUND SEES
+ * THEM: after the round's sweeps, after the Houdayer step or the NMC phases where the round has them.  It lasts from nlmc_elog_begin to
+ * nlmc_elog_end, over any number of calls, and only observes: no call's results change while it is open.  energy [n_rounds][n_chains]
+ * double = (double) tracked integer 2^-nlmc_energy_scale (nlmc_energy_tracked's conversion), slot [n_rounds][n_chains] int32, by LOCAL
+ * chain; a row no observation reached reads NaN / -1; rounds outside the window are not logged and are no error; a second observation
+ * of a round overwrites the first.  12 bytes per chain and round of device memory.
+ *   nlmc_elog_begin(round0, n_rounds)  opens or resets the log (all rows NaN / -1).  After nlmc_pt_init (NLMC_ERR_STATE before).  The
+ *                            buffers are allocated at the first begin and kept (a larger window grows them).  NLMC_ERR_UNSUPPORTED for
+ *                            a context with a communicator (nlmc_comm_init) or a cut ladder (nlmc_apt_shard over several ranks, a
+ *                            chain block that is not whole ladders).
+ *   nlmc_elog_update(round)  one observation of every local chain from the state arrays (k_elog_update: any n), queued on the
+ *                            context's stream, asynchronous.  NLMC_ERR_STATE before nlmc_pt_init or with no log open,
+ *                            NLMC_ERR_UNSUPPORTED under a chain subset.  For drivers that run a round call by call: between the last
+ *                            state-changing step and the swap round.
+ *   nlmc_elog_read           the rows of the window most recently begun; both pointers nullable; one stream synchronisation.  Also
+ *                            after nlmc_elog_end.
+ *   nlmc_elog_end            closes the log: the routes behave as before; the buffers stay for the next begin and for reads.
+ * While a log is open the rounds entry points observe every chain once per round, row = round0 + r of the call: nlmc_pt_rounds_fused
+ * and the in-launch route of nlmc_pt_rounds_deferred inside k_rounds_fused (thread 0 stores what it publishes for the hand-off; the
+ * observing instantiations are those of the best-state record, which test which record is present: the kernels without an observer are
+ * unchanged), the launch-per-round route by a k_elog_update behind every sweep launch, nlmc_pt_rounds_lanes inside k_rounds_lanes (every
+ * live lane stores its energy and slot), nlmc_apt_rounds_lanes inside k_apt_rounds_lanes<.., ELOG> behind the Houdayer step's energy
+ * deltas (it still refuses while a best-state record is open).  nlmc_sweep_*, nlmc_set_spins, nlmc_energy, the Houdayer and swap entry
+ * points do not observe. */
+int nlmc_elog_begin(nlmc_ctx *ctx, uint32_t round0, int n_rounds);
+int nlmc_elog_update(nlmc_ctx *ctx, uint32_t round);
+int nlmc_elog_read(nlmc_ctx *ctx, double *out_energy /*[n_rounds][n_chains]*/, int32_t *out_slot /*[n_rounds][n_chains]*/);
+int nlmc_elog_end(nlmc_ctx *ctx);
 /* mode 1: copy the chains' CURRENT configurations aside; later nlmc_backbone_clusters calls are seeded with that copy instead of the
  * states they find (the m_star of a cycle without a plain phase is the state after the last plain phase, NMC/nmc.py:368-373,433:
  * full_update_frequency != 1).  mode 0: seed with the current states again. */

@@ -40,6 +40,7 @@ EXPORTS = [
     "nlmc_set_fused_f64_real", "nlmc_last_sweep_fused", "nlmc_set_lane_sweeps", "nlmc_last_sweep_route", "nlmc_pt_rounds_lanes",
     "nlmc_apt_rounds_lanes", "nlmc_apt_systems",
     "nlmc_best_begin", "nlmc_best_update", "nlmc_best_read", "nlmc_best_end",
+    "nlmc_elog_begin", "nlmc_elog_update", "nlmc_elog_read", "nlmc_elog_end",
 ]
 
 
@@ -171,6 +172,8 @@ def lib():
                        ("nlmc_apt_rounds_lanes", [_vp, _i, _i, _i, _u32, _u32, _u64, _i, _i, _vp]), ("nlmc_apt_systems", [_vp, _i]),
                        ("nlmc_best_begin", [_vp, _dbl]), ("nlmc_best_update", [_vp, _u32]), ("nlmc_best_read", [_vp, _vp, _vp, _vp, _vp]),
                        ("nlmc_best_end", [_vp]),
+                       ("nlmc_elog_begin", [_vp, _u32, _i]), ("nlmc_elog_update", [_vp, _u32]), ("nlmc_elog_read", [_vp, _vp, _vp]),
+                       ("nlmc_elog_end", [_vp]),
                        ("nlmc_apt_shard", [_vp, _i, _i, _i, _vp]), ("nlmc_apt_pack", [_vp, _vp, _vp, _vp]),
                        ("nlmc_apt_swap_host", [_vp, _u32, _u64, _i, _vp, _vp, _vp, _vp, _vp]),
                        ("nlmc_apt_swap_collective", [_vp, _u32, _u64, _i, _vp, _vp]), ("nlmc_apt_selftest_exchange", [_vp, _vp, _vp])):

@@ -95,7 +95,7 @@ class APT_ICM(SweepMixin):
     # ------------------------------------------------------------------------------------------------
     def run(self, beta_list, num_replicas, num_sweeps_MCMC=1000, num_sweeps_read=1000, num_swap_attempts=100,
             num_swapping_pairs=1, use_hash_table=0, num_cores=8, plot=False, icm_feedback=False, return_trace="float64",
-            device_ids=None, track_best=False, target_energy=None, num_restarts=1):
+            device_ids=None, track_best=False, target_energy=None, num_restarts=1, track_energies=False):
         """NPT/apt_ICM.py:145-305.  Returns (M [R*N, S_swap*10], Energy [R]).  `return_trace` (device-resident path only):
         "float64" (the reference's M), "int8" (same layout, 1 byte per entry) or None (M is not materialised).
         `device_ids` (rng="philox", icm_feedback=True; the reference's knob is num_cores, NPT/apt_ICM.py:145-146): the
@@ -114,7 +114,12 @@ class APT_ICM(SweepMixin):
         num_restarts=1.  self.restart_energies [num_restarts, R] is Energy of every restart; final_energies, final_slots, swap_accepted,
         icm_cluster_sizes and the best-record arrays cover all num_restarts K R chains (restart-major); with track_best also
         self.restart_best_energy [num_restarts] (minimum of the restart's best_energy) and self.restart_first_hit_round [num_restarts]
-        (smallest non-negative first_hit_round of the restart's chains, -1: none)."""
+        (smallest non-negative first_hit_round of the restart's chains, -1: none).
+        `track_energies` (same conditions as track_best, else ValueError): the run keeps, for every round, every chain's tracked energy
+        and temperature slot as that round's swap decision sees them -- behind the Houdayer step -- on the device (Engine.elog_begin;
+        Engine.apt_rounds_lanes keeps the log itself, so such a run still takes it) and sets self.round_energies [rounds, G],
+        self.round_slots [rounds, G] by chain id and self.ladder_report: one report per restart, its K sub-replica ladders pooled
+        (hostlogic.ladder_report / pool_reports).  (M, Energy) and every other attribute are the same bits with or without it."""
         if int(num_restarts) != num_restarts or num_restarts < 1:
             raise ValueError("num_restarts must be an integer >= 1")
         num_restarts = int(num_restarts)
@@ -122,6 +127,8 @@ class APT_ICM(SweepMixin):
             raise ValueError("num_restarts needs rng='philox', icm_feedback=True and no device_ids (the device-resident path of one context)")
         if track_best and not (self.rng == "philox" and icm_feedback and device_ids is None):
             raise ValueError("track_best needs rng='philox', icm_feedback=True and no device_ids (the device-resident path of one context)")
+        if track_energies and not (self.rng == "philox" and icm_feedback and device_ids is None):
+            raise ValueError("track_energies needs rng='philox', icm_feedback=True and no device_ids (the device-resident path of one context)")
         if return_trace not in ("float64", "int8", None):
             raise ValueError("return_trace must be 'float64', 'int8' or None")
         self.num_replicas = num_replicas
@@ -145,7 +152,7 @@ class APT_ICM(SweepMixin):
             return self._run_slot_sharded(inst, beta_list, plot, return_trace, list(device_ids))
         if self.rng == "philox" and icm_feedback:
             return self._run_device_resident(inst, beta_list, plot, return_trace, track_best=bool(track_best), target_energy=target_energy,
-                                             num_restarts=num_restarts)
+                                             num_restarts=num_restarts, track_energies=bool(track_energies))
         numpy_mode = self.rng == "numpy"
         host_rng = None if numpy_mode else np.random.default_rng(self.seed)
         all_pairs = [(i, i + 1) for i in range(1, R)]
@@ -233,7 +240,7 @@ class APT_ICM(SweepMixin):
         return M, Energy
 
     def _run_device_resident(self, inst, beta_list, plot, return_trace="float64", engine_factory=Engine, track_best=False,
-                             target_energy=None, num_restarts=1):
+                             target_energy=None, num_restarts=1, track_energies=False):
         """Throughput path (rng="philox", icm_feedback=True): every (sub-replica, replica) chain lives in ONE context,
         laid out sub-replica-major so that each sub-replica's beta ladder is a block of consecutive chains.  Per round:
         batched sweeps at the ladder temperatures -> iso-cluster moves between randomly paired sub-replicas of every
@@ -270,6 +277,8 @@ class APT_ICM(SweepMixin):
             first = 0
             if track_best:
                 eng.best_begin(target_energy)
+            if track_energies:
+                eng.elog_begin(0, rounds)
             if not track_best and self.lanes != "off" and _engine.APT_LANES_IN_LAUNCH and rounds > 1 and S > 0 and eng.lanes_take():
                 queued, info = eng.apt_rounds_lanes(rounds - 1, S, self.seed, self._sweep_counter, 0, self.num_swapping_pairs,
                                                     katzgraber=self.useKatzgraber, want_info=True)
@@ -295,6 +304,8 @@ class APT_ICM(SweepMixin):
                     icm_sizes.append(info[:, 1].copy())
                 if track_best:                                         # the Houdayer step lowers one partner's energy
                     eng.best_update(ii)
+                if track_energies:                                     # what the swap decision sees: behind the Houdayer step
+                    eng.elog_update(ii)
                 if swaps:
                     eng.pt_swap_philox(ii, self.seed, self.num_swapping_pairs, want_log=False)
             acc_log = [eng.pt_log_read()[1]] if swaps else []
@@ -322,6 +333,11 @@ class APT_ICM(SweepMixin):
                 fh = self.first_hit_round.reshape(num_restarts, G1).astype(np.int64)
                 fh = np.where(fh >= 0, fh, np.iinfo(np.int64).max).min(axis=1)
                 self.restart_first_hit_round = np.where(fh == np.iinfo(np.int64).max, -1, fh).astype(np.int32)
+            if track_energies:
+                from .hostlogic import ladder_report, pool_reports
+                self.round_energies, self.round_slots = eng.elog_read()
+                per_ladder = ladder_report(self.round_energies, self.round_slots, beta_list)
+                self.ladder_report = [pool_reports(per_ladder[s * K:(s + 1) * K]) for s in range(num_restarts)]
             self.final_energies = eng.energy()
             self.final_slots = eng.pt_slots()
             self.swap_accepted = np.concatenate([a.reshape(-1) for a in acc_log]).astype(np.int8) if acc_log else np.zeros(0, np.int8)

@@ -184,6 +184,25 @@ struct nlmc_ctx {
     DevBuf<int32_t> rec_stamp, rec_hit;
     DevBuf<int8_t> rec_state;     // [n_chains][n_pad]
     BestRec best_rec() const { return BestRec{rec_efix.p, rec_stamp.p, rec_hit.p, rec_state.p, best_target}; }
+    // run-long per-round energy log (nlmc_elog_begin): rows of rounds [elog_round0, elog_round0 + elog_rounds), allocated at the first
+    // begin, kept until the context goes (a later, larger window grows them)
+    bool elog_on = false;
+    uint32_t elog_round0 = 0;
+    int elog_rounds = 0;          // rows of the window most recently begun (what nlmc_elog_read returns, also after nlmc_elog_end)
+    DevBuf<double> elog_energy;   // [elog_rounds][n_chains]
+    DevBuf<int32_t> elog_slot;
+    // The open log as the observer of a launch whose first round is r0 and that runs k rounds: energy = nullptr when no log is open or
+    // none of the launch's rounds lies inside the window (rounds outside it are not logged and are no error: pt_log.covers' rule,
+    // per round).  In 64 bits, so that a window or a call at the top of the 32-bit round range does not wrap.
+    ElogRec elog_rec(uint32_t r0, int k) const
+    {
+        ElogRec e{};
+        const int64_t d = (int64_t)r0 - (int64_t)elog_round0;
+        if (!elog_on || d >= (int64_t)elog_rounds || d + (int64_t)k <= 0) return e;
+        e.energy = elog_energy.p; e.slot = elog_slot.p; e.row0 = (int)d; e.n_rows = elog_rounds; e.n_chains = n_chains;
+        return e;
+    }
+    bool observed() const { return best_on || elog_on; }   // the observing instantiations of k_rounds_fused / k_rounds_lanes serve both
     DevBuf<int8_t> seed_snap;    // nlmc_backbone_seed: the configurations later backbone inferences are seeded with
     bool seed_snap_on = false;
     DevBuf<uint8_t> cmask;        // [n_chains][n_pad] backbone mask of the last inference per chain
@@ -735,7 +754,7 @@ const void *fused_kernel(bool diag, bool flags, bool outs, int fmt, int arith, b
     return kernel_at<FusedKernel>(key, std::make_index_sequence<144>{});
 }
 
-// k_rounds_fused<DIAG, FMT, F64, R64, BEST> by {diag, fmt, arith, best}: 36 kernels (best: a best-state record is open)
+// k_rounds_fused<DIAG, FMT, F64, R64, BEST> by {diag, fmt, arith, best}: 36 kernels (best: an observer -- best-state record, energy log -- is open)
 template <int K> struct RoundsKernel {
     static constexpr bool diag = K & 1, best = K / 18;
     static constexpr int fmt = K / 2 % 3, arith = K / 6 % 3;
@@ -1603,6 +1622,7 @@ void nlmc_destroy(nlmc_ctx *c)
     c->pt_tab.release(); c->pt_beta.release(); c->pt_energies_all.release();
     c->rounds_ebuf.release(); c->rounds_rec.release(); c->rounds_args.release(); c->seed_snap.release();
     c->rec_efix.release(); c->rec_stamp.release(); c->rec_hit.release(); c->rec_state.release();
+    c->elog_energy.release(); c->elog_slot.release();
     c->apt_beta.release(); c->apt_e_all.release(); c->apt_send.release(); c->apt_recv.release(); c->apt_bd.release();
     c->slot_of_chain.release(); c->chain_of_slot.release(); c->pt_pairs.release(); c->pt_status.release();
     c->pt_acc.release(); c->pt_log_acc.release(); c->pt_log_pairs.release(); c->pt_plan_pairs.release(); c->pt_plan_ok.release(); c->icm_label.release(); c->icm_info.release(); c->icm_pairs.release();
@@ -2557,6 +2577,18 @@ static int launch_best_update(nlmc_ctx *c, uint32_t stamp)
     return NLMC_OK;
 }
 
+// One observation of every local chain for the open energy log (k_elog_update), on the context's stream: the row of `round`, nothing
+// when the round lies outside the window.
+static int launch_elog_update(nlmc_ctx *c, uint32_t round)
+{
+    const ElogRec e = c->elog_rec(round, 1);
+    if (!e.energy || c->n_chains == 0) return NLMC_OK;
+    hipLaunchKernelGGL(k_elog_update, dim3((unsigned)((c->n_chains + 255) / 256)), dim3(256), 0, c->stream, e, c->efix.p, c->slot_of_chain.p,
+                       c->chain_base, c->escale);
+    HIP_TRY(c, hipGetLastError());
+    return NLMC_OK;
+}
+
 // Why a context cannot run whole rounds by itself whatever the kernel, or nullptr: what nlmc_pt_rounds_fused, nlmc_pt_rounds_deferred
 // and nlmc_pt_rounds_lanes refuse alike.  `strict` (deferred, lanes): a tracked minimum is refused too.
 const char *rounds_context_refusal(const nlmc_ctx *c, bool strict)
@@ -2625,7 +2657,7 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
     if (real && !P.has_val) return fail(c, NLMC_ERR_STATE, "k_rounds_fused: the plan has no fp64 value plane");
     const int kt = arith == ARITH_F64 ? 2 * c->xmax + 1 : 0;          // (the real-valued variant has no K tables: the f32 mode's LDS)
     const FusedLds Lds = fused_lds(c->n_pad, false, false, P.fmt == NLMC_FMT_ADDR, kt);
-    const void *kfun = rounds_kernel(c->has_diag, P.fmt, arith, c->best_on);
+    const void *kfun = rounds_kernel(c->has_diag, P.fmt, arith, c->observed());
     if (!kfun) return fail(c, NLMC_ERR_STATE, "k_rounds_fused: no kernel for this arithmetic");
     { int rc = ensure_lds(c, kfun, Lds.total); if (rc) return rc; }
     const int nt = fused_block(c);
@@ -2662,6 +2694,7 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
         q.rec = c->rounds_rec.p; q.status = c->pt_status.p;
         q.timeout_ticks = 100000000ll * 20;                   // 20 s of the 100 MHz wall clock
         if (c->best_on) q.best = c->best_rec();               // (the record lives in global memory: it carries over from launch to launch)
+        q.elog = c->elog_rec(r0, k);                          // (the row of the launch's first round: round0 + at of the call)
         if (log) {
             const size_t r = c->pt_log.row(r0);
             q.log_pairs = c->pt_log_pairs.p + r * (size_t)nl * n_pairs * 2;
@@ -2727,10 +2760,10 @@ int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep
     LaneLds Lds = lane_lds(c);
     const int map_off = (int)((Lds.total + 15) & ~(size_t)15);          // lane_of_slot | slot_of_lane, 64 bytes each
     Lds.total = (size_t)map_off + 128;
-    const void *kfun = c->best_on ? (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_rounds_lanes<true, true>)
-                                                           : reinterpret_cast<const void *>(k_rounds_lanes<false, true>))
-                                  : (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_rounds_lanes<true>)
-                                                           : reinterpret_cast<const void *>(k_rounds_lanes<false>));
+    const void *kfun = c->observed() ? (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_rounds_lanes<true, true>)
+                                                             : reinterpret_cast<const void *>(k_rounds_lanes<false, true>))
+                                    : (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_rounds_lanes<true>)
+                                                             : reinterpret_cast<const void *>(k_rounds_lanes<false>));
     { int rc = ensure_lds(c, kfun, Lds.total); if (rc) return rc; }
     const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
     const int ladders = c->n_chains / L;
@@ -2763,6 +2796,7 @@ int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep
         }
         q.lds_map_off = map_off;
         if (c->best_on) q.best = c->best_rec();
+        q.elog = c->elog_rec(r0, k);
         void *kargs[] = {&a, &q};
         HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)((ladders + P - 1) / P)), dim3(64), kargs, Lds.total, c->stream));
         HIP_TRY(c, hipGetLastError());
@@ -2875,6 +2909,9 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
         // an open record observes the round here: a swap is a label exchange, so chain c's spins and tracked energy in the state
         // arrays after this launch are the state of round r, whatever the next launch's prologue decides about its slot
         if (c->best_on) { rc = launch_best_update(c, round0 + (uint32_t)r); if (rc) return rc; }
+        // the energy log likewise: this launch's prologue has applied the swap of round r - 1 to the slot maps, so slot_of_chain is
+        // the slot of round r, and the label exchange the next prologue decides leaves chain c's tracked energy where it is
+        if (c->elog_on) { rc = launch_elog_update(c, round0 + (uint32_t)r); if (rc) return rc; }
     }
     c->sub_dirty = true;
     c->rounds_route = NLMC_ROUNDS_LAUNCH_PER_ROUND;
@@ -3199,8 +3236,11 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
     { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
     const bool want_info = out_info && NP > 0;
     if (want_info) HIP_TRY(c, c->icm_info.reserve((size_t)n_rounds * M * NP * 2));
-    const void *kfun = precision == NLMC_F64 ? reinterpret_cast<const void *>(k_apt_rounds_lanes<true>)
-                                             : reinterpret_cast<const void *>(k_apt_rounds_lanes<false>);
+    const bool elog = c->elog_rec(round0, n_rounds).energy != nullptr;          // (a launch none of whose rounds is logged stores nothing anyway)
+    const void *kfun = elog ? (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_apt_rounds_lanes<true, true>)
+                                                     : reinterpret_cast<const void *>(k_apt_rounds_lanes<false, true>))
+                            : (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_apt_rounds_lanes<true>)
+                                                     : reinterpret_cast<const void *>(k_apt_rounds_lanes<false>));
     { int rc = ensure_lds(c, kfun, A.total); if (rc) return rc; }
     const bool log = n_pairs > 0 && c->pt_log.covers(round0, n_rounds, n_pairs);
     for (int at = 0; at < n_rounds; at += R) {
@@ -3232,6 +3272,7 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
             q.log_acc = c->pt_log_acc.p + lr * nl * n_pairs;
         }
         q.lds_map_off = (int)A.map_off;
+        if (elog) q.elog = c->elog_rec(r0, k);
         LaneAptArgs x{};
         x.n_sub = K; x.n_icm = NP; x.katz = katzgraber ? 1 : 0;
         x.info = want_info ? c->icm_info.p + (size_t)at * M * NP * 2 : nullptr;
@@ -3583,6 +3624,59 @@ int nlmc_best_end(nlmc_ctx *c)
 {
     if (!c) return NLMC_ERR_ARG;
     c->best_on = false;
+    return NLMC_OK;
+}
+
+// ---- run-long per-round energy log -----------------------------------------------------------------------------------------------
+int nlmc_elog_begin(nlmc_ctx *c, uint32_t round0, int n_rounds)
+{
+    if (!c) return NLMC_ERR_ARG;
+    if (n_rounds < 0) return fail(c, NLMC_ERR_ARG, "nlmc_elog_begin: bad argument");
+    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, "nlmc_elog_begin: call nlmc_pt_init first");
+    if (c->comm || (c->apt_R > 0 && c->apt_world > 1) || c->chain_base % c->ladder_len != 0 || c->n_chains % c->ladder_len != 0)
+        return fail(c, NLMC_ERR_UNSUPPORTED, "nlmc_elog_begin: the context has a communicator or holds a cut ladder (the log takes contexts of whole ladders)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t tot = (size_t)n_rounds * (size_t)c->n_chains;
+    c->elog_on = false;
+    HIP_TRY(c, c->elog_energy.reserve(std::max<size_t>(tot, 1)));
+    HIP_TRY(c, c->elog_slot.reserve(std::max<size_t>(tot, 1)));
+    if (tot > 0) {                                  // all ones: a NaN and -1, a row no observation reached
+        HIP_TRY(c, hipMemsetAsync(c->elog_energy.p, 0xFF, sizeof(double) * tot, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->elog_slot.p, 0xFF, sizeof(int32_t) * tot, c->stream));
+    }
+    c->elog_round0 = round0; c->elog_rounds = n_rounds;
+    c->elog_on = true;
+    return NLMC_OK;
+}
+
+int nlmc_elog_update(nlmc_ctx *c, uint32_t round)
+{
+    if (!c) return NLMC_ERR_ARG;
+    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, "nlmc_elog_update: call nlmc_pt_init first");
+    if (!c->elog_on) return fail(c, NLMC_ERR_STATE, "nlmc_elog_update: no log is open (nlmc_elog_begin)");
+    if (c->subset != 0 || c->cur != c->stream)
+        return fail(c, NLMC_ERR_UNSUPPORTED, "nlmc_elog_update: a chain subset is selected (an observation takes every local chain: select all chains first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return launch_elog_update(c, round);
+}
+
+int nlmc_elog_read(nlmc_ctx *c, double *out_energy, int32_t *out_slot)
+{
+    if (!c) return NLMC_ERR_ARG;
+    if (!c->elog_energy.p) return fail(c, NLMC_ERR_STATE, "nlmc_elog_read: no log was begun (nlmc_elog_begin)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t tot = (size_t)c->elog_rounds * (size_t)c->n_chains;
+    if (tot == 0) return NLMC_OK;
+    if (out_energy) HIP_TRY(c, hipMemcpyAsync(out_energy, c->elog_energy.p, sizeof(double) * tot, hipMemcpyDeviceToHost, c->stream));
+    if (out_slot) HIP_TRY(c, hipMemcpyAsync(out_slot, c->elog_slot.p, sizeof(int32_t) * tot, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NLMC_OK;
+}
+
+int nlmc_elog_end(nlmc_ctx *c)
+{
+    if (!c) return NLMC_ERR_ARG;
+    c->elog_on = false;
     return NLMC_OK;
 }
 

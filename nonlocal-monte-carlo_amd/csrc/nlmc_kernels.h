@@ -2689,6 +2689,36 @@ __global__ __launch_bounds__(256) void k_best_update(BestArgs a)
     }
 }
 
+// ---- run-long per-round energy log (nlmc_elog_begin) --------------------------------------------------------------------------
+// One row per round of a window of rounds: every local chain's tracked energy, converted as nlmc_energy_tracked converts it, and its
+// temperature slot, as the swap decision of that round sees them.  A row is a function of the observed (energy, slot) pairs alone:
+// the same bits whichever kernel stored them.  Observers: k_elog_update (any n, reads the state arrays), the observing instantiations
+// of k_rounds_fused and k_rounds_lanes (those that also serve the best-state record: each tests which record is present) and
+// k_apt_rounds_lanes<.., ELOG>.  Round r of a launch goes to row row0 + r when that lies in [0, n_rows): rounds outside the window are
+// not logged.
+struct ElogRec {
+    double *energy;                  // [n_rows][n_chains], or nullptr: no log
+    int32_t *slot;                   // [n_rows][n_chains]
+    int row0;                        // row of the launch's first round (may lie outside the window on either side)
+    int n_rows, n_chains;
+};
+__device__ __forceinline__ void elog_store(const ElogRec &e, int r, int c, double Ed, int slot)
+{
+    const int row = e.row0 + r;
+    if ((unsigned)row < (unsigned)e.n_rows) {
+        const size_t at = (size_t)row * (size_t)e.n_chains + (size_t)c;
+        e.energy[at] = Ed;
+        e.slot[at] = slot;
+    }
+}
+
+// One observation of every local chain's CURRENT tracked energy and slot from the state arrays: a thread per chain, coalesced.
+__global__ __launch_bounds__(256) void k_elog_update(ElogRec e, const long long *efix, const int32_t *slot_of_chain, int chain_base, int escale)
+{
+    const int c = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (c < e.n_chains) elog_store(e, 0, c, (double)efix[c] * __longlong_as_double((long long)(1023 - escale) << 52), slot_of_chain[chain_base + c]);
+}
+
 #define NLMC_ROUNDS_PER_LAUNCH 1024     // rows of the record array; longer calls are split by the host
 struct RoundsArgs {
     int n_rounds, n_windows_avail;   // rounds of this launch; planned windows from the first one on (>= n_rounds: the one behind the last is warmed)
@@ -2706,7 +2736,8 @@ struct RoundsArgs {
     uint8_t *log_acc;
     int32_t *status;                 // sticky pt status: 3 = a wait for a partner timed out
     long long timeout_ticks;         // of the 100 MHz wall clock
-    BestRec best;                    // k_rounds_fused<.., BEST>: the open best-state record (last: the other fields keep their offsets)
+    BestRec best;                    // k_rounds_fused<.., BEST>: the open best-state record, efix = nullptr: none (behind the other fields: they keep their offsets)
+    ElogRec elog;                    // k_rounds_fused<.., BEST>: the open energy log, energy = nullptr: none
 };
 
 // (no static LDS in these kernels: the spins sit at LDS offset 0; the words the waves share are in the reduction scratch)
@@ -2750,9 +2781,11 @@ typedef const RoundsArgs __attribute__((address_space(4))) *rounds_args_cptr;
 // R64 (with F64): the real-valued fp64 variant (k_sweep_fused<.., R64>) on the windows' value plane.  It has no K tables (the launch's
 // LDS is the f32 mode's, kt = 0): keep_kt and the slot remembered in sh[4] then decide nothing.  Its uniform tables are the fp64 mode's
 // high words, so the carry of the next round's first two tables is the same.
-// BEST: a best-state record is open (nlmc_best_begin) -- every round is one observation, stamp round0 + r, of the state its sweeps left:
-// after the chain's hand-off record is out (no partner waits for the copy), before the swap step.  A template parameter, not a
-// pointer test: the instantiations without a record are the kernels they were.
+// BEST: an observer is open -- a best-state record (nlmc_best_begin), an energy log (nlmc_elog_begin) or both; which, the kernel reads
+// from the two records' pointers.  Every round is one observation, stamp round0 + r, of the state its sweeps left: after the chain's
+// hand-off record is out (no partner waits for the copy), before the swap step.  For the log thread 0 stores the (energy, slot) it
+// has just published (the slot maps are written at the end of a launch only, so the kernel logs sh[0] itself).  A template
+// parameter, not a pointer test: the instantiations without an observer are the kernels they were.
 template <bool DIAG, int FMT, bool F64, bool R64 = false, bool BEST = false>
 __global__ __launch_bounds__(1024) void k_rounds_fused(const SweepArgs *ap_g, const RoundsArgs *qp_g)
 {
@@ -2843,17 +2876,20 @@ __global__ __launch_bounds__(1024) void k_rounds_fused(const SweepArgs *ap_g, co
                 // Lane 0 reads the record it alone writes and hands the answer to the wave (E is wave-uniform: one LDS word), wave 0
                 // copies the spins out of LDS 16 bytes a lane.  Nothing writes the spins before the barrier that ends the swap step.
                 const int cb = (int)blockIdx.x, n_pad = a.g.n_pad;
-                const int32_t stamp = (int32_t)(q.round0 + (uint32_t)r);
-                int imp = 0;
-                if (lane == 0) {
-                    imp = (double)E < (double)q.best.efix[cb] ? 1 : 0;
-                    if (q.best.first_hit[cb] < 0 && Ed <= q.best.target) q.best.first_hit[cb] = stamp;
-                }
-                if (__builtin_amdgcn_readfirstlane(imp)) {
-                    const int4 *src = reinterpret_cast<const int4 *>(lds_raw);
-                    int4 *dst = reinterpret_cast<int4 *>(q.best.state + (size_t)cb * n_pad);
-                    for (int i = lane; i < n_pad / 16; i += 64) dst[i] = src[i];
-                    if (lane == 0) { q.best.efix[cb] = E; q.best.stamp[cb] = stamp; }
+                if (q.elog.energy && tid == 0) elog_store(q.elog, r, cb, Ed, slot);
+                if (q.best.efix) {
+                    const int32_t stamp = (int32_t)(q.round0 + (uint32_t)r);
+                    int imp = 0;
+                    if (lane == 0) {
+                        imp = (double)E < (double)q.best.efix[cb] ? 1 : 0;
+                        if (q.best.first_hit[cb] < 0 && Ed <= q.best.target) q.best.first_hit[cb] = stamp;
+                    }
+                    if (__builtin_amdgcn_readfirstlane(imp)) {
+                        const int4 *src = reinterpret_cast<const int4 *>(lds_raw);
+                        int4 *dst = reinterpret_cast<int4 *>(q.best.state + (size_t)cb * n_pad);
+                        for (int i = lane; i < n_pad / 16; i += 64) dst[i] = src[i];
+                        if (lane == 0) { q.best.efix[cb] = E; q.best.stamp[cb] = stamp; }
+                    }
                 }
             }
         }

@@ -36,7 +36,9 @@ struct LaneAptArgs {
 };
 
 // SweepArgs / LaneRoundsArgs fields as in k_rounds_lanes; lds_map_off = the maps of wave 0 (128 bytes per wave).
-template <bool F64>
+// ELOG: an energy log is open (nlmc_elog_begin) -- behind the Houdayer step's energy deltas and before the swap round every live lane
+// stores its energy and slot to the round's row (q.elog, rows of the context's chains).  Without ELOG the kernel is the one it was.
+template <bool F64, bool ELOG = false>
 __global__ __launch_bounds__(1024) void k_apt_rounds_lanes(SweepArgs a, LaneRoundsArgs q, LaneAptArgs x)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -209,6 +211,10 @@ __global__ __launch_bounds__(1024) void k_apt_rounds_lanes(SweepArgs a, LaneRoun
             __syncthreads();
             E += dEw[tid] * (1ll << a.eshift);
             dEw[tid] = 0;                                     // (written again only after the next round's first barrier)
+        }
+
+        if constexpr (ELOG) {
+            if (live) elog_store(q.elog, r, (int)c0 + c, (double)E * inv, slot);
         }
 
         // the swap round of k_rounds_lanes

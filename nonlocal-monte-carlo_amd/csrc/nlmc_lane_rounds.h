@@ -27,15 +27,18 @@ struct LaneRoundsArgs {
     int32_t *log_pairs;              // the rows of the device-side swap log at round0, or nullptr
     uint8_t *log_acc;
     int lds_map_off;                 // LDS offset of the two 64-byte maps: lane_of_slot | slot_of_lane
-    BestRec best;                    // k_rounds_lanes<.., BEST>: the open best-state record (nlmc_best_begin)
+    BestRec best;                    // k_rounds_lanes<.., BEST>: the open best-state record (nlmc_best_begin), efix = nullptr: none
+    ElogRec elog;                    // k_rounds_lanes<.., BEST>, k_apt_rounds_lanes<.., ELOG>: the open energy log (nlmc_elog_begin), energy = nullptr: none
 };
 
 // SweepArgs fields of this kernel: those of k_sweep_lanes' shared order without flags and outputs; n_sweeps = sweeps per round, sweep0 =
 // the first sweep of the launch, lane_perm = the orders of all its n_rounds * n_sweeps sweeps, lane_rows = the context's chains,
 // tab = the ladder's table (two entries per slot).
-// BEST: a best-state record is open -- after a round's sweeps every live lane compares its own energy with its chain's record (three
-// registers, read in the prologue and written back at the end of the launch); the columns of the lanes that improved go out one at a
-// time, the whole wave writing one chain's row.  Tail lanes record nothing.  Without BEST the kernel is the one it was.
+// BEST: an observer is open -- a best-state record, an energy log or both (the records' pointers say which).  Record: after a round's
+// sweeps every live lane compares its own energy with its chain's record (three registers, read in the prologue and written back at
+// the end of the launch); the columns of the lanes that improved go out one at a time, the whole wave writing one chain's row.  Log:
+// at the same place every live lane stores its energy and slot to the round's row (chains of a wave are consecutive: the stores
+// coalesce).  Tail lanes record nothing.  Without BEST the kernel is the one it was.
 template <bool F64, bool BEST = false>
 __global__ __launch_bounds__(64) void k_rounds_lanes(SweepArgs a, LaneRoundsArgs q)
 {
@@ -79,7 +82,8 @@ __global__ __launch_bounds__(64) void k_rounds_lanes(SweepArgs a, LaneRoundsArgs
     const int p = lane - base;
     long long rec_e = 0x7FFFFFFFFFFFFFFFll;
     int32_t rec_stamp = -1, rec_hit = -1;
-    if (BEST && live) { rec_e = q.best.efix[c]; rec_stamp = q.best.stamp[c]; rec_hit = q.best.first_hit[c]; }
+    const bool has_best = BEST && q.best.efix != nullptr;
+    if (has_best && live) { rec_e = q.best.efix[c]; rec_stamp = q.best.stamp[c]; rec_hit = q.best.first_hit[c]; }
 
     for (int r = 0; r < q.n_rounds; ++r) {
         long long e_loc = 0;
@@ -136,10 +140,11 @@ __global__ __launch_bounds__(64) void k_rounds_lanes(SweepArgs a, LaneRoundsArgs
         E += e_loc;
 
         if constexpr (BEST) {                               // one observation of every chain of the wave, before the swap round
+            if (q.elog.energy && live) elog_store(q.elog, r, c, (double)E * inv, slot);
             const int32_t stamp = (int32_t)(q.round0 + (uint32_t)r);
-            const bool imp = live && (double)E < (double)rec_e;   // strict: the first attainment is kept
+            const bool imp = has_best && live && (double)E < (double)rec_e;   // strict: the first attainment is kept
             if (imp) { rec_e = E; rec_stamp = stamp; }
-            if (live && rec_hit < 0 && (double)E * inv <= q.best.target) rec_hit = stamp;
+            if (has_best && live && rec_hit < 0 && (double)E * inv <= q.best.target) rec_hit = stamp;
             unsigned long long m = __ballot(imp);
             if (m) lane_lds_fence();
             while (m) {                                     // (only live lanes improve: rows below nrow)
@@ -188,6 +193,6 @@ __global__ __launch_bounds__(64) void k_rounds_lanes(SweepArgs a, LaneRoundsArgs
         if (a.energy_sink) a.energy_sink[c] = (double)E * inv;
         q.slot_of_chain[gc_chain] = slot;
         q.chain_of_slot[(size_t)g * L + slot] = (int)gc_chain;
-        if (BEST) { q.best.efix[c] = rec_e; q.best.stamp[c] = rec_stamp; q.best.first_hit[c] = rec_hit; }
+        if (has_best) { q.best.efix[c] = rec_e; q.best.stamp[c] = rec_stamp; q.best.first_hit[c] = rec_hit; }
     }
 }

@@ -237,14 +237,17 @@ class LocalTempering:
     ShardedTempering."""
 
     def __init__(self, inst, beta_list, n_chains_global, seed, n_pairs, device_ids, precision="f32", engine_factory=None,
-                 engines=None, parts=None, lane_sweeps="off", track_best=False, target_energy=None):
+                 engines=None, parts=None, lane_sweeps="off", track_best=False, target_energy=None, track_energies=False):
         """`parts` (optional): the blocks [(chain_base, count)] this process drives instead of an even cut over device_ids -- one
         rank's share under a launcher; `engines`: contexts that exist already (they must have had pt_init; not closed here... they
         ARE closed by close(): hand over ownership); `lane_sweeps`: Engine.set_lane_sweeps of every engine created here ("off",
         "auto", "force": short chains one per lane, and run_rounds' chunks inside k_rounds_lanes -- same bits); `track_best`: every
         context keeps the record of its chains' lowest-energy states (Engine.best_begin; `target_energy`: the energy whose first
         passage is stamped, in the engine's units) -- one observation per round, stamp = round index, after the round's sweeps (and
-        NMC cycles) and before its swap; best() reads it.  The record only observes: the trajectory is the same bits."""
+        NMC cycles) and before its swap; best() reads it.  The record only observes: the trajectory is the same bits.
+        `track_energies`: every context keeps a per-round log of its chains' tracked energies and temperature slots as the round's
+        swap decision sees them (Engine.elog_begin) -- opened by plan() for the rounds it plans, or by energy_log_begin(); one
+        observation per round at the same place; energy_log() reads it.  Needs whole ladders per context (ValueError otherwise)."""
         self.G, self.seed, self.n_pairs, self.precision = int(n_chains_global), int(seed), int(n_pairs), precision
         devs = list(device_ids)
         self.parts = list(parts) if parts is not None else [block_partition(self.G, len(devs), r) for r in range(len(devs))]
@@ -273,6 +276,10 @@ class LocalTempering:
         self.nmc = None
         self._nmc_planners = None
         self.track_best = bool(track_best)
+        self.track_energies, self._elog_open = bool(track_energies), False
+        if self.track_energies and not self.whole_ladders:
+            self.close()
+            raise ValueError("track_energies needs every ladder inside one context (whole ladders per block)")
         if self.track_best:
             for e in self.engs:
                 e.best_begin(target_energy)
@@ -323,6 +330,16 @@ class LocalTempering:
                                                chunk_rounds=None if chunk_rounds is None else chunk_rounds * n_ph,
                                                slot=1, beta=self.nmc["beta"], fused_outputs=True) for e in self.engs]
             self._planned_rounds = n_rounds
+        if self.track_energies:
+            self.energy_log_begin(n_rounds)
+
+    def energy_log_begin(self, n_rounds):
+        """Open (or reset) every context's energy log for rounds [rounds_done, rounds_done + n_rounds) (track_energies)."""
+        if not self.track_energies:
+            raise ValueError("LocalTempering.energy_log_begin: created without track_energies")
+        for e in self.engs:
+            e.elog_begin(self.rounds_done, n_rounds)
+        self._elog_open = True
 
     def log_begin(self, n_rounds):
         for e in self.engs:
@@ -347,6 +364,8 @@ class LocalTempering:
             if not self.nmc:
                 if self.track_best:
                     e.best_update(self.rounds_done)
+                if self._elog_open:
+                    e.elog_update(self.rounds_done)
                 outs.append(o)
                 continue
             rec = dict(plain=o, nmc=[])
@@ -377,6 +396,8 @@ class LocalTempering:
             e.select("all")
             if self.track_best:                      # (all chains selected again: the NMC chains in the state they carry on)
                 e.best_update(self.rounds_done)
+            if self._elog_open:                      # (behind the NMC chains' phases, before the swap)
+                e.elog_update(self.rounds_done)
             outs.append(rec)
         self.sweeps_done += n_sweeps
         if self.nmc:
@@ -446,6 +467,8 @@ class LocalTempering:
                     pls[j].sweep(ii + r)
                     if self.track_best:
                         self.engs[j].best_update(self.rounds_done + r)
+                    if self._elog_open:
+                        self.engs[j].elog_update(self.rounds_done + r)
                     self.engs[j].pt_swap_philox(self.rounds_done + r, self.seed, self.n_pairs, want_log=False)
             if not one_by_one:
                 self.deferred_rounds += k
@@ -481,6 +504,17 @@ class LocalTempering:
         recs = [self.engs[j].best_read(want_state=want_state) for j in order]
         return {k: (np.concatenate([r[k] for r in recs]) if recs[0][k] is not None else None)
                 for k in ("energy", "stamp", "first_hit", "state")}
+
+    def energy_log(self):
+        """The contexts' per-round energy logs by global chain id (track_energies): (energies [n_rounds, G] float64, slots
+        [n_rounds, G] int32) of the window most recently opened; NaN / -1 in rounds that did not run."""
+        if not self.track_energies:
+            raise ValueError("LocalTempering.energy_log: created without track_energies")
+        if not self._elog_open:
+            raise ValueError("LocalTempering.energy_log: no log was opened (plan() or energy_log_begin())")
+        order = np.argsort([base for base, _ in self.parts], kind="stable")
+        logs = [self.engs[j].elog_read() for j in order]
+        return np.concatenate([l[0] for l in logs], axis=1), np.concatenate([l[1] for l in logs], axis=1)
 
     def check(self):
         if self.n_pairs > 0:

@@ -629,6 +629,42 @@ class Engine:
         """Close the record (best_read still returns it); the rounds routes behave as before."""
         self._ck(self._L.nlmc_best_end(self._ctx))
 
+    # -- run-long per-round energy log (include/nlmc.h: nlmc_elog_begin) -----------------------------------------------------
+    def elog_begin(self, round0, n_rounds):
+        """Open (or reset) the log of rounds [round0, round0 + n_rounds): per round and local chain the tracked energy and the
+        temperature slot as that round's swap decision sees them.  While it is open pt_rounds_fused / pt_rounds_deferred /
+        pt_rounds_lanes / apt_rounds_lanes observe every chain once per round; round-by-round drivers call elog_update between the
+        last state-changing step and the swap.  Rounds outside the window are not logged.  After pt_init; NotImplementedError for a
+        context with a communicator or a cut ladder."""
+        self._ck(self._L.nlmc_elog_begin(self._ctx, int(round0) & 0xFFFFFFFF, int(n_rounds)))
+        self._elog_rounds = int(n_rounds)
+
+    def elog_update(self, round_idx):
+        """One observation of every local chain's tracked energy and slot as round `round_idx` (asynchronous; all chains must be
+        selected).  A second observation of a round overwrites the first."""
+        self._ck(self._L.nlmc_elog_update(self._ctx, int(round_idx) & 0xFFFFFFFF))
+
+    def elog_read(self, by="chain"):
+        """by="chain": (energy [n_rounds, n_chains] float64, slot [n_rounds, n_chains] int32) by local chain; a row no observation
+        reached reads NaN / -1.  by="slot": (energy [n_rounds, n_ladders, L], chain [n_rounds, n_ladders, L]) -- the energy on every
+        temperature slot of every local ladder and the local chain that held the slot.  One synchronisation; also after elog_end."""
+        if by not in ("chain", "slot"):
+            raise ValueError('elog_read: by must be "chain" or "slot"')
+        R = getattr(self, "_elog_rounds", None)
+        if R is None:
+            raise RuntimeError("elog_read: no log was begun (elog_begin)")
+        e, s = np.empty((R, self.n_chains), np.float64), np.empty((R, self.n_chains), np.int32)
+        if e.size:
+            self._ck(self._L.nlmc_elog_read(self._ctx, _abi.ptr(e), _abi.ptr(s)))
+        if by == "chain":
+            return e, s
+        from .hostlogic import log_by_slot
+        return log_by_slot(e, s, self.ladder_len)
+
+    def elog_end(self):
+        """Close the log (elog_read still returns it); the rounds routes behave as before."""
+        self._ck(self._L.nlmc_elog_end(self._ctx))
+
     def backbone_seed(self, snapshot=True):
         """snapshot=True: later backbone_clusters calls are seeded with the configurations as they are NOW; False: with the current ones."""
         self._ck(self._L.nlmc_backbone_seed(self._ctx, 1 if snapshot else 0))

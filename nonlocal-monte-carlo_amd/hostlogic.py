@@ -50,3 +50,119 @@ def phase_flags(n, m_init, clusters, phase):
     else:
         raise ValueError(phase)
     return fl
+
+
+# ---- what a per-round energy log says about a ladder (Engine.elog_read; no device code) --------------------------------------
+def log_by_slot(energies, slots, ladder_len):
+    """A log by chain -> by temperature slot.  energies, slots [n_rounds, G], chains g L .. g L + L - 1 forming ladder g ->
+    (energy [n_rounds, G // L, L], chain [n_rounds, G // L, L]): the energy on every slot and the chain (its index in the log's
+    columns) that held it; NaN / -1 in rows no observation reached."""
+    e, s = np.asarray(energies, dtype=np.float64), np.asarray(slots)
+    L = int(ladder_len)
+    R, G = e.shape
+    if L < 1 or G % L != 0 or s.shape != e.shape:
+        raise ValueError("log_by_slot: energies and slots must be [n_rounds, n_ladders * ladder_len]")
+    nl = G // L
+    by_e, by_c = np.full((R, nl, L), np.nan), np.full((R, nl, L), -1, dtype=np.int32)
+    seen = s >= 0
+    rr, cc = np.nonzero(seen)
+    by_e[rr, cc // L, s[rr, cc]] = e[rr, cc]
+    by_c[rr, cc // L, s[rr, cc]] = cc
+    return by_e, by_c
+
+
+def ladder_report(energies, slots, beta_list):
+    """Mixing statistics of every ladder of a per-round energy log.  energies, slots [n_rounds, G] by chain as elog_read returns
+    them (rows no observation reached, NaN / -1, are left out), beta_list [L], chains g L .. g L + L - 1 forming ladder g.  A list
+    with one dict per ladder:
+      beta [L]; mean_energy [L], sigma_energy [L]  by temperature slot, over the observed rounds; sigma is the population standard
+                                                   deviation (np.std), what APT_preprocessor calls sigma_E (NPT/apt_preprocessor.py:179)
+      swap_attempts [L - 1]   transitions between two consecutive observed rounds: every adjacent pair of slots had that many chances
+      swap_accepts [L - 1]    transitions in which the chains on slots i and i + 1 exchanged their slots
+      acceptance [L - 1]      accepts / attempts: the rate of exchange per ROUND (a round selects n_pairs of the L - 1 pairs, so this
+                              is the chance of being selected times the acceptance of a selected pair -- what the ladder mixes with);
+                              NaN without a transition.  Derived from the slots alone: the swap log is not needed.
+      round_trips [L]         per chain of the ladder: completed journeys slot 0 -> slot L - 1 -> slot 0
+      tau_round_trip          observed rounds x chains / all round trips: rounds a chain needs per trip, inf if there was none
+      n_rounds                observed rounds"""
+    beta = np.asarray(beta_list, dtype=np.float64).reshape(-1)
+    L = beta.size
+    by_e, by_c = log_by_slot(energies, slots, L)
+    s_all = np.asarray(slots)
+    out = []
+    for g in range(by_e.shape[1]):
+        ok = (by_c[:, g, :] >= 0).all(axis=1)
+        e, c = by_e[ok, g, :], by_c[ok, g, :]
+        n_obs = int(e.shape[0])
+        with np.errstate(invalid="ignore"):
+            mean = e.mean(axis=0) if n_obs else np.full(L, np.nan)
+            sigma = e.std(axis=0) if n_obs else np.full(L, np.nan)
+        # transitions between CONSECUTIVE rounds that were both observed
+        idx = np.nonzero(ok)[0]
+        cons = np.nonzero(np.diff(idx) == 1)[0]
+        attempts = np.full(max(L - 1, 0), cons.size, dtype=np.int64)
+        accepts = np.zeros(max(L - 1, 0), dtype=np.int64)
+        if L > 1 and cons.size:
+            a, b = c[cons], c[cons + 1]
+            accepts = ((a[:, :-1] == b[:, 1:]) & (a[:, 1:] == b[:, :-1])).sum(axis=0).astype(np.int64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            acceptance = np.where(attempts > 0, accepts / np.maximum(attempts, 1), np.nan)
+        trips = np.zeros(L, dtype=np.int64)
+        sl = s_all[ok][:, g * L:(g + 1) * L]
+        for j in range(L):
+            leg = 0                                   # 0: not at the bottom yet, 1: left slot 0 for the top, 2: reached the top
+            for v in sl[:, j]:
+                if v == 0:
+                    if leg == 2:
+                        trips[j] += 1
+                    leg = 1
+                elif v == L - 1 and leg == 1:
+                    leg = 2
+        total = int(trips.sum())
+        out.append(dict(beta=beta.copy(), mean_energy=mean, sigma_energy=sigma, swap_attempts=attempts, swap_accepts=accepts,
+                        acceptance=acceptance, round_trips=trips, tau_round_trip=(n_obs * L / total) if total else float("inf"),
+                        n_rounds=n_obs))
+    return out
+
+
+def pool_reports(reports):
+    """One report for several ladders at the same temperatures (the sub-replicas of an APT system): means of mean_energy and
+    sigma_energy over the ladders (APT_preprocessor averages the replicas' standard deviations), attempts and accepts summed,
+    round_trips concatenated."""
+    reports = list(reports)
+    att = np.sum([r["swap_attempts"] for r in reports], axis=0)
+    acc = np.sum([r["swap_accepts"] for r in reports], axis=0)
+    trips = np.concatenate([r["round_trips"] for r in reports])
+    n_obs = max(r["n_rounds"] for r in reports)
+    total = int(trips.sum())
+    with np.errstate(invalid="ignore", divide="ignore"):
+        acceptance = np.where(att > 0, acc / np.maximum(att, 1), np.nan)
+    return dict(beta=reports[0]["beta"].copy(), mean_energy=np.mean([r["mean_energy"] for r in reports], axis=0),
+                sigma_energy=np.mean([r["sigma_energy"] for r in reports], axis=0), swap_attempts=att, swap_accepts=acc,
+                acceptance=acceptance, round_trips=trips, tau_round_trip=(n_obs * trips.size / total) if total else float("inf"),
+                n_rounds=n_obs)
+
+
+def suggest_ladder(report, beta_list, alpha=1.25, beta_max=None, sigma_min=0.0, max_len=4096):
+    """A new ladder from the measured energy spread, by APT_preprocessor's recurrence beta_{i+1} = beta_i + alpha / sigma_E(beta_i)
+    (NPT/apt_preprocessor.py:151-186), starting at the smallest measured beta.  sigma_E(beta) is report["sigma_energy"] interpolated
+    linearly in beta between the measured slots and held constant outside them.  It stops as the preprocessor stops: when sigma_E at
+    the last beta is not above `sigma_min` (the caller passes 0.5 min|J_ij|, the preprocessor's freeze-out), or when the last beta
+    exceeds `beta_max` (default: the largest measured beta) -- like the preprocessor's list, the result may END with the one value
+    above beta_max.  `report`: one dict of ladder_report / pool_reports.  Returns a strictly increasing float64 array."""
+    b = np.asarray(beta_list, dtype=np.float64).reshape(-1)
+    sig = np.asarray(report["sigma_energy"], dtype=np.float64).reshape(-1)
+    if b.size != sig.size or b.size == 0:
+        raise ValueError("suggest_ladder: the report and beta_list differ in length")
+    if not (alpha > 0):
+        raise ValueError("suggest_ladder: alpha must be positive")
+    order = np.argsort(b, kind="stable")
+    b, sig = b[order], sig[order]
+    bmax = float(b[-1]) if beta_max is None else float(beta_max)
+    out = [float(b[0])]
+    while len(out) < int(max_len):
+        s = float(np.interp(out[-1], b, sig))
+        if not (s > sigma_min) or not np.isfinite(s) or out[-1] > bmax:
+            break
+        out.append(out[-1] + alpha / s)
+    return np.asarray(out, dtype=np.float64)

@@ -91,7 +91,7 @@ class NPT(Common):
             lambda_start=0.5, lambda_end=0.01, lambda_reduction_factor=0.9, threshold_initial=0.999999,
             threshold_cutoff=0.99999, max_iterations=100, tolerance=np.finfo(float).eps, use_hash_table=False,
             num_cores=8, plot=False, num_restarts=1, device_ids=None, return_trace="float64", track_best=False,
-            target_energy=None):
+            target_energy=None, track_energies=False):
         """Run the NPT algorithm (NPT/npt.py:535-700).  Returns (M [R*N, S_swap], Energy [R]).
 
         Additive keyword arguments (defaults = the reference's behaviour): `num_restarts` independent ladders advanced
@@ -106,7 +106,13 @@ class NPT(Common):
         [G] (round of the first attainment) and self.first_hit_round [G] (first round at or below `target_energy`, -1: never or no
         target), G = num_restarts * num_replicas by global chain id (under a launcher with whole ladders per rank: this rank's
         chains).  The trajectory is the same bits with or without it.  ValueError on the host-managed / rng="numpy" paths and where
-        a launcher cuts a ladder across ranks."""
+        a launcher cuts a ladder across ranks.
+        `track_energies` (same conditions; every ladder inside one context, so device_ids that cut a ladder raise ValueError): the
+        run keeps, for every round, the tracked energy and temperature slot of every chain as that round's swap decision sees them
+        (Engine.elog_begin: no synchronisation inside the run) and sets self.round_energies [rounds, G] (normalised units like
+        Energy), self.round_slots [rounds, G] by global chain id and self.ladder_report: hostlogic.ladder_report's statistics, one
+        per restart (sigma_E per temperature, swap acceptance per adjacent pair, round trips; hostlogic.suggest_ladder turns one into
+        a new ladder).  (M, Energy) and every other attribute are the same bits with or without it."""
         self.num_replicas = num_replicas
         self.num_sweeps_MCMC = num_sweeps_MCMC
         self.num_sweeps_read = num_sweeps_read
@@ -142,6 +148,12 @@ class NPT(Common):
             raise ValueError("num_restarts must be >= 1")
         if track_best and not device_resident:
             raise ValueError("track_best needs the device-resident path: rng='philox' (with NMC replicas: a phase length M_skip divides)")
+        if track_energies:
+            n_ctx = len(list(device_ids)) if device_ids else 1
+            if not device_resident:
+                raise ValueError("track_energies needs the device-resident path: rng='philox' (with NMC replicas: a phase length M_skip divides)")
+            if int(num_restarts) % n_ctx != 0:
+                raise ValueError("track_energies needs every ladder on one device: num_restarts % len(device_ids) != 0")
         if device_resident:
             nmc = None
             if any_nmc:
@@ -150,7 +162,8 @@ class NPT(Common):
                            lambda_reduction_factor=lambda_reduction_factor, threshold_initial=threshold_initial,
                            threshold_cutoff=threshold_cutoff, max_iterations=max_iterations, tolerance=tolerance, M_skip=int(M_skip))
             M, Energy = self._run_device_resident(beta_list, int(num_restarts), device_ids, return_trace, nmc,
-                                                  track_best=bool(track_best), target_energy=target_energy)
+                                                  track_best=bool(track_best), target_energy=target_energy,
+                                                  track_energies=bool(track_energies))
         else:
             M, Energy = self._run_host_managed(beta_list, num_cycles, full_update_frequency, M_skip, temp_x, global_beta,
                                                lambda_start, lambda_end, lambda_reduction_factor, threshold_initial,
@@ -323,7 +336,7 @@ class NPT(Common):
 
     # ------------------------------------------------------------------------------------------------
     def _run_device_resident(self, beta_list, n_restarts=1, device_ids=None, return_trace="float64", nmc=None, track_best=False,
-                             target_energy=None):
+                             target_energy=None, track_energies=False):
         """Throughput path: all replicas (x restarts) stay on the device(s); label-exchange swaps decided by a kernel; the
         swap log is kept on the device and read once; only the last round's trace comes back (as int8 until the
         reference-shaped float64 M is asked for).  `nmc`: NMC_task parameters when some slots have doNMC set -- those
@@ -356,6 +369,8 @@ class NPT(Common):
                 raise ValueError("with NMC replicas every ladder must lie on one rank: num_restarts % ranks != 0")
             if track_best and cut:
                 raise ValueError("track_best needs every ladder on one rank: num_restarts % ranks != 0")
+            if track_energies and cut:
+                raise ValueError("track_energies needs every ladder on one rank: num_restarts % ranks != 0")
             devs = [lrank_]
         if G % len(devs):
             raise ValueError("num_replicas * num_restarts must be a multiple of len(device_ids)")
@@ -383,10 +398,10 @@ class NPT(Common):
             return e
         if ctx is None:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, precision=prec, lane_sweeps=self.lanes,
-                                track_best=track_best, target_energy=target_energy)
+                                track_best=track_best, target_energy=target_energy, track_energies=track_energies)
         elif not cut:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, parts=[(base_, count_)], precision=prec,
-                                lane_sweeps=self.lanes, track_best=track_best, target_energy=target_energy)
+                                lane_sweeps=self.lanes, track_best=track_best, target_energy=target_energy, track_energies=track_energies)
         else:
             lt = ShardedAsLocal(ShardedTempering(
                 lambda i, n, b, g: opt_in(Engine(i, None, n, device=lrank_, chain_base=b, n_chains_global=g)), inst, beta_list, G,
@@ -458,6 +473,10 @@ class NPT(Common):
             if track_best:
                 b = lt.best()
                 self.best_energy, self.best_state, self.best_round, self.first_hit_round = b["energy"], b["state"], b["stamp"], b["first_hit"]
+            if track_energies:                           # (plan() opened the log for the run's rounds)
+                from .hostlogic import ladder_report
+                self.round_energies, self.round_slots = lt.energy_log()
+                self.ladder_report = ladder_report(self.round_energies, self.round_slots, beta_list)
             Energy = np.zeros(R)
             E_all = np.zeros((n_restarts, R))
             if last is not None and S > 0:
