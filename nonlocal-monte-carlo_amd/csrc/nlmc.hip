@@ -1166,6 +1166,44 @@ const void *lanes_kernel(bool f64, bool per_chain)
     return table[f64 ? 1 : 0][per_chain ? 1 : 0];
 }
 
+const void *rounds_lanes_kernel(bool f64, bool observed)
+{
+    static const void *const table[2][2] = {
+        {reinterpret_cast<const void *>(k_rounds_lanes<false, false>), reinterpret_cast<const void *>(k_rounds_lanes<false, true>)},
+        {reinterpret_cast<const void *>(k_rounds_lanes<true, false>), reinterpret_cast<const void *>(k_rounds_lanes<true, true>)}};
+    return table[f64 ? 1 : 0][observed ? 1 : 0];
+}
+
+const void *apt_lanes_kernel(bool f64, bool elog)
+{
+    static const void *const table[2][2] = {
+        {reinterpret_cast<const void *>(k_apt_rounds_lanes<false, false>), reinterpret_cast<const void *>(k_apt_rounds_lanes<false, true>)},
+        {reinterpret_cast<const void *>(k_apt_rounds_lanes<true, false>), reinterpret_cast<const void *>(k_apt_rounds_lanes<true, true>)}};
+    return table[f64 ? 1 : 0][elog ? 1 : 0];
+}
+
+// k_lane_orders: the n_orders visiting orders of a lane launch into c->lane_perm, n_sweeps from sweep0 on (per_chain: for each chain).
+int launch_lane_orders(nlmc_ctx *c, hipStream_t st, size_t n_orders, int n_sweeps, int per_chain, uint32_t sweep0, uint64_t seed)
+{
+    LaneOrderArgs oa{};
+    oa.n = c->n; oa.n_sweeps = n_sweeps; oa.per_chain = per_chain; oa.chain_base = c->chain_base;
+    oa.seed_lo = (uint32_t)seed; oa.seed_hi = (uint32_t)(seed >> 32); oa.sweep0 = sweep0;
+    oa.perm = c->lane_perm.p;
+    hipLaunchKernelGGL(k_lane_orders, dim3((unsigned)n_orders), dim3(256), 0, st, oa);
+    HIP_TRY(c, hipGetLastError());
+    c->stat_lane_orders += (int64_t)n_orders;
+    return NLMC_OK;
+}
+
+// The SweepArgs fields every lane kernel reads besides those of sweep_args: `rows` chains, the orders launch_lane_orders wrote, the
+// random-number table at LDS offset u_off where there is one.
+void lane_fields(const nlmc_ctx *c, SweepArgs &a, int rows, bool tab, size_t u_off)
+{
+    a.energy_sink = c->energy_sink;
+    a.lane_perm = c->lane_perm.p; a.lane_rows = rows; a.lane_diag = c->has_diag ? 1 : 0; a.lane_tab = tab ? 1 : 0;
+    a.lds_u_off = (int)u_off;
+}
+
 // The chain-per-lane half of run_sweeps: windows of sweeps -> k_lane_orders (the "levelize" half of the timings) -> k_sweep_lanes, one
 // launch per window.  Windows are cut against the scratch bound of run_sweeps_stepwise.  The outputs stay in the context's buffers.
 int run_sweeps_lanes(nlmc_ctx *c, int precision, int order_mode, int n_sweeps, uint32_t sweep0, uint64_t seed, const double *tab_dev,
@@ -1187,19 +1225,12 @@ int run_sweeps_lanes(nlmc_ctx *c, int precision, int order_mode, int n_sweeps, u
         const int w = std::min(W, n_sweeps - t0);
         TimerSpan ts;
         if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->cur); if (rc) return rc; }
-        LaneOrderArgs oa{};
-        oa.n = n; oa.n_sweeps = w; oa.per_chain = per_chain; oa.chain_base = c->chain_base;
-        oa.seed_lo = (uint32_t)seed; oa.seed_hi = (uint32_t)(seed >> 32); oa.sweep0 = sweep0 + (uint32_t)t0;
-        oa.perm = c->lane_perm.p;
-        const size_t n_orders = per_sweep_orders * (size_t)w;
-        hipLaunchKernelGGL(k_lane_orders, dim3((unsigned)n_orders), dim3(256), 0, c->cur, oa);
-        HIP_TRY(c, hipGetLastError());
-        c->stat_lane_orders += (int64_t)n_orders;
+        { int rc = launch_lane_orders(c, c->cur, per_sweep_orders * (size_t)w, w, per_chain, sweep0 + (uint32_t)t0, seed); if (rc) return rc; }
         { int rc = span_mid(c, ts); if (rc) return rc; }
 
         SweepArgs a = sweep_args(c, sweep0 + (uint32_t)t0, w, seed, tab_dev + (size_t)t0 * tab_ss, tab_cs, tab_ss, use_slots);
+        lane_fields(c, a, R, L.tab, L.u_off);
         a.per_chain = per_chain;
-        a.energy_sink = c->energy_sink;
         a.etrace = want_energy ? c->etrace.p : nullptr;
         a.trace_sweeps = n_sweeps;
         a.t0 = t0;
@@ -1207,8 +1238,7 @@ int run_sweeps_lanes(nlmc_ctx *c, int precision, int order_mode, int n_sweeps, u
         a.strace = rec ? c->strace.p : nullptr;
         a.emin = want_min ? c->emin.p : nullptr;
         a.best = (want_min && want_state) ? c->best.p : nullptr;
-        a.lane_perm = c->lane_perm.p; a.lane_rows = R; a.lane_diag = c->has_diag ? 1 : 0; a.lane_tab = L.tab ? 1 : 0;
-        a.lds_flags_off = L.flags_off; a.lds_u_off = L.u_off;
+        a.lds_flags_off = L.flags_off;
         void *kargs[] = {&a};
         HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)((R + 63) / 64)), dim3(64), kargs, L.total, c->cur));
         HIP_TRY(c, hipGetLastError());
@@ -2601,6 +2631,33 @@ const char *rounds_context_refusal(const nlmc_ctx *c, bool strict)
     return nullptr;
 }
 
+// What every rounds entry point (`name`) checks first, in this order: the arguments, a ladder, anything to do.  NLMC_OK with go = false
+// when there is nothing to do.
+int rounds_entry_check(nlmc_ctx *c, const std::string &name, int precision, int n_rounds, int T, int n_pairs, bool &go)
+{
+    go = false;
+    if (n_rounds < 0 || T < 1 || (precision != NLMC_F32 && precision != NLMC_F64) || n_pairs < 0)
+        return fail(c, NLMC_ERR_ARG, name + "bad argument");
+    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, name + "call nlmc_pt_init first");
+    go = n_rounds != 0 && c->n_chains != 0;
+    return NLMC_OK;
+}
+
+// The plan rows and the log rows (nullptr where `log` is false) of `round`, nl ladders wide: where a launch that starts at that round
+// finds its planned selections and writes its pairs and decisions.  The windows cover the round (RoundWindow::covers).
+struct RoundRows { const int32_t *plan_pairs; int32_t *log_pairs; uint8_t *log_acc; };
+RoundRows round_rows(const nlmc_ctx *c, uint32_t round, size_t nl, int n_pairs, bool log)
+{
+    RoundRows r{};
+    const size_t per_round = nl * (size_t)n_pairs;
+    if (n_pairs > 0) r.plan_pairs = c->pt_plan_pairs.p + c->pt_plan.row(round) * per_round * 2;
+    if (log) {
+        r.log_pairs = c->pt_log_pairs.p + c->pt_log.row(round) * per_round * 2;
+        r.log_acc = c->pt_log_acc.p + c->pt_log.row(round) * per_round;
+    }
+    return r;
+}
+
 // The checks nlmc_pt_rounds_fused (via rounds) and nlmc_pt_rounds_deferred (via deferred) share, in their order.  NLMC_OK with the
 // plan slot and the arithmetic of the rounds in fslot / arith, fslot = -1 when there is nothing to do.
 int rounds_check(nlmc_ctx *c, Via via, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs,
@@ -2609,10 +2666,8 @@ int rounds_check(nlmc_ctx *c, Via via, int precision, int n_rounds, int T, uint3
     const bool d = via == Via::deferred;
     const std::string name = d ? "nlmc_pt_rounds_deferred: " : "nlmc_pt_rounds_fused: ";
     fslot = -1;
-    if (n_rounds < 0 || T < 1 || (precision != NLMC_F32 && precision != NLMC_F64) || n_pairs < 0)
-        return fail(c, NLMC_ERR_ARG, name + "bad argument");
-    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, name + "call nlmc_pt_init first");
-    if (n_rounds == 0 || c->n_chains == 0) return NLMC_OK;
+    bool go = false;
+    { int rc = rounds_entry_check(c, name, precision, n_rounds, T, n_pairs, go); if (rc || !go) return rc; }
     const int L = c->ladder_len;
     auto no = [&](const char *why) { return fail(c, NLMC_ERR_UNSUPPORTED, name + why); };
     if (d ? c->knobs.no_deferred : c->knobs.no_persistent) return no(d ? "switched off (NLMC_NO_DEFERRED)" : "switched off (NLMC_NO_PERSISTENT)");
@@ -2689,17 +2744,13 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
         q.loff = A.loff; q.nlev = A.nlev; q.himax = A.himax; q.send = A.send; q.npos = A.npos; q.head = A.head; q.ell = A.ell;
         q.val = real ? A.val : nullptr;
         q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = nl; q.round0 = r0;
-        q.plan_pairs = n_pairs > 0 ? c->pt_plan_pairs.p + c->pt_plan.row(r0) * nl * n_pairs * 2 : nullptr;
+        const RoundRows rows = round_rows(c, r0, (size_t)nl, n_pairs, log);
+        q.plan_pairs = rows.plan_pairs; q.log_pairs = rows.log_pairs; q.log_acc = rows.log_acc;
         q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
         q.rec = c->rounds_rec.p; q.status = c->pt_status.p;
         q.timeout_ticks = 100000000ll * 20;                   // 20 s of the 100 MHz wall clock
         if (c->best_on) q.best = c->best_rec();               // (the record lives in global memory: it carries over from launch to launch)
         q.elog = c->elog_rec(r0, k);                          // (the row of the launch's first round: round0 + at of the call)
-        if (log) {
-            const size_t r = c->pt_log.row(r0);
-            q.log_pairs = c->pt_log_pairs.p + r * (size_t)nl * n_pairs * 2;
-            q.log_acc = c->pt_log_acc.p + r * (size_t)nl * n_pairs;
-        }
         // events around the launch while timings accumulate: its time counts for its k rounds
         TimerSpan ts;
         if (c->ev_accumulate) { int rc = span_begin(c, ts, 1, c->stream); if (rc) return rc; }
@@ -2744,61 +2795,44 @@ const char *rounds_lanes_refusal(const nlmc_ctx *c, int n_rounds, int T, uint32_
     return nullptr;
 }
 
-// n_rounds rounds in launches of k_rounds_lanes, as many whole rounds per launch as the order scratch holds visiting orders for.
-// rounds_lanes_refusal said nullptr.
-int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
+// The LaneRoundsArgs of a launch of k rounds from round r0 on, nl ladders in the plan and log rows, the slot maps at LDS offset map_off.
+// Observers: the open best-state record and the rows of the open energy log the launch falls on.
+LaneRoundsArgs lane_rounds_args(const nlmc_ctx *c, int k, uint32_t r0, int n_pairs, size_t nl, bool log, size_t map_off)
 {
-    const int L = c->ladder_len, n = c->n, nl = c->n_chains_global / L, P = 64 / L;
-    const size_t bytes_per_round = (size_t)T * (size_t)n * sizeof(uint16_t);
+    LaneRoundsArgs q{};
+    q.n_rounds = k; q.ladder_len = c->ladder_len; q.n_pairs = n_pairs; q.n_ladders = (int)nl; q.round0 = r0;
+    const RoundRows rows = round_rows(c, r0, nl, n_pairs, log);
+    q.plan_pairs = rows.plan_pairs; q.log_pairs = rows.log_pairs; q.log_acc = rows.log_acc;
+    q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
+    q.lds_map_off = (int)map_off;
+    if (c->best_on) q.best = c->best_rec();
+    q.elog = c->elog_rec(r0, k);
+    return q;
+}
+
+// The launches of a lane rounds driver: n_rounds rounds in chunks of as many whole rounds as the order scratch holds visiting orders
+// for.  Per chunk of k rounds from round r0 (sweep s0, `at` rounds into the call): k_lane_orders (the "levelize" half of the timings),
+// then launch(at, k, s0, r0) puts the caller's kernel kfun (lds bytes of dynamic LDS) on the context's stream.
+extern "C++" template <typename Launch>
+int lane_rounds_chunks(nlmc_ctx *c, const void *kfun, size_t lds, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, Launch launch)
+{
+    const size_t bytes_per_round = (size_t)T * (size_t)c->n * sizeof(uint16_t);
     const int K = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_rounds, c->knobs.lane_scratch / bytes_per_round, (size_t)(INT_MAX / 2) / (size_t)T}));
     begin_sweep_call(c);
     c->stat_orders = 0; c->stat_levels = 0; c->stats_pending = false;
     c->stat_fused_window = -1;
     c->stat_lane_orders = 0;
-    HIP_TRY(c, c->lane_perm.reserve((size_t)K * (size_t)T * (size_t)n));
+    HIP_TRY(c, c->lane_perm.reserve((size_t)K * (size_t)T * (size_t)c->n));
     { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
-    LaneLds Lds = lane_lds(c);
-    const int map_off = (int)((Lds.total + 15) & ~(size_t)15);          // lane_of_slot | slot_of_lane, 64 bytes each
-    Lds.total = (size_t)map_off + 128;
-    const void *kfun = c->observed() ? (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_rounds_lanes<true, true>)
-                                                             : reinterpret_cast<const void *>(k_rounds_lanes<false, true>))
-                                    : (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_rounds_lanes<true>)
-                                                             : reinterpret_cast<const void *>(k_rounds_lanes<false>));
-    { int rc = ensure_lds(c, kfun, Lds.total); if (rc) return rc; }
-    const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
-    const int ladders = c->n_chains / L;
+    { int rc = ensure_lds(c, kfun, lds); if (rc) return rc; }
     for (int at = 0; at < n_rounds; at += K) {
         const int k = std::min(K, n_rounds - at);
         const uint32_t s0 = sweep0 + (uint32_t)at * (uint32_t)T, r0 = round0 + (uint32_t)at;
         TimerSpan ts;
         if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->stream); if (rc) return rc; }
-        LaneOrderArgs oa{};
-        oa.n = n; oa.n_sweeps = k * T; oa.per_chain = 0; oa.chain_base = c->chain_base;
-        oa.seed_lo = (uint32_t)seed; oa.seed_hi = (uint32_t)(seed >> 32); oa.sweep0 = s0;
-        oa.perm = c->lane_perm.p;
-        hipLaunchKernelGGL(k_lane_orders, dim3((unsigned)(k * T)), dim3(256), 0, c->stream, oa);
-        HIP_TRY(c, hipGetLastError());
-        c->stat_lane_orders += (int64_t)k * T;
+        { int rc = launch_lane_orders(c, c->stream, (size_t)k * T, k * T, 0, s0, seed); if (rc) return rc; }
         { int rc = span_mid(c, ts); if (rc) return rc; }
-
-        SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
-        a.energy_sink = c->energy_sink;
-        a.lane_perm = c->lane_perm.p; a.lane_rows = c->n_chains; a.lane_diag = c->has_diag ? 1 : 0; a.lane_tab = Lds.tab ? 1 : 0;
-        a.lds_u_off = Lds.u_off;
-        LaneRoundsArgs q{};
-        q.n_rounds = k; q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = nl; q.round0 = r0;
-        q.plan_pairs = c->pt_plan_pairs.p + c->pt_plan.row(r0) * (size_t)nl * n_pairs * 2;
-        q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
-        if (log) {
-            const size_t lr = c->pt_log.row(r0);
-            q.log_pairs = c->pt_log_pairs.p + lr * (size_t)nl * n_pairs * 2;
-            q.log_acc = c->pt_log_acc.p + lr * (size_t)nl * n_pairs;
-        }
-        q.lds_map_off = map_off;
-        if (c->best_on) q.best = c->best_rec();
-        q.elog = c->elog_rec(r0, k);
-        void *kargs[] = {&a, &q};
-        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)((ladders + P - 1) / P)), dim3(64), kargs, Lds.total, c->stream));
+        { int rc = launch(at, k, s0, r0); if (rc) return rc; }
         HIP_TRY(c, hipGetLastError());
         { int rc = span_end(c, ts); if (rc) return rc; }
         if (c->ev_accumulate) c->launches_timed += k;
@@ -2807,6 +2841,27 @@ int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep
     }
     c->sub_dirty = true;
     c->last_route = NLMC_ROUTE_LANES;
+    return NLMC_OK;
+}
+
+// n_rounds rounds in launches of k_rounds_lanes.  rounds_lanes_refusal said nullptr.
+int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
+{
+    const int L = c->ladder_len, P = 64 / L, ladders = c->n_chains / L;
+    LaneLds Lds = lane_lds(c);
+    const size_t map_off = (Lds.total + 15) & ~(size_t)15;              // lane_of_slot | slot_of_lane, 64 bytes each
+    Lds.total = map_off + 128;
+    const void *kfun = rounds_lanes_kernel(precision == NLMC_F64, c->observed());
+    const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
+    int rc = lane_rounds_chunks(c, kfun, Lds.total, n_rounds, T, sweep0, round0, seed, [&](int, int k, uint32_t s0, uint32_t r0) -> int {
+        SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
+        lane_fields(c, a, c->n_chains, Lds.tab, Lds.u_off);
+        LaneRoundsArgs q = lane_rounds_args(c, k, r0, n_pairs, (size_t)(c->n_chains_global / L), log, map_off);
+        void *kargs[] = {&a, &q};
+        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)((ladders + P - 1) / P)), dim3(64), kargs, Lds.total, c->stream));
+        return NLMC_OK;
+    });
+    if (rc) return rc;
     c->rounds_route = NLMC_ROUNDS_LANES;
     return NLMC_OK;
 }
@@ -2817,10 +2872,8 @@ int nlmc_pt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_pe
 {
     if (!c) return NLMC_ERR_ARG;
     const std::string name = "nlmc_pt_rounds_lanes: ";
-    if (n_rounds < 0 || sweeps_per_round < 1 || (precision != NLMC_F32 && precision != NLMC_F64) || n_pairs < 0)
-        return fail(c, NLMC_ERR_ARG, name + "bad argument");
-    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, name + "call nlmc_pt_init first");
-    if (n_rounds == 0 || c->n_chains == 0) return NLMC_OK;
+    bool go = false;
+    { int rc = rounds_entry_check(c, name, precision, n_rounds, sweeps_per_round, n_pairs, go); if (rc || !go) return rc; }
     if (n_pairs > std::max(0, c->ladder_len - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
     if (const char *why = rounds_lanes_refusal(c, n_rounds, sweeps_per_round, round0, seed, n_pairs)) return fail(c, NLMC_ERR_UNSUPPORTED, name + why);
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2893,13 +2946,9 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
         if (r > 0) {                          // the swap of round round0 + r - 1, on the energies the previous launch published
             const uint32_t rr = round0 + (uint32_t)(r - 1);
             d.n_pairs = n_pairs; d.round = rr;
-            d.plan_pairs = c->pt_plan_pairs.p + c->pt_plan.row(rr) * nl * n_pairs * 2;
+            const RoundRows rows = round_rows(c, rr, (size_t)nl, n_pairs, log);
+            d.plan_pairs = rows.plan_pairs; d.log_pairs = rows.log_pairs; d.log_acc = rows.log_acc;
             d.e_prev = c->rounds_ebuf.p + (size_t)((r - 1) & 1) * G;
-            if (log) {
-                const size_t lr = c->pt_log.row(rr);
-                d.log_pairs = c->pt_log_pairs.p + lr * (size_t)nl * n_pairs * 2;
-                d.log_acc = c->pt_log_acc.p + lr * (size_t)nl * n_pairs;
-            }
         }
         // (this launch publishes its chains' final energies for the next one: rows of the local chains inside the global vector)
         double *sink = c->rounds_ebuf.p + (size_t)(r & 1) * G + c->chain_base;
@@ -3209,10 +3258,8 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
     if (!c) return NLMC_ERR_ARG;
     const std::string name = "nlmc_apt_rounds_lanes: ";
     const int T = sweeps_per_round;
-    if (n_rounds < 0 || T < 1 || (precision != NLMC_F32 && precision != NLMC_F64) || n_pairs < 0)
-        return fail(c, NLMC_ERR_ARG, name + "bad argument");
-    if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, name + "call nlmc_pt_init first");
-    if (n_rounds == 0 || c->n_chains == 0) return NLMC_OK;
+    bool go = false;
+    { int rc = rounds_entry_check(c, name, precision, n_rounds, T, n_pairs, go); if (rc || !go) return rc; }
     if (n_pairs > std::max(0, c->ladder_len - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
     auto no = [&](const char *why) { return fail(c, NLMC_ERR_UNSUPPORTED, name + why); };
     if (c->best_on) return no("a best-state record is open: k_apt_rounds_lanes keeps none (run the round step by step with nlmc_best_update)");
@@ -3220,59 +3267,21 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
     if (c->rng_stride != 0) return no("random numbers keyed by temperature slot (nlmc_apt_shard) keep the round-by-round route");
     if (const char *why = rounds_lanes_refusal(c, n_rounds, T, round0, seed, n_pairs, true)) return no(why);
     // (M systems, nlmc_apt_systems: a workgroup each; K, W, NP and the LDS carve-up are those of ONE system)
-    const int L = c->ladder_len, n = c->n, M = c->apt_systems, K = c->n_chains_global / L / M, P = 64 / L, W = (K + P - 1) / P, NP = L * (K / 2);
+    const int L = c->ladder_len, M = c->apt_systems, K = c->n_chains_global / L / M, P = 64 / L, W = (K + P - 1) / P, NP = L * (K / 2);
     if (W > 16) return no("the system needs more than 16 waves: it does not fit one workgroup");
     const AptLanesLds A = apt_lanes_lds(c, K, L, W);
     if (!A.ok) return no("the system's chains and labels exceed one workgroup's LDS (150 KB)");
     HIP_TRY(c, hipSetDevice(c->device));
 
-    const size_t bytes_per_round = (size_t)T * (size_t)n * sizeof(uint16_t);
-    const int R = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_rounds, c->knobs.lane_scratch / bytes_per_round, (size_t)(INT_MAX / 2) / (size_t)T}));
-    begin_sweep_call(c);
-    c->stat_orders = 0; c->stat_levels = 0; c->stats_pending = false;
-    c->stat_fused_window = -1;
-    c->stat_lane_orders = 0;
-    HIP_TRY(c, c->lane_perm.reserve((size_t)R * (size_t)T * (size_t)n));
-    { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
     const bool want_info = out_info && NP > 0;
     if (want_info) HIP_TRY(c, c->icm_info.reserve((size_t)n_rounds * M * NP * 2));
     const bool elog = c->elog_rec(round0, n_rounds).energy != nullptr;          // (a launch none of whose rounds is logged stores nothing anyway)
-    const void *kfun = elog ? (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_apt_rounds_lanes<true, true>)
-                                                     : reinterpret_cast<const void *>(k_apt_rounds_lanes<false, true>))
-                            : (precision == NLMC_F64 ? reinterpret_cast<const void *>(k_apt_rounds_lanes<true>)
-                                                     : reinterpret_cast<const void *>(k_apt_rounds_lanes<false>));
-    { int rc = ensure_lds(c, kfun, A.total); if (rc) return rc; }
+    const void *kfun = apt_lanes_kernel(precision == NLMC_F64, elog);
     const bool log = n_pairs > 0 && c->pt_log.covers(round0, n_rounds, n_pairs);
-    for (int at = 0; at < n_rounds; at += R) {
-        const int k = std::min(R, n_rounds - at);
-        const uint32_t s0 = sweep0 + (uint32_t)at * (uint32_t)T, r0 = round0 + (uint32_t)at;
-        TimerSpan ts;
-        if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->stream); if (rc) return rc; }
-        LaneOrderArgs oa{};
-        oa.n = n; oa.n_sweeps = k * T; oa.per_chain = 0; oa.chain_base = 0;
-        oa.seed_lo = (uint32_t)seed; oa.seed_hi = (uint32_t)(seed >> 32); oa.sweep0 = s0;
-        oa.perm = c->lane_perm.p;
-        hipLaunchKernelGGL(k_lane_orders, dim3((unsigned)(k * T)), dim3(256), 0, c->stream, oa);
-        HIP_TRY(c, hipGetLastError());
-        c->stat_lane_orders += (int64_t)k * T;
-        { int rc = span_mid(c, ts); if (rc) return rc; }
-
+    int rc = lane_rounds_chunks(c, kfun, A.total, n_rounds, T, sweep0, round0, seed, [&](int at, int k, uint32_t s0, uint32_t r0) -> int {
         SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
-        a.energy_sink = c->energy_sink;
-        a.lane_perm = c->lane_perm.p; a.lane_rows = c->n_chains; a.lane_diag = c->has_diag ? 1 : 0; a.lane_tab = A.tab ? 1 : 0;
-        a.lds_u_off = (int)A.u_off;
-        LaneRoundsArgs q{};
-        const size_t nl = (size_t)M * K;                       // plan and log rows hold every ladder of the context
-        q.n_rounds = k; q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = (int)nl; q.round0 = r0;
-        q.beta = c->pt_beta.p; q.slot_of_chain = c->slot_of_chain.p; q.chain_of_slot = c->chain_of_slot.p;
-        if (n_pairs > 0) q.plan_pairs = c->pt_plan_pairs.p + c->pt_plan.row(r0) * nl * n_pairs * 2;
-        if (log) {
-            const size_t lr = c->pt_log.row(r0);
-            q.log_pairs = c->pt_log_pairs.p + lr * nl * n_pairs * 2;
-            q.log_acc = c->pt_log_acc.p + lr * nl * n_pairs;
-        }
-        q.lds_map_off = (int)A.map_off;
-        if (elog) q.elog = c->elog_rec(r0, k);
+        lane_fields(c, a, c->n_chains, A.tab, A.u_off);
+        LaneRoundsArgs q = lane_rounds_args(c, k, r0, n_pairs, (size_t)M * K, log, A.map_off);   // (plan and log rows hold every ladder of the context)
         LaneAptArgs x{};
         x.n_sub = K; x.n_icm = NP; x.katz = katzgraber ? 1 : 0;
         x.info = want_info ? c->icm_info.p + (size_t)at * M * NP * 2 : nullptr;
@@ -3280,14 +3289,9 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
         x.lds_lab_off = (int)A.u_off; x.lab_stride = A.lab_stride;
         void *kargs[] = {&a, &q, &x};
         HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)M), dim3((unsigned)(64 * W)), kargs, A.total, c->stream));
-        HIP_TRY(c, hipGetLastError());
-        { int rc = span_end(c, ts); if (rc) return rc; }
-        if (c->ev_accumulate) c->launches_timed += k;
-        c->launches_sweep += k;
-        c->launches_total += k;
-    }
-    c->sub_dirty = true;
-    c->last_route = NLMC_ROUTE_LANES;
+        return NLMC_OK;
+    });
+    if (rc) return rc;
     c->rounds_route = NLMC_ROUNDS_APT_LANES;
     if (want_info) {
         const size_t cnt = (size_t)n_rounds * M * NP * 2;

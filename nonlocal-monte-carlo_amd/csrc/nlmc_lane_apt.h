@@ -217,7 +217,8 @@ __global__ __launch_bounds__(1024) void k_apt_rounds_lanes(SweepArgs a, LaneRoun
             if (live) elog_store(q.elog, r, (int)c0 + c, (double)E * inv, slot);
         }
 
-        // the swap round of k_rounds_lanes
+        // the swap round of k_rounds_lanes: lane_swap_round (nlmc_lane_rounds.h) written out, as the prologue above is lane_ladders_in.
+        // Calling the two here moves this kernel's register allocation and costs 1 .. 4 % a round.
         if (q.n_pairs > 0) {
             const size_t at = ((size_t)r * q.n_ladders + g) * q.n_pairs + (decides ? p : 0);
             const int i = decides ? q.plan_pairs[2 * at] : 0;

@@ -12,7 +12,8 @@
 //   swaps  : the planned selection of the round; lane p of a ladder's lane group decides pair p from the two energies the wave
 //            shuffles to it, with the key and arithmetic of k_pt_swap (pt_swap_decide).  Chains never move: two byte maps in LDS,
 //            lane_of_slot[ladder in wave][slot] and slot_of_lane[lane], exchange entries, and a lane whose slot moved reloads its
-//            inverse temperature (and its RNG key where that follows the slot).
+//            inverse temperature (and its RNG key where that follows the slot).  One body, lane_swap_round, here and in
+//            k_apt_rounds_lanes.
 // Same bits as nlmc_sweep_philox(beta = NULL) + nlmc_pt_swap_philox round by round, on any route.
 #pragma once
 #include "nlmc_lanes.h"
@@ -30,6 +31,61 @@ struct LaneRoundsArgs {
     BestRec best;                    // k_rounds_lanes<.., BEST>: the open best-state record (nlmc_best_begin), efix = nullptr: none
     ElogRec elog;                    // k_rounds_lanes<.., BEST>, k_apt_rounds_lanes<.., ELOG>: the open energy log (nlmc_elog_begin), energy = nullptr: none
 };
+
+// The wave's chains come in: their nrow rows (consecutive, `rows` the first) read coalesced and written transposed to the wave's LDS
+// region, the columns of the tail lanes zeroed (tail lanes walk the wave's first chain on a zeroed column and write nothing), and the
+// two slot maps set up from the lane's slot.  The workgroup's LDS accesses of one wave execute in program order (lane_lds_fence).
+__device__ __forceinline__ void lane_ladders_in(unsigned char *lds, const int8_t *rows, int n_pad, int nrow, int lane, bool live, int base,
+                                                int slot, uint8_t *lane_of_slot, uint8_t *slot_of_lane)
+{
+    for (int r = 0; r < 64; ++r) {
+        if (r < nrow) lane_column_in(lds, NLMC_LANE_STRIDE, r, rows + (size_t)r * n_pad, n_pad, lane);
+        else for (int j = lane; j < n_pad; j += 64) lds[j * NLMC_LANE_STRIDE + r] = 0;
+    }
+    lane_of_slot[lane] = (uint8_t)lane;
+    slot_of_lane[lane] = (uint8_t)slot;
+    lane_lds_fence();
+    if (live) lane_of_slot[base + slot] = (uint8_t)lane;                // (the slots of a ladder are a permutation: every entry below nrow)
+    lane_lds_fence();
+}
+
+// THE swap round of k_pt_swap inside a wave, for round r of the launch: planned selection, one lane per pair (lane p of a ladder's lane
+// group decides pair p), energies by shuffle, the key and arithmetic of pt_swap_decide.  g: the lane's global ladder, base: its first
+// entry of lane_of_slot, E: the lane's tracked energy; p = lane - base and decides = live && p < n_pairs are the caller's, computed
+// once per launch (inside this function they cost k_apt_rounds_lanes<f64> its register allocation: DESIGN.md section 6).  Chains never
+// move: the two maps exchange entries.  Returns whether the lane's slot moved (slot is then the new one): the caller reloads what it
+// keeps per slot.
+__device__ __forceinline__ bool lane_swap_round(const LaneRoundsArgs &q, int r, int g, int base, int lane, int p, bool decides, long long E, double inv,
+                                                uint32_t seed_lo, uint32_t seed_hi, uint8_t *lane_of_slot, uint8_t *slot_of_lane, int &slot)
+{
+    if (q.n_pairs <= 0) return false;
+    const uint32_t round = q.round0 + (uint32_t)r;
+    const size_t at = ((size_t)r * q.n_ladders + g) * q.n_pairs + (decides ? p : 0);
+    const int i = decides ? q.plan_pairs[2 * at] : 0;
+    const int la = decides ? (int)lane_of_slot[base + i] : lane, lb = decides ? (int)lane_of_slot[base + i + 1] : lane;
+    const int elo = (int)(unsigned)(unsigned long long)E, ehi = (int)(unsigned)((unsigned long long)E >> 32);
+    const unsigned alo = (unsigned)__shfl(elo, la, 64), ahi = (unsigned)__shfl(ehi, la, 64);
+    const unsigned blo = (unsigned)__shfl(elo, lb, 64), bhi = (unsigned)__shfl(ehi, lb, 64);
+    const double Ea = (double)(long long)(((unsigned long long)ahi << 32) | alo) * inv;
+    const double Eb = (double)(long long)(((unsigned long long)bhi << 32) | blo) * inv;
+    lane_lds_fence();
+    if (decides) {
+        const bool acc = pt_swap_decide(p, i, i, Ea, Eb, q.beta, round, g, seed_lo, seed_hi);
+        if (acc) {                                   // selected pairs are disjoint: no two lanes touch one entry
+            lane_of_slot[base + i] = (uint8_t)lb; lane_of_slot[base + i + 1] = (uint8_t)la;
+            slot_of_lane[la] = (uint8_t)(i + 1); slot_of_lane[lb] = (uint8_t)i;
+        }
+        if (q.log_pairs) {
+            q.log_pairs[2 * at] = i; q.log_pairs[2 * at + 1] = i + 1;
+            q.log_acc[at] = acc ? 1 : 0;
+        }
+    }
+    lane_lds_fence();
+    const int ns = (int)slot_of_lane[lane];
+    const bool moved = ns != slot;
+    slot = ns;
+    return moved;
+}
 
 // SweepArgs fields of this kernel: those of k_sweep_lanes' shared order without flags and outputs; n_sweeps = sweeps per round, sweep0 =
 // the first sweep of the launch, lane_perm = the orders of all its n_rounds * n_sweeps sweeps, lane_rows = the context's chains,
@@ -59,18 +115,9 @@ __global__ __launch_bounds__(64) void k_rounds_lanes(SweepArgs a, LaneRoundsArgs
     uint32_t *rtab = a.lane_tab ? reinterpret_cast<uint32_t *>(lds_raw + a.lds_u_off) : nullptr;   // word (spin k, lane l) at k * 64 + l
     uint8_t *lane_of_slot = lds_raw + q.lds_map_off, *slot_of_lane = lane_of_slot + 64;
 
-    // prologue: the rows of the wave's chains, read coalesced, written transposed
-    for (int r = 0; r < 64; ++r) {
-        if (r < nrow) lane_column_in(lds_raw, stride, r, a.spins + (size_t)(row0 + r) * n_pad, n_pad, lane);
-        else for (int j = lane; j < n_pad; j += 64) lds_raw[j * stride + r] = 0;
-    }
     const uint32_t gc_chain = (uint32_t)(a.chain_base + c);
     int slot = q.slot_of_chain[gc_chain];
-    lane_of_slot[lane] = (uint8_t)lane;
-    slot_of_lane[lane] = (uint8_t)slot;
-    lane_lds_fence();
-    if (live) lane_of_slot[base + slot] = (uint8_t)lane;                // (the slots of a ladder are a permutation: every entry below nrow)
-    lane_lds_fence();
+    lane_ladders_in(lds_raw, a.spins + (size_t)row0 * n_pad, n_pad, nrow, lane, live, base, slot, lane_of_slot, slot_of_lane);
 
     const bool key_by_slot = a.rng_stride != 0;
     uint32_t gc = key_by_slot ? (uint32_t)((c / a.rng_ladder_len) * a.rng_stride + a.rng_base + slot) : gc_chain;
@@ -78,8 +125,8 @@ __global__ __launch_bounds__(64) void k_rounds_lanes(SweepArgs a, LaneRoundsArgs
     const double esc = __longlong_as_double((long long)(1023 + a.escale) << 52);   // 2^escale
     const double inv = __longlong_as_double((long long)(1023 - a.escale) << 52);   // 2^-escale
     long long E = a.efix[c];
-    const bool decides = live && (lane - base) < q.n_pairs;            // lane p of a ladder's group decides pair p
     const int p = lane - base;
+    const bool decides = live && p < q.n_pairs;                        // lane p of a ladder's group decides pair p
     long long rec_e = 0x7FFFFFFFFFFFFFFFll;
     int32_t rec_stamp = -1, rec_hit = -1;
     const bool has_best = BEST && q.best.efix != nullptr;
@@ -154,36 +201,9 @@ __global__ __launch_bounds__(64) void k_rounds_lanes(SweepArgs a, LaneRoundsArgs
             }
         }
 
-        // the swap round of k_pt_swap inside the wave: planned selection, one lane per pair, energies by shuffle
-        if (q.n_pairs > 0) {
-            const uint32_t round = q.round0 + (uint32_t)r;
-            const size_t at = ((size_t)r * q.n_ladders + g) * q.n_pairs + (decides ? p : 0);
-            const int i = decides ? q.plan_pairs[2 * at] : 0;
-            const int la = decides ? (int)lane_of_slot[base + i] : lane, lb = decides ? (int)lane_of_slot[base + i + 1] : lane;
-            const int elo = (int)(unsigned)(unsigned long long)E, ehi = (int)(unsigned)((unsigned long long)E >> 32);
-            const unsigned alo = (unsigned)__shfl(elo, la, 64), ahi = (unsigned)__shfl(ehi, la, 64);
-            const unsigned blo = (unsigned)__shfl(elo, lb, 64), bhi = (unsigned)__shfl(ehi, lb, 64);
-            const double Ea = (double)(long long)(((unsigned long long)ahi << 32) | alo) * inv;
-            const double Eb = (double)(long long)(((unsigned long long)bhi << 32) | blo) * inv;
-            lane_lds_fence();
-            if (decides) {
-                const bool acc = pt_swap_decide(p, i, i, Ea, Eb, q.beta, round, g, a.seed_lo, a.seed_hi);
-                if (acc) {                                   // selected pairs are disjoint: no two lanes touch one entry
-                    lane_of_slot[base + i] = (uint8_t)lb; lane_of_slot[base + i + 1] = (uint8_t)la;
-                    slot_of_lane[la] = (uint8_t)(i + 1); slot_of_lane[lb] = (uint8_t)i;
-                }
-                if (q.log_pairs) {
-                    q.log_pairs[2 * at] = i; q.log_pairs[2 * at + 1] = i + 1;
-                    q.log_acc[at] = acc ? 1 : 0;
-                }
-            }
-            lane_lds_fence();
-            const int ns = (int)slot_of_lane[lane];
-            if (ns != slot) {
-                slot = ns;
-                cb0 = scale_cb((T)a.tab[(size_t)slot * a.tab_cs], a.qinv);
-                if (key_by_slot) gc = (uint32_t)((c / a.rng_ladder_len) * a.rng_stride + a.rng_base + slot);
-            }
+        if (lane_swap_round(q, r, g, base, lane, p, decides, E, inv, a.seed_lo, a.seed_hi, lane_of_slot, slot_of_lane, slot)) {
+            cb0 = scale_cb((T)a.tab[(size_t)slot * a.tab_cs], a.qinv);
+            if (key_by_slot) gc = (uint32_t)((c / a.rng_ladder_len) * a.rng_stride + a.rng_base + slot);
         }
     }
     lane_lds_fence();

@@ -111,9 +111,13 @@ def five():
     return make_instance(37, seed=9, with_h=True, gaussian=True)
 
 
-@pytest.mark.parametrize("precision", ["f32", "f64"])
-def test_twelve_ladders_a_wave_with_idle_lanes_and_a_short_last_wave(product, five, precision):
-    """L = 5: 12 ladders per wave leave 4 idle lanes; 27 ladders make the last wave hold 3."""
+@pytest.mark.parametrize("precision,rng", [("f32", None), ("f64", None), ("f32", "0"), ("f32", "1"), ("f64", "0"), ("f64", "1")],
+                         ids=["f32", "f64", "f32-rng0", "f32-rng1", "f64-rng0", "f64-rng1"])
+def test_twelve_ladders_a_wave_with_idle_lanes_and_a_short_last_wave(product, five, precision, rng, monkeypatch):
+    """L = 5: 12 ladders per wave leave 4 idle lanes; 27 ladders make the last wave hold 3.  rng: NLMC_LANE_RNG (read when the engine is
+    created) -- the Philox call per update, or the table per sweep; None leaves the default."""
+    if rng is not None:
+        monkeypatch.setenv("NLMC_LANE_RNG", rng)
     three_runs(product, *five, 5, 27, 3, 6, precision, oracle_ladders=(0, 11, 12, 26))
 
 

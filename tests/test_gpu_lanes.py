@@ -92,8 +92,12 @@ def assert_oracle(J, h, m0, res, chains, beta_of, S, esc, f64, order, sweep0=0, 
 
 @pytest.mark.parametrize("order", ["shared", "per_chain"])
 @pytest.mark.parametrize("precision", ["f32", "f64"])
-@pytest.mark.parametrize("rows", [1, 63, 65, 130])
-def test_lane_tail_and_blocks(product, rows, precision, order):
+@pytest.mark.parametrize("rows,rng", [(1, None), (63, None), (65, None), (130, None), (65, "0"), (65, "1")],
+                         ids=["1", "63", "65", "130", "65-rng0", "65-rng1"])
+def test_lane_tail_and_blocks(product, rows, rng, precision, order, monkeypatch):
+    """rng: NLMC_LANE_RNG (read when the engine is created) -- the Philox call per update, or the table per sweep; None: the default."""
+    if rng is not None:
+        monkeypatch.setenv("NLMC_LANE_RNG", rng)
     J, h = make_instance(37, seed=9, with_h=True, gaussian=True)
     S, N, f64 = 5, 37, precision == "f64"
     m0 = init_spins(rows, N)
