@@ -123,9 +123,10 @@ int nlmc_sweep_stream(nlmc_ctx *ctx, int n_sweeps, const int32_t *perm, const do
  * draws one word of philox(k>>2, t, c, UNIFORM) (f32: 32 bits -> logistic threshold; f64: its high 27 bits + the high 26 bits of the same word of philox(k>>2, t, c, UNIFORM_LO) -> 53-bit uniform); results are a pure function of (seed, global chain id, sweep index, spin) and
  * therefore independent of how chains are sharded over GPUs.
  *   beta : as above, or NULL to take each chain's beta from the PT ladder (nlmc_pt_init).
- * Three routes compute a call, with the same bits: sweep by sweep (a level schedule per order, one workgroup per chain), fused
- * windows (nlmc_plan_philox_fused; n >= 256) and, for chains of at most NLMC_LANE_N spins, one chain per lane
- * (nlmc_set_lane_sweeps).  nlmc_last_sweep_route tells which one the most recent call took. */
+ * Four routes compute a call, with the same bits: sweep by sweep (a level schedule per order, one workgroup per chain), fused
+ * windows (nlmc_plan_philox_fused; n >= 256), for chains of at most NLMC_LANE_N spins one chain per lane (nlmc_set_lane_sweeps)
+ * and, for chains of at most NLMC_WAVE_N spins in NLMC_F32, one chain per wave (nlmc_set_wave_sweeps).  nlmc_last_sweep_route
+ * tells which one the most recent call took. */
 int nlmc_sweep_philox(nlmc_ctx *ctx, int precision, int order_mode, int n_sweeps, uint32_t sweep0, uint64_t seed,
                       const double *beta, int chain_stride, int sweep_stride, int record_stride, int8_t *out_spins,
                       double *out_energy, double *out_min_energy, int32_t *out_argmin, int8_t *out_argmin_state);
@@ -147,8 +148,32 @@ int nlmc_sweep_philox(nlmc_ctx *ctx, int precision, int order_mode, int n_sweeps
 int nlmc_set_lane_sweeps(nlmc_ctx *ctx, int mode);
 /* Route of the most recent nlmc_sweep_philox call: NLMC_ROUTE_NONE before any, a call whose launches mixed routes reports
  * NLMC_ROUTE_STEPWISE. */
-enum { NLMC_ROUTE_NONE = 0, NLMC_ROUTE_STEPWISE = 1, NLMC_ROUTE_FUSED = 2, NLMC_ROUTE_LANES = 3 };
+enum { NLMC_ROUTE_NONE = 0, NLMC_ROUTE_STEPWISE = 1, NLMC_ROUTE_FUSED = 2, NLMC_ROUTE_LANES = 3, NLMC_ROUTE_WAVES = 4 };
 int nlmc_last_sweep_route(const nlmc_ctx *ctx);
+
+/* Wave-per-chain sweeps (csrc/nlmc_waves.h): a wave owns ONE chain and keeps its local fields resident.  In NLMC_F32 the field of a
+ * spin is an exact int32 whatever the order of the sum, so lane l holds the fields and spins l, l + 64, .. in registers, the decision
+ * for the visited spin is a v_readlane and one compare, and a flip corrects every field by one multiply-add on a row of a dense
+ * fixed-point matrix (built once per context on the first such call, freed with it; staged in LDS up to n = 192) -- no level
+ * schedule, no barrier, no atomic, and the per-chain visiting order costs what the shared one costs.  Made for tens to a few
+ * thousand chains of a short instance (complete graphs of 8..40 spins, Chimera-128), where a workgroup per chain runs one lane per
+ * barrier round and a lane per chain walks three dependent loads per update.  mode: 0 off (the default); 1 auto --
+ * nlmc_sweep_philox calls in NLMC_F32 with n <= NLMC_WAVE_N over at most NLMC_WAVE_AUTO_MAX_ROWS rows (chains of the call) take it;
+ * 2 force -- every nlmc_sweep_philox call in NLMC_F32 with n <= NLMC_WAVE_N takes it.  A call it does not take (NLMC_F64, stream
+ * mode, a longer chain) goes on to the lane rule and the other routes as before: never an error.  The route is asked before the
+ * lane one.  Everything such a call accepts runs there: both order modes, phase flags, a temperature per sweep, ladder
+ * temperatures, chain subsets (shared order), the running minimum, every output.  Results are bit-identical to the other routes.
+ * nlmc_last_sweep_route is NLMC_ROUTE_WAVES and nlmc_last_sweep_fused is 0 after such a call, nlmc_last_schedule_stats reports the
+ * visiting orders built and 0 levels, the timings count the order kernel as the levelize half.  The rounds entry points
+ * (nlmc_pt_rounds_deferred / _lanes / _fused, nlmc_apt_rounds_lanes) do not look at this mode: rounds driven call by call get the
+ * route through their sweep calls.  Environment, read at nlmc_create: NLMC_WAVE_WAVES fixes the waves (chains) per workgroup
+ * (1..16; no result depends on it), NLMC_WAVE_JLDS=0 reads the matrix rows from global memory at every n. */
+#define NLMC_WAVE_N 256
+/* Rows up to which `auto` takes the wave route.  A measured constant: the largest measured row count such
+ * that at every measured row count up to it the route is at least 1.2 times the route the call takes with every mode off, on every
+ * instance of the measured grid; 0 (never) if that holds nowhere, 2147483647 if it holds at every measured row count. */
+#define NLMC_WAVE_AUTO_MAX_ROWS 0
+int nlmc_set_wave_sweeps(nlmc_ctx *ctx, int mode);
 
 /* Optional: build and cache the level schedules of sweeps [sweep0, sweep0+n_sweeps) ahead of time (shared-order
  * philox mode).  Later nlmc_sweep_philox calls inside that range with the same seed and precision skip their

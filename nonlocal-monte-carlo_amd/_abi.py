@@ -24,7 +24,10 @@ CHAINS_ALL, CHAINS_UNMARKED, CHAINS_MARKED = 0, 1, 2
 LANE_N = 1024                        # include/nlmc.h: NLMC_LANE_N, longest chain of the chain-per-lane sweeps
 LANE_AUTO_ROWS = 2147483647          # include/nlmc.h: NLMC_LANE_AUTO_ROWS, rows from which "auto" takes them (2^31 - 1: never)
 LANES_OFF, LANES_AUTO, LANES_FORCE = 0, 1, 2
-ROUTE_NONE, ROUTE_STEPWISE, ROUTE_FUSED, ROUTE_LANES = 0, 1, 2, 3
+WAVE_N = 256                         # include/nlmc.h: NLMC_WAVE_N, longest chain of the wave-per-chain sweeps
+WAVE_AUTO_MAX_ROWS = 0               # include/nlmc.h: NLMC_WAVE_AUTO_MAX_ROWS, rows up to which "auto" takes them (0: never)
+WAVES_OFF, WAVES_AUTO, WAVES_FORCE = 0, 1, 2
+ROUTE_NONE, ROUTE_STEPWISE, ROUTE_FUSED, ROUTE_LANES, ROUTE_WAVES = 0, 1, 2, 3, 4
 ROUNDS_IN_LAUNCH, ROUNDS_LAUNCH_PER_ROUND, ROUNDS_LANES, ROUNDS_APT_LANES = 1, 2, 3, 4     # include/nlmc.h: nlmc_pt_rounds_route
 PHASE_ALL, PHASE_BACKBONE_HOT, PHASE_BACKBONE_FROZEN = 0, 1, 2
 
@@ -37,7 +40,7 @@ EXPORTS = [
     "nlmc_last_timing", "nlmc_timing_reset", "nlmc_timing_total", "nlmc_last_schedule_stats",
     "nlmc_pt_mark_slots", "nlmc_select_chains", "nlmc_subset_count", "nlmc_get_subset", "nlmc_track_minimum", "nlmc_backbone_seed", "nlmc_adopt_best",
     "nlmc_backbone_clusters", "nlmc_backbone_check", "nlmc_get_cluster_mask", "nlmc_set_phase", "nlmc_plan_slot", "nlmc_overlap_subsets", "nlmc_own_stream", "nlmc_plan_get_levels", "nlmc_probe_level_round", "nlmc_comm_unique_id", "nlmc_comm_init", "nlmc_comm_probe", "nlmc_comm_check", "nlmc_apt_shard", "nlmc_apt_pack", "nlmc_apt_swap_host", "nlmc_apt_swap_collective", "nlmc_apt_selftest_exchange", "nlmc_pt_swap_philox_collective", "nlmc_set_cluster_mask", "nlmc_host_prefault",
-    "nlmc_set_fused_f64_real", "nlmc_last_sweep_fused", "nlmc_set_lane_sweeps", "nlmc_last_sweep_route", "nlmc_pt_rounds_lanes",
+    "nlmc_set_fused_f64_real", "nlmc_last_sweep_fused", "nlmc_set_lane_sweeps", "nlmc_set_wave_sweeps", "nlmc_last_sweep_route", "nlmc_pt_rounds_lanes",
     "nlmc_apt_rounds_lanes", "nlmc_apt_systems",
     "nlmc_best_begin", "nlmc_best_update", "nlmc_best_read", "nlmc_best_end",
     "nlmc_elog_begin", "nlmc_elog_update", "nlmc_elog_read", "nlmc_elog_end",
@@ -163,7 +166,7 @@ def lib():
                        ("nlmc_get_subset", [_vp, _vp]), ("nlmc_track_minimum", [_vp, _i]), ("nlmc_backbone_seed", [_vp, _i]), ("nlmc_adopt_best", [_vp]),
                        ("nlmc_backbone_clusters", [_vp, _vp, _vp, _i, _dbl, _dbl, _i, _dbl, _vp, _i]),
                        ("nlmc_backbone_check", [_vp]), ("nlmc_get_cluster_mask", [_vp, _vp]), ("nlmc_set_cluster_mask", [_vp, _vp]), ("nlmc_set_phase", [_vp, _i, _dbl]),
-                       ("nlmc_plan_slot", [_vp, _i]), ("nlmc_set_fused_f64_real", [_vp, _i]), ("nlmc_last_sweep_fused", [_vp]), ("nlmc_set_lane_sweeps", [_vp, _i]), ("nlmc_last_sweep_route", [_vp]), ("nlmc_pt_rounds_route", [_vp]), ("nlmc_overlap_subsets", [_vp, _i]), ("nlmc_own_stream", [_vp]),
+                       ("nlmc_plan_slot", [_vp, _i]), ("nlmc_set_fused_f64_real", [_vp, _i]), ("nlmc_last_sweep_fused", [_vp]), ("nlmc_set_lane_sweeps", [_vp, _i]), ("nlmc_set_wave_sweeps", [_vp, _i]), ("nlmc_last_sweep_route", [_vp]), ("nlmc_pt_rounds_route", [_vp]), ("nlmc_overlap_subsets", [_vp, _i]), ("nlmc_own_stream", [_vp]),
                        ("nlmc_plan_get_levels", [_vp, _i, _vp, _i, _vp]), ("nlmc_comm_unique_id", [_vp]), ("nlmc_comm_init", [_vp, _vp, _i, _i]),
                        ("nlmc_pt_swap_philox_collective", [_vp, _u32, _u64, _i, _i, _vp, _vp]), ("nlmc_comm_probe", []), ("nlmc_comm_check", [_vp, _i]),
                        ("nlmc_pt_rounds_fused", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),

@@ -27,14 +27,19 @@ class APT_ICM(SweepMixin):
     num_subreplicas = 10      # NPT/apt_ICM.py:177
     useKatzgraber = True      # NPT/apt_ICM.py:178
 
-    def __init__(self, J, h, rng=None, seed=None, device=0, lanes="off"):
+    def __init__(self, J, h, rng=None, seed=None, device=0, lanes="off", waves="off"):
         """`lanes` (additive keyword, rng="philox" only; run(..., icm_feedback=True) without device_ids, the device-resident route):
         "off" (default), "auto" or "force" -- Engine.set_lane_sweeps of the run's engine ("auto" never fires today: its row threshold
         NLMC_LANE_AUTO_ROWS is 2^31 - 1).  Short chains (n <= 1024, at most 64 temperatures) then sweep one per lane; where
         engine.APT_LANES_IN_LAUNCH says so (today it does not: measured behind), all rounds but the last run inside
-        k_apt_rounds_lanes (Engine.apt_rounds_lanes).  Same bits as "off"."""
+        k_apt_rounds_lanes (Engine.apt_rounds_lanes).  Same bits as "off".
+        `waves` (additive keyword, under the same conditions): "off" (default), "auto" or "force" -- Engine.set_wave_sweeps of the
+        run's engine: chains of at most 256 spins sweep one per wave with resident local fields, a call per step (the rounds inside
+        k_apt_rounds_lanes do not look at it).  Same bits as "off"."""
         if lanes not in ("off", "auto", "force"):
             raise ValueError("lanes must be 'off', 'auto' or 'force'")
+        if waves not in ("off", "auto", "force"):
+            raise ValueError("waves must be 'off', 'auto' or 'force'")
         self.J = J
         if isinstance(h, list):
             h = np.array(h)
@@ -44,7 +49,10 @@ class APT_ICM(SweepMixin):
         self._init_backend(rng, seed, device)
         if lanes != "off" and self.rng != "philox":
             raise ValueError("lanes applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
+        if waves != "off" and self.rng != "philox":
+            raise ValueError("waves applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
         self.lanes = lanes
+        self.waves = waves
 
     def _hflat(self):
         return np.asarray(self.h, dtype=np.float64).reshape(-1)
@@ -148,6 +156,8 @@ class APT_ICM(SweepMixin):
             raise ValueError("device_ids needs rng='philox' and icm_feedback=True (the device-resident path)")
         if self.lanes != "off" and (not icm_feedback or device_ids is not None):
             raise ValueError("lanes needs icm_feedback=True and no device_ids (the device-resident path of one context)")
+        if self.waves != "off" and (not icm_feedback or device_ids is not None):
+            raise ValueError("waves needs icm_feedback=True and no device_ids (the device-resident path of one context)")
         if self.rng == "philox" and icm_feedback and device_ids is not None:
             return self._run_slot_sharded(inst, beta_list, plot, return_trace, list(device_ids))
         if self.rng == "philox" and icm_feedback:
@@ -261,6 +271,8 @@ class APT_ICM(SweepMixin):
         try:
             if self.lanes != "off":
                 eng.set_lane_sweeps(self.lanes)
+            if self.waves != "off":
+                eng.set_wave_sweeps(self.waves)
             eng.set_spins((2 * host_rng.integers(0, 2, size=(G, N), dtype=np.int8) - 1).astype(np.int8))
             eng.pt_init(beta_list)
             if num_restarts > 1:

@@ -10,6 +10,8 @@
 #include "nlmc_lanes.h"
 #include "nlmc_lane_rounds.h"
 #include "nlmc_lane_apt.h"
+#include "nlmc_waves.h"
+#include "nlmc_wave_shape.h"
 #include "nlmc_host.h"
 
 #include <dlfcn.h>
@@ -86,6 +88,8 @@ struct Knobs {
     size_t lane_scratch = (size_t)256 << 20;   // NLMC_LANE_SCRATCH: bytes of visiting orders one window of chain-per-lane sweeps may hold (test knob)
     int lane_rng = -1;               // NLMC_LANE_RNG: chain-per-lane sweeps make the Philox call per update (0) / keep a table per sweep in LDS
                                      // where it fits (1); -1: the default
+    int wave_waves = 0;              // NLMC_WAVE_WAVES: waves (chains) per workgroup of the wave-per-chain sweeps (1..16; 0: by row count)
+    bool wave_jlds = true;           // NLMC_WAVE_JLDS=0: the wave-per-chain sweeps read the matrix rows from global memory at every n
     int dbg_flags = 0;               // NLMC_DBG_FLAGS: timing experiments of NLMC_DEBUG_KNOBS builds
     std::string stamp_file;          // NLMC_STAMP_FILE: NLMC_STAMPS builds dump the last launch's per-wave cycle sums here
 };
@@ -109,6 +113,8 @@ Knobs read_knobs()
     k.lbp_group = num("NLMC_LBP_GROUP", 0); k.lbp_poll_budget = num("NLMC_LBP_POLL_BUDGET", 0); k.lbp_global = on("NLMC_LBP_GLOBAL");
     if (const char *s = getenv("NLMC_LANE_SCRATCH")) k.lane_scratch = std::max<size_t>(1, (size_t)strtoull(s, nullptr, 0));
     k.lane_rng = on("NLMC_LANE_RNG") ? (num("NLMC_LANE_RNG", 0) != 0) : -1;
+    k.wave_waves = std::min(16, std::max(0, num("NLMC_WAVE_WAVES", 0)));
+    k.wave_jlds = num("NLMC_WAVE_JLDS", 1) != 0;
     k.dbg_flags = num("NLMC_DBG_FLAGS", 0);
     if (const char *s = getenv("NLMC_STAMP_FILE")) k.stamp_file = s;
     return k;
@@ -214,6 +220,10 @@ struct nlmc_ctx {
     int last_route = 0;           // nlmc_last_sweep_route: NLMC_ROUTE_* of the most recent sweep call
     int64_t stat_lane_orders = 0; // visiting orders the most recent sweep call built for the lane kernels
     DevBuf<uint16_t> lane_perm;   // [orders of a window][n]
+    // wave-per-chain sweeps (csrc/nlmc_waves.h)
+    int wave_mode = 0;            // nlmc_set_wave_sweeps: 0 off, 1 auto, 2 force
+    DevBuf<int32_t> wave_J;       // [n][64 R] dense fixed-point matrix, built on the first wave call (k_wave_matrix)
+    bool wave_J_built = false;
     DevBuf<int32_t> nmc_status;   // sticky: a backbone inference diverged at its first lambda
     DevBuf<double> nmc_thr;       // thresholds of the cluster growth
     std::vector<double> nmc_thr_host, tab_host, lbp_eps_host, lbp_lams_host;   // contents of the device copies (uploads skipped when unchanged)
@@ -1250,6 +1260,90 @@ int run_sweeps_lanes(nlmc_ctx *c, int precision, int order_mode, int n_sweeps, u
     return NLMC_OK;
 }
 
+// Whether a philox call over R rows takes the wave-per-chain kernels (nlmc_set_wave_sweeps): fixed point only, chains of at most
+// NLMC_WAVE_N spins; forced, every such call; auto, up to NLMC_WAVE_AUTO_MAX_ROWS rows (include/nlmc.h: where the route was measured
+// ahead).  A call it does not take goes on to the lane rule and the rest: never an error.
+bool waves_route(const nlmc_ctx *c, int R, int precision)
+{
+    if (c->wave_mode == 0 || precision != NLMC_F32 || c->knobs.force_big || c->n > NLMC_WAVE_N) return false;
+    return c->wave_mode == 2 || (long long)R <= (long long)NLMC_WAVE_AUTO_MAX_ROWS;
+}
+
+const void *waves_kernel(int R, bool jlds)
+{
+    static const void *const table[3][2] = {
+        {reinterpret_cast<const void *>(k_sweep_waves<1, false>), reinterpret_cast<const void *>(k_sweep_waves<1, true>)},
+        {reinterpret_cast<const void *>(k_sweep_waves<2, false>), reinterpret_cast<const void *>(k_sweep_waves<2, true>)},
+        {reinterpret_cast<const void *>(k_sweep_waves<4, false>), reinterpret_cast<const void *>(k_sweep_waves<4, true>)}};
+    return table[R == 1 ? 0 : R == 2 ? 1 : 2][jlds ? 1 : 0];
+}
+
+// The dense matrix of the wave kernels, once per context (the couplings of a context never change).  Built on the stream of the
+// first wave call and waited for, so that a later call on the other stream finds it complete.
+int ensure_wave_matrix(nlmc_ctx *c, size_t stride)
+{
+    if (c->wave_J_built) return NLMC_OK;
+    const size_t count = (size_t)c->n * stride;
+    HIP_TRY(c, c->wave_J.reserve(count));
+    HIP_TRY(c, hipMemsetAsync(c->wave_J.p, 0, count * sizeof(int32_t), c->cur));
+    WaveMatrixArgs m{};
+    m.n = c->n; m.stride = (int)stride; m.rowptr = c->g.rowptr; m.edge32 = c->g.edge32; m.Jd = c->wave_J.p;
+    hipLaunchKernelGGL(k_wave_matrix, dim3((unsigned)c->n), dim3(64), 0, c->cur, m);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->cur));
+    c->wave_J_built = true;
+    return NLMC_OK;
+}
+
+// The wave-per-chain half of run_sweeps, modelled on run_sweeps_lanes: the same windows against the order scratch, k_lane_orders for
+// the orders (the "levelize" half of the timings), one k_sweep_waves launch per window.
+int run_sweeps_waves(nlmc_ctx *c, int order_mode, int n_sweeps, uint32_t sweep0, uint64_t seed, const double *tab_dev, int tab_cs, int tab_ss,
+                     bool use_slots, bool want_energy, bool want_min, bool want_state, int rec)
+{
+    const int R = c->sub_count(), n = c->n;
+    if (c->cur != c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the order scratch is shared with the main stream's sweeps)
+    const int per_chain = order_mode == NLMC_ORDER_PER_CHAIN ? 1 : 0;
+    if (per_chain && c->subset != 0) return fail(c, NLMC_ERR_UNSUPPORTED, "chain subsets run shared-order philox sweeps only");
+    const size_t per_sweep_orders = per_chain ? (size_t)R : 1;
+    const size_t bytes_per_sweep = per_sweep_orders * (size_t)n * sizeof(uint16_t);
+    const int W = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_sweeps, c->knobs.lane_scratch / bytes_per_sweep));
+    if (per_sweep_orders * (size_t)W > (size_t)INT_MAX) return fail(c, NLMC_ERR_UNSUPPORTED, "too many per-chain orders in one window");
+    HIP_TRY(c, c->lane_perm.reserve(per_sweep_orders * (size_t)W * (size_t)n));
+    if (c->n_cu == 0) HIP_TRY(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+    const NlmcWaveShape S = nlmc_wave_shape(n, c->n_pad, R, c->n_cu, c->knobs.wave_waves, c->knobs.wave_jlds ? 1 : 0);
+    if (S.R == 0) return fail(c, NLMC_ERR_STATE, "run_sweeps_waves: the chain does not fit the wave kernels");
+    const void *kfun = waves_kernel(S.R, S.jlds != 0);
+    { int rc = ensure_lds(c, kfun, S.lds); if (rc) return rc; }
+    { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
+    for (int t0 = 0; t0 < n_sweeps; t0 += W) {
+        const int w = std::min(W, n_sweeps - t0);
+        TimerSpan ts;
+        if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->cur); if (rc) return rc; }
+        { int rc = launch_lane_orders(c, c->cur, per_sweep_orders * (size_t)w, w, per_chain, sweep0 + (uint32_t)t0, seed); if (rc) return rc; }
+        { int rc = span_mid(c, ts); if (rc) return rc; }
+
+        SweepArgs a = sweep_args(c, sweep0 + (uint32_t)t0, w, seed, tab_dev + (size_t)t0 * tab_ss, tab_cs, tab_ss, use_slots);
+        lane_fields(c, a, R, false, 0);
+        a.wave_J = c->wave_J.p;
+        a.per_chain = per_chain;
+        a.etrace = want_energy ? c->etrace.p : nullptr;
+        a.trace_sweeps = n_sweeps;
+        a.t0 = t0;
+        a.rec_stride = rec ? rec : 1;
+        a.strace = rec ? c->strace.p : nullptr;
+        a.emin = want_min ? c->emin.p : nullptr;
+        a.best = (want_min && want_state) ? c->best.p : nullptr;
+        void *kargs[] = {&a};
+        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)S.blocks), dim3((unsigned)(64 * S.W)), kargs, S.lds, c->cur));
+        HIP_TRY(c, hipGetLastError());
+        { int rc = span_end(c, ts); if (rc) return rc; }
+        if (c->ev_accumulate) c->launches_timed++;
+        c->launches_sweep++;
+        c->launches_total++;
+    }
+    return NLMC_OK;
+}
+
 // Shared driver: windows of sweeps -> (levelize) -> k_sweep.  `stream_mode` selects the kernel flavour.
 int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int n_sweeps, uint32_t sweep0,
                uint64_t seed, const double *tab_dev, int tab_cs, int tab_ss, bool use_slots, const uint32_t *keys_dev,
@@ -1282,9 +1376,10 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
     const int fslot = fused_plan_for(c, sweep0, n_sweeps, seed);
     int arith = fslot < 0 ? NOT_FUSED : fused_route(c, precision, order_mode, tab_ss != 0, c->has_flags, fslot, c->fz[fslot].T, Via::sweeps);
     if (outs && c->knobs.no_fused_out) arith = NOT_FUSED;
-    const bool lanes = !stream_mode && lanes_route(c, R);        // short chains, one per lane (csrc/nlmc_lanes.h): before the fused windows
-    if (lanes) arith = NOT_FUSED;
-    c->last_route = lanes ? NLMC_ROUTE_LANES : arith != NOT_FUSED ? NLMC_ROUTE_FUSED : NLMC_ROUTE_STEPWISE;
+    const bool waves = !stream_mode && waves_route(c, R, precision);   // short chains, one per wave (csrc/nlmc_waves.h): asked first
+    const bool lanes = !waves && !stream_mode && lanes_route(c, R);    // short chains, one per lane (csrc/nlmc_lanes.h): before the fused windows
+    if (lanes || waves) arith = NOT_FUSED;
+    c->last_route = waves ? NLMC_ROUTE_WAVES : lanes ? NLMC_ROUTE_LANES : arith != NOT_FUSED ? NLMC_ROUTE_FUSED : NLMC_ROUTE_STEPWISE;
     if (o.out_energy) HIP_TRY(c, c->etrace.reserve((size_t)R * n_sweeps));
     if (rec) HIP_TRY(c, c->strace.reserve((size_t)R * n_rec * n));
     c->strace_nrec = n_rec;
@@ -1301,6 +1396,10 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
                                use_slots, outs, o.out_energy != nullptr, want_min, want_state, rec, outs ? j * P.T : 0, n_sweeps, arith);
             if (rc) return rc;
         }
+    } else if (waves) {
+        int rc = run_sweeps_waves(c, order_mode, n_sweeps, sweep0, seed, tab_dev, tab_cs, tab_ss, use_slots, o.out_energy != nullptr, want_min,
+                                  want_state, rec);
+        if (rc) return rc;
     } else if (lanes) {
         int rc = run_sweeps_lanes(c, precision, order_mode, n_sweeps, sweep0, seed, tab_dev, tab_cs, tab_ss, use_slots, o.out_energy != nullptr,
                                   want_min, want_state, rec);
@@ -1643,7 +1742,7 @@ void nlmc_destroy(nlmc_ctx *c)
     c->spins.release(); c->best.release(); c->flags.release(); c->efix.release(); c->emin.release(); c->etrace.release();
     c->argmin.release(); c->energy.release(); c->tab.release(); c->ustream.release(); c->etrace_d.release();
     c->keys.release(); c->perm_raw.release(); c->u_raw.release(); c->stream_bad.release(); c->strace.release(); c->cfg.release(); c->snap_g.release(); c->scratch.release(); c->plan.release();
-    c->slot_mark.release(); c->sub_list_buf.release(); c->cmask.release(); c->cmask_scratch.release(); c->big_flag.release(); c->big_esum.release(); c->lane_perm.release(); c->nmc_status.release(); c->nmc_thr.release();
+    c->slot_mark.release(); c->sub_list_buf.release(); c->cmask.release(); c->cmask_scratch.release(); c->big_flag.release(); c->big_esum.release(); c->lane_perm.release(); c->wave_J.release(); c->nmc_status.release(); c->nmc_thr.release();
     c->fz_glv.release(); c->fz_perm.release(); c->fz_adj.release(); c->fz_stats.release(); c->fz[0].release(); c->fz[1].release();
     c->lbp_src.release(); c->lbp_rev.release(); c->lbp_flag.release(); c->lbp_out_i.release(); c->lbp_tJ.release();
     c->lbp_eps.release(); c->lbp_ms.release(); c->lbp_lams.release(); c->lbp_w0.release(); c->lbp_w1.release();
@@ -2034,6 +2133,14 @@ int nlmc_set_lane_sweeps(nlmc_ctx *c, int mode)
     return NLMC_OK;
 }
 
+int nlmc_set_wave_sweeps(nlmc_ctx *c, int mode)
+{
+    if (!c) return NLMC_ERR_ARG;
+    if (mode < 0 || mode > 2) return fail(c, NLMC_ERR_ARG, "nlmc_set_wave_sweeps: mode must be 0 (off), 1 (auto) or 2 (force)");
+    c->wave_mode = mode;
+    return NLMC_OK;
+}
+
 int nlmc_last_sweep_route(const nlmc_ctx *c) { return c ? c->last_route : NLMC_ROUTE_NONE; }
 
 int nlmc_probe_level_round(nlmc_ctx *c, int waves, int conflict_free, int rounds, int n_workgroups, double *out_ns_per_round)
@@ -2129,7 +2236,7 @@ int nlmc_last_schedule_stats(nlmc_ctx *c, int64_t *n_orders, int64_t *n_levels)
 {
     if (!c) return NLMC_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->last_route == NLMC_ROUTE_LANES && c->stat_fused_window < 0) {   // chain-per-lane sweeps: visiting orders, no levels
+    if ((c->last_route == NLMC_ROUTE_LANES || c->last_route == NLMC_ROUTE_WAVES) && c->stat_fused_window < 0) {   // chain-per-lane / wave-per-chain sweeps: visiting orders, no levels
         if (n_orders) *n_orders = c->stat_lane_orders;
         if (n_levels) *n_levels = 0;
         return NLMC_OK;

@@ -845,6 +845,7 @@ struct SweepArgs {
     int lane_rows;                // rows (chains) of the call: lane l of block b owns row 64 b + l
     int lane_diag;                // the instance has diagonal entries (left out of the energy deltas)
     int lane_tab;                 // 1: a sweep's random numbers sit in an LDS table at lds_u_off, 0: the Philox call is made per update
+    const int32_t *wave_J;        // wave-per-chain sweeps (k_sweep_waves, csrc/nlmc_waves.h): the dense fixed-point matrix [n][64 R]
     int dbg_flags;            // -DNLMC_DEBUG_KNOBS builds only (NLMC_DBG_FLAGS): 1 = no threshold production, 2 = no updates, 4 = no item loads,
                               // 512 / 1024 = bank-conflict-free addresses for the neighbour gather / the spin's own accesses (wrong results)
 };

@@ -237,11 +237,14 @@ class LocalTempering:
     ShardedTempering."""
 
     def __init__(self, inst, beta_list, n_chains_global, seed, n_pairs, device_ids, precision="f32", engine_factory=None,
-                 engines=None, parts=None, lane_sweeps="off", track_best=False, target_energy=None, track_energies=False):
+                 engines=None, parts=None, lane_sweeps="off", track_best=False, target_energy=None, track_energies=False,
+                 wave_sweeps="off"):
         """`parts` (optional): the blocks [(chain_base, count)] this process drives instead of an even cut over device_ids -- one
         rank's share under a launcher; `engines`: contexts that exist already (they must have had pt_init; not closed here... they
         ARE closed by close(): hand over ownership); `lane_sweeps`: Engine.set_lane_sweeps of every engine created here ("off",
-        "auto", "force": short chains one per lane, and run_rounds' chunks inside k_rounds_lanes -- same bits); `track_best`: every
+        "auto", "force": short chains one per lane, and run_rounds' chunks inside k_rounds_lanes -- same bits); `wave_sweeps`:
+        Engine.set_wave_sweeps of every engine created here ("off", "auto", "force": f32 sweeps of chains of at most 256 spins one per
+        wave with resident local fields, round by round through the sweep calls -- same bits); `track_best`: every
         context keeps the record of its chains' lowest-energy states (Engine.best_begin; `target_energy`: the energy whose first
         passage is stamped, in the engine's units) -- one observation per round, stamp = round index, after the round's sweeps (and
         NMC cycles) and before its swap; best() reads it.  The record only observes: the trajectory is the same bits.
@@ -266,6 +269,8 @@ class LocalTempering:
                                own_stream=len(devs) > 1)
                 if lane_sweeps != "off":
                     e.set_lane_sweeps(lane_sweeps)
+                if wave_sweeps != "off":
+                    e.set_wave_sweeps(wave_sweeps)
                 e.pt_init(np.asarray(beta_list, dtype=np.float64))
                 self.engs.append(e)
         except Exception:

@@ -78,6 +78,7 @@ class Engine:
         self.fused_f64_real = False
         self._flags_on = False           # phase flags in force (set_flags / set_phase)
         self.lane_sweeps = "off"         # set_lane_sweeps
+        self.wave_sweeps = "off"         # set_wave_sweeps
         self.energy_scale = int(self._L.nlmc_energy_scale(self._ctx))
         self.field_scale = int(self._L.nlmc_field_scale(self._ctx))      # qs of the "f32" path: Jq = rint(J 2^qs)
 
@@ -236,7 +237,8 @@ class Engine:
         self.fused_f64_real = bool(on)
 
     LANE_MODES = {"off": _abi.LANES_OFF, "auto": _abi.LANES_AUTO, "force": _abi.LANES_FORCE}
-    ROUTES = {_abi.ROUTE_STEPWISE: "stepwise", _abi.ROUTE_FUSED: "fused", _abi.ROUTE_LANES: "lanes"}
+    WAVE_MODES = {"off": _abi.WAVES_OFF, "auto": _abi.WAVES_AUTO, "force": _abi.WAVES_FORCE}
+    ROUTES = {_abi.ROUTE_STEPWISE: "stepwise", _abi.ROUTE_FUSED: "fused", _abi.ROUTE_LANES: "lanes", _abi.ROUTE_WAVES: "waves"}
 
     def set_lane_sweeps(self, mode):
         """Chain-per-lane sweeps for short chains (include/nlmc.h: nlmc_set_lane_sweeps): "off" (the default), "auto" (sweep_philox
@@ -247,8 +249,29 @@ class Engine:
         self._ck(self._L.nlmc_set_lane_sweeps(self._ctx, self.LANE_MODES[mode]))
         self.lane_sweeps = mode
 
+    def set_wave_sweeps(self, mode):
+        """Wave-per-chain sweeps with resident local fields for short chains (include/nlmc.h: nlmc_set_wave_sweeps): "off" (the
+        default), "auto" (f32 sweep_philox calls with n <= 256 over at most NLMC_WAVE_AUTO_MAX_ROWS rows), "force" (every f32
+        sweep_philox call with n <= 256).  Calls the route does not take (f64, longer chains) run as before.  The results are the
+        same bits on every route; last_sweep_route() tells which one a call took."""
+        if mode not in self.WAVE_MODES:
+            raise ValueError(f"set_wave_sweeps: mode must be one of {sorted(self.WAVE_MODES)}, got {mode!r}")
+        self._ck(self._L.nlmc_set_wave_sweeps(self._ctx, self.WAVE_MODES[mode]))
+        self.wave_sweeps = mode
+
+    def waves_take(self, rows=None, precision="f32"):
+        """Whether the context routes a sweep_philox call over `rows` rows (default: the selected chains) in `precision` to the
+        wave-per-chain kernels -- the rule of nlmc_set_wave_sweeps, asked before lanes_take.  Such a call needs no fused-window plan."""
+        mode = getattr(self, "wave_sweeps", "off")
+        if mode == "off" or precision != "f32" or self.n > _abi.WAVE_N:
+            return False
+        if mode == "force":
+            return True
+        rows = self.rows() if rows is None else int(rows)
+        return rows <= _abi.WAVE_AUTO_MAX_ROWS
+
     def last_sweep_route(self):
-        """Route of the most recent sweep_philox call: "stepwise", "fused", "lanes", or None before any (nlmc_last_sweep_route)."""
+        """Route of the most recent sweep_philox call: "stepwise", "fused", "lanes", "waves", or None before any (nlmc_last_sweep_route)."""
         return self.ROUTES.get(int(self._L.nlmc_last_sweep_route(self._ctx)))
 
     def lanes_take(self, rows=None):
@@ -277,7 +300,7 @@ class Engine:
         T = fused_window(S) if window is None else int(window)
         budget = self.FUSED_PLAN_BUDGET if budget_bytes is None else int(budget_bytes)
         rec_e = bool(want_recorded_energy and record_stride)
-        if S > 0 and self.lanes_take():         # the context runs this call one chain per lane: no windows to plan
+        if S > 0 and (self.waves_take(precision=precision) or self.lanes_take()):   # the context runs this call one chain per wave or per lane: no windows to plan
             o = self.sweep_philox(S, seed, sweep0=sweep0, beta=beta, record_stride=record_stride, want_energy=want_energy,
                                   want_min=want_min, want_state=want_state, precision=precision)
             self.fused_last_call = False
@@ -904,6 +927,11 @@ class RoundPlanner:
         fused or plain -- a chunk is planned once its pair selections are -- and may go to the engine's batched rounds call."""
         return hasattr(self.eng, "lanes_take") and bool(self.eng.lanes_take())
 
+    def waves(self):
+        """Whether the engine runs this planner's sweeps one chain per wave (Engine.waves_take): such rounds need no level schedule
+        either, and go round by round through the sweep calls (the batched rounds calls do not look at the wave mode)."""
+        return hasattr(self.eng, "waves_take") and bool(self.eng.waves_take(precision=self.precision))
+
     def _plan(self, ii, want_fused):
         r0, r1 = ii, min(self.R, ii + self.chunk)
         self.chunks_planned += 1
@@ -912,6 +940,10 @@ class RoundPlanner:
         if self.lanes():
             self._fused_from, self._fused_to = self._plain_from, self._plain_to = r0, r1
             return True
+        if self.waves():                 # a chain per wave: nothing to plan but the chunk's pair selections, no window to ask for
+            self.window = 0
+            self._plain_from, self._plain_to = r0, r1
+            return False
         if want_fused and self.window:
             if hasattr(self.eng, "plan_slot"):
                 self.eng.plan_slot(self.slot)

@@ -30,24 +30,34 @@ class NPT(Common):
     """NMC + Adaptive Parallel Tempering (NPT/npt.py:15)."""
     _variant = "npt"
 
-    def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32", lanes="off"):
+    def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32", lanes="off", waves="off"):
         """`precision` (additive keyword, rng="philox" only): "f32" (default) -- the throughput mode's fixed-point couplings and
         logistic thresholds; "f64" -- the device-resident rounds in the reference's arithmetic (fp64 field, 53-bit uniform), on
         fused windows for real couplings too (Engine.set_fused_f64_real).  Replicas with doNMC set are not supported with "f64".
         `lanes` (additive keyword, rng="philox" only): "off" (default), "auto" or "force" -- Engine.set_lane_sweeps of the run's
         engines ("auto" never fires today: its row threshold NLMC_LANE_AUTO_ROWS is 2^31 - 1, so it runs as "off"): short chains (n <= 1024, a ladder of at most 64 temperatures) run one per lane, their rounds inside k_rounds_lanes
-        launches -- same results.  Plain replicas only; a ladder cut across ranks keeps its route."""
+        launches -- same results.  Plain replicas only; a ladder cut across ranks keeps its route.
+        `waves` (additive keyword, rng="philox" only, not with precision="f64"): "off" (default), "auto" or "force" --
+        Engine.set_wave_sweeps of the run's engines: f32 sweeps of chains of at most 256 spins run one chain per wave with resident
+        local fields, round by round through the sweep calls -- same results.  A ladder cut across ranks keeps its route."""
         if precision not in ("f32", "f64"):
             raise ValueError("precision must be 'f32' or 'f64'")
         if lanes not in ("off", "auto", "force"):
             raise ValueError("lanes must be 'off', 'auto' or 'force'")
+        if waves not in ("off", "auto", "force"):
+            raise ValueError("waves must be 'off', 'auto' or 'force'")
         super().__init__(J, h, rng=rng, seed=seed, device=device, lbp=lbp)
         if precision != "f32" and self.rng != "philox":
             raise ValueError("precision applies to rng='philox' (rng='numpy' runs the reference's own arithmetic)")
         if lanes != "off" and self.rng != "philox":
             raise ValueError("lanes applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
+        if waves != "off" and self.rng != "philox":
+            raise ValueError("waves applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
+        if waves != "off" and precision == "f64":
+            raise ValueError("waves applies to precision='f32' (the wave-per-chain sweeps have no fp64 arithmetic)")
         self.precision = precision
         self.lanes = lanes
+        self.waves = waves
 
     # ------------------------------------------------------------------------------------------------
     def replica_energy(self, M, num_sweeps):
@@ -398,10 +408,10 @@ class NPT(Common):
             return e
         if ctx is None:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, precision=prec, lane_sweeps=self.lanes,
-                                track_best=track_best, target_energy=target_energy, track_energies=track_energies)
+                                wave_sweeps=self.waves, track_best=track_best, target_energy=target_energy, track_energies=track_energies)
         elif not cut:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, parts=[(base_, count_)], precision=prec,
-                                lane_sweeps=self.lanes, track_best=track_best, target_energy=target_energy, track_energies=track_energies)
+                                lane_sweeps=self.lanes, wave_sweeps=self.waves, track_best=track_best, target_energy=target_energy, track_energies=track_energies)
         else:
             lt = ShardedAsLocal(ShardedTempering(
                 lambda i, n, b, g: opt_in(Engine(i, None, n, device=lrank_, chain_base=b, n_chains_global=g)), inst, beta_list, G,
