@@ -6,7 +6,8 @@ reference uses NumPy's pairwise association and NumPy's own SIMD tanh/arctanh ->
 point of the message map is reached to ~1 ulp by both, so marginals agree to 1e-10 absolute where both visit the same
 lambdas; the lambda at which the iteration budget runs out is a knife-edge (convergence is tested against machine
 epsilon: it is a 1-ulp limit cycle), so the tests compare every lambda both sides converged on and compare clusters
-only when both stopped at the same lambda.
+only when both stopped at the same lambda.  The sharp bound (8 eps against high-precision fixed points, on inputs where
+the reference converges at every lambda) is in tests/test_gpu_lbp_exact.py.
 """
 import numpy as np
 import pytest
