@@ -365,13 +365,35 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *ctx, int precision, int n_rounds, int swee
  * reports the visiting orders built, the timings count the order kernel as the levelize half. */
 int nlmc_pt_rounds_lanes(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0,
                          uint64_t seed, int n_pairs);
-/* The route the most recent nlmc_pt_rounds_fused / nlmc_pt_rounds_deferred / nlmc_pt_rounds_lanes call that ran took:
- * NLMC_ROUNDS_IN_LAUNCH (the rounds inside k_rounds_fused launches), NLMC_ROUNDS_LAUNCH_PER_ROUND, NLMC_ROUNDS_LANES (inside
- * k_rounds_lanes launches), NLMC_ROUNDS_APT_LANES (nlmc_apt_rounds_lanes), or 0 (no such call yet). */
+/* n_rounds whole rounds of short chains in launches of k_rounds_waves (csrc/nlmc_wave_rounds.h), whatever the wave mode is: a chain
+ * per wave with its exact int32 local fields resident in registers (k_sweep_waves' update), a workgroup of up to 16 waves holding
+ * whole ladders (up to 64 chains: a wave then runs up to four chains in turn, their state parked in LDS between turns), the field
+ * prologue and the staging of the coupling matrix into LDS paid once per launch, the swap round decided by the workgroup's first wave
+ * from energies in LDS between two workgroup barriers.  No workgroup waits for another one (no atomic, no cooperative launch, no
+ * residency condition).  Bit-identical to nlmc_sweep_philox(beta = NULL, shared order) + nlmc_pt_swap_philox round by round on any
+ * route; the rounds' decisions go to the device-side swap log when one covers them, an open best-state record and energy log observe
+ * every chain once per round.  Needs: precision NLMC_F32, n <= NLMC_WAVE_N, ladder_len <= 64, a context of whole ladders without a
+ * communicator, no phase flags / chain subset / second stream / tracked minimum, n_pairs >= 1 with the pair selections of rounds
+ * [round0, round0 + n_rounds) planned (nlmc_pt_plan, same seed and n_pairs); no fused-window plan.  A call is cut into launches of
+ * whole rounds against the order scratch as nlmc_pt_rounds_lanes' is.  NLMC_ERR_UNSUPPORTED (nothing was run, the reason in
+ * nlmc_last_error) when a condition is not met.  NLMC_WAVE_ROUNDS_LADDERS (read at nlmc_create) fixes the ladders per workgroup; no
+ * result depends on it.  nlmc_last_sweep_route is NLMC_ROUTE_WAVES after such a call, nlmc_pt_rounds_route NLMC_ROUNDS_WAVES,
+ * nlmc_last_schedule_stats reports the visiting orders built. */
+int nlmc_pt_rounds_waves(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0,
+                         uint64_t seed, int n_pairs);
+/* on != 0: nlmc_pt_rounds_deferred takes k_rounds_waves first -- before the lane rule and before it asks for a fused plan -- when
+ * nlmc_set_wave_sweeps routes the context's sweeps to the wave kernels and nlmc_pt_rounds_waves' conditions hold; where they do not
+ * the call goes on as with the option off.  Default: off, and then nothing changes for any caller. */
+int nlmc_set_wave_rounds(nlmc_ctx *ctx, int on);
+/* The route the most recent nlmc_pt_rounds_fused / nlmc_pt_rounds_deferred / nlmc_pt_rounds_lanes / nlmc_pt_rounds_waves call that ran
+ * took: NLMC_ROUNDS_IN_LAUNCH (the rounds inside k_rounds_fused launches), NLMC_ROUNDS_LAUNCH_PER_ROUND, NLMC_ROUNDS_LANES (inside
+ * k_rounds_lanes launches), NLMC_ROUNDS_APT_LANES (nlmc_apt_rounds_lanes), NLMC_ROUNDS_WAVES (inside k_rounds_waves launches), or 0
+ * (no such call yet). */
 #define NLMC_ROUNDS_IN_LAUNCH 1
 #define NLMC_ROUNDS_LAUNCH_PER_ROUND 2
 #define NLMC_ROUNDS_LANES 3
 #define NLMC_ROUNDS_APT_LANES (NLMC_ROUNDS_LANES + 1) /* 4 */
+#define NLMC_ROUNDS_WAVES (NLMC_ROUNDS_LANES + 2) /* 5 */
 int nlmc_pt_rounds_route(nlmc_ctx *ctx);
 /* n_rounds APT rounds of short chains -- sweeps_per_round sweeps at the slot temperatures, the Houdayer step of
  * nlmc_icm_round_ladders, the swap round of nlmc_pt_swap_philox -- in launches of k_apt_rounds_lanes (csrc/nlmc_lane_apt.h): the whole

@@ -11,6 +11,7 @@
 #include "nlmc_lane_rounds.h"
 #include "nlmc_lane_apt.h"
 #include "nlmc_waves.h"
+#include "nlmc_wave_rounds.h"
 #include "nlmc_wave_shape.h"
 #include "nlmc_host.h"
 
@@ -90,6 +91,7 @@ struct Knobs {
                                      // where it fits (1); -1: the default
     int wave_waves = 0;              // NLMC_WAVE_WAVES: waves (chains) per workgroup of the wave-per-chain sweeps (1..16; 0: by row count)
     bool wave_jlds = true;           // NLMC_WAVE_JLDS=0: the wave-per-chain sweeps read the matrix rows from global memory at every n
+    int wave_rounds_ladders = 0;     // NLMC_WAVE_ROUNDS_LADDERS: ladders per workgroup of the rounds inside a wave launch (0: by the rule)
     int dbg_flags = 0;               // NLMC_DBG_FLAGS: timing experiments of NLMC_DEBUG_KNOBS builds
     std::string stamp_file;          // NLMC_STAMP_FILE: NLMC_STAMPS builds dump the last launch's per-wave cycle sums here
 };
@@ -115,6 +117,7 @@ Knobs read_knobs()
     k.lane_rng = on("NLMC_LANE_RNG") ? (num("NLMC_LANE_RNG", 0) != 0) : -1;
     k.wave_waves = std::min(16, std::max(0, num("NLMC_WAVE_WAVES", 0)));
     k.wave_jlds = num("NLMC_WAVE_JLDS", 1) != 0;
+    k.wave_rounds_ladders = std::min(64, std::max(0, num("NLMC_WAVE_ROUNDS_LADDERS", 0)));
     k.dbg_flags = num("NLMC_DBG_FLAGS", 0);
     if (const char *s = getenv("NLMC_STAMP_FILE")) k.stamp_file = s;
     return k;
@@ -222,6 +225,7 @@ struct nlmc_ctx {
     DevBuf<uint16_t> lane_perm;   // [orders of a window][n]
     // wave-per-chain sweeps (csrc/nlmc_waves.h)
     int wave_mode = 0;            // nlmc_set_wave_sweeps: 0 off, 1 auto, 2 force
+    bool wave_rounds = false;     // nlmc_set_wave_rounds: nlmc_pt_rounds_deferred takes k_rounds_waves where the sweeps go to the wave kernels
     DevBuf<int32_t> wave_J;       // [n][64 R] dense fixed-point matrix, built on the first wave call (k_wave_matrix)
     bool wave_J_built = false;
     DevBuf<int32_t> nmc_status;   // sticky: a backbone inference diverged at its first lambda
@@ -483,6 +487,7 @@ int sweep_block_for(const nlmc_ctx *c, bool f64_philox, bool f32_diag = false)
 // beyond the default dynamic-LDS window a kernel has to opt in (once per kernel and size step)
 constexpr size_t NLMC_LDS_BYTES_MAX = (size_t)158 * 1024;      // dynamic LDS a workgroup may ask for
 
+static_assert(NLMC_WAVE_ROUNDS_LDS_MAX == NLMC_LDS_BYTES_MAX, "csrc/nlmc_wave_shape.h keeps its own copy of the ceiling");
 int ensure_lds(nlmc_ctx *c, const void *func, size_t bytes)
 {
     if (bytes > NLMC_LDS_BYTES_MAX) return fail(c, NLMC_ERR_UNSUPPORTED, "instance too large for the LDS-resident kernels of this build");
@@ -2919,9 +2924,11 @@ LaneRoundsArgs lane_rounds_args(const nlmc_ctx *c, int k, uint32_t r0, int n_pai
 
 // The launches of a lane rounds driver: n_rounds rounds in chunks of as many whole rounds as the order scratch holds visiting orders
 // for.  Per chunk of k rounds from round r0 (sweep s0, `at` rounds into the call): k_lane_orders (the "levelize" half of the timings),
-// then launch(at, k, s0, r0) puts the caller's kernel kfun (lds bytes of dynamic LDS) on the context's stream.
+// then launch(at, k, s0, r0) puts the caller's kernel kfun (lds bytes of dynamic LDS) on the context's stream.  `route`: the
+// NLMC_ROUTE_* nlmc_last_sweep_route reports after the call.
 extern "C++" template <typename Launch>
-int lane_rounds_chunks(nlmc_ctx *c, const void *kfun, size_t lds, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, Launch launch)
+int lane_rounds_chunks(nlmc_ctx *c, const void *kfun, size_t lds, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int route,
+                       Launch launch)
 {
     const size_t bytes_per_round = (size_t)T * (size_t)c->n * sizeof(uint16_t);
     const int K = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_rounds, c->knobs.lane_scratch / bytes_per_round, (size_t)(INT_MAX / 2) / (size_t)T}));
@@ -2947,7 +2954,7 @@ int lane_rounds_chunks(nlmc_ctx *c, const void *kfun, size_t lds, int n_rounds, 
         c->launches_total += k;
     }
     c->sub_dirty = true;
-    c->last_route = NLMC_ROUTE_LANES;
+    c->last_route = route;
     return NLMC_OK;
 }
 
@@ -2960,7 +2967,7 @@ int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep
     Lds.total = map_off + 128;
     const void *kfun = rounds_lanes_kernel(precision == NLMC_F64, c->observed());
     const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
-    int rc = lane_rounds_chunks(c, kfun, Lds.total, n_rounds, T, sweep0, round0, seed, [&](int, int k, uint32_t s0, uint32_t r0) -> int {
+    int rc = lane_rounds_chunks(c, kfun, Lds.total, n_rounds, T, sweep0, round0, seed, NLMC_ROUTE_LANES, [&](int, int k, uint32_t s0, uint32_t r0) -> int {
         SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
         lane_fields(c, a, c->n_chains, Lds.tab, Lds.u_off);
         LaneRoundsArgs q = lane_rounds_args(c, k, r0, n_pairs, (size_t)(c->n_chains_global / L), log, map_off);
@@ -2985,6 +2992,78 @@ int nlmc_pt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_pe
     if (const char *why = rounds_lanes_refusal(c, n_rounds, sweeps_per_round, round0, seed, n_pairs)) return fail(c, NLMC_ERR_UNSUPPORTED, name + why);
     HIP_TRY(c, hipSetDevice(c->device));
     return rounds_lanes(c, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+}
+
+// ---- tempering rounds inside a wave launch: a ladder per workgroup (k_rounds_waves, csrc/nlmc_wave_rounds.h) -------------------------
+// Why this context cannot run rounds [round0, round0 + n_rounds) in k_rounds_waves, or nullptr: the checks of rounds_lanes_refusal with
+// the reach of the wave kernels (fixed point, n <= NLMC_WAVE_N) and a ladder inside one workgroup.  Arguments are checked by the callers.
+const char *rounds_waves_refusal(const nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t round0, uint64_t seed, int n_pairs)
+{
+    if (const char *why = rounds_context_refusal(c, true)) return why;
+    if (n_pairs < 1) return "no swap pairs";
+    if (precision != NLMC_F32) return "the wave-per-chain kernels have the fixed-point arithmetic (NLMC_F32) only";
+    if (c->knobs.force_big || c->n > NLMC_WAVE_N) return "the wave-per-chain kernels take chains of at most NLMC_WAVE_N spins";
+    if (c->ladder_len > 64) return "a ladder of more than 64 temperatures does not fit a workgroup's swap wave";
+    if (!c->pt_plan.covers(round0, n_rounds, n_pairs, seed)) return "the pair selections of these rounds are not planned (nlmc_pt_plan)";
+    if ((size_t)T * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
+        return "the visiting orders of one round exceed the order scratch (NLMC_LANE_SCRATCH)";
+    return nullptr;
+}
+
+const void *rounds_waves_kernel(int R, bool jlds, bool observed)
+{
+#define NLMC_RW(R_) {{reinterpret_cast<const void *>(k_rounds_waves<R_, false, false>), reinterpret_cast<const void *>(k_rounds_waves<R_, false, true>)}, \
+                     {reinterpret_cast<const void *>(k_rounds_waves<R_, true, false>), reinterpret_cast<const void *>(k_rounds_waves<R_, true, true>)}}
+    static const void *const table[3][2][2] = {NLMC_RW(1), NLMC_RW(2), NLMC_RW(4)};
+#undef NLMC_RW
+    return table[R == 1 ? 0 : R == 2 ? 1 : 2][jlds ? 1 : 0][observed ? 1 : 0];
+}
+
+// n_rounds rounds in launches of k_rounds_waves.  rounds_waves_refusal said nullptr.
+int rounds_waves(nlmc_ctx *c, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
+{
+    const int L = c->ladder_len, ladders = c->n_chains / L;
+    if (c->n_cu == 0) HIP_TRY(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+    const NlmcWaveRoundsShape S = nlmc_wave_rounds_shape(c->n, c->n_pad, L, ladders, c->n_cu, c->knobs.wave_rounds_ladders, c->knobs.wave_jlds ? 1 : 0);
+    if (S.R == 0) return fail(c, NLMC_ERR_STATE, "rounds_waves: the chain or the ladder does not fit the wave kernels");
+    const void *kfun = rounds_waves_kernel(S.R, S.jlds != 0, c->observed());
+    { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
+    const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
+    WaveRoundsArgs w{};
+    w.P = S.P; w.C = S.C; w.x_off = (int)S.x_off; w.s_off = (int)S.s_off; w.e_off = (int)S.e_off; w.map_off = (int)S.map_off;
+    int rc = lane_rounds_chunks(c, kfun, S.lds, n_rounds, T, sweep0, round0, seed, NLMC_ROUTE_WAVES, [&](int, int k, uint32_t s0, uint32_t r0) -> int {
+        SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
+        lane_fields(c, a, c->n_chains, false, 0);
+        a.wave_J = c->wave_J.p;
+        LaneRoundsArgs q = lane_rounds_args(c, k, r0, n_pairs, (size_t)(c->n_chains_global / L), log, S.map_off);
+        void *kargs[] = {&a, &q, &w};
+        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)S.blocks), dim3((unsigned)(64 * S.W)), kargs, S.lds, c->stream));
+        return NLMC_OK;
+    });
+    if (rc) return rc;
+    c->rounds_route = NLMC_ROUNDS_WAVES;
+    return NLMC_OK;
+}
+
+// n_rounds rounds in launches of k_rounds_waves, whatever the wave mode is and whatever nlmc_pt_rounds_deferred would choose.
+int nlmc_pt_rounds_waves(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
+                         int n_pairs)
+{
+    if (!c) return NLMC_ERR_ARG;
+    const std::string name = "nlmc_pt_rounds_waves: ";
+    bool go = false;
+    { int rc = rounds_entry_check(c, name, precision, n_rounds, sweeps_per_round, n_pairs, go); if (rc || !go) return rc; }
+    if (n_pairs > std::max(0, c->ladder_len - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
+    if (const char *why = rounds_waves_refusal(c, precision, n_rounds, sweeps_per_round, round0, seed, n_pairs)) return fail(c, NLMC_ERR_UNSUPPORTED, name + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return rounds_waves(c, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+}
+
+int nlmc_set_wave_rounds(nlmc_ctx *c, int on)
+{
+    if (!c) return NLMC_ERR_ARG;
+    c->wave_rounds = on != 0;
+    return NLMC_OK;
 }
 
 // Whether nlmc_pt_rounds_deferred takes k_rounds_lanes where the lane mode routes the context's sweeps to the lane kernels.  The rule
@@ -3023,6 +3102,13 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
                             int n_pairs)
 {
     if (!c) return NLMC_ERR_ARG;
+    // nlmc_set_wave_rounds and sweeps on the wave kernels: the rounds inside k_rounds_waves, before the lane rule and any fused plan
+    if (c->wave_rounds && !c->knobs.no_deferred && c->ladder_len > 0 && n_rounds > 0 && c->n_chains > 0 && sweeps_per_round >= 1 &&
+        (precision == NLMC_F32 || precision == NLMC_F64) && n_pairs >= 1 && n_pairs <= c->ladder_len - 1 && waves_route(c, c->n_chains, precision) &&
+        !rounds_waves_refusal(c, precision, n_rounds, sweeps_per_round, round0, seed, n_pairs)) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        return rounds_waves(c, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+    }
     // short chains under the lane mode: the rounds inside k_rounds_lanes, before a fused plan is asked for
     if (ROUNDS_LANES_IN_LAUNCH && !c->knobs.no_deferred && c->ladder_len > 0 && n_rounds > 0 && c->n_chains > 0 && sweeps_per_round >= 1 &&
         (precision == NLMC_F32 || precision == NLMC_F64) && n_pairs >= 1 && n_pairs <= c->ladder_len - 1 && lanes_route(c, c->n_chains) &&
@@ -3385,7 +3471,7 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
     const bool elog = c->elog_rec(round0, n_rounds).energy != nullptr;          // (a launch none of whose rounds is logged stores nothing anyway)
     const void *kfun = apt_lanes_kernel(precision == NLMC_F64, elog);
     const bool log = n_pairs > 0 && c->pt_log.covers(round0, n_rounds, n_pairs);
-    int rc = lane_rounds_chunks(c, kfun, A.total, n_rounds, T, sweep0, round0, seed, [&](int at, int k, uint32_t s0, uint32_t r0) -> int {
+    int rc = lane_rounds_chunks(c, kfun, A.total, n_rounds, T, sweep0, round0, seed, NLMC_ROUTE_LANES, [&](int at, int k, uint32_t s0, uint32_t r0) -> int {
         SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
         lane_fields(c, a, c->n_chains, A.tab, A.u_off);
         LaneRoundsArgs q = lane_rounds_args(c, k, r0, n_pairs, (size_t)M * K, log, A.map_off);   // (plan and log rows hold every ladder of the context)

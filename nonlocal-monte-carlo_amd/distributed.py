@@ -238,19 +238,23 @@ class LocalTempering:
 
     def __init__(self, inst, beta_list, n_chains_global, seed, n_pairs, device_ids, precision="f32", engine_factory=None,
                  engines=None, parts=None, lane_sweeps="off", track_best=False, target_energy=None, track_energies=False,
-                 wave_sweeps="off"):
+                 wave_sweeps="off", wave_rounds=False):
         """`parts` (optional): the blocks [(chain_base, count)] this process drives instead of an even cut over device_ids -- one
         rank's share under a launcher; `engines`: contexts that exist already (they must have had pt_init; not closed here... they
         ARE closed by close(): hand over ownership); `lane_sweeps`: Engine.set_lane_sweeps of every engine created here ("off",
         "auto", "force": short chains one per lane, and run_rounds' chunks inside k_rounds_lanes -- same bits); `wave_sweeps`:
         Engine.set_wave_sweeps of every engine created here ("off", "auto", "force": f32 sweeps of chains of at most 256 spins one per
-        wave with resident local fields, round by round through the sweep calls -- same bits); `track_best`: every
+        wave with resident local fields, round by round through the sweep calls -- same bits); `wave_rounds`:
+        Engine.set_wave_rounds of every engine created here (needs wave_sweeps != "off", ValueError otherwise): run_rounds' chunks of
+        such chains run inside k_rounds_waves -- same bits); `track_best`: every
         context keeps the record of its chains' lowest-energy states (Engine.best_begin; `target_energy`: the energy whose first
         passage is stamped, in the engine's units) -- one observation per round, stamp = round index, after the round's sweeps (and
         NMC cycles) and before its swap; best() reads it.  The record only observes: the trajectory is the same bits.
         `track_energies`: every context keeps a per-round log of its chains' tracked energies and temperature slots as the round's
         swap decision sees them (Engine.elog_begin) -- opened by plan() for the rounds it plans, or by energy_log_begin(); one
         observation per round at the same place; energy_log() reads it.  Needs whole ladders per context (ValueError otherwise)."""
+        if wave_rounds and wave_sweeps == "off":
+            raise ValueError("wave_rounds needs wave_sweeps 'auto' or 'force' (the rounds run inside the wave kernels' launches)")
         self.G, self.seed, self.n_pairs, self.precision = int(n_chains_global), int(seed), int(n_pairs), precision
         devs = list(device_ids)
         self.parts = list(parts) if parts is not None else [block_partition(self.G, len(devs), r) for r in range(len(devs))]
@@ -271,6 +275,8 @@ class LocalTempering:
                     e.set_lane_sweeps(lane_sweeps)
                 if wave_sweeps != "off":
                     e.set_wave_sweeps(wave_sweeps)
+                if wave_rounds:
+                    e.set_wave_rounds(True)
                 e.pt_init(np.asarray(beta_list, dtype=np.float64))
                 self.engs.append(e)
         except Exception:
@@ -422,7 +428,8 @@ class LocalTempering:
         """`n_rounds` rounds of `n_sweeps` sweeps + one swap round each, without outputs -- same bits as round(n_sweeps) called
         n_rounds times, which is what everything that does not qualify falls back to.  ShardedTempering.run_rounds' rule: no NMC
         slots, swap pairs, every context owns whole ladders, one fused window per round -- or sweeps that run one chain per lane
-        (lane_sweeps: such a chunk needs only its pair selections planned, and the engine runs it inside k_rounds_lanes) -- an engine
+        (lane_sweeps: such a chunk needs only its pair selections planned, and the engine runs it inside k_rounds_lanes) or one chain
+        per wave with wave_rounds (likewise, inside k_rounds_waves) -- an engine
         with pt_rounds_deferred, NLMC_NO_DEFERRED unset.  Every context is handed the rest of its planned chunk at a time (the engine picks the route:
         Engine.pt_rounds_deferred); the calls are asynchronous, so all contexts have their chunk queued before any of them is
         waited for.  A context whose engine refuses is not asked again and runs its rounds one by one from then on (whole ladders:
@@ -436,7 +443,8 @@ class LocalTempering:
             self._rounds_refused = [False] * len(self.engs)
         eligible = bool(not self.nmc and self.n_pairs > 0 and self.whole_ladders and pls
                         and not os.environ.get("NLMC_NO_DEFERRED")
-                        and all(n_sweeps == pl.S and (pl.window == n_sweeps or pl.lanes()) for pl in pls)
+                        and all(n_sweeps == pl.S and (pl.window == n_sweeps or pl.lanes() or (pl.waves() and getattr(pl.eng, "wave_rounds", False)))
+                            for pl in pls)
                         and all(hasattr(e, "pt_rounds_deferred") for e in self.engs))
         done = 0
         while done < n_rounds:

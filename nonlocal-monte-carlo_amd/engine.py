@@ -79,6 +79,7 @@ class Engine:
         self._flags_on = False           # phase flags in force (set_flags / set_phase)
         self.lane_sweeps = "off"         # set_lane_sweeps
         self.wave_sweeps = "off"         # set_wave_sweeps
+        self.wave_rounds = False         # set_wave_rounds
         self.energy_scale = int(self._L.nlmc_energy_scale(self._ctx))
         self.field_scale = int(self._L.nlmc_field_scale(self._ctx))      # qs of the "f32" path: Jq = rint(J 2^qs)
 
@@ -258,6 +259,13 @@ class Engine:
             raise ValueError(f"set_wave_sweeps: mode must be one of {sorted(self.WAVE_MODES)}, got {mode!r}")
         self._ck(self._L.nlmc_set_wave_sweeps(self._ctx, self.WAVE_MODES[mode]))
         self.wave_sweeps = mode
+
+    def set_wave_rounds(self, on):
+        """Whether pt_rounds_deferred runs its rounds inside k_rounds_waves launches (include/nlmc.h: nlmc_set_wave_rounds) where the
+        context's sweeps go to the wave kernels (waves_take) and pt_rounds_waves' conditions hold: asked before the lane rule and
+        before any fused-window plan.  Default off: nothing changes for any caller.  Same bits either way."""
+        self._ck(self._L.nlmc_set_wave_rounds(self._ctx, 1 if on else 0))
+        self.wave_rounds = bool(on)
 
     def waves_take(self, rows=None, precision="f32"):
         """Whether the context routes a sweep_philox call over `rows` rows (default: the selected chains) in `precision` to the
@@ -562,6 +570,21 @@ class Engine:
         self._ck(rc)
         return True
 
+    def pt_rounds_waves(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
+        """n_rounds whole rounds of short chains inside k_rounds_waves launches, whatever the wave mode is (include/nlmc.h:
+        nlmc_pt_rounds_waves): a chain per wave with resident local fields, whole ladders of at most 64 temperatures per workgroup,
+        f32 only, n <= 256, pair selections planned (pt_plan), no fused-window plan.  True when the rounds were queued, False when
+        the context does not qualify (nothing was run; the reason is in rounds_fused_refusal).  pt_rounds_deferred takes this route
+        by itself under set_wave_sweeps("force") with set_wave_rounds(True)."""
+        prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
+        rc = self._L.nlmc_pt_rounds_waves(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
+                                          int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs))
+        if rc == _abi.ERR_UNSUPPORTED:
+            self.rounds_fused_refusal = _abi.lib().nlmc_last_error(self._ctx).decode()
+            return False
+        self._ck(rc)
+        return True
+
     def apt_rounds_lanes(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, katzgraber=True, precision="f32",
                          want_info=False):
         """n_rounds whole APT rounds of short chains -- sweeps, the Houdayer step of icm_round_ladders, the swap round -- inside
@@ -582,11 +605,12 @@ class Engine:
         return True, info
 
     def last_rounds_route(self):
-        """The route the last pt_rounds_fused / pt_rounds_deferred / pt_rounds_lanes / apt_rounds_lanes call that ran took: "in launch"
-        (the rounds inside k_rounds_fused launches), "launch per round", "lanes" (inside k_rounds_lanes launches), "apt lanes" (inside
-        k_apt_rounds_lanes launches), or None before any such call (include/nlmc.h: nlmc_pt_rounds_route)."""
+        """The route the last pt_rounds_fused / pt_rounds_deferred / pt_rounds_lanes / pt_rounds_waves / apt_rounds_lanes call that ran
+        took: "in launch" (the rounds inside k_rounds_fused launches), "launch per round", "lanes" (inside k_rounds_lanes launches),
+        "apt lanes" (inside k_apt_rounds_lanes launches), "waves" (inside k_rounds_waves launches), or None before any such call
+        (include/nlmc.h: nlmc_pt_rounds_route)."""
         return {_abi.ROUNDS_IN_LAUNCH: "in launch", _abi.ROUNDS_LAUNCH_PER_ROUND: "launch per round",
-                _abi.ROUNDS_LANES: "lanes", _abi.ROUNDS_APT_LANES: "apt lanes"}.get(self._L.nlmc_pt_rounds_route(self._ctx))
+                _abi.ROUNDS_LANES: "lanes", _abi.ROUNDS_APT_LANES: "apt lanes", _abi.ROUNDS_WAVES: "waves"}.get(self._L.nlmc_pt_rounds_route(self._ctx))
 
     def pt_log_begin(self, round0, n_rounds, n_pairs):
         """Keep the swap log of the next rounds on the device (rounds called with want_log=False)."""
@@ -894,6 +918,14 @@ def fused_window(n_sweeps, lo=3, hi=64):
 # and Chimera-128.  So the class keeps a call per step, and Engine.apt_rounds_lanes reaches the kernel by name.
 APT_LANES_IN_LAUNCH = False
 
+# What the documents recommend for wave_rounds where the wave sweeps are on (the default of every wave_rounds keyword stays False
+# whatever this says; nothing in the package reads it).  The rule is that of ROUNDS_LANES_IN_LAUNCH: True only if the in-launch median
+# time per run is not above that of wave sweeps round by round on the same build by more than the run-to-run spread at any shape of
+# scripts/wave_rounds_throughput.py.  Measured (profiles/wave_rounds_in_launch_throughput.txt): below it at every
+# shape with T = 1 and L = 16 (1.3-2.7x), level at T = 10, but above it at T = 1000 with 64 ladders of 16 (1.2-1.35x: a ladder per
+# workgroup leaves three quarters of the compute units idle) and at every shape with L = 64 (1.2-5.3x: four chains a wave, in turn).
+WAVE_ROUNDS_IN_LAUNCH = False
+
 
 class RoundPlanner:
     """Level schedules planned ahead for `n_rounds` rounds of `sweeps_per_round` sweeps each (they depend on the RNG
@@ -929,7 +961,8 @@ class RoundPlanner:
 
     def waves(self):
         """Whether the engine runs this planner's sweeps one chain per wave (Engine.waves_take): such rounds need no level schedule
-        either, and go round by round through the sweep calls (the batched rounds calls do not look at the wave mode)."""
+        either, and go round by round through the sweep calls unless the engine's wave_rounds is on (Engine.set_wave_rounds: the
+        batched rounds call then runs a chunk inside k_rounds_waves)."""
         return hasattr(self.eng, "waves_take") and bool(self.eng.waves_take(precision=self.precision))
 
     def _plan(self, ii, want_fused):
@@ -938,6 +971,9 @@ class RoundPlanner:
         if self.pt_pairs > 0 and hasattr(self.eng, "pt_plan"):
             self.eng.pt_plan(self.pt_round0 + r0, r1 - r0, self.seed, self.pt_pairs)
         if self.lanes():
+            self._fused_from, self._fused_to = self._plain_from, self._plain_to = r0, r1
+            return True
+        if self.waves() and getattr(self.eng, "wave_rounds", False):   # ... and the engine's batched rounds call takes the chunk (k_rounds_waves)
             self._fused_from, self._fused_to = self._plain_from, self._plain_to = r0, r1
             return True
         if self.waves():                 # a chain per wave: nothing to plan but the chunk's pair selections, no window to ask for

@@ -30,7 +30,7 @@ class NPT(Common):
     """NMC + Adaptive Parallel Tempering (NPT/npt.py:15)."""
     _variant = "npt"
 
-    def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32", lanes="off", waves="off"):
+    def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32", lanes="off", waves="off", wave_rounds=False):
         """`precision` (additive keyword, rng="philox" only): "f32" (default) -- the throughput mode's fixed-point couplings and
         logistic thresholds; "f64" -- the device-resident rounds in the reference's arithmetic (fp64 field, 53-bit uniform), on
         fused windows for real couplings too (Engine.set_fused_f64_real).  Replicas with doNMC set are not supported with "f64".
@@ -39,7 +39,10 @@ class NPT(Common):
         launches -- same results.  Plain replicas only; a ladder cut across ranks keeps its route.
         `waves` (additive keyword, rng="philox" only, not with precision="f64"): "off" (default), "auto" or "force" --
         Engine.set_wave_sweeps of the run's engines: f32 sweeps of chains of at most 256 spins run one chain per wave with resident
-        local fields, round by round through the sweep calls -- same results.  A ladder cut across ranks keeps its route."""
+        local fields, round by round through the sweep calls -- same results.  A ladder cut across ranks keeps its route.
+        `wave_rounds` (additive keyword, needs waves != "off", hence rng="philox" and precision="f32"): Engine.set_wave_rounds of the
+        run's engines -- the rounds without output run inside k_rounds_waves launches, a chunk of rounds per launch -- same results.
+        Plain replicas only."""
         if precision not in ("f32", "f64"):
             raise ValueError("precision must be 'f32' or 'f64'")
         if lanes not in ("off", "auto", "force"):
@@ -55,9 +58,14 @@ class NPT(Common):
             raise ValueError("waves applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
         if waves != "off" and precision == "f64":
             raise ValueError("waves applies to precision='f32' (the wave-per-chain sweeps have no fp64 arithmetic)")
+        if wave_rounds and waves == "off":
+            raise ValueError("wave_rounds needs waves='auto' or 'force' (the rounds run inside the wave kernels' launches)")
+        if wave_rounds and precision == "f64":
+            raise ValueError("wave_rounds applies to precision='f32' (the wave-per-chain kernels have no fp64 arithmetic)")
         self.precision = precision
         self.lanes = lanes
         self.waves = waves
+        self.wave_rounds = bool(wave_rounds)
 
     # ------------------------------------------------------------------------------------------------
     def replica_energy(self, M, num_sweeps):
@@ -148,6 +156,8 @@ class NPT(Common):
             raise ValueError("precision='f64' runs plain replicas only: doNMC slots are not supported")
         if any_nmc and self.lanes != "off":
             raise ValueError("lanes runs plain replicas only: doNMC slots are not supported")
+        if any_nmc and self.wave_rounds:
+            raise ValueError("wave_rounds runs plain replicas only: doNMC slots are not supported")
         # (with NMC replicas and M_skip > 1 the phases' traces and argmin hand-offs are strided on the device; a phase length that M_skip
         # does not divide raises the reference's own shape error on the host-managed path)
         device_resident = self.rng == "philox" and (not any_nmc or (int(M_skip) >= 1 and self.num_sweeps_per_NMC_phase_per_swap % int(M_skip) == 0))
@@ -408,10 +418,10 @@ class NPT(Common):
             return e
         if ctx is None:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, precision=prec, lane_sweeps=self.lanes,
-                                wave_sweeps=self.waves, track_best=track_best, target_energy=target_energy, track_energies=track_energies)
+                                wave_sweeps=self.waves, wave_rounds=self.wave_rounds, track_best=track_best, target_energy=target_energy, track_energies=track_energies)
         elif not cut:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, parts=[(base_, count_)], precision=prec,
-                                lane_sweeps=self.lanes, wave_sweeps=self.waves, track_best=track_best, target_energy=target_energy, track_energies=track_energies)
+                                lane_sweeps=self.lanes, wave_sweeps=self.waves, wave_rounds=self.wave_rounds, track_best=track_best, target_energy=target_energy, track_energies=track_energies)
         else:
             lt = ShardedAsLocal(ShardedTempering(
                 lambda i, n, b, g: opt_in(Engine(i, None, n, device=lrank_, chain_base=b, n_chains_global=g)), inst, beta_list, G,
