@@ -36,10 +36,7 @@ class APT_ICM(SweepMixin):
         `waves` (additive keyword, under the same conditions): "off" (default), "auto" or "force" -- Engine.set_wave_sweeps of the
         run's engine: chains of at most 256 spins sweep one per wave with resident local fields, a call per step (the rounds inside
         k_apt_rounds_lanes do not look at it).  Same bits as "off"."""
-        if lanes not in ("off", "auto", "force"):
-            raise ValueError("lanes must be 'off', 'auto' or 'force'")
-        if waves not in ("off", "auto", "force"):
-            raise ValueError("waves must be 'off', 'auto' or 'force'")
+        hostlogic.check_route_keywords(lanes, waves)
         self.J = J
         if isinstance(h, list):
             h = np.array(h)
@@ -47,10 +44,7 @@ class APT_ICM(SweepMixin):
             h = h[:, np.newaxis]                      # NPT/apt_ICM.py:27-34: h kept as an [N,1] column
         self.h = h
         self._init_backend(rng, seed, device)
-        if lanes != "off" and self.rng != "philox":
-            raise ValueError("lanes applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
-        if waves != "off" and self.rng != "philox":
-            raise ValueError("waves applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
+        hostlogic.check_route_keywords(lanes, waves, rng=self.rng)
         self.lanes = lanes
         self.waves = waves
 
@@ -269,10 +263,7 @@ class APT_ICM(SweepMixin):
         host_rng = np.random.default_rng(self.seed)      # initial states only
         eng = engine_factory(inst, None, G, device=self._cache.device)
         try:
-            if self.lanes != "off":
-                eng.set_lane_sweeps(self.lanes)
-            if self.waves != "off":
-                eng.set_wave_sweeps(self.waves)
+            hostlogic.set_route_modes(eng, self.lanes, self.waves)
             eng.set_spins((2 * host_rng.integers(0, 2, size=(G, N), dtype=np.int8) - 1).astype(np.int8))
             eng.pt_init(beta_list)
             if num_restarts > 1:

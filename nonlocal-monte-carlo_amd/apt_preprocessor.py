@@ -22,8 +22,7 @@ class APT_preprocessor(SweepMixin):
     def __init__(self, J, h, rng=None, seed=None, device=0, waves="off"):
         """`waves` (additive keyword, rng="philox" only): "off" (default), "auto" or "force" -- Engine.set_wave_sweeps of the engine
         run() creates: chains of at most 256 spins sweep one per wave with resident local fields.  Same bits as "off"."""
-        if waves not in ("off", "auto", "force"):
-            raise ValueError("waves must be 'off', 'auto' or 'force'")
+        hostlogic.check_route_keywords(waves=waves)
         self.J = J
         if isinstance(h, list):
             h = np.array(h)
@@ -32,8 +31,7 @@ class APT_preprocessor(SweepMixin):
         self.h = h
         self.N = J.shape[0]
         self._init_backend(rng, seed, device)
-        if waves != "off" and self.rng != "philox":
-            raise ValueError("waves applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
+        hostlogic.check_route_keywords(waves=waves, rng=self.rng)
         self.waves = waves
 
     def _hflat(self):
@@ -85,8 +83,7 @@ class APT_preprocessor(SweepMixin):
         saved_state = np.zeros((R, N))
         eng = Engine(inst, None, R, device=self._cache.device)
         try:
-            if self.waves != "off":
-                eng.set_wave_sweeps(self.waves)
+            hostlogic.set_route_modes(eng, waves=self.waves)
             while sigma_E > sigma_E_min:
                 if it != 1:
                     beta.append(beta[-1] + alpha / sigma_E)

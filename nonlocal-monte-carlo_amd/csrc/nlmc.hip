@@ -2745,14 +2745,27 @@ const char *rounds_context_refusal(const nlmc_ctx *c, bool strict)
 
 // What every rounds entry point (`name`) checks first, in this order: the arguments, a ladder, anything to do.  NLMC_OK with go = false
 // when there is nothing to do.
+bool rounds_args_ok(int precision, int n_rounds, int T, int n_pairs)
+{
+    return n_rounds >= 0 && T >= 1 && (precision == NLMC_F32 || precision == NLMC_F64) && n_pairs >= 0;
+}
+
 int rounds_entry_check(nlmc_ctx *c, const std::string &name, int precision, int n_rounds, int T, int n_pairs, bool &go)
 {
     go = false;
-    if (n_rounds < 0 || T < 1 || (precision != NLMC_F32 && precision != NLMC_F64) || n_pairs < 0)
-        return fail(c, NLMC_ERR_ARG, name + "bad argument");
+    if (!rounds_args_ok(precision, n_rounds, T, n_pairs)) return fail(c, NLMC_ERR_ARG, name + "bad argument");
     if (c->ladder_len == 0) return fail(c, NLMC_ERR_STATE, name + "call nlmc_pt_init first");
     go = n_rounds != 0 && c->n_chains != 0;
     return NLMC_OK;
+}
+
+// The same without a word, for nlmc_pt_rounds_deferred before it tries a short-chain route: the arguments are fine, there is a ladder
+// and something to do, the pairs are in range and NLMC_NO_DEFERRED is unset.  (Where this says no the call goes on to rounds_check, which
+// reports what is wrong.)
+bool rounds_deferred_quiet_ok(const nlmc_ctx *c, int precision, int n_rounds, int T, int n_pairs)
+{
+    return rounds_args_ok(precision, n_rounds, T, n_pairs) && c->ladder_len > 0 && n_rounds != 0 && c->n_chains != 0 && n_pairs >= 1 &&
+           n_pairs <= c->ladder_len - 1 && !c->knobs.no_deferred;
 }
 
 // The plan rows and the log rows (nullptr where `log` is false) of `round`, nl ladders wide: where a launch that starts at that round
@@ -2891,16 +2904,23 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
 }
 
 // ---- tempering rounds of short chains: a ladder per wave (k_rounds_lanes, csrc/nlmc_lane_rounds.h) ----------------------------------
-// Why this context cannot run rounds [round0, round0 + n_rounds) in k_rounds_lanes, or nullptr: the checks of rounds_check that do not
-// concern fused plans, the reach of the lane kernels (n <= NLMC_LANE_N) and a ladder inside one wave.  Arguments are checked by the
-// callers.
-// `swaps_optional` (the APT rounds, which have their Houdayer step): n_pairs = 0, a round without swaps, is taken.
-const char *rounds_lanes_refusal(const nlmc_ctx *c, int n_rounds, int T, uint32_t round0, uint64_t seed, int n_pairs, bool swaps_optional = false)
+// The routes that run whole rounds of short chains in one launch: k_rounds_lanes, k_rounds_waves, k_apt_rounds_lanes.
+enum class ShortRounds { lanes, waves, apt_lanes };
+
+// Why this context cannot run rounds [round0, round0 + n_rounds) on `route`, or nullptr: the checks of rounds_check that do not concern
+// fused plans, the reach of the route's kernels (lanes: n <= NLMC_LANE_N; waves: fixed point, n <= NLMC_WAVE_N) and a ladder inside one
+// wave (waves: one workgroup's swap wave).  The APT rounds have their Houdayer step: n_pairs = 0, a round without swaps, is taken.
+// Arguments are checked by the callers.
+const char *short_rounds_refusal(const nlmc_ctx *c, ShortRounds route, int precision, int n_rounds, int T, uint32_t round0, uint64_t seed, int n_pairs)
 {
+    const bool waves = route == ShortRounds::waves;
     if (const char *why = rounds_context_refusal(c, true)) return why;
-    if (n_pairs < 1 && !swaps_optional) return "no swap pairs";
-    if (c->knobs.force_big || c->n > NLMC_LANE_N) return "the chain-per-lane kernels take chains of at most NLMC_LANE_N spins";
-    if (c->ladder_len > 64) return "a ladder of more than 64 temperatures does not fit a wave";
+    if (n_pairs < 1 && route != ShortRounds::apt_lanes) return "no swap pairs";
+    if (waves && precision != NLMC_F32) return "the wave-per-chain kernels have the fixed-point arithmetic (NLMC_F32) only";
+    if (c->knobs.force_big || c->n > (waves ? NLMC_WAVE_N : NLMC_LANE_N))
+        return waves ? "the wave-per-chain kernels take chains of at most NLMC_WAVE_N spins" : "the chain-per-lane kernels take chains of at most NLMC_LANE_N spins";
+    if (c->ladder_len > 64)
+        return waves ? "a ladder of more than 64 temperatures does not fit a workgroup's swap wave" : "a ladder of more than 64 temperatures does not fit a wave";
     if (n_pairs >= 1 && !c->pt_plan.covers(round0, n_rounds, n_pairs, seed)) return "the pair selections of these rounds are not planned (nlmc_pt_plan)";
     if ((size_t)T * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
         return "the visiting orders of one round exceed the order scratch (NLMC_LANE_SCRATCH)";
@@ -2920,6 +2940,17 @@ LaneRoundsArgs lane_rounds_args(const nlmc_ctx *c, int k, uint32_t r0, int n_pai
     if (c->best_on) q.best = c->best_rec();
     q.elog = c->elog_rec(r0, k);
     return q;
+}
+
+// What every launch of a lane rounds driver passes first: the SweepArgs of T sweeps from s0 at the ladder temperatures (lane_fields over
+// all chains; uniform tables in LDS at u_off where `tab`) and the LaneRoundsArgs of k rounds from r0 (lane_rounds_args).
+struct LaneLaunchArgs { SweepArgs a; LaneRoundsArgs q; };
+LaneLaunchArgs lane_launch_args(const nlmc_ctx *c, int T, uint64_t seed, uint32_t s0, int k, uint32_t r0, int n_pairs, size_t nl, bool log, bool tab,
+                                size_t u_off, size_t map_off)
+{
+    LaneLaunchArgs x{sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true), lane_rounds_args(c, k, r0, n_pairs, nl, log, map_off)};
+    lane_fields(c, x.a, c->n_chains, tab, u_off);
+    return x;
 }
 
 // The launches of a lane rounds driver: n_rounds rounds in chunks of as many whole rounds as the order scratch holds visiting orders
@@ -2958,7 +2989,7 @@ int lane_rounds_chunks(nlmc_ctx *c, const void *kfun, size_t lds, int n_rounds, 
     return NLMC_OK;
 }
 
-// n_rounds rounds in launches of k_rounds_lanes.  rounds_lanes_refusal said nullptr.
+// n_rounds rounds in launches of k_rounds_lanes.  short_rounds_refusal said nullptr.
 int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
 {
     const int L = c->ladder_len, P = 64 / L, ladders = c->n_chains / L;
@@ -2968,10 +2999,8 @@ int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep
     const void *kfun = rounds_lanes_kernel(precision == NLMC_F64, c->observed());
     const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
     int rc = lane_rounds_chunks(c, kfun, Lds.total, n_rounds, T, sweep0, round0, seed, NLMC_ROUTE_LANES, [&](int, int k, uint32_t s0, uint32_t r0) -> int {
-        SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
-        lane_fields(c, a, c->n_chains, Lds.tab, Lds.u_off);
-        LaneRoundsArgs q = lane_rounds_args(c, k, r0, n_pairs, (size_t)(c->n_chains_global / L), log, map_off);
-        void *kargs[] = {&a, &q};
+        LaneLaunchArgs x = lane_launch_args(c, T, seed, s0, k, r0, n_pairs, (size_t)(c->n_chains_global / L), log, Lds.tab, Lds.u_off, map_off);
+        void *kargs[] = {&x.a, &x.q};
         HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)((ladders + P - 1) / P)), dim3(64), kargs, Lds.total, c->stream));
         return NLMC_OK;
     });
@@ -2980,36 +3009,7 @@ int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep
     return NLMC_OK;
 }
 
-// n_rounds rounds in launches of k_rounds_lanes, whatever the lane mode is and whatever nlmc_pt_rounds_deferred would choose.
-int nlmc_pt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
-                         int n_pairs)
-{
-    if (!c) return NLMC_ERR_ARG;
-    const std::string name = "nlmc_pt_rounds_lanes: ";
-    bool go = false;
-    { int rc = rounds_entry_check(c, name, precision, n_rounds, sweeps_per_round, n_pairs, go); if (rc || !go) return rc; }
-    if (n_pairs > std::max(0, c->ladder_len - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
-    if (const char *why = rounds_lanes_refusal(c, n_rounds, sweeps_per_round, round0, seed, n_pairs)) return fail(c, NLMC_ERR_UNSUPPORTED, name + why);
-    HIP_TRY(c, hipSetDevice(c->device));
-    return rounds_lanes(c, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
-}
-
 // ---- tempering rounds inside a wave launch: a ladder per workgroup (k_rounds_waves, csrc/nlmc_wave_rounds.h) -------------------------
-// Why this context cannot run rounds [round0, round0 + n_rounds) in k_rounds_waves, or nullptr: the checks of rounds_lanes_refusal with
-// the reach of the wave kernels (fixed point, n <= NLMC_WAVE_N) and a ladder inside one workgroup.  Arguments are checked by the callers.
-const char *rounds_waves_refusal(const nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t round0, uint64_t seed, int n_pairs)
-{
-    if (const char *why = rounds_context_refusal(c, true)) return why;
-    if (n_pairs < 1) return "no swap pairs";
-    if (precision != NLMC_F32) return "the wave-per-chain kernels have the fixed-point arithmetic (NLMC_F32) only";
-    if (c->knobs.force_big || c->n > NLMC_WAVE_N) return "the wave-per-chain kernels take chains of at most NLMC_WAVE_N spins";
-    if (c->ladder_len > 64) return "a ladder of more than 64 temperatures does not fit a workgroup's swap wave";
-    if (!c->pt_plan.covers(round0, n_rounds, n_pairs, seed)) return "the pair selections of these rounds are not planned (nlmc_pt_plan)";
-    if ((size_t)T * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
-        return "the visiting orders of one round exceed the order scratch (NLMC_LANE_SCRATCH)";
-    return nullptr;
-}
-
 const void *rounds_waves_kernel(int R, bool jlds, bool observed)
 {
 #define NLMC_RW(R_) {{reinterpret_cast<const void *>(k_rounds_waves<R_, false, false>), reinterpret_cast<const void *>(k_rounds_waves<R_, false, true>)}, \
@@ -3019,7 +3019,7 @@ const void *rounds_waves_kernel(int R, bool jlds, bool observed)
     return table[R == 1 ? 0 : R == 2 ? 1 : 2][jlds ? 1 : 0][observed ? 1 : 0];
 }
 
-// n_rounds rounds in launches of k_rounds_waves.  rounds_waves_refusal said nullptr.
+// n_rounds rounds in launches of k_rounds_waves.  short_rounds_refusal said nullptr.
 int rounds_waves(nlmc_ctx *c, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
 {
     const int L = c->ladder_len, ladders = c->n_chains / L;
@@ -3032,11 +3032,9 @@ int rounds_waves(nlmc_ctx *c, int n_rounds, int T, uint32_t sweep0, uint32_t rou
     WaveRoundsArgs w{};
     w.P = S.P; w.C = S.C; w.x_off = (int)S.x_off; w.s_off = (int)S.s_off; w.e_off = (int)S.e_off; w.map_off = (int)S.map_off;
     int rc = lane_rounds_chunks(c, kfun, S.lds, n_rounds, T, sweep0, round0, seed, NLMC_ROUTE_WAVES, [&](int, int k, uint32_t s0, uint32_t r0) -> int {
-        SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
-        lane_fields(c, a, c->n_chains, false, 0);
-        a.wave_J = c->wave_J.p;
-        LaneRoundsArgs q = lane_rounds_args(c, k, r0, n_pairs, (size_t)(c->n_chains_global / L), log, S.map_off);
-        void *kargs[] = {&a, &q, &w};
+        LaneLaunchArgs x = lane_launch_args(c, T, seed, s0, k, r0, n_pairs, (size_t)(c->n_chains_global / L), log, false, 0, S.map_off);
+        x.a.wave_J = c->wave_J.p;
+        void *kargs[] = {&x.a, &x.q, &w};
         HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)S.blocks), dim3((unsigned)(64 * S.W)), kargs, S.lds, c->stream));
         return NLMC_OK;
     });
@@ -3045,18 +3043,38 @@ int rounds_waves(nlmc_ctx *c, int n_rounds, int T, uint32_t sweep0, uint32_t rou
     return NLMC_OK;
 }
 
-// n_rounds rounds in launches of k_rounds_waves, whatever the wave mode is and whatever nlmc_pt_rounds_deferred would choose.
+// n_rounds rounds on `route` (lanes or waves), for which short_rounds_refusal said nullptr.
+int short_rounds(nlmc_ctx *c, ShortRounds route, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    return route == ShortRounds::waves ? rounds_waves(c, n_rounds, T, sweep0, round0, seed, n_pairs)
+                                       : rounds_lanes(c, precision, n_rounds, T, sweep0, round0, seed, n_pairs);
+}
+
+// nlmc_pt_rounds_lanes / nlmc_pt_rounds_waves (`fn`): n_rounds rounds in launches of k_rounds_lanes / k_rounds_waves, whatever the lane
+// or wave mode is and whatever nlmc_pt_rounds_deferred would choose.
+int short_rounds_by_name(nlmc_ctx *c, ShortRounds route, const char *fn, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0,
+                         uint64_t seed, int n_pairs)
+{
+    if (!c) return NLMC_ERR_ARG;
+    const std::string name = std::string(fn) + ": ";
+    bool go = false;
+    { int rc = rounds_entry_check(c, name, precision, n_rounds, T, n_pairs, go); if (rc || !go) return rc; }
+    if (n_pairs > std::max(0, c->ladder_len - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
+    if (const char *why = short_rounds_refusal(c, route, precision, n_rounds, T, round0, seed, n_pairs)) return fail(c, NLMC_ERR_UNSUPPORTED, name + why);
+    return short_rounds(c, route, precision, n_rounds, T, sweep0, round0, seed, n_pairs);
+}
+
+int nlmc_pt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
+                         int n_pairs)
+{
+    return short_rounds_by_name(c, ShortRounds::lanes, "nlmc_pt_rounds_lanes", precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+}
+
 int nlmc_pt_rounds_waves(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
                          int n_pairs)
 {
-    if (!c) return NLMC_ERR_ARG;
-    const std::string name = "nlmc_pt_rounds_waves: ";
-    bool go = false;
-    { int rc = rounds_entry_check(c, name, precision, n_rounds, sweeps_per_round, n_pairs, go); if (rc || !go) return rc; }
-    if (n_pairs > std::max(0, c->ladder_len - 1)) return fail(c, NLMC_ERR_ARG, "Cannot find non-overlapping pairs.");
-    if (const char *why = rounds_waves_refusal(c, precision, n_rounds, sweeps_per_round, round0, seed, n_pairs)) return fail(c, NLMC_ERR_UNSUPPORTED, name + why);
-    HIP_TRY(c, hipSetDevice(c->device));
-    return rounds_waves(c, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+    return short_rounds_by_name(c, ShortRounds::waves, "nlmc_pt_rounds_waves", precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
 }
 
 int nlmc_set_wave_rounds(nlmc_ctx *c, int on)
@@ -3102,19 +3120,14 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
                             int n_pairs)
 {
     if (!c) return NLMC_ERR_ARG;
-    // nlmc_set_wave_rounds and sweeps on the wave kernels: the rounds inside k_rounds_waves, before the lane rule and any fused plan
-    if (c->wave_rounds && !c->knobs.no_deferred && c->ladder_len > 0 && n_rounds > 0 && c->n_chains > 0 && sweeps_per_round >= 1 &&
-        (precision == NLMC_F32 || precision == NLMC_F64) && n_pairs >= 1 && n_pairs <= c->ladder_len - 1 && waves_route(c, c->n_chains, precision) &&
-        !rounds_waves_refusal(c, precision, n_rounds, sweeps_per_round, round0, seed, n_pairs)) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        return rounds_waves(c, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
-    }
-    // short chains under the lane mode: the rounds inside k_rounds_lanes, before a fused plan is asked for
-    if (ROUNDS_LANES_IN_LAUNCH && !c->knobs.no_deferred && c->ladder_len > 0 && n_rounds > 0 && c->n_chains > 0 && sweeps_per_round >= 1 &&
-        (precision == NLMC_F32 || precision == NLMC_F64) && n_pairs >= 1 && n_pairs <= c->ladder_len - 1 && lanes_route(c, c->n_chains) &&
-        !rounds_lanes_refusal(c, n_rounds, sweeps_per_round, round0, seed, n_pairs)) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        return rounds_lanes(c, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+    // a short-chain route the context's sweeps are on, before any fused plan is asked for: under nlmc_set_wave_rounds the rounds inside
+    // k_rounds_waves where the sweeps go to the wave kernels, then the rounds inside k_rounds_lanes where they go to the lane kernels
+    if (rounds_deferred_quiet_ok(c, precision, n_rounds, sweeps_per_round, n_pairs)) {
+        auto takes = [&](ShortRounds route) { return !short_rounds_refusal(c, route, precision, n_rounds, sweeps_per_round, round0, seed, n_pairs); };
+        if (c->wave_rounds && waves_route(c, c->n_chains, precision) && takes(ShortRounds::waves))
+            return short_rounds(c, ShortRounds::waves, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+        if (ROUNDS_LANES_IN_LAUNCH && lanes_route(c, c->n_chains) && takes(ShortRounds::lanes))
+            return short_rounds(c, ShortRounds::lanes, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
     }
     int fslot = -1, arith = NOT_FUSED;
     { int rc = rounds_check(c, Via::deferred, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs, fslot, arith); if (rc || fslot < 0) return rc; }
@@ -3458,7 +3471,7 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
     if (c->best_on) return no("a best-state record is open: k_apt_rounds_lanes keeps none (run the round step by step with nlmc_best_update)");
     if (c->chain_base != 0 || c->n_chains != c->n_chains_global) return no("the sub-replicas of a temperature must live in one context");
     if (c->rng_stride != 0) return no("random numbers keyed by temperature slot (nlmc_apt_shard) keep the round-by-round route");
-    if (const char *why = rounds_lanes_refusal(c, n_rounds, T, round0, seed, n_pairs, true)) return no(why);
+    if (const char *why = short_rounds_refusal(c, ShortRounds::apt_lanes, precision, n_rounds, T, round0, seed, n_pairs)) return no(why);
     // (M systems, nlmc_apt_systems: a workgroup each; K, W, NP and the LDS carve-up are those of ONE system)
     const int L = c->ladder_len, M = c->apt_systems, K = c->n_chains_global / L / M, P = 64 / L, W = (K + P - 1) / P, NP = L * (K / 2);
     if (W > 16) return no("the system needs more than 16 waves: it does not fit one workgroup");
@@ -3472,15 +3485,13 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
     const void *kfun = apt_lanes_kernel(precision == NLMC_F64, elog);
     const bool log = n_pairs > 0 && c->pt_log.covers(round0, n_rounds, n_pairs);
     int rc = lane_rounds_chunks(c, kfun, A.total, n_rounds, T, sweep0, round0, seed, NLMC_ROUTE_LANES, [&](int at, int k, uint32_t s0, uint32_t r0) -> int {
-        SweepArgs a = sweep_args(c, s0, T, seed, c->pt_tab.p, 2, 0, true);
-        lane_fields(c, a, c->n_chains, A.tab, A.u_off);
-        LaneRoundsArgs q = lane_rounds_args(c, k, r0, n_pairs, (size_t)M * K, log, A.map_off);   // (plan and log rows hold every ladder of the context)
+        LaneLaunchArgs la = lane_launch_args(c, T, seed, s0, k, r0, n_pairs, (size_t)M * K, log, A.tab, A.u_off, A.map_off);   // (plan and log rows hold every ladder of the context)
         LaneAptArgs x{};
         x.n_sub = K; x.n_icm = NP; x.katz = katzgraber ? 1 : 0;
         x.info = want_info ? c->icm_info.p + (size_t)at * M * NP * 2 : nullptr;
         x.lds_wave_bytes = (int)A.wave; x.lds_tab_bytes = (int)A.tab_wave; x.lds_pcol_off = (int)A.pcol_off; x.lds_de_off = (int)A.de_off;
         x.lds_lab_off = (int)A.u_off; x.lab_stride = A.lab_stride;
-        void *kargs[] = {&a, &q, &x};
+        void *kargs[] = {&la.a, &la.q, &x};
         HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)M), dim3((unsigned)(64 * W)), kargs, A.total, c->stream));
         return NLMC_OK;
     });

@@ -13,6 +13,7 @@ import sys
 
 import numpy as np
 
+from . import hostlogic
 from .engine import Engine, RoundPlanner
 
 
@@ -28,6 +29,65 @@ def block_partition(n_global, world, rank):
     count = q + (1 if rank < r else 0)
     base = rank * q + min(rank, r)
     return base, count
+
+
+def run_round_chunks(drv, engs, planners, n_rounds, n_sweeps, eligible, by_name=False, observe=None):
+    """The loop of ShardedTempering.run_rounds and LocalTempering.run_rounds: `n_rounds` rounds of driver `drv` over its contexts
+    `engs` (each owns whole ladders and decides their swaps by itself) and their RoundPlanners, the rest of a planned chunk at a
+    time through the engines' batched rounds call -- pt_rounds_deferred, or pt_rounds_fused with `by_name` -- and through
+    drv.round(), round by round, wherever that does not apply.  It applies where the driver says so (`eligible`), there are swap
+    pairs and planners, every engine has the call, NLMC_NO_DEFERRED is unset (it does not bind calls by name) and every planner's
+    rounds may be batched (RoundPlanner.batchable: the one place that knows which routes may).  Per chunk: every planner still asked
+    plans it and says how many rounds are ready; the smallest number goes to every such engine before any is waited for (the calls
+    are asynchronous); an engine that refuses -- or whose planner has nothing ready -- is not asked again (drv._rounds_refused; the
+    reason is in its rounds_fused_refusal) and runs the same rounds one by one: the planner's sweep, `observe(engine, round)` where
+    given, the swap.  Keeps drv.deferred_calls and drv.rounds_routes (per context: last_rounds_route() after its last batched
+    call, or None), advances drv.sweeps_done / rounds_done and returns the rounds that every context took in batched calls."""
+    call = "pt_rounds_fused" if by_name else "pt_rounds_deferred"
+    if not hasattr(drv, "_rounds_refused"):
+        drv.deferred_calls, drv.rounds_routes, drv._rounds_refused = 0, [None] * len(engs), [False] * len(engs)
+    refused = drv._rounds_refused
+    eligible = bool(eligible and planners and drv.n_pairs > 0 and (by_name or not os.environ.get("NLMC_NO_DEFERRED"))
+                    and all(hasattr(e, call) for e in engs) and all(pl.batchable(n_sweeps, by_name) for pl in planners))
+    done = batched = 0
+    while done < n_rounds:
+        ii = drv.rounds_done - (drv._planner_round0 if planners else 0)
+        if not eligible or not (0 <= ii < planners[0].R) or all(refused):
+            drv.round(n_sweeps)
+            done += 1
+            continue
+        # this chunk's schedules and pair selections (inside whatever the caller times), the same chunk for every context
+        k = n_rounds - done
+        for j, pl in enumerate(planners):
+            if not refused[j]:
+                ready = pl.rounds_ready(ii, by_name)
+                if ready:
+                    k = min(k, ready)
+                else:
+                    refused[j] = True                # (the instance does not take fused windows after all)
+        if all(refused):
+            continue
+        one_by_one = []
+        for j, e in enumerate(engs):
+            if not refused[j] and getattr(e, call)(k, n_sweeps, drv.seed, drv.sweeps_done, drv.rounds_done, drv.n_pairs,
+                                                   precision=drv.precision):
+                drv.rounds_routes[j] = e.last_rounds_route() if hasattr(e, "last_rounds_route") else None
+                drv.deferred_calls += 1
+            else:
+                refused[j] = True
+                one_by_one.append(j)
+        for j in one_by_one:                         # the same k rounds of a context that was refused: round()'s calls
+            for r in range(k):
+                planners[j].sweep(ii + r)
+                if observe is not None:
+                    observe(engs[j], drv.rounds_done + r)
+                engs[j].pt_swap_philox(drv.rounds_done + r, drv.seed, drv.n_pairs, want_log=False)
+        if not one_by_one:
+            batched += k
+        drv.sweeps_done += k * n_sweeps
+        drv.rounds_done += k
+        done += k
+    return batched
 
 
 class ShardedTempering:
@@ -100,7 +160,7 @@ class ShardedTempering:
             if reserve_rounds and self._planner.window and hasattr(self.eng, "plan_reserve_fused"):
                 self.eng.plan_reserve_fused(int(reserve_rounds) * (self._planner.S // self._planner.window), self._planner.window)
             if not lazy:
-                self._planner._plan(0, True)
+                self._planner.prepare(0)
             return
         self.eng.plan_philox(self.sweeps_done, n_sweeps, self.seed, precision=self.precision)
         if n_rounds > 0 and self.n_pairs > 0 and hasattr(self.eng, "pt_plan"):
@@ -165,41 +225,18 @@ class ShardedTempering:
         DESIGN.md section 5).  Otherwise, or with NLMC_NO_PERSISTENT=1 when the engine is created, the engine runs a sweep launch per
         round that decides the previous round's swap in its prologue; eng.last_rounds_route() tells which.  `persistent` (default: the
         environment variable NLMC_PERSISTENT) asks for k_rounds_fused by name (pt_rounds_fused: a refusal instead of the launch per
-        round) and counts the rounds in persistent_rounds instead of deferred_rounds."""
-        done = 0
-        pl = getattr(self, "_planner", None)
+        round) and counts the rounds in persistent_rounds instead of deferred_rounds.  Sweeps that run one chain per lane, or per wave
+        with wave_rounds, need no window: the engine runs such chunks inside k_rounds_lanes / k_rounds_waves, for any round length
+        (not by name: pt_rounds_fused would refuse them and is not asked).  The loop and the rule: run_round_chunks."""
         if persistent is None:
             persistent = bool(os.environ.get("NLMC_PERSISTENT"))
-        # default where it applies (one process, whole ladders, fused windows of one round): nlmc_pt_rounds_deferred, which runs the
-        # chunk in launch or, failing that, as sweep launches that decide the PREVIOUS round's swap in their prologue
-        # (a context whose sweeps run one chain per lane needs no window: pt_rounds_deferred runs its rounds inside k_rounds_lanes)
-        eligible = (pl is not None and self._lt is None and not self.collective and self.n_pairs > 0 and n_sweeps == pl.S
-                    and (pl.window == n_sweeps or (not persistent and pl.lanes()))
-                    and hasattr(self.eng, "pt_rounds_fused") and not getattr(self, "_persistent_refused", False))
-        can = eligible
-        batch = self.eng.pt_rounds_fused if persistent else getattr(self.eng, "pt_rounds_deferred", None)
-        if batch is None or (not persistent and os.environ.get("NLMC_NO_DEFERRED")):
-            can = False
-        while done < n_rounds:
-            ii = self.rounds_done - (self._planner_round0 if pl is not None else 0)
-            if can and 0 <= ii < pl.R:
-                if not (pl._fused_from <= ii < pl._fused_to):
-                    pl._plan(ii, True)                      # this chunk's schedules and pair selections (inside whatever is timed)
-                if pl._fused_from <= ii < pl._fused_to:
-                    k = min(pl._fused_to - ii, n_rounds - done)
-                    if batch(k, n_sweeps, self.seed, self.sweeps_done, self.rounds_done, self.n_pairs, precision=self.precision):
-                        self.sweeps_done += k * n_sweeps
-                        self.rounds_done += k
-                        done += k
-                        if persistent:
-                            self.persistent_rounds = getattr(self, "persistent_rounds", 0) + k
-                        else:
-                            self.deferred_rounds = getattr(self, "deferred_rounds", 0) + k
-                        continue
-                    self._persistent_refused = True          # stop asking; the reason is in eng.rounds_fused_refusal
-                can = False
-            self.round(n_sweeps)
-            done += 1
+        pl = getattr(self, "_planner", None)
+        k = run_round_chunks(self, [self.eng], [pl] if pl is not None else None, n_rounds, n_sweeps,
+                             self._lt is None and not self.collective, by_name=persistent)
+        if persistent:
+            self.persistent_rounds = getattr(self, "persistent_rounds", 0) + k
+        else:
+            self.deferred_rounds = getattr(self, "deferred_rounds", 0) + k
 
     def gather_spins(self):
         """All chains' configurations on every rank (read-out only; not part of a round)."""
@@ -253,8 +290,7 @@ class LocalTempering:
         `track_energies`: every context keeps a per-round log of its chains' tracked energies and temperature slots as the round's
         swap decision sees them (Engine.elog_begin) -- opened by plan() for the rounds it plans, or by energy_log_begin(); one
         observation per round at the same place; energy_log() reads it.  Needs whole ladders per context (ValueError otherwise)."""
-        if wave_rounds and wave_sweeps == "off":
-            raise ValueError("wave_rounds needs wave_sweeps 'auto' or 'force' (the rounds run inside the wave kernels' launches)")
+        hostlogic.check_wave_rounds(wave_rounds, wave_sweeps, needs="wave_sweeps 'auto' or 'force'")
         self.G, self.seed, self.n_pairs, self.precision = int(n_chains_global), int(seed), int(n_pairs), precision
         devs = list(device_ids)
         self.parts = list(parts) if parts is not None else [block_partition(self.G, len(devs), r) for r in range(len(devs))]
@@ -271,12 +307,7 @@ class LocalTempering:
                 else:
                     e = Engine(inst, None, count, device=int(d), chain_base=base, n_chains_global=self.G,
                                own_stream=len(devs) > 1)
-                if lane_sweeps != "off":
-                    e.set_lane_sweeps(lane_sweeps)
-                if wave_sweeps != "off":
-                    e.set_wave_sweeps(wave_sweeps)
-                if wave_rounds:
-                    e.set_wave_rounds(True)
+                hostlogic.set_route_modes(e, lane_sweeps, wave_sweeps, wave_rounds)
                 e.pt_init(np.asarray(beta_list, dtype=np.float64))
                 self.engs.append(e)
         except Exception:
@@ -356,6 +387,13 @@ class LocalTempering:
         for e in self.engs:
             e.pt_log_begin(self.rounds_done, n_rounds, self.n_pairs)
 
+    def _observe(self, e, round_idx):
+        """Round `round_idx` of context e as its swap decision will see it, for the records that are open (track_best, track_energies)."""
+        if self.track_best:
+            e.best_update(round_idx)
+        if self._elog_open:
+            e.elog_update(round_idx)
+
     def round(self, n_sweeps, energy_columns=0, **outputs):
         """Sweeps of every block (launched back to back: the devices work concurrently), then one swap round.  Returns
         the per-context sweep outputs; with NMC slots configured (configure_nmc) every entry is a dict
@@ -373,10 +411,7 @@ class LocalTempering:
             else:
                 o = e.sweep_philox(n_sweeps, self.seed, sweep0=self.sweeps_done, beta=None, precision=self.precision, **outputs)
             if not self.nmc:
-                if self.track_best:
-                    e.best_update(self.rounds_done)
-                if self._elog_open:
-                    e.elog_update(self.rounds_done)
+                self._observe(e, self.rounds_done)
                 outs.append(o)
                 continue
             rec = dict(plain=o, nmc=[])
@@ -405,10 +440,7 @@ class LocalTempering:
             e.track_minimum(False)
             e.set_phase("ALL")
             e.select("all")
-            if self.track_best:                      # (all chains selected again: the NMC chains in the state they carry on)
-                e.best_update(self.rounds_done)
-            if self._elog_open:                      # (behind the NMC chains' phases, before the swap)
-                e.elog_update(self.rounds_done)
+            self._observe(e, self.rounds_done)      # (all chains selected again, the NMC chains in the state they carry on; before the swap)
             outs.append(rec)
         self.sweeps_done += n_sweeps
         if self.nmc:
@@ -426,68 +458,15 @@ class LocalTempering:
 
     def run_rounds(self, n_rounds, n_sweeps):
         """`n_rounds` rounds of `n_sweeps` sweeps + one swap round each, without outputs -- same bits as round(n_sweeps) called
-        n_rounds times, which is what everything that does not qualify falls back to.  ShardedTempering.run_rounds' rule: no NMC
-        slots, swap pairs, every context owns whole ladders, one fused window per round -- or sweeps that run one chain per lane
-        (lane_sweeps: such a chunk needs only its pair selections planned, and the engine runs it inside k_rounds_lanes) or one chain
-        per wave with wave_rounds (likewise, inside k_rounds_waves) -- an engine
-        with pt_rounds_deferred, NLMC_NO_DEFERRED unset.  Every context is handed the rest of its planned chunk at a time (the engine picks the route:
-        Engine.pt_rounds_deferred); the calls are asynchronous, so all contexts have their chunk queued before any of them is
-        waited for.  A context whose engine refuses is not asked again and runs its rounds one by one from then on (whole ladders:
-        the contexts never meet).  Counters: deferred_rounds (rounds every context took in batched calls), deferred_calls, and
-        rounds_routes (per context: last_rounds_route() after its last batched call, or None)."""
-        n_rounds, n_sweeps = int(n_rounds), int(n_sweeps)
-        pls = self._planners
-        if not hasattr(self, "rounds_routes"):
-            self.deferred_rounds, self.deferred_calls = 0, 0
-            self.rounds_routes = [None] * len(self.engs)
-            self._rounds_refused = [False] * len(self.engs)
-        eligible = bool(not self.nmc and self.n_pairs > 0 and self.whole_ladders and pls
-                        and not os.environ.get("NLMC_NO_DEFERRED")
-                        and all(n_sweeps == pl.S and (pl.window == n_sweeps or pl.lanes() or (pl.waves() and getattr(pl.eng, "wave_rounds", False)))
-                            for pl in pls)
-                        and all(hasattr(e, "pt_rounds_deferred") for e in self.engs))
-        done = 0
-        while done < n_rounds:
-            ii = self.rounds_done - (self._planner_round0 if pls else 0)
-            if not eligible or not (0 <= ii < pls[0].R) or all(self._rounds_refused):
-                self.round(n_sweeps)
-                done += 1
-                continue
-            # this chunk's schedules and pair selections, for the contexts that are still asked (the same chunk for all of them)
-            k = n_rounds - done
-            for j, pl in enumerate(pls):
-                if self._rounds_refused[j]:
-                    continue
-                if not (pl._fused_from <= ii < pl._fused_to):
-                    pl._plan(ii, True)
-                if pl._fused_from <= ii < pl._fused_to:
-                    k = min(k, pl._fused_to - ii)
-                else:
-                    self._rounds_refused[j] = True           # (the instance does not take fused windows after all)
-            if all(self._rounds_refused):
-                continue
-            one_by_one = []
-            for j, e in enumerate(self.engs):
-                if not self._rounds_refused[j] and e.pt_rounds_deferred(k, n_sweeps, self.seed, self.sweeps_done, self.rounds_done,
-                                                                        self.n_pairs, precision=self.precision):
-                    self.rounds_routes[j] = e.last_rounds_route() if hasattr(e, "last_rounds_route") else None
-                    self.deferred_calls += 1
-                else:
-                    self._rounds_refused[j] = True           # stop asking; the reason is in e.rounds_fused_refusal
-                    one_by_one.append(j)
-            for j in one_by_one:                             # the same k rounds of a context that was refused: round()'s two calls
-                for r in range(k):
-                    pls[j].sweep(ii + r)
-                    if self.track_best:
-                        self.engs[j].best_update(self.rounds_done + r)
-                    if self._elog_open:
-                        self.engs[j].elog_update(self.rounds_done + r)
-                    self.engs[j].pt_swap_philox(self.rounds_done + r, self.seed, self.n_pairs, want_log=False)
-            if not one_by_one:
-                self.deferred_rounds += k
-            self.sweeps_done += k * n_sweeps
-            self.rounds_done += k
-            done += k
+        n_rounds times, which is what everything that does not qualify falls back to.  ShardedTempering.run_rounds' loop and rule
+        (run_round_chunks) over contexts without NMC slots that own whole ladders: one fused window per round -- or sweeps that run
+        one chain per lane (lane_sweeps: such a chunk needs only its pair selections planned, and the engine runs it inside
+        k_rounds_lanes) or one chain per wave with wave_rounds (likewise, inside k_rounds_waves); the engine picks the route
+        (Engine.pt_rounds_deferred).  A context whose engine refuses is not asked again and runs its rounds one by one from then on
+        (whole ladders: the contexts never meet).  Counters: deferred_rounds (rounds every context took in batched calls),
+        deferred_calls, and rounds_routes (per context: last_rounds_route() after its last batched call, or None)."""
+        self.deferred_rounds = getattr(self, "deferred_rounds", 0) + run_round_chunks(
+            self, self.engs, self._planners, int(n_rounds), int(n_sweeps), not self.nmc and self.whole_ladders, observe=self._observe)
 
     def slots(self):
         if len(self.engs) == 1 or not self.whole_ladders:

@@ -52,6 +52,11 @@ def _beta_table(beta, R, S):
     raise ValueError("pass a scalar or a 2-D table; use per_chain()/per_sweep() helpers for 1-D inputs")
 
 
+def _precision(precision):
+    """ "f32" / "f64" -> the library's NLMC_F32 / NLMC_F64 (KeyError for anything else)."""
+    return {"f32": _abi.F32, "f64": _abi.F64}[precision]
+
+
 class Engine:
     n_systems = 1            # independent APT systems the ladders are divided into (apt_systems; pt_init resets it)
 
@@ -214,7 +219,7 @@ class Engine:
             tab, cs, ss = _beta_table(beta, R, S)
             tabp = _abi.ptr(tab)
         o = self._outputs(S, record_stride, want_energy, want_min, want_state)
-        prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
+        prec = _precision(precision)
         om = {"shared": _abi.ORDER_SHARED, "per_chain": _abi.ORDER_PER_CHAIN}[order]
         self._ck(self._L.nlmc_sweep_philox(self._ctx, prec, om, S, int(sweep0) & 0xFFFFFFFF, int(seed), tabp, cs, ss,
                                            max(1, record_stride), _abi.ptr(o["spins"]), _abi.ptr(o["energy"]),
@@ -320,9 +325,8 @@ class Engine:
                 and 0 <= (int(sweep0) - a.sweep0) // max(1, S) < a.R
                 and sweeps_per_plan_piece(self.fused_plan_bytes(a.window), S, a.window, budget, record_stride) == S):
             ii = (int(sweep0) - a.sweep0) // S          # launch ii of the run announced with plan_ahead: its windows are (or get)
-            if not (a._fused_from <= ii < a._fused_to):  # planned together with those of the launches that follow
-                a._plan(ii, True)
-            if a._fused_from <= ii < a._fused_to:
+            a.prepare(ii)                                # planned together with those of the launches that follow
+            if a.fused_covers(ii):
                 o = self.sweep_philox(S, seed, sweep0=sweep0, beta=beta, record_stride=record_stride, want_energy=want_energy,
                                       want_min=want_min, want_state=want_state, precision=precision)
                 self.fused_last_call = self._last_fused()
@@ -340,7 +344,7 @@ class Engine:
         b = None if beta is None else np.asarray(beta, dtype=np.float64)
         outs, fused, ran_fused = [], True, True
         if a is not None:                    # this call plans into the slot the announced run's windows live in: they are gone
-            a._fused_from = a._fused_to = 0
+            a.drop_windows()
             self.plan_slot(a.slot)
         for t0 in range(0, S, per_piece):
             t1 = min(S, t0 + per_piece)
@@ -372,8 +376,7 @@ class Engine:
                                    fused_outputs=True)
 
     def plan_philox(self, sweep0, n_sweeps, seed, precision="f32"):
-        prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
-        self._ck(self._L.nlmc_plan_philox(self._ctx, prec, _abi.ORDER_SHARED, int(sweep0), int(n_sweeps), int(seed)))
+        self._ck(self._L.nlmc_plan_philox(self._ctx, _precision(precision), _abi.ORDER_SHARED, int(sweep0), int(n_sweeps), int(seed)))
 
     def plan_philox_fused(self, sweep0, n_windows, window, seed):
         """Fused-window schedules for `n_windows` launches of exactly `window` sweeps (include/nlmc.h).  Returns the
@@ -527,19 +530,23 @@ class Engine:
     def pt_plan(self, round0, n_rounds, seed, n_pairs):
         self._ck(self._L.nlmc_pt_plan(self._ctx, int(round0), int(n_rounds), int(seed), int(n_pairs)))
 
-    def pt_rounds_fused(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
-        """n_rounds whole rounds (sweeps + swap round) inside cooperative launches (include/nlmc.h: nlmc_pt_rounds_fused), in any of the
-        three arithmetics: "f32", "f64" on dyadic instances, "f64" on real-valued ones with set_fused_f64_real on.  True when the
-        rounds were queued, False when the context / plans do not qualify (nothing was run: drive the rounds one by one; the reason
-        is in rounds_fused_refusal)."""
-        prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
-        rc = self._L.nlmc_pt_rounds_fused(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
-                                          int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs))
+    def _rounds_call(self, fn, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision, *more):
+        """One call of a rounds entry point of the library (they share their leading arguments; `more`: what follows them).  True when
+        the rounds were queued; False, with the library's reason in rounds_fused_refusal, when it answers NLMC_ERR_UNSUPPORTED."""
+        rc = fn(self._ctx, _precision(precision), int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
+                int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs), *more)
         if rc == _abi.ERR_UNSUPPORTED:
             self.rounds_fused_refusal = _abi.lib().nlmc_last_error(self._ctx).decode()
             return False
         self._ck(rc)
         return True
+
+    def pt_rounds_fused(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
+        """n_rounds whole rounds (sweeps + swap round) inside cooperative launches (include/nlmc.h: nlmc_pt_rounds_fused), in any of the
+        three arithmetics: "f32", "f64" on dyadic instances, "f64" on real-valued ones with set_fused_f64_real on.  True when the
+        rounds were queued, False when the context / plans do not qualify (nothing was run: drive the rounds one by one; the reason
+        is in rounds_fused_refusal)."""
+        return self._rounds_call(self._L.nlmc_pt_rounds_fused, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision)
 
     def pt_rounds_deferred(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
         """n_rounds rounds on the route that fits (include/nlmc.h: nlmc_pt_rounds_deferred): inside k_rounds_fused launches where all
@@ -547,28 +554,14 @@ class Engine:
         swap launch; last_rounds_route() tells which.  Real-valued "f64" instances (set_fused_f64_real) keep the launch per round
         by default (include/nlmc.h says why); pt_rounds_fused asks for their k_rounds_fused variant by name.  True when queued, False
         when the context / plans do not qualify.  What LocalTempering.run_rounds and ShardedTempering.run_rounds call."""
-        prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
-        rc = self._L.nlmc_pt_rounds_deferred(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
-                                             int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs))
-        if rc == _abi.ERR_UNSUPPORTED:
-            self.rounds_fused_refusal = _abi.lib().nlmc_last_error(self._ctx).decode()
-            return False
-        self._ck(rc)
-        return True
+        return self._rounds_call(self._L.nlmc_pt_rounds_deferred, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision)
 
     def pt_rounds_lanes(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
         """n_rounds whole rounds of short chains inside k_rounds_lanes launches, whatever the lane mode is (include/nlmc.h:
         nlmc_pt_rounds_lanes): a chain per lane, a ladder of at most 64 temperatures inside one wave, n <= 1024, pair selections planned
         (pt_plan), no fused-window plan.  True when the rounds were queued, False when the context does not qualify (nothing was run;
         the reason is in rounds_fused_refusal).  pt_rounds_deferred takes this route by itself under set_lane_sweeps("force")."""
-        prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
-        rc = self._L.nlmc_pt_rounds_lanes(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
-                                          int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs))
-        if rc == _abi.ERR_UNSUPPORTED:
-            self.rounds_fused_refusal = _abi.lib().nlmc_last_error(self._ctx).decode()
-            return False
-        self._ck(rc)
-        return True
+        return self._rounds_call(self._L.nlmc_pt_rounds_lanes, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision)
 
     def pt_rounds_waves(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
         """n_rounds whole rounds of short chains inside k_rounds_waves launches, whatever the wave mode is (include/nlmc.h:
@@ -576,14 +569,7 @@ class Engine:
         f32 only, n <= 256, pair selections planned (pt_plan), no fused-window plan.  True when the rounds were queued, False when
         the context does not qualify (nothing was run; the reason is in rounds_fused_refusal).  pt_rounds_deferred takes this route
         by itself under set_wave_sweeps("force") with set_wave_rounds(True)."""
-        prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
-        rc = self._L.nlmc_pt_rounds_waves(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
-                                          int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs))
-        if rc == _abi.ERR_UNSUPPORTED:
-            self.rounds_fused_refusal = _abi.lib().nlmc_last_error(self._ctx).decode()
-            return False
-        self._ck(rc)
-        return True
+        return self._rounds_call(self._L.nlmc_pt_rounds_waves, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision)
 
     def apt_rounds_lanes(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, katzgraber=True, precision="f32",
                          want_info=False):
@@ -594,15 +580,10 @@ class Engine:
         rounds_fused_refusal); info [n_rounds, L * (K // 2), 2] = {n_components, picked size} with want_info (a read-back: it
         synchronises the stream), else None.  Same bits as sweep_philox(beta=None) + icm_round_ladders + pt_swap_philox round by round.
         Under apt_systems(M): a workgroup per system, K the ladders of one system, info [n_rounds, M * L * (K // 2), 2]."""
-        prec = {"f32": _abi.F32, "f64": _abi.F64}[precision]
         info = np.zeros((int(n_rounds), self._icm_rows(), 2), np.int32) if want_info else None
-        rc = self._L.nlmc_apt_rounds_lanes(self._ctx, prec, int(n_rounds), int(sweeps_per_round), int(sweep0) & 0xFFFFFFFF,
-                                           int(round0) & 0xFFFFFFFF, int(seed), int(n_pairs), int(bool(katzgraber)), _abi.ptr(info))
-        if rc == _abi.ERR_UNSUPPORTED:
-            self.rounds_fused_refusal = _abi.lib().nlmc_last_error(self._ctx).decode()
-            return False, None
-        self._ck(rc)
-        return True, info
+        queued = self._rounds_call(self._L.nlmc_apt_rounds_lanes, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision,
+                                   int(bool(katzgraber)), _abi.ptr(info))
+        return queued, (info if queued else None)
 
     def last_rounds_route(self):
         """The route the last pt_rounds_fused / pt_rounds_deferred / pt_rounds_lanes / pt_rounds_waves / apt_rounds_lanes call that ran
@@ -932,7 +913,9 @@ class RoundPlanner:
     only), a bounded number of rounds at a time.  Rounds whose sweeps need no per-sweep output run on the fused-window
     schedule when the instance qualifies (one or more launches of `window` sweeps), everything else on the
     sweep-by-sweep schedule; the results are the same bits either way.  With `pt_pairs` > 0 the pair selections of the
-    swap rounds `pt_round0 + ii` (they depend on the RNG only, too) are planned with every chunk."""
+    swap rounds `pt_round0 + ii` (they depend on the RNG only, too) are planned with every chunk.  The planner is also the one place
+    that says which route its rounds take (route) and whether a chunk of them may go to the engine's batched rounds call (batchable,
+    rounds_ready); its planned ranges are private."""
 
     BYTES_PER_UPDATE = 140              # packed schedule: head 8 + row window 128 + scratch
 
@@ -951,66 +934,96 @@ class RoundPlanner:
         if chunk_rounds:
             self.chunk = max(1, min(self.chunk, int(chunk_rounds)))
         self.pt_pairs, self.pt_round0 = int(pt_pairs), int(pt_round0)
-        self._fused_from = self._fused_to = self._plain_from = self._plain_to = 0      # planned round ranges
+        # planned round ranges [from, to): fused windows, the sweep-by-sweep schedule, and -- on the short-chain routes, which need no
+        # level schedule -- the pair selections alone
+        self._fused = self._plain = self._pairs = (0, 0)
         self.chunks_planned = 0
 
-    def lanes(self):
-        """Whether the engine runs this planner's sweeps one chain per lane (Engine.lanes_take): such rounds need no level schedule,
-        fused or plain -- a chunk is planned once its pair selections are -- and may go to the engine's batched rounds call."""
-        return hasattr(self.eng, "lanes_take") and bool(self.eng.lanes_take())
+    SHORT_CHAIN = ("lanes", "wave rounds", "waves")
 
-    def waves(self):
-        """Whether the engine runs this planner's sweeps one chain per wave (Engine.waves_take): such rounds need no level schedule
-        either, and go round by round through the sweep calls unless the engine's wave_rounds is on (Engine.set_wave_rounds: the
-        batched rounds call then runs a chunk inside k_rounds_waves)."""
-        return hasattr(self.eng, "waves_take") and bool(self.eng.waves_take(precision=self.precision))
+    def route(self):
+        """The route this planner's rounds take, decided here and nowhere else: "lanes" (the engine runs the sweeps one chain per lane,
+        Engine.lanes_take), "wave rounds" (one chain per wave, Engine.waves_take, with the engine's wave_rounds on), "waves" (one chain
+        per wave, round by round through the sweep calls), "windows" (fused windows of `window` sweeps) or "plain" (the sweep-by-sweep
+        schedule; also what "windows" becomes once the engine has turned a window plan down).  The three short-chain routes need no
+        level schedule: a chunk is planned once its pair selections are."""
+        e = self.eng
+        if hasattr(e, "lanes_take") and e.lanes_take():
+            return "lanes"
+        if hasattr(e, "waves_take") and e.waves_take(precision=self.precision):
+            return "wave rounds" if getattr(e, "wave_rounds", False) else "waves"
+        return "windows" if self.window else "plain"
 
-    def _plan(self, ii, want_fused):
+    def _batchable(self, route, n_sweeps, by_name):
+        if int(n_sweeps) != self.S:
+            return False
+        return (route == "windows" and self.window == self.S) or (not by_name and route in ("lanes", "wave rounds"))
+
+    def batchable(self, n_sweeps, by_name=False):
+        """Whether a chunk of rounds of `n_sweeps` sweeps may go to the engine's batched rounds call (Engine.pt_rounds_deferred): rounds
+        of the planned length on one fused window each, or on a short-chain route the engine runs whole rounds on (k_rounds_lanes,
+        k_rounds_waves).  `by_name`: the caller asks for Engine.pt_rounds_fused, which takes the fused-window route only."""
+        return self._batchable(self.route(), n_sweeps, by_name)
+
+    def _planned(self, ii, route):
+        a, b = self._pairs if route in self.SHORT_CHAIN else self._fused if route == "windows" else self._plain
+        return a <= ii < b
+
+    def rounds_ready(self, ii, by_name=False):
+        """Plan the chunk that holds round ii unless it is planned, and return how many rounds from ii on are ready for the batched
+        rounds call: 0 when the planner's rounds are not batchable(), when ii lies outside the planned rounds, and once the engine has
+        turned fused windows down."""
+        route = self.route()
+        if not (0 <= ii < self.R) or not self._batchable(route, self.S, by_name):
+            return 0
+        if not self._planned(ii, route):
+            self._plan(ii, route)
+        return (self._pairs if route in self.SHORT_CHAIN else self._fused)[1] - ii if self._planned(ii, route) else 0
+
+    def prepare(self, ii):
+        """Plan the chunk that starts at round ii unless round ii is planned: its pair selections and the level schedules the route
+        needs -- none on a short-chain route; fused windows on "windows", and if the engine turns them down the sweep-by-sweep
+        schedule, now and from then on; the sweep-by-sweep schedule on "plain"."""
+        route = self.route()
+        if not self._planned(ii, route):
+            self._plan(ii, route)
+
+    def fused_covers(self, ii):
+        """Whether fused windows are planned for round ii."""
+        return self._fused[0] <= ii < self._fused[1]
+
+    def drop_windows(self):
+        """The planned fused windows are gone (another planning call wrote to the engine's plan slot)."""
+        self._fused = (0, 0)
+
+    def _plan(self, ii, route):
         r0, r1 = ii, min(self.R, ii + self.chunk)
         self.chunks_planned += 1
         if self.pt_pairs > 0 and hasattr(self.eng, "pt_plan"):
             self.eng.pt_plan(self.pt_round0 + r0, r1 - r0, self.seed, self.pt_pairs)
-        if self.lanes():
-            self._fused_from, self._fused_to = self._plain_from, self._plain_to = r0, r1
-            return True
-        if self.waves() and getattr(self.eng, "wave_rounds", False):   # ... and the engine's batched rounds call takes the chunk (k_rounds_waves)
-            self._fused_from, self._fused_to = self._plain_from, self._plain_to = r0, r1
-            return True
-        if self.waves():                 # a chain per wave: nothing to plan but the chunk's pair selections, no window to ask for
-            self.window = 0
-            self._plain_from, self._plain_to = r0, r1
-            return False
-        if want_fused and self.window:
+        if route in self.SHORT_CHAIN:    # a chain per lane or per wave: nothing to plan but the chunk's pair selections
+            self._pairs = (r0, r1)
+            return
+        if route == "windows":
             if hasattr(self.eng, "plan_slot"):
                 self.eng.plan_slot(self.slot)
             k = self.eng.plan_philox_fused(self.sweep0 + r0 * self.S, (r1 - r0) * (self.S // self.window), self.window, self.seed)
             if k == (r1 - r0) * (self.S // self.window):
-                self._fused_from, self._fused_to = r0, r1
-                return True
+                self._fused = (r0, r1)
+                return
             self.window = 0              # the instance does not qualify: stop asking
-        if not want_fused or not self.window:
-            self.eng.plan_philox(self.sweep0 + r0 * self.S, (r1 - r0) * self.S, self.seed, precision=self.precision)
-            self._plain_from, self._plain_to = r0, r1
-        return False
+        self.eng.plan_philox(self.sweep0 + r0 * self.S, (r1 - r0) * self.S, self.seed, precision=self.precision)
+        self._plain = (r0, r1)
 
     def sweep(self, ii, **outputs):
         """The sweeps of round ii at the PT ladder temperatures.  `outputs`: record_stride / want_* of sweep_philox."""
-        needs_plain = any(outputs.get(k) for k in ("record_stride", "want_energy", "want_min", "want_state")) and not self.fused_outputs
+        needs_plain = bool(outputs) and not self.fused_outputs and any(outputs.get(k) for k in ("record_stride", "want_energy", "want_min", "want_state"))
         if self.S == 0:
             return self.eng.sweep_philox(0, self.seed, sweep0=self.sweep0, beta=self.beta, precision=self.precision, **outputs)
-        if self.lanes():                                     # a chain per lane: nothing to plan but the chunk's pair selections
-            if not (self._fused_from <= ii < self._fused_to):
-                self._plan(ii, True)
-            return self.eng.sweep_philox(self.S, self.seed, sweep0=self.sweep0 + ii * self.S, beta=self.beta, precision=self.precision,
-                                         **outputs)
-        if not needs_plain and self.window:
-            if not (self._fused_from <= ii < self._fused_to):
-                self._plan(ii, True)
-            if self._fused_from <= ii < self._fused_to:      # one call: the library walks the windows of the round
-                return self.eng.sweep_philox(self.S, self.seed, sweep0=self.sweep0 + ii * self.S, beta=self.beta,
-                                             precision=self.precision, **outputs)
-        if not (self._plain_from <= ii < self._plain_to) and not needs_plain:
-            self._plan(ii, False)
-        # (a round with outputs outside the planned range builds its schedule inside the call)
+        route = self.route()
+        if (not needs_plain or route in self.SHORT_CHAIN) and not self._planned(ii, route):
+            self._plan(ii, route)
+        # (a round with outputs outside the planned range builds its schedule inside the call; one call either way: on fused windows
+        # the library walks the windows of the round)
         return self.eng.sweep_philox(self.S, self.seed, sweep0=self.sweep0 + ii * self.S, beta=self.beta, precision=self.precision,
                                      **outputs)

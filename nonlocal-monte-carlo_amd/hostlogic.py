@@ -31,6 +31,40 @@ def draw_legacy_stream(n_sweeps, n):
     return perm, u
 
 
+def check_wave_rounds(wave_rounds, waves, needs="waves='auto' or 'force'"):
+    """wave_rounds without wave sweeps: ValueError.  `needs`: how the caller's keyword is spelled in the message."""
+    if wave_rounds and waves == "off":
+        raise ValueError(f"wave_rounds needs {needs} (the rounds run inside the wave kernels' launches)")
+
+
+def check_route_keywords(lanes="off", waves="off", wave_rounds=False, rng=None, precision="f32"):
+    """The `lanes` / `waves` / `wave_rounds` keywords of NPT, APT_ICM and APT_preprocessor.  rng None (a constructor that does not know
+    its backend yet): the mode values only; otherwise also what they need of `rng` and `precision`."""
+    for name, mode in (("lanes", lanes), ("waves", waves)):
+        if mode not in ("off", "auto", "force"):
+            raise ValueError(f"{name} must be 'off', 'auto' or 'force'")
+    if rng is None:
+        return
+    for name, mode in (("lanes", lanes), ("waves", waves)):
+        if mode != "off" and rng != "philox":
+            raise ValueError(f"{name} applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
+    if waves != "off" and precision == "f64":
+        raise ValueError("waves applies to precision='f32' (the wave-per-chain sweeps have no fp64 arithmetic)")
+    check_wave_rounds(wave_rounds, waves)
+    if wave_rounds and precision == "f64":
+        raise ValueError("wave_rounds applies to precision='f32' (the wave-per-chain kernels have no fp64 arithmetic)")
+
+
+def set_route_modes(eng, lanes="off", waves="off", wave_rounds=False):
+    """Engine.set_lane_sweeps / set_wave_sweeps / set_wave_rounds of a fresh engine, for the modes that are not the default."""
+    if lanes != "off":
+        eng.set_lane_sweeps(lanes)
+    if waves != "off":
+        eng.set_wave_sweeps(waves)
+    if wave_rounds:
+        eng.set_wave_rounds(True)
+
+
 def phase_flags(n, m_init, clusters, phase):
     """Flags realising the three NMC phases (NMC/nmc.py:377-381, 398-401, 419-421):
        'C'  : cluster rows of (J,h) / temp_x, every other spin frozen by h = 10000 * m_init

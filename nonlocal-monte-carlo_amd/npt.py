@@ -45,23 +45,11 @@ class NPT(Common):
         Plain replicas only."""
         if precision not in ("f32", "f64"):
             raise ValueError("precision must be 'f32' or 'f64'")
-        if lanes not in ("off", "auto", "force"):
-            raise ValueError("lanes must be 'off', 'auto' or 'force'")
-        if waves not in ("off", "auto", "force"):
-            raise ValueError("waves must be 'off', 'auto' or 'force'")
+        hostlogic.check_route_keywords(lanes, waves)
         super().__init__(J, h, rng=rng, seed=seed, device=device, lbp=lbp)
         if precision != "f32" and self.rng != "philox":
             raise ValueError("precision applies to rng='philox' (rng='numpy' runs the reference's own arithmetic)")
-        if lanes != "off" and self.rng != "philox":
-            raise ValueError("lanes applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
-        if waves != "off" and self.rng != "philox":
-            raise ValueError("waves applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
-        if waves != "off" and precision == "f64":
-            raise ValueError("waves applies to precision='f32' (the wave-per-chain sweeps have no fp64 arithmetic)")
-        if wave_rounds and waves == "off":
-            raise ValueError("wave_rounds needs waves='auto' or 'force' (the rounds run inside the wave kernels' launches)")
-        if wave_rounds and precision == "f64":
-            raise ValueError("wave_rounds applies to precision='f32' (the wave-per-chain kernels have no fp64 arithmetic)")
+        hostlogic.check_route_keywords(lanes, waves, wave_rounds, rng=self.rng, precision=precision)
         self.precision = precision
         self.lanes = lanes
         self.waves = waves

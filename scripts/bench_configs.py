@@ -62,7 +62,7 @@ def c3():
     G = L * NL
     eng = P.Engine(J, h, G)
     eng.set_spins(init_spins(G, N)); eng.pt_init(np.geomspace(0.1, 3.0, L))
-    planner = P.engine.RoundPlanner(eng, 0, rounds + 1, S, 3); planner._plan(0, True); eng.pt_plan(0, rounds + 1, 3, pairs)
+    planner = P.engine.RoundPlanner(eng, 0, rounds + 1, S, 3); planner.prepare(0); eng.pt_plan(0, rounds + 1, 3, pairs)
     planner.sweep(0); eng.pt_swap_philox(0, 3, pairs, want_log=False); eng.energy()
     def run():
         for r in range(1, rounds + 1):
@@ -81,7 +81,7 @@ def c5():
     G = R * K
     eng = P.Engine(J, h, G)
     eng.set_spins(init_spins(G, N)); eng.pt_init(np.geomspace(0.05, 4.0, R))
-    planner = P.engine.RoundPlanner(eng, 0, rounds + 1, S, 5, budget_bytes=8 << 30); planner._plan(0, True); eng.pt_plan(0, rounds + 1, 5, 10)
+    planner = P.engine.RoundPlanner(eng, 0, rounds + 1, S, 5, budget_bytes=8 << 30); planner.prepare(0); eng.pt_plan(0, rounds + 1, 5, 10)
     def one(r):
         planner.sweep(r)
         eng.icm_round_ladders(r, 5, True)

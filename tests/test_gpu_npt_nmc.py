@@ -70,8 +70,8 @@ def test_rounds_with_nmc_slots_match_the_oracle_at_c3_size(product):
         for ii in range(rounds):
             outs = lt.round(S, record_stride=1, want_energy=True)[0]
             # both sweep paths ran on fused windows (plan slots 0 and 1)
-            assert lt._planners[0]._fused_from <= ii < lt._planners[0]._fused_to
-            assert lt._nmc_planners[0]._fused_from <= ii * 3 < lt._nmc_planners[0]._fused_to
+            assert lt._planners[0].fused_covers(ii)
+            assert lt._nmc_planners[0].fused_covers(ii * 3)
             pc, nc = outs["plain_chains"], outs["nmc_chains"]
             assert len(pc) == (R - n_nmc) * n_restarts and len(nc) == n_nmc * n_restarts
             assert np.array_equal(np.sort(np.concatenate([pc, nc])), np.arange(G))
