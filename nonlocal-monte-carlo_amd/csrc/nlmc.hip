@@ -450,6 +450,21 @@ void begin_sweep_call(nlmc_ctx *c)
     c->launches_sweep = 0;
 }
 
+// k launches of the open sweep call are on their stream (a chunk of k rounds in one launch counts k); `timed`: inside a timer span
+void count_launches(nlmc_ctx *c, int k, bool timed)
+{
+    c->launches_sweep += k;
+    c->launches_total += k;
+    if (timed) c->launches_timed += k;
+}
+
+// c->n_cu, asked of the device once
+int cu_count(nlmc_ctx *c)
+{
+    if (c->n_cu == 0) HIP_TRY(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+    return NLMC_OK;
+}
+
 // elapsed (levelize, sweep) milliseconds of triple t
 int triple_ms(nlmc_ctx *c, size_t t, float &lev, float &sw)
 {
@@ -848,20 +863,54 @@ struct SweepOut {
     int8_t *out_argmin_state;
 };
 
-// One fused window on arithmetic `arith` (fused_route).  `outs`: the launch also produces per-sweep outputs into the context's device
-// buffers (etrace / emin / argmin / best / strace, sized by the caller) as sweeps [t0, t0 + T) of a call of n_total sweeps.  `defer`
-// (nullable): the previous round's swap decided in this launch's prologue (plain chains, no outputs: checked by the caller).
-int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, const double *tab_dev, int tab_cs, int tab_ss, bool use_slots,
-              bool outs, bool want_energy, bool want_min, bool want_state, int rec, int t0, int n_total, int arith,
-              const DeferSwap *defer = nullptr, double *sink_override = nullptr)
+// What a sweep call is, built once per call (run_sweeps, nlmc_pt_rounds_deferred) and read by the route drivers: n_sweeps sweeps from
+// sweep0 on, the temperatures (`tab` with strides tab_cs / tab_ss; use_slots: its rows by temperature slot), the caller's orders and
+// uniforms (stream mode), and what the sweeps leave in the context's device buffers besides the state (run_sweeps derives these from
+// the caller's SweepOut): the energy trace, the running minimum, its state, a configuration every `rec` sweeps (0: none).
+struct SweepCall {
+    bool stream_mode; int precision, order_mode, n_sweeps; uint32_t sweep0; uint64_t seed;
+    const double *tab; int tab_cs, tab_ss; bool use_slots;
+    const uint32_t *keys_dev; const double *ustream_dev;
+    bool want_energy, want_min, want_state; int rec;
+    // per-sweep outputs, or a temperature per sweep: the output variant of the fused kernels
+    bool outs() const { return want_energy || want_min || rec != 0 || tab_ss != 0; }
+    int per_chain() const { return (stream_mode || order_mode == NLMC_ORDER_PER_CHAIN) ? 1 : 0; }
+};
+
+// sweep_args of the window of w sweeps that starts `at` sweeps into the call
+SweepArgs window_args(const nlmc_ctx *c, const SweepCall &s, int at, int w)
+{
+    return sweep_args(c, s.sweep0 + (uint32_t)at, w, s.seed, s.tab + (size_t)at * s.tab_ss, s.tab_cs, s.tab_ss, s.use_slots);
+}
+
+// The per-sweep output fields of a launch whose sweeps are [t0, t0 + a.n_sweeps) of the call's: rows of the traces, the running minimum
+// and its state in the context's device buffers (sized by run_sweeps).  `outs` false (the plain fused variant): none of them, a trace
+// of the launch's own sweeps.
+void sweep_outputs(const nlmc_ctx *c, const SweepCall &s, bool outs, int t0, SweepArgs &a)
+{
+    a.trace_sweeps = outs ? s.n_sweeps : a.n_sweeps;
+    a.t0 = t0;
+    a.rec_stride = s.rec ? s.rec : 1;
+    if (!outs) return;
+    a.etrace = s.want_energy ? c->etrace.p : nullptr;
+    a.strace = s.rec ? c->strace.p : nullptr;
+    a.emin = s.want_min ? c->emin.p : nullptr;
+    a.best = (s.want_min && s.want_state) ? c->best.p : nullptr;
+}
+
+// One fused window on arithmetic `arith` (fused_route): window w of plan `slot`, `at` sweeps into the call.  Where the call has
+// per-sweep outputs (SweepCall::outs) the launch also produces them, as sweeps [at, at + T) of the call.  `defer` (nullable): the
+// previous round's swap decided in this launch's prologue (plain chains, no outputs: checked by the caller).
+int run_fused(nlmc_ctx *c, const SweepCall &s, int slot, int w, int at, int arith, const DeferSwap *defer = nullptr,
+              double *sink_override = nullptr)
 {
     const nlmc_ctx::FusedPlan &P = c->fz[slot];
     const int R = c->sub_count(), T = P.T;
-    const bool real = arith == ARITH_R64;
+    const bool real = arith == ARITH_R64, outs = s.outs();
     if (real && !P.has_val) return fail(c, NLMC_ERR_STATE, "run_fused: the plan has no fp64 value plane");
     // per-sweep outputs: three snapshot slots in LDS when they fit beside the threshold tables, in global memory otherwise
     // (phase flags: K0 and K1; a temperature per sweep: one table per threshold slot)
-    const int kt = arith == ARITH_F64 ? (c->has_flags ? 2 : tab_ss != 0 ? 3 : 1) * (2 * c->xmax + 1) : 0;
+    const int kt = arith == ARITH_F64 ? (c->has_flags ? 2 : s.tab_ss != 0 ? 3 : 1) * (2 * c->xmax + 1) : 0;
     const bool snap_lds = outs && fused_lds(c->n_pad, c->has_flags, true, P.fmt == NLMC_FMT_ADDR, kt).total <= (size_t)150 * 1024;
     const FusedLds L = fused_lds(c->n_pad, c->has_flags, snap_lds, P.fmt == NLMC_FMT_ADDR, kt);
     if (outs && !snap_lds) HIP_TRY(c, c->snap_g.reserve((size_t)R * (3 * (size_t)c->n_pad + 16)));
@@ -873,7 +922,7 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
     const bool timed = c->ev_accumulate && (c->ev_every <= 1 || c->launches_total % c->ev_every == 0);
     TimerSpan ts;
     if (timed) { int rc = span_begin(c, ts, 1, c->cur); if (rc) return rc; }
-    SweepArgs a = sweep_args(c, sweep0, T, seed, tab_dev, tab_cs, tab_ss, use_slots);
+    SweepArgs a = window_args(c, s, at, T);
     fused_args(c, P, L, a);
     const nlmc_ctx::FusedPlan::Arrays A = P.at(w);
     a.lvl_off = A.loff; a.nlev = A.nlev; a.hi_max = A.himax; a.fsend = A.send;
@@ -885,15 +934,7 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
     }
     a.energy_sink = sink_override ? sink_override : c->energy_sink;
     if (defer) a.defer = *defer;
-    a.trace_sweeps = outs ? n_total : T;
-    a.t0 = t0;
-    a.rec_stride = rec ? rec : 1;
-    if (outs) {
-        a.etrace = want_energy ? c->etrace.p : nullptr;
-        a.strace = rec ? c->strace.p : nullptr;
-        a.emin = want_min ? c->emin.p : nullptr;
-        a.best = (want_min && want_state) ? c->best.p : nullptr;
-    }
+    sweep_outputs(c, s, outs, outs ? at : 0, a);
     a.snap_g = (outs && !snap_lds) ? c->snap_g.p : nullptr;
     a.fz_val = real ? A.val : nullptr;
     { int rc = stamps_arm(c, a, R, c->cur); if (rc) return rc; }
@@ -901,9 +942,7 @@ int run_fused(nlmc_ctx *c, int slot, int w, uint32_t sweep0, uint64_t seed, cons
     HIP_TRY(c, hipLaunchKernel(kfun, dim3(R), dim3(fused_block(c)), kargs, L.total, c->cur));
     HIP_TRY(c, hipGetLastError());
     { int rc = span_end(c, ts); if (rc) return rc; }
-    if (timed) c->launches_timed++;
-    c->launches_sweep++;
-    c->launches_total++;
+    count_launches(c, 1, timed);
     c->stat_fused_window = w;
     c->stat_fused_slot = slot;
     return NLMC_OK;
@@ -1022,24 +1061,29 @@ const void *big_kernel(bool per_level, bool stream_mode, bool f64)
     return table[per_level ? 1 : 0][stream_mode ? 0 : f64 ? 1 : 2];
 }
 
+// What the routes with schedule or order scratch (sweep by sweep, short chains) do first: the scratch is shared with whatever the main
+// stream is sweeping, so a call on the second stream waits for it; and an order per chain has no rows for a chain subset.  (Not the
+// fused route: its plans are read-only.)
+int scratch_route_begin(nlmc_ctx *c, const SweepCall &s)
+{
+    if (c->cur != c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (s.per_chain() && c->subset != 0) return fail(c, NLMC_ERR_UNSUPPORTED, "chain subsets run shared-order philox sweeps only");
+    return NLMC_OK;
+}
+
 // The sweep-by-sweep half of run_sweeps: windows of sweeps -> levelize (or the cached plan) -> the sweep kernel, one launch per window
 // (chains too long for LDS: per window or per level).  The outputs stay in the context's device buffers.
-int run_sweeps_stepwise(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int n_sweeps, uint32_t sweep0, uint64_t seed,
-                        const double *tab_dev, int tab_cs, int tab_ss, bool use_slots, const uint32_t *keys_dev, const double *ustream_dev,
-                        bool want_energy, bool want_min, bool want_state, int rec)
+int run_sweeps_stepwise(nlmc_ctx *c, const SweepCall &s)
 {
-    const int R = c->sub_count(), n = c->n;
-    // (its schedule buffers are shared with whatever the main stream is sweeping)
-    if (c->cur != c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const int per_chain = (stream_mode || order_mode == NLMC_ORDER_PER_CHAIN) ? 1 : 0;
-    if (per_chain && c->subset != 0) return fail(c, NLMC_ERR_UNSUPPORTED, "chain subsets run shared-order philox sweeps only");
+    const int R = c->sub_count(), n = c->n, n_sweeps = s.n_sweeps, per_chain = s.per_chain();
+    { int rc = scratch_route_begin(c, s); if (rc) return rc; }
     // plan cache hit?
-    const bool f64 = stream_mode || precision == NLMC_F64;
-    const bool big = sweeps_big(c, stream_mode, f64);      // spins stay in global memory (csrc/nlmc_big.h)
-    const int ell_mode = big ? -1 : stream_mode ? 0 : (f64 ? 2 : 1);
-    const bool cached = !stream_mode && c->plan_valid && c->plan_mode == order_mode && c->plan_seed == seed && c->plan_big == big &&
-                        c->plan_precision == precision && !per_chain && sweep0 >= c->plan_sweep0 &&
-                        (uint64_t)sweep0 + (uint64_t)n_sweeps <= (uint64_t)c->plan_sweep0 + (uint64_t)c->plan_count;
+    const bool f64 = s.stream_mode || s.precision == NLMC_F64;
+    const bool big = sweeps_big(c, s.stream_mode, f64);      // spins stay in global memory (csrc/nlmc_big.h)
+    const int ell_mode = big ? -1 : s.stream_mode ? 0 : (f64 ? 2 : 1);
+    const bool cached = !s.stream_mode && c->plan_valid && c->plan_mode == s.order_mode && c->plan_seed == s.seed && c->plan_big == big &&
+                        c->plan_precision == s.precision && !per_chain && s.sweep0 >= c->plan_sweep0 &&
+                        (uint64_t)s.sweep0 + (uint64_t)n_sweeps <= (uint64_t)c->plan_sweep0 + (uint64_t)c->plan_count;
     // window size: keep the schedule scratch under ~256 MiB
     const size_t per_sweep_orders = per_chain ? (size_t)R : 1;
     const size_t item_bytes = big ? 8 + 12 : ell_mode == 1 ? 8 + 8 + 8 * NLMC_ELL_W32 : (ell_mode == 2 ? 8 + 8 + 12 * NLMC_ELL_W : 8);
@@ -1047,15 +1091,15 @@ int run_sweeps_stepwise(nlmc_ctx *c, bool stream_mode, int precision, int order_
     int W = n_sweeps;
     if (!cached) {
         // stream mode indexes its uniforms/keys by (chain, sweep) over the WHOLE call -> single window there
-        if (!stream_mode) W = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_sweeps, ((size_t)256 << 20) / bytes_per_sweep));
+        if (!s.stream_mode) W = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_sweeps, ((size_t)256 << 20) / bytes_per_sweep));
         const size_t orders = per_sweep_orders * (size_t)W;
-        if (big) HIP_TRY(c, c->scratch.reserve_big(orders, (size_t)n, !stream_mode));
+        if (big) HIP_TRY(c, c->scratch.reserve_big(orders, (size_t)n, !s.stream_mode));
         else HIP_TRY(c, c->scratch.reserve(orders, (size_t)n, ell_mode));
     }
 
-    const int nt = big ? 1024 : sweep_block_for(c, !stream_mode && f64, !stream_mode && !f64 && c->has_diag);
-    const StepLds L = step_lds(c, stream_mode, f64);
-    const void *kfun = sweep_kernel(stream_mode, f64, c->has_diag, f64 && c->f64_pack16);
+    const int nt = big ? 1024 : sweep_block_for(c, !s.stream_mode && f64, !s.stream_mode && !f64 && c->has_diag);
+    const StepLds L = step_lds(c, s.stream_mode, f64);
+    const void *kfun = sweep_kernel(s.stream_mode, f64, c->has_diag, f64 && c->f64_pack16);
     if (!big) { int rc = ensure_lds(c, kfun, L.total); if (rc) return rc; }
     // chains too long for LDS (csrc/nlmc_big.h): enough of them to fill the chip -> one workgroup per chain for the whole
     // window (its spins stay in that CU's L1 from level to level); few -> one launch per level over all chains, so that a
@@ -1063,11 +1107,11 @@ int run_sweeps_stepwise(nlmc_ctx *c, bool stream_mode, int precision, int order_
     bool per_level = false;
     const void *kbig = nullptr;
     if (big) {
-        if (c->n_cu == 0) HIP_TRY(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+        { int rc = cu_count(c); if (rc) return rc; }
         per_level = (long long)R * 8 <= c->n_cu;
         if (c->knobs.big_per_level >= 0) per_level = c->knobs.big_per_level != 0;
         if (R > 65535) per_level = false;
-        kbig = big_kernel(per_level, stream_mode, f64);
+        kbig = big_kernel(per_level, s.stream_mode, f64);
     }
 
     for (int t0 = 0; t0 < n_sweeps; t0 += W) {
@@ -1077,10 +1121,10 @@ int run_sweeps_stepwise(nlmc_ctx *c, bool stream_mode, int precision, int order_
         TimerSpan ts;
         if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->cur); if (rc) return rc; }
         if (cached) {
-            o0 = (size_t)(sweep0 - c->plan_sweep0) + t0;
+            o0 = (size_t)(s.sweep0 - c->plan_sweep0) + t0;
         } else {
             const int n_orders = (int)per_sweep_orders * w;
-            int rc = run_levelize(c, n_orders, keys_dev, per_chain, w, sweep0 + (uint32_t)t0, seed, c->scratch, ell_mode);
+            int rc = run_levelize(c, n_orders, s.keys_dev, per_chain, w, s.sweep0 + (uint32_t)t0, s.seed, c->scratch, ell_mode);
             if (rc) return rc;
             c->stats_nlev_ptr = c->scratch.nlev.p;
             c->stats_nlev_count = n_orders;
@@ -1088,7 +1132,7 @@ int run_sweeps_stepwise(nlmc_ctx *c, bool stream_mode, int precision, int order_
         }
         { int rc = span_mid(c, ts); if (rc) return rc; }
 
-        SweepArgs a = sweep_args(c, sweep0 + (uint32_t)t0, w, seed, tab_dev + (size_t)t0 * tab_ss, tab_cs, tab_ss, use_slots);
+        SweepArgs a = window_args(c, s, t0, w);
         a.ord2 = sc.order.p + o0 * n;
         a.lvl_off = sc.lvl_off.p + o0 * (size_t)(n + 1);
         a.nlev = sc.nlev.p + o0;
@@ -1100,15 +1144,9 @@ int run_sweeps_stepwise(nlmc_ctx *c, bool stream_mode, int precision, int order_
             a.headh64 = sc.headh64.p + o0 * n;
         }
         a.per_chain = per_chain;
-        a.ustream = ustream_dev;
+        a.ustream = s.ustream_dev;
         a.energy_sink = c->energy_sink;
-        a.etrace = want_energy ? c->etrace.p : nullptr;
-        a.trace_sweeps = n_sweeps;
-        a.t0 = t0;
-        a.rec_stride = rec ? rec : 1;
-        a.strace = rec ? c->strace.p : nullptr;
-        a.emin = want_min ? c->emin.p : nullptr;
-        a.best = (want_min && want_state) ? c->best.p : nullptr;
+        sweep_outputs(c, s, true, t0, a);
         { int rc = stamps_arm(c, a, R, c->cur); if (rc) return rc; }
         a.lds_u_stride = L.dbuf ? L.u_bytes : 0;
         a.lds_loff_stride = L.dbuf ? NLMC_LCAP * 4 : 0;
@@ -1142,9 +1180,7 @@ int run_sweeps_stepwise(nlmc_ctx *c, bool stream_mode, int precision, int order_
         }
         HIP_TRY(c, hipGetLastError());
         { int rc = span_end(c, ts); if (rc) return rc; }
-        if (c->ev_accumulate) c->launches_timed++;
-        c->launches_sweep++;
-        c->launches_total++;
+        count_launches(c, 1, c->ev_accumulate);
     }
     return NLMC_OK;
 }
@@ -1219,50 +1255,19 @@ void lane_fields(const nlmc_ctx *c, SweepArgs &a, int rows, bool tab, size_t u_o
     a.lds_u_off = (int)u_off;
 }
 
-// The chain-per-lane half of run_sweeps: windows of sweeps -> k_lane_orders (the "levelize" half of the timings) -> k_sweep_lanes, one
-// launch per window.  Windows are cut against the scratch bound of run_sweeps_stepwise.  The outputs stay in the context's buffers.
-int run_sweeps_lanes(nlmc_ctx *c, int precision, int order_mode, int n_sweeps, uint32_t sweep0, uint64_t seed, const double *tab_dev,
-                     int tab_cs, int tab_ss, bool use_slots, bool want_energy, bool want_min, bool want_state, int rec)
-{
-    const int R = c->sub_count(), n = c->n;
-    if (c->cur != c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the order scratch is shared with the main stream's sweeps)
-    const int per_chain = order_mode == NLMC_ORDER_PER_CHAIN ? 1 : 0;
-    if (per_chain && c->subset != 0) return fail(c, NLMC_ERR_UNSUPPORTED, "chain subsets run shared-order philox sweeps only");
-    const size_t per_sweep_orders = per_chain ? (size_t)R : 1;
-    const size_t bytes_per_sweep = per_sweep_orders * (size_t)n * sizeof(uint16_t);
-    const int W = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_sweeps, c->knobs.lane_scratch / bytes_per_sweep));
-    if (per_sweep_orders * (size_t)W > (size_t)INT_MAX) return fail(c, NLMC_ERR_UNSUPPORTED, "too many per-chain orders in one window");
-    HIP_TRY(c, c->lane_perm.reserve(per_sweep_orders * (size_t)W * (size_t)n));
-    const LaneLds L = lane_lds(c);
-    const void *kfun = lanes_kernel(precision == NLMC_F64, per_chain != 0);
-    { int rc = ensure_lds(c, kfun, L.total); if (rc) return rc; }
-    for (int t0 = 0; t0 < n_sweeps; t0 += W) {
-        const int w = std::min(W, n_sweeps - t0);
-        TimerSpan ts;
-        if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->cur); if (rc) return rc; }
-        { int rc = launch_lane_orders(c, c->cur, per_sweep_orders * (size_t)w, w, per_chain, sweep0 + (uint32_t)t0, seed); if (rc) return rc; }
-        { int rc = span_mid(c, ts); if (rc) return rc; }
+// What a short-chain route supplies to run_sweeps_short: its kernel with dynamic LDS, grid and block (LDS limit raised, whatever the
+// kernel reads once per context in place), and the SweepArgs fields of its own -- lanes: the flags plane and the random-number table
+// (lane_lds); waves: the dense matrix.  The rest stay zero.
+struct ShortRoute { const void *kfun; size_t lds; dim3 grid, block; int lds_flags_off; bool tab; size_t u_off; const int32_t *wave_J; };
 
-        SweepArgs a = sweep_args(c, sweep0 + (uint32_t)t0, w, seed, tab_dev + (size_t)t0 * tab_ss, tab_cs, tab_ss, use_slots);
-        lane_fields(c, a, R, L.tab, L.u_off);
-        a.per_chain = per_chain;
-        a.etrace = want_energy ? c->etrace.p : nullptr;
-        a.trace_sweeps = n_sweeps;
-        a.t0 = t0;
-        a.rec_stride = rec ? rec : 1;
-        a.strace = rec ? c->strace.p : nullptr;
-        a.emin = want_min ? c->emin.p : nullptr;
-        a.best = (want_min && want_state) ? c->best.p : nullptr;
-        a.lds_flags_off = L.flags_off;
-        void *kargs[] = {&a};
-        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)((R + 63) / 64)), dim3(64), kargs, L.total, c->cur));
-        HIP_TRY(c, hipGetLastError());
-        { int rc = span_end(c, ts); if (rc) return rc; }
-        if (c->ev_accumulate) c->launches_timed++;
-        c->launches_sweep++;
-        c->launches_total++;
-    }
-    return NLMC_OK;
+// k_sweep_lanes: a chain per lane, 64 to a workgroup of one wave
+int lanes_sweeps(nlmc_ctx *c, const SweepCall &s, ShortRoute &r)
+{
+    const LaneLds L = lane_lds(c);
+    r.kfun = lanes_kernel(s.precision == NLMC_F64, s.per_chain() != 0);
+    r.lds = L.total; r.grid = dim3((unsigned)((c->sub_count() + 63) / 64)); r.block = dim3(64);
+    r.lds_flags_off = L.flags_off; r.tab = L.tab; r.u_off = (size_t)L.u_off;
+    return ensure_lds(c, r.kfun, r.lds);
 }
 
 // Whether a philox call over R rows takes the wave-per-chain kernels (nlmc_set_wave_sweeps): fixed point only, chains of at most
@@ -1300,61 +1305,61 @@ int ensure_wave_matrix(nlmc_ctx *c, size_t stride)
     return NLMC_OK;
 }
 
-// The wave-per-chain half of run_sweeps, modelled on run_sweeps_lanes: the same windows against the order scratch, k_lane_orders for
-// the orders (the "levelize" half of the timings), one k_sweep_waves launch per window.
-int run_sweeps_waves(nlmc_ctx *c, int order_mode, int n_sweeps, uint32_t sweep0, uint64_t seed, const double *tab_dev, int tab_cs, int tab_ss,
-                     bool use_slots, bool want_energy, bool want_min, bool want_state, int rec)
+// k_sweep_waves: a chain per wave, in the shape nlmc_wave_shape picks for the device, over the dense matrix
+int waves_sweeps(nlmc_ctx *c, const SweepCall &, ShortRoute &r)
 {
-    const int R = c->sub_count(), n = c->n;
-    if (c->cur != c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));     // (the order scratch is shared with the main stream's sweeps)
-    const int per_chain = order_mode == NLMC_ORDER_PER_CHAIN ? 1 : 0;
-    if (per_chain && c->subset != 0) return fail(c, NLMC_ERR_UNSUPPORTED, "chain subsets run shared-order philox sweeps only");
-    const size_t per_sweep_orders = per_chain ? (size_t)R : 1;
-    const size_t bytes_per_sweep = per_sweep_orders * (size_t)n * sizeof(uint16_t);
-    const int W = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_sweeps, c->knobs.lane_scratch / bytes_per_sweep));
-    if (per_sweep_orders * (size_t)W > (size_t)INT_MAX) return fail(c, NLMC_ERR_UNSUPPORTED, "too many per-chain orders in one window");
-    HIP_TRY(c, c->lane_perm.reserve(per_sweep_orders * (size_t)W * (size_t)n));
-    if (c->n_cu == 0) HIP_TRY(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
-    const NlmcWaveShape S = nlmc_wave_shape(n, c->n_pad, R, c->n_cu, c->knobs.wave_waves, c->knobs.wave_jlds ? 1 : 0);
-    if (S.R == 0) return fail(c, NLMC_ERR_STATE, "run_sweeps_waves: the chain does not fit the wave kernels");
-    const void *kfun = waves_kernel(S.R, S.jlds != 0);
-    { int rc = ensure_lds(c, kfun, S.lds); if (rc) return rc; }
+    { int rc = cu_count(c); if (rc) return rc; }
+    const NlmcWaveShape S = nlmc_wave_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves, c->knobs.wave_jlds ? 1 : 0);
+    if (S.R == 0) return fail(c, NLMC_ERR_STATE, "waves_sweeps: the chain does not fit the wave kernels");
+    r.kfun = waves_kernel(S.R, S.jlds != 0);
+    r.lds = S.lds; r.grid = dim3((unsigned)S.blocks); r.block = dim3((unsigned)(64 * S.W));
+    { int rc = ensure_lds(c, r.kfun, r.lds); if (rc) return rc; }
     { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
-    for (int t0 = 0; t0 < n_sweeps; t0 += W) {
-        const int w = std::min(W, n_sweeps - t0);
+    r.wave_J = c->wave_J.p;
+    return NLMC_OK;
+}
+
+// The short-chain half of run_sweeps (`route`: lanes_sweeps, waves_sweeps): windows of sweeps -> k_lane_orders (the "levelize" half of
+// the timings) -> the route's kernel, one launch per window.  Windows are cut against the order scratch (NLMC_LANE_SCRATCH), as those
+// of run_sweeps_stepwise against its bound.  The outputs stay in the context's buffers.
+int run_sweeps_short(nlmc_ctx *c, const SweepCall &s, int (*route)(nlmc_ctx *, const SweepCall &, ShortRoute &))
+{
+    const int R = c->sub_count(), per_chain = s.per_chain();
+    { int rc = scratch_route_begin(c, s); if (rc) return rc; }
+    const size_t per_sweep_orders = per_chain ? (size_t)R : 1;
+    const size_t bytes_per_sweep = per_sweep_orders * (size_t)c->n * sizeof(uint16_t);
+    const int W = (int)std::max<size_t>(1, std::min<size_t>((size_t)s.n_sweeps, c->knobs.lane_scratch / bytes_per_sweep));
+    if (per_sweep_orders * (size_t)W > (size_t)INT_MAX) return fail(c, NLMC_ERR_UNSUPPORTED, "too many per-chain orders in one window");
+    HIP_TRY(c, c->lane_perm.reserve(per_sweep_orders * (size_t)W * (size_t)c->n));
+    ShortRoute r{};
+    { int rc = route(c, s, r); if (rc) return rc; }
+    for (int t0 = 0; t0 < s.n_sweeps; t0 += W) {
+        const int w = std::min(W, s.n_sweeps - t0);
         TimerSpan ts;
         if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->cur); if (rc) return rc; }
-        { int rc = launch_lane_orders(c, c->cur, per_sweep_orders * (size_t)w, w, per_chain, sweep0 + (uint32_t)t0, seed); if (rc) return rc; }
+        { int rc = launch_lane_orders(c, c->cur, per_sweep_orders * (size_t)w, w, per_chain, s.sweep0 + (uint32_t)t0, s.seed); if (rc) return rc; }
         { int rc = span_mid(c, ts); if (rc) return rc; }
 
-        SweepArgs a = sweep_args(c, sweep0 + (uint32_t)t0, w, seed, tab_dev + (size_t)t0 * tab_ss, tab_cs, tab_ss, use_slots);
-        lane_fields(c, a, R, false, 0);
-        a.wave_J = c->wave_J.p;
+        SweepArgs a = window_args(c, s, t0, w);
+        lane_fields(c, a, R, r.tab, r.u_off);
         a.per_chain = per_chain;
-        a.etrace = want_energy ? c->etrace.p : nullptr;
-        a.trace_sweeps = n_sweeps;
-        a.t0 = t0;
-        a.rec_stride = rec ? rec : 1;
-        a.strace = rec ? c->strace.p : nullptr;
-        a.emin = want_min ? c->emin.p : nullptr;
-        a.best = (want_min && want_state) ? c->best.p : nullptr;
+        a.lds_flags_off = r.lds_flags_off;
+        a.wave_J = r.wave_J;
+        sweep_outputs(c, s, true, t0, a);
         void *kargs[] = {&a};
-        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)S.blocks), dim3((unsigned)(64 * S.W)), kargs, S.lds, c->cur));
+        HIP_TRY(c, hipLaunchKernel(r.kfun, r.grid, r.block, kargs, r.lds, c->cur));
         HIP_TRY(c, hipGetLastError());
         { int rc = span_end(c, ts); if (rc) return rc; }
-        if (c->ev_accumulate) c->launches_timed++;
-        c->launches_sweep++;
-        c->launches_total++;
+        count_launches(c, 1, c->ev_accumulate);
     }
     return NLMC_OK;
 }
 
-// Shared driver: windows of sweeps -> (levelize) -> k_sweep.  `stream_mode` selects the kernel flavour.
-int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int n_sweeps, uint32_t sweep0,
-               uint64_t seed, const double *tab_dev, int tab_cs, int tab_ss, bool use_slots, const uint32_t *keys_dev,
-               const double *ustream_dev, const SweepOut &o)
+// Shared driver: completes the call's descriptor (the output wishes, from `o` and nlmc_track_minimum), picks the route, runs its driver
+// and reads the outputs back.
+int run_sweeps(nlmc_ctx *c, SweepCall s, const SweepOut &o)
 {
-    const int R = c->sub_count(), n = c->n;
+    const int R = c->sub_count(), n = c->n, n_sweeps = s.n_sweeps;
     begin_sweep_call(c);
     c->stat_orders = 0;
     c->stat_levels = 0;
@@ -1366,55 +1371,44 @@ int run_sweeps(nlmc_ctx *c, bool stream_mode, int precision, int order_mode, int
     { int rc = ensure_subset(c); if (rc) return rc; }
     // running minimum + argmin state: asked for through host outputs, or kept on the device for the hand-off between NMC
     // phases (nlmc_track_minimum; NMC/nmc.py:394-395)
-    const bool want_min = o.out_min_energy || o.out_argmin || o.out_argmin_state || c->track_min;
-    const bool want_state = o.out_argmin_state || c->track_min;
+    s.want_energy = o.out_energy != nullptr;
+    s.want_min = o.out_min_energy || o.out_argmin || o.out_argmin_state || c->track_min;
+    s.want_state = o.out_argmin_state || c->track_min;
     c->stat_fused_window = -1;
-    const int rec = o.out_spins ? std::max(1, o.record_stride) : 0;
-    const int n_rec = rec ? (n_sweeps + rec - 1) / rec : 0;
-    const bool any_out = o.out_spins || o.out_energy || want_min;
+    s.rec = o.out_spins ? std::max(1, o.record_stride) : 0;
+    const int n_rec = s.rec ? (n_sweeps + s.rec - 1) / s.rec : 0;
     // Fused-window schedule: planned ahead (nlmc_plan_philox_fused), same results.  Calls without per-sweep outputs
     // and with one temperature per chain take the plain variant; calls WITH outputs (energy trace, running minimum /
     // argmin state, recorded configurations) or a temperature per sweep take the output variant (its three snapshot slots in
     // LDS or, for large n, in a global ring: run_fused); any whole number of planned windows per call either way.  Which calls
     // run there, and on which arithmetic: fused_route.
-    const bool outs = any_out || tab_ss != 0;
-    const int fslot = fused_plan_for(c, sweep0, n_sweeps, seed);
-    int arith = fslot < 0 ? NOT_FUSED : fused_route(c, precision, order_mode, tab_ss != 0, c->has_flags, fslot, c->fz[fslot].T, Via::sweeps);
-    if (outs && c->knobs.no_fused_out) arith = NOT_FUSED;
-    const bool waves = !stream_mode && waves_route(c, R, precision);   // short chains, one per wave (csrc/nlmc_waves.h): asked first
-    const bool lanes = !waves && !stream_mode && lanes_route(c, R);    // short chains, one per lane (csrc/nlmc_lanes.h): before the fused windows
+    const int fslot = fused_plan_for(c, s.sweep0, n_sweeps, s.seed);
+    int arith = fslot < 0 ? NOT_FUSED : fused_route(c, s.precision, s.order_mode, s.tab_ss != 0, c->has_flags, fslot, c->fz[fslot].T, Via::sweeps);
+    if (s.outs() && c->knobs.no_fused_out) arith = NOT_FUSED;
+    const bool waves = !s.stream_mode && waves_route(c, R, s.precision);   // short chains, one per wave (csrc/nlmc_waves.h): asked first
+    const bool lanes = !waves && !s.stream_mode && lanes_route(c, R);      // short chains, one per lane (csrc/nlmc_lanes.h): before the fused windows
     if (lanes || waves) arith = NOT_FUSED;
     c->last_route = waves ? NLMC_ROUTE_WAVES : lanes ? NLMC_ROUTE_LANES : arith != NOT_FUSED ? NLMC_ROUTE_FUSED : NLMC_ROUTE_STEPWISE;
     if (o.out_energy) HIP_TRY(c, c->etrace.reserve((size_t)R * n_sweeps));
-    if (rec) HIP_TRY(c, c->strace.reserve((size_t)R * n_rec * n));
+    if (s.rec) HIP_TRY(c, c->strace.reserve((size_t)R * n_rec * n));
     c->strace_nrec = n_rec;
-    c->strace_rows = rec ? R : 0;
-    if (want_min) {
+    c->strace_rows = s.rec ? R : 0;
+    if (s.want_min) {
         hipLaunchKernelGGL(k_fill_min, dim3((R + 255) / 256), dim3(256), 0, c->cur, R, c->sub_list(), c->emin.p, c->argmin.p);
         HIP_TRY(c, hipGetLastError());
     }
+    int rc = NLMC_OK;
     if (arith != NOT_FUSED) {
         const nlmc_ctx::FusedPlan &P = c->fz[fslot];
-        const int w0 = (int)((sweep0 - P.sweep0) / (uint32_t)P.T), nw = n_sweeps / P.T;
-        for (int j = 0; j < nw; ++j) {
-            int rc = run_fused(c, fslot, w0 + j, sweep0 + (uint32_t)(j * P.T), seed, tab_dev + (size_t)j * P.T * tab_ss, tab_cs, tab_ss,
-                               use_slots, outs, o.out_energy != nullptr, want_min, want_state, rec, outs ? j * P.T : 0, n_sweeps, arith);
-            if (rc) return rc;
-        }
-    } else if (waves) {
-        int rc = run_sweeps_waves(c, order_mode, n_sweeps, sweep0, seed, tab_dev, tab_cs, tab_ss, use_slots, o.out_energy != nullptr, want_min,
-                                  want_state, rec);
-        if (rc) return rc;
-    } else if (lanes) {
-        int rc = run_sweeps_lanes(c, precision, order_mode, n_sweeps, sweep0, seed, tab_dev, tab_cs, tab_ss, use_slots, o.out_energy != nullptr,
-                                  want_min, want_state, rec);
-        if (rc) return rc;
+        const int w0 = (int)((s.sweep0 - P.sweep0) / (uint32_t)P.T), nw = n_sweeps / P.T;
+        for (int j = 0; j < nw && !rc; ++j) rc = run_fused(c, s, fslot, w0 + j, j * P.T, arith);
+    } else if (waves || lanes) {
+        rc = run_sweeps_short(c, s, waves ? waves_sweeps : lanes_sweeps);
     } else {
-        int rc = run_sweeps_stepwise(c, stream_mode, precision, order_mode, n_sweeps, sweep0, seed, tab_dev, tab_cs, tab_ss, use_slots, keys_dev,
-                                     ustream_dev, o.out_energy != nullptr, want_min, want_state, rec);
-        if (rc) return rc;
+        rc = run_sweeps_stepwise(c, s);
     }
-    return read_sweep_outputs(c, o, n_sweeps, rec, n_rec);
+    if (rc) return rc;
+    return read_sweep_outputs(c, o, n_sweeps, s.rec, n_rec);
 }
 
 // ---- RCCL, bound at run time (dlopen): a process that never shards a ladder over GPUs needs no librccl -----------------
@@ -1939,8 +1933,10 @@ int nlmc_sweep_stream(nlmc_ctx *c, int n_sweeps, const int32_t *perm, const doub
     HIP_TRY(c, hipStreamSynchronize(c->stream));          // (also: the caller's buffers and `tab` may go away)
     if (bad) return fail(c, NLMC_ERR_ARG, "nlmc_sweep_stream: perm is not a permutation");
     SweepOut o{record_stride, out_spins, out_energy, out_min_energy, out_argmin, out_argmin_state};
-    int rc = run_sweeps(c, true, NLMC_F64, NLMC_ORDER_PER_CHAIN, n_sweeps, 0, 0, c->tab.p, n_sweeps, 1, false, c->keys.p,
-                        c->ustream.p, o);
+    SweepCall s{};
+    s.stream_mode = true; s.precision = NLMC_F64; s.order_mode = NLMC_ORDER_PER_CHAIN; s.n_sweeps = n_sweeps;
+    s.tab = c->tab.p; s.tab_cs = n_sweeps; s.tab_ss = 1; s.keys_dev = c->keys.p; s.ustream_dev = c->ustream.p;
+    int rc = run_sweeps(c, s, o);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NLMC_OK;
@@ -1960,9 +1956,8 @@ int nlmc_sweep_philox(nlmc_ctx *c, int precision, int order_mode, int n_sweeps, 
     if (R == 0 || n_sweeps == 0) return NLMC_OK;
     if (beta && chain_stride && c->subset != 0)
         return fail(c, NLMC_ERR_UNSUPPORTED, "nlmc_sweep_philox: a per-chain beta table with a chain subset (use the ladder or one beta)");
-    const double *tab_dev;
-    int tcs, tss;
-    bool use_slots = false;
+    SweepCall s{};
+    s.precision = precision; s.order_mode = order_mode; s.n_sweeps = n_sweeps; s.sweep0 = sweep0; s.seed = seed;
     if (beta) {
         const int rows = chain_stride ? R : 1, T = sweep_stride ? n_sweeps : 1;
         std::vector<double> tab((size_t)rows * T * 2);
@@ -1979,18 +1974,13 @@ int nlmc_sweep_philox(nlmc_ctx *c, int precision, int order_mode, int n_sweeps, 
             HIP_TRY(c, hipStreamSynchronize(c->cur));
             c->tab_host.swap(tab);
         }
-        tab_dev = c->tab.p;
-        tcs = chain_stride ? T * 2 : 0;
-        tss = sweep_stride ? 2 : 0;
+        s.tab = c->tab.p; s.tab_cs = chain_stride ? T * 2 : 0; s.tab_ss = sweep_stride ? 2 : 0;
     } else {
         { int rc = upload_ladder_tab(c, c->cur); if (rc) return rc; }
-        tab_dev = c->pt_tab.p;
-        tcs = 2; tss = 0;
-        use_slots = true;
+        s.tab = c->pt_tab.p; s.tab_cs = 2; s.use_slots = true;
     }
     SweepOut o{record_stride, out_spins, out_energy, out_min_energy, out_argmin, out_argmin_state};
-    return run_sweeps(c, false, precision, order_mode, n_sweeps, sweep0, seed, tab_dev, tcs, tss, use_slots, nullptr,
-                      nullptr, o);
+    return run_sweeps(c, s, o);
 }
 
 int nlmc_plan_philox(nlmc_ctx *c, int precision, int order_mode, uint32_t sweep0, int n_sweeps, uint64_t seed)
@@ -2892,9 +2882,7 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
         HIP_TRY(c, hipLaunchCooperativeKernel(kfun, dim3(c->n_chains), dim3(nt), kargs, (unsigned)Lds.total, c->stream));
         HIP_TRY(c, hipGetLastError());
         { int rc = span_end(c, ts); if (rc) return rc; }
-        if (c->ev_accumulate) c->launches_timed += k;
-        c->launches_sweep += k;
-        c->launches_total += k;
+        count_launches(c, k, c->ev_accumulate);
         c->stat_fused_window = w0 + k - 1;
     }
     c->stat_fused_slot = fslot;
@@ -2980,9 +2968,7 @@ int lane_rounds_chunks(nlmc_ctx *c, const void *kfun, size_t lds, int n_rounds, 
         { int rc = launch(at, k, s0, r0); if (rc) return rc; }
         HIP_TRY(c, hipGetLastError());
         { int rc = span_end(c, ts); if (rc) return rc; }
-        if (c->ev_accumulate) c->launches_timed += k;
-        c->launches_sweep += k;
-        c->launches_total += k;
+        count_launches(c, k, c->ev_accumulate);
     }
     c->sub_dirty = true;
     c->last_route = route;
@@ -3023,7 +3009,7 @@ const void *rounds_waves_kernel(int R, bool jlds, bool observed)
 int rounds_waves(nlmc_ctx *c, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
 {
     const int L = c->ladder_len, ladders = c->n_chains / L;
-    if (c->n_cu == 0) HIP_TRY(c, hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+    { int rc = cu_count(c); if (rc) return rc; }
     const NlmcWaveRoundsShape S = nlmc_wave_rounds_shape(c->n, c->n_pad, L, ladders, c->n_cu, c->knobs.wave_rounds_ladders, c->knobs.wave_jlds ? 1 : 0);
     if (S.R == 0) return fail(c, NLMC_ERR_STATE, "rounds_waves: the chain or the ladder does not fit the wave kernels");
     const void *kfun = rounds_waves_kernel(S.R, S.jlds != 0, c->observed());
@@ -3145,6 +3131,10 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
     HIP_TRY(c, c->rounds_ebuf.reserve(2 * G));
     { int rc = upload_ladder_tab(c, c->stream); if (rc) return rc; }
     const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
+    // the rounds' sweeps as one call: the ladder's temperatures by slot, no per-sweep outputs
+    SweepCall s{};
+    s.precision = precision; s.order_mode = NLMC_ORDER_SHARED; s.n_sweeps = n_rounds * T; s.sweep0 = sweep0; s.seed = seed;
+    s.tab = c->pt_tab.p; s.tab_cs = 2; s.use_slots = true;
     for (int r = 0; r < n_rounds; ++r) {
         DeferSwap d{};
         d.ladder_len = L; d.n_ladders = nl; d.beta = c->pt_beta.p;
@@ -3158,8 +3148,7 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
         }
         // (this launch publishes its chains' final energies for the next one: rows of the local chains inside the global vector)
         double *sink = c->rounds_ebuf.p + (size_t)(r & 1) * G + c->chain_base;
-        int rc = run_fused(c, fslot, w0 + r, sweep0 + (uint32_t)(r * T), seed, c->pt_tab.p, 2, 0, true, false, false, false, false, 0, 0, T,
-                           arith, &d, sink);
+        int rc = run_fused(c, s, fslot, w0 + r, r * T, arith, &d, sink);
         if (rc) return rc;
         // an open record observes the round here: a swap is a label exchange, so chain c's spins and tracked energy in the state
         // arrays after this launch are the state of round r, whatever the next launch's prologue decides about its slot

@@ -96,6 +96,41 @@ def test_timing_counters(product, precision, monkeypatch):
         assert (tm["ms_levelize"], tm["ms_sweep"], tm["launches_sweep"], tm["launches_timed"]) == (0, 0, K, 0)
 
 
+@pytest.mark.parametrize("route", ["lanes", "waves"])
+def test_timing_counters_short_routes(product, route, monkeypatch):
+    """The short-chain routes cut a per-chain-order call into windows against the order scratch: every window is one counted launch,
+    timed whenever timings accumulate (`every` thins the events of fused windows only), with the k_lane_orders launch as its
+    levelize half; the schedule statistics are the visiting orders of the call, no levels."""
+    n, R, S = 37, 9, 7
+    J, h = make_instance(n, seed=9, with_h=True, gaussian=True)
+    tab = np.linspace(0.1, 2.0, R)[:, None] * np.linspace(0.5, 1.5, S)[None, :]
+    monkeypatch.setenv("NLMC_LANE_SCRATCH", str(2 * R * n * 3))                        # the orders of three sweeps: windows of 3, 3, 1
+    with product.Engine(J, h, R) as eng:
+        eng.set_spins(init_spins(R, n))
+        (eng.set_lane_sweeps if route == "lanes" else eng.set_wave_sweeps)("force")
+
+        def call():
+            eng.sweep_philox(S, SEED, sweep0=11, beta=tab, precision="f32", order="per_chain", record_stride=2, want_energy=True,
+                             want_min=True, want_state=True)
+            assert eng.last_sweep_route() == route
+
+        eng.timing_reset(True, every=1)
+        call()
+        tm = eng.timing_total()
+        assert (tm["launches_sweep"], tm["launches_timed"]) == (3, 3) and tm["ms_levelize"] > 0 and tm["ms_sweep"] > 0
+        assert eng.last_timing()["launches_sweep"] == 3
+        assert eng.last_schedule_stats() == {"orders": R * S, "levels": 0}
+        eng.timing_reset(True, every=3)
+        call()
+        tm = eng.timing_total()
+        assert (tm["launches_sweep"], tm["launches_timed"]) == (3, 3)
+        eng.timing_reset(False)
+        call()
+        lt, tm = eng.last_timing(), eng.timing_total()
+        assert (lt["ms_levelize"], lt["ms_sweep"], lt["launches_sweep"]) == (0, 0, 3)
+        assert (tm["ms_levelize"], tm["ms_sweep"], tm["launches_sweep"], tm["launches_timed"]) == (0, 0, 3, 0)
+
+
 ROUNDS, A, B = 9, 2, 6            # rounds of a run; the window [A, B) of rounds that is logged / planned
 
 
