@@ -18,6 +18,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <thread>
 #include <climits>
@@ -35,10 +36,16 @@ namespace {
 constexpr double LOG2E = 1.4426950408889634;
 std::string g_create_error;
 
+// A device buffer that owns its memory: freed when the buffer goes (for a context's buffers, at `delete c` in nlmc_destroy, with the
+// context's device current) unless it is borrowed.  Not copyable and not movable: every buffer is a member of nlmc_ctx, built in place.
 template <typename T> struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;   // elements
     bool borrowed = false;      // p points into the context's arena (nlmc_create): not freed here
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     hipError_t reserve(size_t n)
     {
         if (n <= cap) return hipSuccess;
@@ -55,9 +62,10 @@ template <typename T> struct DevBuf {
         cap = n; borrowed = true;
         offset += std::max<size_t>(n, 1) * sizeof(T);
     }
-    static size_t arena_bytes(size_t n) { return ((std::max<size_t>(n, 1) * sizeof(T)) + 255 + 255) & ~(size_t)255; }
-    void release() { if (p && !borrowed) (void)hipFree(p); p = nullptr; cap = 0; borrowed = false; }
+    static size_t arena_bytes(size_t n) { return ((std::max<size_t>(n, 1) * sizeof(T)) + 255 + 255) & ~(size_t)255; }   // covers what borrow takes
+    void release() { if (p && !borrowed) (void)hipFree(p); p = nullptr; cap = 0; borrowed = false; }   // early give-back (nlmc_plan_philox_fused)
 };
+static_assert(!std::is_copy_constructible_v<DevBuf<int>> && !std::is_move_constructible_v<DevBuf<int>>, "DevBuf owns device memory");
 
 // Every NLMC_* environment variable of the library: tuning, test and diagnostic switches.  read_knobs() reads them when a context is
 // created (nlmc_create); they hold for the context's life, and setting a variable later does not reach a context that exists.
@@ -129,8 +137,9 @@ struct nlmc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool owns_stream = false;             // nlmc_own_stream: `stream` was created by the library
-    void *arena = nullptr;                // ONE allocation behind the fixed-size buffers of nlmc_create (13 hipMalloc + 7 blocking
-                                          // memsets + 6 blocking copies were 6 of the 29 ms of an NPT.run call at the C4 shape)
+    DevBuf<unsigned char> arena;          // ONE allocation behind the fixed-size buffers of nlmc_create (13 hipMalloc + 7 blocking
+                                          // memsets + 6 blocking copies were 6 of the 29 ms of an NPT.run call at the C4 shape);
+                                          // declared before the buffers that borrow from it, so it is freed after they are gone
     // Work on the MARKED chain subset may run on a second stream beside the unmarked chains' sweeps (nlmc_overlap_subsets):
     // `cur` is the stream the subset-aware launches go to, forked from / joined to `stream` by nlmc_select_chains.
     hipStream_t aux = nullptr, cur = nullptr;
@@ -173,6 +182,16 @@ struct nlmc_ctx {
     DevBuf<double> u_raw;
     DevBuf<int32_t> stream_bad;
     DevBuf<int8_t> strace, cfg, snap_g;
+    // The buffers that live in the arena, with their element counts, in arena order: nlmc_create sizes the arena by this list and
+    // carves it up by it.  +16 entries of padding behind the row arrays: fixed-width row windows are read unconditionally (never used
+    // past the row end).
+    template <typename F> void arena_buffers(F &&f)
+    {
+        const size_t N = (size_t)n, nz = (size_t)nnz + 16, R = (size_t)std::max(n_chains, 1), states = R * (size_t)n_pad;
+        f(rowptr, N + 1); f(col, nz); f(val64, nz); f(edge32, nz); f(h64, N); f(hq, N);
+        f(spins, states); f(best, states); f(flags, states);
+        f(efix, R); f(emin, R); f(argmin, R); f(energy, R);
+    }
     int strace_nrec = 0;          // recorded configurations per chain held in strace by the last sweep call (0: none)
     int strace_rows = 0;          // chains (rows) of that trace: the subset the call ran on
     // chain subsets (nlmc_pt_mark_slots / nlmc_select_chains): sweeps, hand-offs and backbone inference of a call act on
@@ -268,7 +287,6 @@ struct nlmc_ctx {
             }
             return hipSuccess;
         }
-        void release() { order.release(); head32.release(); lvl_off.release(); nlev.release(); hi_max.release(); ellc64.release(); ell32.release(); ellv64.release(); headh64.release(); bkey.release(); bcur.release(); blvl.release(); }
     };
     Sched scratch, plan;
     int n_cu = 0;                        // compute units of the device (asked once)
@@ -1543,26 +1561,10 @@ int nlmc_create(nlmc_ctx **out, int device, void *hip_stream, int n, int64_t nnz
                 const int32_t *colidx, const double *vals, const double *h, int n_chains, int chain_base,
                 int n_chains_global)
 {
-    if (!out) return fail(nullptr, NLMC_ERR_ARG, "nlmc_create: out is NULL");
-    *out = nullptr;
-    if (n < 1 || nnz < 0 || !rowptr || (nnz > 0 && (!colidx || !vals)) || !h || n_chains < 0 || chain_base < 0 ||
-        n_chains_global < chain_base + n_chains)
-        return fail(nullptr, NLMC_ERR_ARG, "nlmc_create: bad sizes or NULL arrays");
-    if (n > NLMC_MAX_N) return fail(nullptr, NLMC_ERR_UNSUPPORTED, "nlmc_create: n exceeds NLMC_MAX_N");
-    if (rowptr[0] != 0 || rowptr[n] != nnz) return fail(nullptr, NLMC_ERR_ARG, "nlmc_create: rowptr[0] != 0 or rowptr[n] != nnz");
-    bool diag = false, zero_vals = false;
-    int max_deg = 0, n_gt8 = 0, n_gt16 = 0;     // rows longer than one / two row windows of a fused plan
-    for (int k = 0; k < n; ++k) {
-        if (rowptr[k + 1] < rowptr[k]) return fail(nullptr, NLMC_ERR_ARG, "nlmc_create: rowptr not monotone");
-        max_deg = std::max(max_deg, (int)(rowptr[k + 1] - rowptr[k]));
-        n_gt8 += (rowptr[k + 1] - rowptr[k]) > NLMC_FZ_W;
-        n_gt16 += (rowptr[k + 1] - rowptr[k]) > 2 * NLMC_FZ_W;
-        for (int e = rowptr[k]; e < rowptr[k + 1]; ++e) {
-            if (colidx[e] < 0 || colidx[e] >= n) return fail(nullptr, NLMC_ERR_ARG, "nlmc_create: column index out of range");
-            if (colidx[e] == k && vals[e] != 0.0) diag = true;
-            if (vals[e] == 0.0) zero_vals = true;
-        }
-    }
+    NlmcInstance I;     // every instance error comes before the device is asked for
+    const int irc = nlmc_instance_prepare(I, out, n, nnz, rowptr, colidx, vals, h, n_chains, chain_base, n_chains_global, NLMC_FZ_W);
+    if (out) *out = nullptr;
+    if (irc != NLMC_OK) return fail(nullptr, irc, I.err);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(nullptr, NLMC_ERR_HIP, "nlmc_create: no HIP device visible (this library has no CPU fallback)");
@@ -1583,126 +1585,34 @@ int nlmc_create(nlmc_ctx **out, int device, void *hip_stream, int n, int64_t nnz
     c->n_chains = n_chains;
     c->chain_base = chain_base;
     c->n_chains_global = n_chains_global;
-    c->has_diag = diag;
-    c->has_zero_vals = zero_vals;
-    c->max_deg = max_deg;
-    c->n_long = n_gt8 + (c->knobs.no_quads ? 0 : 2 * n_gt16);
+    c->has_diag = I.has_diag;
+    c->has_zero_vals = I.has_zero_vals;
+    c->max_deg = I.max_deg;
+    c->n_long = I.n_gt1 + (c->knobs.no_quads ? 0 : 2 * I.n_gt2);
+    c->qs = I.qs;
+    c->escale = I.escale;
+    c->xmax = I.xmax;
+    c->compact16 = I.fits16 && !c->knobs.no_compact;
+    c->f64_pack16 = I.fits16 && I.exact_q && n <= 65535 && !c->knobs.no_pack64;
+    c->sign8 = c->compact16 && I.pm1 && nnz > 0 && !c->knobs.no_signfmt;
+    c->f64_exact = I.exact_q && I.exact_h;
 
-    // fixed-point scales.  Energies: integers in units of 2^-escale, |E| <= sum|J|/2 + sum|h|.  Couplings of the "f32"
-    // throughput path: Jq = rint(J 2^qs), hq = rint(h 2^qs) with qs the largest exponent such that every |Jq| fits a
-    // signed 24-bit multiplier and every row sum  sum|Jq| + |hq|  fits int32 (the field is then an exact int32);
-    // qs <= escale <= qs + 29, so that an energy delta is the field times +-2^(escale - qs + 1) in one 32 x 32 -> 64
-    // bit multiply-add.  (Restated in oracle/nlo.c: nlo_field_scale.)
-    double bound = 0.0, maxabs = 0.0, maxh = 0.0;
-    for (int64_t e = 0; e < nnz; ++e) { bound += std::fabs(vals[e]) * 0.5; maxabs = std::max(maxabs, std::fabs(vals[e])); }
-    for (int k = 0; k < n; ++k) { bound += std::fabs(h[k]); maxh = std::max(maxh, std::fabs(h[k])); }
-    int ex = 0;
-    std::frexp(std::max(bound, 1.0), &ex);       // bound < 2^ex
-    const int escale0 = std::max(0, std::min(52, 60 - ex));
-    int qs = 0;
-    auto rq = [](double v, int q) { return (int64_t)std::llrint(std::ldexp(v, q)); };
-    const double ref = maxabs > 0.0 ? maxabs : maxh;
-    if (ref > 0.0) {
-        int exr = 0;
-        std::frexp(ref, &exr);
-        qs = std::min(23 - exr, escale0);
-        for (;;) {
-            bool ok = true;
-            for (int k = 0; k < n && ok; ++k) {
-                int64_t row = std::llabs(rq(h[k], qs));
-                for (int e = rowptr[k]; e < rowptr[k + 1]; ++e) {
-                    const int64_t q = std::llabs(rq(vals[e], qs));
-                    if (q > 8388607) ok = false;
-                    row += q;
-                }
-                if (row > 2147483647LL) ok = false;
-            }
-            if (ok) break;
-            --qs;
-        }
-        // canonical form: drop the power of two common to every Jq and hq (+-J instances: Jq = +-1).  Where every value is an exact
-        // multiple of 2^-qs (so that a smaller scale just shifts the integers) the common power is found in ONE pass -- the loop
-        // below, one pass per bit, was 22 passes over the couplings for a +-J instance: most of the 6 ms of nlmc_create at N = 10^4.
-        {
-            bool exact = true, any = false;
-            int min_tz = 63;
-            auto scan = [&](double v) {
-                const int64_t q = rq(v, qs);
-                if (std::ldexp((double)q, -qs) != v) exact = false;
-                if (q) { any = true; min_tz = std::min(min_tz, __builtin_ctzll((unsigned long long)(q < 0 ? -q : q))); }
-            };
-            for (int64_t e = 0; e < nnz && exact; ++e) scan(vals[e]);
-            for (int k = 0; k < n && exact; ++k) scan(h[k]);
-            if (exact && any && min_tz > 0) qs -= min_tz;        // (the loop below then stops at its first pass: some integer is odd)
-        }
-        for (;;) {
-            bool even = true, any = false;
-            for (int64_t e = 0; e < nnz && even; ++e) { const int64_t q = rq(vals[e], qs); if (q & 1) even = false; if (q) any = true; }
-            for (int k = 0; k < n && even; ++k) { const int64_t q = rq(h[k], qs); if (q & 1) even = false; if (q) any = true; }
-            if (!even || !any) break;
-            --qs;
-        }
-    }
-    c->qs = qs;
-    c->escale = std::min(escale0, qs + 29);
-
-    std::vector<EdgeQ> e32((size_t)std::max<int64_t>(nnz, 1));
-    std::vector<int32_t> hq((size_t)n);
-    bool fits16 = n <= 65535;        // compact schedule entries of the fused windows: col << 16 | (Jq & 0xFFFF)
-    bool pm1 = true;                 // sign format: col | (Jq < 0) << 15
-    bool exact_q = true;             // every J is Jq 2^-qs exactly (packed fp64 schedule window)
-    for (int64_t e = 0; e < nnz; ++e) {
-        e32[e].col = colidx[e]; e32[e].q = (int32_t)rq(vals[e], qs);
-        if (e32[e].q > 32767 || e32[e].q < -32768) fits16 = false;
-        if (std::ldexp((double)e32[e].q, -qs) != vals[e]) exact_q = false;
-        if (e32[e].q != 1 && e32[e].q != -1) pm1 = false;
-    }
-    c->compact16 = fits16 && !c->knobs.no_compact;
-    c->f64_pack16 = fits16 && exact_q && n <= 65535 && !c->knobs.no_pack64;
-    c->sign8 = c->compact16 && pm1 && nnz > 0 && !c->knobs.no_signfmt;
-    bool exact_h = true;
-    for (int k = 0; k < n; ++k) {
-        hq[k] = (int32_t)rq(h[k], qs);
-        if (std::ldexp((double)hq[k], -qs) != h[k]) exact_h = false;
-        int64_t row = std::llabs((int64_t)hq[k]);
-        for (int e = rowptr[k]; e < rowptr[k + 1]; ++e) row += std::llabs((int64_t)e32[e].q);
-        c->xmax = (int)std::min<int64_t>(std::max<int64_t>(c->xmax, row), INT_MAX);
-    }
-    c->f64_exact = exact_q && exact_h;
-
-    // +16 entries of padding behind the row arrays: fixed-width row windows are read unconditionally (never used past the row end)
-    const size_t R = (size_t)std::max(n_chains, 1), npad = (size_t)c->n_pad, nz = (size_t)nnz + 16;
-    const size_t total = DevBuf<int32_t>::arena_bytes((size_t)n + 1) + DevBuf<int32_t>::arena_bytes(nz) + DevBuf<double>::arena_bytes(nz) +
-                         DevBuf<EdgeQ>::arena_bytes(nz) + DevBuf<double>::arena_bytes((size_t)n) + DevBuf<int32_t>::arena_bytes((size_t)n) +
-                         3 * DevBuf<int8_t>::arena_bytes(R * npad) + 2 * DevBuf<long long>::arena_bytes(R) +
-                         DevBuf<int32_t>::arena_bytes(R) + DevBuf<double>::arena_bytes(R) + 256;
-    CT(hipMalloc(&c->arena, total));
-    size_t off = 0;
-    c->rowptr.borrow(c->arena, off, (size_t)n + 1);
-    c->col.borrow(c->arena, off, nz);
-    c->val64.borrow(c->arena, off, nz);
-    c->edge32.borrow(c->arena, off, nz);
-    c->h64.borrow(c->arena, off, (size_t)n);
-    c->hq.borrow(c->arena, off, (size_t)n);
-    c->spins.borrow(c->arena, off, R * npad);
-    c->best.borrow(c->arena, off, R * npad);
-    c->flags.borrow(c->arena, off, R * npad);
-    c->efix.borrow(c->arena, off, R);
-    c->emin.borrow(c->arena, off, R);
-    c->argmin.borrow(c->arena, off, R);
-    c->energy.borrow(c->arena, off, R);
-    if (off > total) { c->err = "nlmc_create: arena accounting"; return bail(NLMC_ERR_HIP); }
+    size_t total = 256, off = 0;
+    c->arena_buffers([&](auto &buf, size_t count) { total += buf.arena_bytes(count); });
+    CT(c->arena.reserve(total));
+    c->arena_buffers([&](auto &buf, size_t count) { buf.borrow(c->arena.p, off, count); });
+    assert(off <= total);
     // everything zero (padding, states, flags, tracked energies), then the instance: stream-ordered, ONE wait (the host arrays
     // handed to the copies are the caller's and this function's own: both outlive the wait)
-    CT(hipMemsetAsync(c->arena, 0, total, c->stream));
+    CT(hipMemsetAsync(c->arena.p, 0, total, c->stream));
     CT(hipMemcpyAsync(c->rowptr.p, rowptr, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
     if (nnz > 0) {
         CT(hipMemcpyAsync(c->col.p, colidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
         CT(hipMemcpyAsync(c->val64.p, vals, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
-        CT(hipMemcpyAsync(c->edge32.p, e32.data(), sizeof(EdgeQ) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+        CT(hipMemcpyAsync(c->edge32.p, I.e32.data(), sizeof(EdgeQ) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
     }
     CT(hipMemcpyAsync(c->h64.p, h, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    CT(hipMemcpyAsync(c->hq.p, hq.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    CT(hipMemcpyAsync(c->hq.p, I.hq.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     CT(hipStreamSynchronize(c->stream));
 
     c->g.n = n; c->g.n_pad = c->n_pad;
@@ -1728,7 +1638,6 @@ void nlmc_destroy(nlmc_ctx *c)
             }
         }
     }
-    c->dbg.release();
 #endif
     if (c->comm && g_rccl.ok) (void)g_rccl.CommDestroy(c->comm);
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
@@ -1736,26 +1645,7 @@ void nlmc_destroy(nlmc_ctx *c)
     if (c->owns_stream && c->stream) { (void)hipStreamDestroy(c->stream); c->stream = nullptr; }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    c->rowptr.release(); c->col.release(); c->val64.release(); c->h64.release(); c->edge32.release(); c->hq.release();
-    // (borrowed buffers: released above / below without a free; the arena goes last)
-    c->spins.release(); c->best.release(); c->flags.release(); c->efix.release(); c->emin.release(); c->etrace.release();
-    c->argmin.release(); c->energy.release(); c->tab.release(); c->ustream.release(); c->etrace_d.release();
-    c->keys.release(); c->perm_raw.release(); c->u_raw.release(); c->stream_bad.release(); c->strace.release(); c->cfg.release(); c->snap_g.release(); c->scratch.release(); c->plan.release();
-    c->slot_mark.release(); c->sub_list_buf.release(); c->cmask.release(); c->cmask_scratch.release(); c->big_flag.release(); c->big_esum.release(); c->lane_perm.release(); c->wave_J.release(); c->nmc_status.release(); c->nmc_thr.release();
-    c->fz_glv.release(); c->fz_perm.release(); c->fz_adj.release(); c->fz_stats.release(); c->fz[0].release(); c->fz[1].release();
-    c->lbp_src.release(); c->lbp_rev.release(); c->lbp_flag.release(); c->lbp_out_i.release(); c->lbp_tJ.release();
-    c->lbp_eps.release(); c->lbp_ms.release(); c->lbp_lams.release(); c->lbp_w0.release(); c->lbp_w1.release();
-    c->lbp_bar.release(); c->lbp_part.release();
-    c->lbp_hm.release(); c->lbp_tot.release(); c->lbp_mag.release(); c->lbp_mag_all.release();
-    c->pt_tab.release(); c->pt_beta.release(); c->pt_energies_all.release();
-    c->rounds_ebuf.release(); c->rounds_rec.release(); c->rounds_args.release(); c->seed_snap.release();
-    c->rec_efix.release(); c->rec_stamp.release(); c->rec_hit.release(); c->rec_state.release();
-    c->elog_energy.release(); c->elog_slot.release();
-    c->apt_beta.release(); c->apt_e_all.release(); c->apt_send.release(); c->apt_recv.release(); c->apt_bd.release();
-    c->slot_of_chain.release(); c->chain_of_slot.release(); c->pt_pairs.release(); c->pt_status.release();
-    c->pt_acc.release(); c->pt_log_acc.release(); c->pt_log_pairs.release(); c->pt_plan_pairs.release(); c->pt_plan_ok.release(); c->icm_label.release(); c->icm_info.release(); c->icm_pairs.release();
-    if (c->arena) (void)hipFree(c->arena);
-    delete c;
+    delete c;       // every buffer, then the arena, with the context's device current
 }
 
 int nlmc_set_spins(nlmc_ctx *c, const int8_t *spins)

@@ -11,10 +11,7 @@
 //   k_energy   : E = -(m^T J m/2 + m^T h) in fp64, one workgroup per configuration.
 #pragma once
 #include "nlmc_device.h"
-
-// 8-byte packed CSR entry of the "f32" throughput path (one dwordx2 load): column and the coupling in 24-bit fixed
-// point, q = rint(J 2^qs) (nlmc_create).  The field of a spin is then an exact int32, independent of summation order.
-struct EdgeQ { int32_t col; int32_t q; };
+#include "nlmc_instance.h"      // EdgeQ
 
 struct CsrDev {
     int n, n_pad;

@@ -143,7 +143,7 @@ LOG2E = 1.4426950408889634
 
 def field_scale(csr, h):
     """(qs, escale) of the "f32" throughput mode: couplings are held as rint(J 2^qs) (24-bit fixed point), energies as
-    integers in units of 2^-escale (restated from nlmc_create)."""
+    integers in units of 2^-escale (restated from csrc/nlmc_instance.h)."""
     qs, es = ctypes.c_int(0), ctypes.c_int(0)
     lib().nlo_field_scale(csr.n, csr.indptr, csr.data, np.ascontiguousarray(h, dtype=np.float64).reshape(-1),
                           ctypes.byref(qs), ctypes.byref(es))

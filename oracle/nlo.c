@@ -209,7 +209,7 @@ uint64_t nlo_accept_count_f64(double z)
 /* ------------------------------------------------------------------------------------------------ */
 /* "f32" throughput mode: fixed-point couplings and the logistic threshold                            */
 /* ------------------------------------------------------------------------------------------------ */
-/* Field scale qs and energy scale escale of an instance (restated from nlmc_create, csrc/nlmc.hip):
+/* Field scale qs and energy scale escale of an instance (restated from nlmc_instance_prepare, csrc/nlmc_instance.h):
  *   Jq_e = rint(J_e 2^qs), hq_k = rint(h_k 2^qs) with qs the largest exponent such that every |Jq_e| <= 2^23 - 1
  *   (signed 24-bit multiplier) and every row sum  sum_e |Jq_e| + |hq_k| <= 2^31 - 1  (the field is an exact int32),
  *   then lowered by the number of trailing zero bits common to every Jq and hq (canonical form; no value changes);

@@ -37,7 +37,7 @@ def init_spins(R, N, base=1000):
 
 
 def energy_scale(csr, h):
-    """log2 of the engine's fixed-point energy scale for oracle.Csr `csr` (nlmc_create's rule, restated in
+    """log2 of the engine's fixed-point energy scale for oracle.Csr `csr` (the rule of csrc/nlmc_instance.h, restated in
     oracle/nlo.c:nlo_field_scale)."""
     import oracle
     return oracle.field_scale(csr, h)[1]

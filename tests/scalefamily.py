@@ -2,11 +2,11 @@
 
 Every other GPU test instance has couplings of order one, so the fixed-point machinery of the "f32" throughput mode runs at one
 operating point (qs 0 or 22, escale 51).  family() scales one Gaussian instance from 1e-20 to 3e15 and adds the shapes that take
-the remaining branches of the scale rule (nlmc_create; restated in oracle/nlo.c:nlo_field_scale): a hub row and |h| >> |J| (the
+the remaining branches of the scale rule (csrc/nlmc_instance.h; restated in oracle/nlo.c:nlo_field_scale): a hub row and |h| >> |J| (the
 int32 row-sum limit decides), dyadic instances (the common power of two is dropped), couplings that all quantise to 0, fields only.
 
 The references are plain Python: int and fractions.Fraction, no floating point except math.frexp for an exponent.
-  scale_rule        (qs, escale) from the rule as include/nlmc.h and the comment in nlmc_create state it -- not the code's loops
+  scale_rule        (qs, escale) from the rule as include/nlmc.h and the comment in csrc/nlmc_instance.h state it -- not the code's loops
   quantise          Jq, hq = rint(J 2^qs), rint(h 2^qs) as Python ints
   exact_efix_f32    energy of the quantised model in units of 2^-escale, an int
   exact_energy      energy of the real (J, h), a Fraction
@@ -21,7 +21,8 @@ import scipy.sparse as sp
 from helpers import make_instance
 
 # (qs, escale) per member: what oracle.field_scale returned when the family was written.  A change is a finding, not a number to
-# update (tests/test_scale_rule_cpu.py compares the oracle, scale_rule and, on the GPU, nlmc_create with these).
+# update (tests/test_scale_rule_cpu.py compares the oracle and scale_rule with these, tests/test_instance_prep_cpu.py the shipped
+# rule of csrc/nlmc_instance.h, tests/test_gpu_magnitude.py nlmc_create on the GPU).
 PINNED = {
     "x1": (22, 51), "x1e9": (-7, 21), "x2p40": (-18, 11), "x3e15": (-29, 0), "x1e-9": (52, 52), "x2m30": (52, 52),
     "x1e-20": (52, 52), "pmJ_2p7": (-7, 22), "pmJ_2m10_h": (13, 42), "wide": (23, 52), "hub": (19, 48), "bigh": (21, 43),
@@ -112,7 +113,7 @@ def quantise(J, h, qs):
 
 def scale_rule(J, h):
     """(qs, escale) as the interface states them (include/nlmc.h: nlmc_field_scale, nlmc_energy_scale; the comment on the
-    fixed-point scales in nlmc_create):
+    fixed-point scales in csrc/nlmc_instance.h):
       energies are integers in units of 2^-escale with |E| <= B = sum|J|/2 + sum|h|:  escale0 = 60 - ex clamped to [0, 52], where
       2^ex is the first power of two above max(B, 1);
       qs is the largest exponent, at most escale0 and at most 23 - (exponent of the largest |J|; of the largest |h| where there

@@ -1,6 +1,7 @@
 """Host-side bookkeeping of the launch layer (csrc/nlmc.hip), which no kernel test sees: the timing counters behind
 nlmc_last_timing / nlmc_timing_total (bench.py reads them), and the edges of the two round windows -- the device-side swap log
-(nlmc_pt_log_begin) and the planned pair selections (nlmc_pt_plan) -- as the swap launchers and the rounds entry points apply them."""
+(nlmc_pt_log_begin) and the planned pair selections (nlmc_pt_plan) -- as the swap launchers and the rounds entry points apply them;
+and the end of a context that holds every family of buffers, beside one that lives on."""
 import functools
 
 import numpy as np
@@ -213,3 +214,83 @@ def test_round_window_edges(product, precision, monkeypatch):
         for name, x, y in zip(("spins", "energies", "slots"), got, (eng.get_spins(), eng.energy(), eng.pt_slots())):
             assert np.array_equal(x, y), ("planned window", name)
         assert not np.array_equal(got[0], m0)
+
+
+# ---- context lifetime ---------------------------------------------------------------------------------------------------------------
+
+NA, NA2, LA, RA = 48, 256, 4, 8  # engine A: 2 ladders of 4 chains of 48 spins; A2: the same at 256 spins, where fused windows exist
+NB, RB, SB = 96, 4, 4            # engine B: 4 chains of 96 spins, one call of 4 sweeps
+
+
+@functools.lru_cache(maxsize=None)
+def lifetime_case(product):
+    """Instances of the engines, and B's sweep on a fresh engine with nothing beside it: (spins, energies)."""
+    A = product.Instance(*make_instance(NA, seed=23))
+    A2 = product.Instance(*make_instance(NA2, seed=23))
+    B = product.Instance(*make_instance(NB, seed=29, with_h=True, gaussian=True))
+    with product.Engine(B, None, RB) as eng:
+        ref = sweep_b(eng)
+    for x in ref:
+        x.setflags(write=False)
+    return A, A2, B, ref
+
+
+def sweep_b(eng):
+    eng.set_spins(init_spins(RB, NB))
+    eng.sweep_philox(SB, SEED, sweep0=5, beta=0.7)
+    return eng.get_spins(), eng.energy()
+
+
+def every_buffer_family(product, inst):
+    """An engine on `inst` after one call of every kind that makes buffers: a sweep call on each route, tempering, a plan and two
+    rounds, the best-state record, the energy log, an ICM round, a loopy-BP batch.  Fused windows exist from 256 spins on: below,
+    the plan call declines, the sweeps stay sweep by sweep, and the rounds run where such chains' rounds run, inside a lane launch."""
+    n, fused = inst.n, inst.n >= 256
+    a = product.Engine(inst, None, RA)
+    a.set_spins(init_spins(RA, n))
+    a.pt_init(np.geomspace(0.2, 2.0, LA))
+    a.sweep_philox(3, SEED, sweep0=0, beta=None)                                       # sweep by sweep
+    assert a.last_sweep_route() == "stepwise"
+    assert a.plan_philox_fused(3, 1, 3, SEED) == int(fused)                            # one fused window of 3
+    a.sweep_philox(3, SEED, sweep0=3, beta=None)
+    assert a._last_fused() == fused
+    for setter, route in ((a.set_lane_sweeps, "lanes"), (a.set_wave_sweeps, "waves")):
+        setter("force")
+        a.sweep_philox(3, SEED, sweep0=6, beta=None, order="per_chain")
+        assert a.last_sweep_route() == route
+        setter("off")
+    a.best_begin()
+    a.elog_begin(0, 2)
+    assert a.plan_philox_fused(9, 2, 3, SEED) == 2 * int(fused)
+    if not fused:
+        a.set_lane_sweeps("force")
+    a.pt_plan(0, 2, SEED, 1)
+    assert a.pt_rounds_deferred(2, 3, SEED, 9, 0, 1), getattr(a, "rounds_fused_refusal", "")
+    assert a.last_rounds_route() == (IN_LAUNCH if fused else "lanes")
+    best = a.best_read()
+    assert best["state"].shape == (RA, n) and np.all(np.isfinite(best["energy"]))
+    e, slot = a.elog_read()
+    assert e.shape == (2, RA) and np.all(np.isfinite(e)) and np.all((slot >= 0) & (slot < LA))
+    assert a.icm_round_ladders(0, SEED, True, want_info=True).shape == (LA * (RA // LA // 2), 2)
+    o = a.lbp_convexified(np.ones((1, n)), product.lbp.EdgeGraph(inst).epsilon(inst.h), [0.5, 0.45], 2.5, np.finfo(float).eps, 20,
+                          np.tanh(19.06) - np.finfo(float).eps)
+    assert o["mag"].shape == (1, n) and np.all(np.abs(o["mag"]) <= 1.0)
+    return a
+
+
+def test_every_buffer_family_goes_with_its_context(product):
+    """Contexts that have made every family of their buffers exist (sweep schedules of each route, fused plans, lane orders, the wave
+    matrix, tempering, plans and logs of rounds, the best-state record, the energy log, the ICM and loopy-BP buffers) are closed
+    while another context on the device lives: the other's next sweep is that of a fresh engine, bit for bit, and closing twice is
+    harmless.  Three cycles in one process.  Results and clean returns only: free device memory is not this test's to read."""
+    inst_a, inst_a2, inst_b, ref = lifetime_case(product)
+    for cycle in range(3):
+        a, a2 = every_buffer_family(product, inst_a), every_buffer_family(product, inst_a2)
+        b = product.Engine(inst_b, None, RB)                                           # created while A lives
+        a.close()
+        a2.close()
+        got = sweep_b(b)
+        assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]), cycle
+        b.close()
+        b.close()                                                                      # a second close does nothing
+        a.close()
