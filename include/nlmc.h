@@ -559,6 +559,32 @@ int nlmc_get_cluster_mask(nlmc_ctx *ctx, uint8_t *out /*[n_chains][n]*/);
 /* Caller-provided backbones instead of an inference (NMC_subroutine's `all_clusters` argument, NPT/npt.py:357-359): 1 = in a cluster. */
 int nlmc_set_cluster_mask(nlmc_ctx *ctx, const uint8_t *mask /*[n_chains][n]*/);
 int nlmc_set_phase(nlmc_ctx *ctx, int kind, double temp_x);
+/* All phases of an NMC cycle of short chains in launches of k_nmc_phases_lanes (csrc/nlmc_lane_nmc.h), a chain per lane, on the selected
+ * chains: for phase p of kind kinds[p] (NLMC_PHASE_*) -- p > 0: nlmc_adopt_best -- nlmc_set_phase(kinds[p], temp_x) and
+ * nlmc_sweep_philox(shared order, sweeps_per_phase sweeps from sweep0 + p sweeps_per_phase, one beta) under
+ * nlmc_track_minimum(min_stride), with spins, backbone mask and (where it fits) the best state in LDS across the hand-offs: the flag
+ * of a spin is computed from its mask byte, the context's flags array and nlmc_set_phase's setting are neither read nor changed.  Same
+ * bits as that call sequence on any route: spins, tracked energies, energy sink, minimum, argmin and best state are left as its last
+ * sweep call leaves them.  Reached by name: nlmc_set_lane_sweeps is not looked at.
+ * Optional read-backs (each nullable; any of them synchronises the stream): out_phase_min [rows][n_phases], the minimum of every phase
+ * in the fixed point of the tracked energies (times 2^-nlmc_energy_scale), out_phase_argmin [rows][n_phases] (sweep of the first
+ * attainment, counted from 0 within the phase), out_last_best [rows][n], the best state of the last phase; rows = nlmc_subset_count.
+ * Without them the call is asynchronous on the stream the subset's sweeps use (nlmc_overlap_subsets), with visiting orders of its own.
+ * The orders come from one k_lane_orders launch per launch: a call whose orders exceed the order scratch (NLMC_LANE_SCRATCH), or of
+ * more than 128 phases, is cut into launches of whole phases, the state carried over by the context's arrays.
+ * NLMC_ERR_ARG: n_phases < 1, sweeps_per_phase < 1, min_stride < 1, a bad kind or precision, temp_x = 0.  NLMC_ERR_STATE: no backbone
+ * mask yet (nlmc_backbone_clusters / nlmc_set_cluster_mask), or nlmc_track_minimum is on (the call keeps the minimum itself).
+ * NLMC_ERR_UNSUPPORTED (nothing was run, the reason in nlmc_last_error; nlmc_nmc_phases_lanes_refusal asks without a call): n >
+ * NLMC_LANE_N or the global-memory kernels (NLMC_FORCE_BIG); one phase's orders exceed the order scratch; random numbers keyed by
+ * temperature slot (nlmc_apt_shard); spins + mask exceed a workgroup's LDS; NLMC_NO_LANE_NMC=1 at nlmc_create (test knob).  Afterwards
+ * nlmc_last_sweep_route is NLMC_ROUTE_LANES, nlmc_last_schedule_stats reports the visiting orders built, the launch counters count a
+ * phase each, the timings count the order kernel as the levelize half. */
+int nlmc_nmc_phases_lanes(nlmc_ctx *ctx, int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0,
+                          uint64_t seed, double beta, double temp_x, int min_stride, int64_t *out_phase_min, int32_t *out_phase_argmin,
+                          int8_t *out_last_best);
+/* NULL when nlmc_nmc_phases_lanes would take phases of sweeps_per_phase sweeps on this context, else the reason of its
+ * NLMC_ERR_UNSUPPORTED (a static string). */
+const char *nlmc_nmc_phases_lanes_refusal(const nlmc_ctx *ctx, int sweeps_per_phase);
 /* Fused-window plans live in two slots; nlmc_plan_philox_fused / nlmc_plan_reserve_fused write to the selected one, sweep
  * calls use whichever slot covers their sweeps (a round sweeps its plain chains on windows of num_sweeps_MCMC_per_swap and
  * its NMC phases on windows of num_sweeps_per_NMC_phase_per_swap, NPT/npt.py:577-580). */

@@ -10,6 +10,7 @@
 #include "nlmc_lanes.h"
 #include "nlmc_lane_rounds.h"
 #include "nlmc_lane_apt.h"
+#include "nlmc_lane_nmc.h"
 #include "nlmc_waves.h"
 #include "nlmc_wave_rounds.h"
 #include "nlmc_wave_shape.h"
@@ -97,6 +98,7 @@ struct Knobs {
     size_t lane_scratch = (size_t)256 << 20;   // NLMC_LANE_SCRATCH: bytes of visiting orders one window of chain-per-lane sweeps may hold (test knob)
     int lane_rng = -1;               // NLMC_LANE_RNG: chain-per-lane sweeps make the Philox call per update (0) / keep a table per sweep in LDS
                                      // where it fits (1); -1: the default
+    bool no_lane_nmc = false;        // NLMC_NO_LANE_NMC: nlmc_nmc_phases_lanes refuses (test knob)
     int wave_waves = 0;              // NLMC_WAVE_WAVES: waves (chains) per workgroup of the wave-per-chain sweeps (1..16; 0: by row count)
     bool wave_jlds = true;           // NLMC_WAVE_JLDS=0: the wave-per-chain sweeps read the matrix rows from global memory at every n
     int wave_rounds_ladders = 0;     // NLMC_WAVE_ROUNDS_LADDERS: ladders per workgroup of the rounds inside a wave launch (0: by the rule)
@@ -123,6 +125,7 @@ Knobs read_knobs()
     k.lbp_group = num("NLMC_LBP_GROUP", 0); k.lbp_poll_budget = num("NLMC_LBP_POLL_BUDGET", 0); k.lbp_global = on("NLMC_LBP_GLOBAL");
     if (const char *s = getenv("NLMC_LANE_SCRATCH")) k.lane_scratch = std::max<size_t>(1, (size_t)strtoull(s, nullptr, 0));
     k.lane_rng = on("NLMC_LANE_RNG") ? (num("NLMC_LANE_RNG", 0) != 0) : -1;
+    k.no_lane_nmc = num("NLMC_NO_LANE_NMC", 0) != 0;
     k.wave_waves = std::min(16, std::max(0, num("NLMC_WAVE_WAVES", 0)));
     k.wave_jlds = num("NLMC_WAVE_JLDS", 1) != 0;
     k.wave_rounds_ladders = std::min(64, std::max(0, num("NLMC_WAVE_ROUNDS_LADDERS", 0)));
@@ -242,6 +245,11 @@ struct nlmc_ctx {
     int last_route = 0;           // nlmc_last_sweep_route: NLMC_ROUTE_* of the most recent sweep call
     int64_t stat_lane_orders = 0; // visiting orders the most recent sweep call built for the lane kernels
     DevBuf<uint16_t> lane_perm;   // [orders of a window][n]
+    // NMC phase cycles inside a lane launch (csrc/nlmc_lane_nmc.h): orders of their own, so that a call on the second stream does not
+    // wait for the lane sweeps of the main one; the per-phase minima of the last call that asked for them
+    DevBuf<uint16_t> nmc_perm;    // [orders of a launch][n]
+    DevBuf<long long> nmc_pmin;   // [rows][phases]
+    DevBuf<int32_t> nmc_pargmin;
     // wave-per-chain sweeps (csrc/nlmc_waves.h)
     int wave_mode = 0;            // nlmc_set_wave_sweeps: 0 off, 1 auto, 2 force
     bool wave_rounds = false;     // nlmc_set_wave_rounds: nlmc_pt_rounds_deferred takes k_rounds_waves where the sweeps go to the wave kernels
@@ -1251,13 +1259,15 @@ const void *apt_lanes_kernel(bool f64, bool elog)
     return table[f64 ? 1 : 0][elog ? 1 : 0];
 }
 
-// k_lane_orders: the n_orders visiting orders of a lane launch into c->lane_perm, n_sweeps from sweep0 on (per_chain: for each chain).
-int launch_lane_orders(nlmc_ctx *c, hipStream_t st, size_t n_orders, int n_sweeps, int per_chain, uint32_t sweep0, uint64_t seed)
+// k_lane_orders: the n_orders visiting orders of a lane launch into c->lane_perm (or `perm`), n_sweeps from sweep0 on (per_chain: for
+// each chain).
+int launch_lane_orders(nlmc_ctx *c, hipStream_t st, size_t n_orders, int n_sweeps, int per_chain, uint32_t sweep0, uint64_t seed,
+                       uint16_t *perm = nullptr)
 {
     LaneOrderArgs oa{};
     oa.n = c->n; oa.n_sweeps = n_sweeps; oa.per_chain = per_chain; oa.chain_base = c->chain_base;
     oa.seed_lo = (uint32_t)seed; oa.seed_hi = (uint32_t)(seed >> 32); oa.sweep0 = sweep0;
-    oa.perm = c->lane_perm.p;
+    oa.perm = perm ? perm : c->lane_perm.p;
     hipLaunchKernelGGL(k_lane_orders, dim3((unsigned)n_orders), dim3(256), 0, st, oa);
     HIP_TRY(c, hipGetLastError());
     c->stat_lane_orders += (int64_t)n_orders;
@@ -3383,6 +3393,125 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
         for (size_t p = 0; p < cnt; p += 2)
             if (out_info[p] < 0) return fail(c, NLMC_ERR_STATE, "icm: the component search did not converge");
     }
+    return NLMC_OK;
+}
+
+// ---- NMC phase cycles of short chains in one launch: a chain per lane (k_nmc_phases_lanes, csrc/nlmc_lane_nmc.h) ---------------------
+// LDS of k_nmc_phases_lanes: transposed spins | transposed backbone mask | (where it fits) a transposed best-state plane | (where it
+// fits) one sweep's random numbers.  The table under lane_lds' rule -- four waves still share a compute unit, 40 KB per wave -- and the
+// best-state plane where that still holds beside the rest; best_off = 0: the best state stays in global memory.
+struct LaneNmcLds { size_t mask_off, best_off, u_off, total; bool tab, ok; };
+static LaneNmcLds lane_nmc_lds(const nlmc_ctx *c)
+{
+    LaneNmcLds L{};
+    const size_t plane = (size_t)c->n_pad * NLMC_LANE_STRIDE, tab = (size_t)((c->n + 3) / 4 * 4) * 256, share = (size_t)40 * 1024;
+    size_t state = 2 * plane;
+    L.mask_off = plane;
+    L.ok = state <= NLMC_LDS_BYTES_MAX;
+    L.tab = c->knobs.lane_rng != 0 && state + tab <= share;
+    if (state + plane + (L.tab ? tab : 0) <= share) { L.best_off = state; state += plane; }
+    L.u_off = state;
+    L.total = state + (L.tab ? tab : 0);
+    return L;
+}
+
+// Why this context cannot run NMC phases of S sweeps inside k_nmc_phases_lanes, or nullptr.  (The entry point has the shared visiting
+// order only: a per-chain order cannot be asked for.)  Arguments and call order are checked by the caller.
+static const char *lane_nmc_refusal(const nlmc_ctx *c, int S)
+{
+    if (c->knobs.no_lane_nmc) return "switched off (NLMC_NO_LANE_NMC)";
+    if (c->knobs.force_big || c->big || c->n > NLMC_LANE_N) return "the chain-per-lane kernels take chains of at most NLMC_LANE_N spins, resident in LDS";
+    if (c->rng_stride != 0) return "random numbers keyed by temperature slot (nlmc_apt_shard) keep the phase-by-phase route";
+    if ((size_t)S * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
+        return "the visiting orders of one phase exceed the order scratch (NLMC_LANE_SCRATCH)";
+    if (!lane_nmc_lds(c).ok) return "spins and backbone mask exceed one workgroup's LDS";
+    return nullptr;
+}
+
+const char *nlmc_nmc_phases_lanes_refusal(const nlmc_ctx *c, int sweeps_per_phase)
+{
+    if (!c) return "no context";
+    return lane_nmc_refusal(c, std::max(1, sweeps_per_phase));
+}
+
+int nlmc_nmc_phases_lanes(nlmc_ctx *c, int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0, uint64_t seed,
+                          double beta, double temp_x, int min_stride, int64_t *out_phase_min, int32_t *out_phase_argmin, int8_t *out_last_best)
+{
+    if (!c) return NLMC_ERR_ARG;
+    const std::string name = "nlmc_nmc_phases_lanes: ";
+    const int P = n_phases, S = sweeps_per_phase;
+    if ((precision != NLMC_F32 && precision != NLMC_F64) || !kinds || P < 1 || S < 1 || min_stride < 1 || (long long)P * S > (long long)(INT_MAX / 2))
+        return fail(c, NLMC_ERR_ARG, name + "bad argument");
+    for (int p = 0; p < P; ++p)
+        if (kinds[p] < NLMC_PHASE_ALL || kinds[p] > NLMC_PHASE_BACKBONE_FROZEN) return fail(c, NLMC_ERR_ARG, name + "bad phase");
+    if (!(temp_x > 0.0) && !(temp_x < 0.0)) return fail(c, NLMC_ERR_ARG, name + "temp_x must be non-zero");
+    if (!c->cmask.p) return fail(c, NLMC_ERR_STATE, name + "no backbone inference has run");
+    if (c->track_min) return fail(c, NLMC_ERR_STATE, name + "a tracked minimum is open (nlmc_track_minimum): the call keeps its own");
+    if (const char *why = lane_nmc_refusal(c, S)) return fail(c, NLMC_ERR_UNSUPPORTED, name + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int R = c->sub_count(), n = c->n;
+    if (R == 0) return NLMC_OK;
+    { int rc = ensure_subset(c); if (rc) return rc; }
+    const LaneNmcLds L = lane_nmc_lds(c);
+    const void *kfun = precision == NLMC_F64 ? reinterpret_cast<const void *>(k_nmc_phases_lanes<true>) : reinterpret_cast<const void *>(k_nmc_phases_lanes<false>);
+    { int rc = ensure_lds(c, kfun, L.total); if (rc) return rc; }
+    // launches of as many whole phases as the order scratch holds visiting orders for (and the kernel arguments hold kinds for)
+    const size_t bytes_per_phase = (size_t)S * (size_t)n * sizeof(uint16_t);
+    const int K = (int)std::max<size_t>(1, std::min<size_t>({(size_t)P, c->knobs.lane_scratch / bytes_per_phase, (size_t)NLMC_NMC_PHASES_LAUNCH}));
+    begin_sweep_call(c);
+    c->stat_orders = 0; c->stat_levels = 0; c->stats_pending = false;
+    c->stat_fused_window = -1;
+    c->stat_lane_orders = 0;
+    c->strace_nrec = 0; c->strace_rows = 0;
+    HIP_TRY(c, c->nmc_perm.reserve((size_t)K * (size_t)S * (size_t)n));
+    const bool want_min = out_phase_min || out_phase_argmin;
+    if (want_min) {
+        HIP_TRY(c, c->nmc_pmin.reserve((size_t)R * P));
+        HIP_TRY(c, c->nmc_pargmin.reserve((size_t)R * P));
+    }
+    for (int at = 0; at < P; at += K) {
+        const int k = std::min(K, P - at);
+        const uint32_t s0 = sweep0 + (uint32_t)at * (uint32_t)S;
+        TimerSpan ts;
+        if (c->ev_accumulate) { int rc = span_begin(c, ts, 0, c->cur); if (rc) return rc; }
+        { int rc = launch_lane_orders(c, c->cur, (size_t)k * S, k * S, 0, s0, seed, c->nmc_perm.p); if (rc) return rc; }
+        { int rc = span_mid(c, ts); if (rc) return rc; }
+        SweepArgs a = sweep_args(c, s0, S, seed, nullptr, 0, 0, false);
+        lane_fields(c, a, R, L.tab, L.u_off);
+        a.flags = nullptr; a.lane_perm = c->nmc_perm.p; a.min_stride = min_stride;
+        a.emin = c->emin.p; a.best = c->best.p;
+        LaneNmcArgs q{};
+        q.n_phases = k; q.phase0 = at; q.phases_total = P;
+        for (int p = 0; p < k; ++p) q.kinds[p >> 4] |= (uint32_t)kinds[at + p] << (2 * (p & 15));
+        q.cb0 = -2.0 * LOG2E * beta; q.cb1 = -2.0 * LOG2E * (beta / temp_x);
+        q.mask = c->cmask.p;
+        q.phase_min = want_min ? c->nmc_pmin.p : nullptr; q.phase_argmin = want_min ? c->nmc_pargmin.p : nullptr;
+        q.lds_mask_off = (int)L.mask_off; q.lds_best_off = (int)L.best_off;
+        void *kargs[] = {&a, &q};
+        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)((R + 63) / 64)), dim3(64), kargs, L.total, c->cur));
+        HIP_TRY(c, hipGetLastError());
+        { int rc = span_end(c, ts); if (rc) return rc; }
+        count_launches(c, k, c->ev_accumulate);
+    }
+    c->last_route = NLMC_ROUTE_LANES;
+    if (!want_min && !out_last_best) return NLMC_OK;
+
+    // the optional read-backs: rows of the subset (the best states live in per-chain rows: gathered through the chain list)
+    std::vector<int32_t> h_list;
+    if (out_phase_min) HIP_TRY(c, hipMemcpyAsync(out_phase_min, c->nmc_pmin.p, sizeof(long long) * (size_t)R * P, hipMemcpyDeviceToHost, c->cur));
+    if (out_phase_argmin) HIP_TRY(c, hipMemcpyAsync(out_phase_argmin, c->nmc_pargmin.p, sizeof(int32_t) * (size_t)R * P, hipMemcpyDeviceToHost, c->cur));
+    if (out_last_best) {
+        if (c->subset != 0) {
+            h_list.resize((size_t)R);
+            HIP_TRY(c, hipMemcpyAsync(h_list.data(), c->sub_list(), sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost, c->cur));
+        }
+        int rc = rows_to_host_begin(c, c->best.p, c->n_chains);
+        if (rc) return rc;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->cur));
+    if (out_last_best)
+        for (int i = 0; i < R; ++i)
+            std::memcpy(out_last_best + (size_t)i * n, c->stage_out.data() + (size_t)(c->subset != 0 ? h_list[(size_t)i] : i) * c->n_pad, (size_t)n);
     return NLMC_OK;
 }
 

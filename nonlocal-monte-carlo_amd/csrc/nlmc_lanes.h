@@ -118,6 +118,63 @@ __device__ __forceinline__ void lane_field(const CsrDev &g, const int8_t *s, int
     }
 }
 
+// Random numbers of sweep tt of chain gc into the lane's column of the table, one Philox call per four spins: f32 the logistic
+// thresholds, f64 the UNIFORM words (the 27 high bits of u; the UNIFORM_LO call is made at the update).  (The table has
+// (n + 3) / 4 * 4 rows.)
+template <bool F64>
+__device__ __forceinline__ void lane_fill_rtab(uint32_t *rtab, int n, int lane, uint32_t tt, uint32_t gc, uint32_t seed_lo, uint32_t seed_hi)
+{
+    for (int b = 0; b < (n + 3) / 4; ++b) {
+        const u32x4 r = philox4x32_10((uint32_t)b, tt, gc, NLMC_TAG_UNIFORM, seed_lo, seed_hi);
+        uint32_t *d = rtab + (size_t)(4 * b) * 64 + lane;
+        if (F64) { d[0] = r.x; d[64] = r.y; d[128] = r.z; d[192] = r.w; }
+        else {
+            d[0] = __float_as_uint(threshold_spec(r.x)); d[64] = __float_as_uint(threshold_spec(r.y));
+            d[128] = __float_as_uint(threshold_spec(r.z)); d[192] = __float_as_uint(threshold_spec(r.w));
+        }
+    }
+}
+
+// The update of spin k of the lane's chain in sweep tt, as k_sweep_lanes writes it out (k_nmc_phases_lanes; k_sweep_lanes, k_rounds_lanes
+// and k_apt_rounds_lanes keep their own text: sharing this body cost them speed): phase flag f (1: cb1, >= 2: the spin keeps
+// its value and adds no energy), random numbers from the table where there is one (rtab), else a Philox call.  The energy delta goes to
+// e_loc.  UNI: k is wave-uniform.
+template <bool F64, bool UNI, typename T>
+__device__ __forceinline__ void lane_update(const SweepArgs &a, int8_t *s, const uint32_t *rtab, int lane, int k, unsigned f, uint32_t tt,
+                                            uint32_t gc, T cb0, T cb1, double esc, long long &e_loc)
+{
+    constexpr int stride = NLMC_LANE_STRIDE;
+    const int so = (int)s[k * stride + lane];
+    const int rs = lane_ro<UNI>(a.g.rowptr + k), re = lane_ro<UNI>(a.g.rowptr + k + 1);
+    const uint32_t hi = rtab ? rtab[(size_t)k * 64 + lane]
+                             : (F64 ? lane_word(philox4x32_10((uint32_t)(k >> 2), tt, gc, NLMC_TAG_UNIFORM, a.seed_lo, a.seed_hi), k)
+                                    : __float_as_uint(threshold_spec(lane_word(philox4x32_10((uint32_t)(k >> 2), tt, gc, NLMC_TAG_UNIFORM, a.seed_lo, a.seed_hi), k))));
+    int sn;
+    long long de;
+    if constexpr (F64) {
+        double xs, xd;                               // xd: the diagonal term, left out of the energy delta
+        if (a.lane_diag) lane_field<UNI, true>(a.g, s, lane, k, rs, re, xs, xd);
+        else lane_field<UNI, false>(a.g, s, lane, k, rs, re, xs, xd);
+        const double hk = lane_ro<UNI>(a.g.h64 + k);
+        const double x_true = (xs - xd) + hk, xf = xs + hk;
+        const uint32_t lo = lane_word(philox4x32_10((uint32_t)(k >> 2), tt, gc, NLMC_TAG_UNIFORM_LO, a.seed_lo, a.seed_hi), k);
+        const double z = (f == 1u ? cb1 : cb0) * xf;
+        sn = accept_up(uniform53_spec(hi, lo), z) ? 1 : -1;
+        de = (sn != so) ? fixed_delta_slow(x_true, sn - so, esc) : 0ll;
+    } else {
+        int X = lane_ro<UNI>(a.g.hq + k), Xd;
+        if (a.lane_diag) lane_field<UNI, true>(a.g, s, lane, k, rs, re, X, Xd);
+        else lane_field<UNI, false>(a.g, s, lane, k, rs, re, X, Xd);
+        const float z = (f == 1u ? cb1 : cb0) * (float)X;
+        sn = (z < __uint_as_float(hi)) ? 1 : -1;
+        de = (long long)(X - Xd) * (long long)((so - sn) * (1 << a.eshift));
+    }
+    if (f < 2u) {                                    // frozen spins keep their value
+        e_loc += de;
+        s[k * stride + lane] = (int8_t)sn;
+    }
+}
+
 // F64: the fp64 mode (update_spin<double>), else the fixed-point "f32" mode (update_spin_q).  PER_CHAIN: every chain has its own
 // visiting order.  Phase flags, diagonal entries, outputs, temperature source and chain subset are runtime branches, wave-uniform
 // or plain per-lane predicates.  SweepArgs fields of this kernel: lane_perm, lane_rows, lane_tab, lane_diag; lds_flags_off,

@@ -22,6 +22,11 @@ from .engine import Engine, RoundPlanner
 # unplanned fallback used to reuse the next round's plain indices).
 NMC_SWEEP_SPACE = 1 << 31
 
+# Whether LocalTempering runs the NMC phases of a round without outputs inside one k_nmc_phases_lanes launch per context
+# (Engine.nmc_phases_lanes) where the engine takes them, when the caller does not say (lane_nmc=None).  Set from
+# scripts/lane_nmc_throughput.py (profiles/lane_nmc_throughput.txt).
+LANE_NMC_IN_LAUNCH = True
+
 
 def block_partition(n_global, world, rank):
     """Contiguous block of chains owned by `rank` (first `n_global % world` ranks get one extra)."""
@@ -275,7 +280,7 @@ class LocalTempering:
 
     def __init__(self, inst, beta_list, n_chains_global, seed, n_pairs, device_ids, precision="f32", engine_factory=None,
                  engines=None, parts=None, lane_sweeps="off", track_best=False, target_energy=None, track_energies=False,
-                 wave_sweeps="off", wave_rounds=False):
+                 wave_sweeps="off", wave_rounds=False, lane_nmc=None):
         """`parts` (optional): the blocks [(chain_base, count)] this process drives instead of an even cut over device_ids -- one
         rank's share under a launcher; `engines`: contexts that exist already (they must have had pt_init; not closed here... they
         ARE closed by close(): hand over ownership); `lane_sweeps`: Engine.set_lane_sweeps of every engine created here ("off",
@@ -289,7 +294,11 @@ class LocalTempering:
         NMC cycles) and before its swap; best() reads it.  The record only observes: the trajectory is the same bits.
         `track_energies`: every context keeps a per-round log of its chains' tracked energies and temperature slots as the round's
         swap decision sees them (Engine.elog_begin) -- opened by plan() for the rounds it plans, or by energy_log_begin(); one
-        observation per round at the same place; energy_log() reads it.  Needs whole ladders per context (ValueError otherwise)."""
+        observation per round at the same place; energy_log() reads it.  Needs whole ladders per context (ValueError otherwise).
+        `lane_nmc` (None: LANE_NMC_IN_LAUNCH where the engine's sweeps run one chain per lane, Engine.lanes_take; True, False): with NMC slots (configure_nmc), a round that wants no per-sweep output runs
+        the marked chains' phases in one Engine.nmc_phases_lanes call per context instead of the phase loop -- same bits.  A context
+        whose engine refuses (long chains, ...) keeps the phase loop and is not asked again.  Counters: lane_nmc_rounds (rounds in
+        which every context took the call), lane_nmc_calls (calls that ran)."""
         hostlogic.check_wave_rounds(wave_rounds, wave_sweeps, needs="wave_sweeps 'auto' or 'force'")
         self.G, self.seed, self.n_pairs, self.precision = int(n_chains_global), int(seed), int(n_pairs), precision
         devs = list(device_ids)
@@ -317,6 +326,11 @@ class LocalTempering:
         self._planners = None
         self.nmc = None
         self._nmc_planners = None
+        self.lane_nmc = LANE_NMC_IN_LAUNCH if lane_nmc is None else bool(lane_nmc)
+        self._lane_nmc_by_default = lane_nmc is None      # ... then only where the context's sweeps run on the lane kernels anyway
+        self._lane_nmc_refused = set()       # contexts (by index) whose engine turned nmc_phases_lanes down
+        self._lane_nmc_asked = set()         # ... whose engine was asked (Engine.nmc_phases_lanes_refusal)
+        self.lane_nmc_rounds = self.lane_nmc_calls = 0
         self.track_best = bool(track_best)
         self.track_energies, self._elog_open = bool(track_energies), False
         if self.track_energies and not self.whole_ladders:
@@ -350,6 +364,22 @@ class LocalTempering:
         # M_skip > 1 (NPT/npt.py:434-437: M = M[:, ::M_skip] before the energies and the argmin): the phases' running minimum looks at
         # every M_skip-th sweep only (nlmc_track_minimum(M_skip)), their recorded traces are strided the same way
 
+    def _lane_nmc_takes(self, k):
+        """Whether context k's NMC phases go to Engine.nmc_phases_lanes: the option is on, and the engine has not refused (asked
+        once per context: a refusal is remembered)."""
+        if not (self.nmc and self.lane_nmc) or k in self._lane_nmc_refused:
+            return False
+        if k in self._lane_nmc_asked:
+            return True
+        e = self.engs[k]
+        self._lane_nmc_asked.add(k)
+        on_lanes = hasattr(e, "lanes_take") and e.lanes_take()
+        if not hasattr(e, "nmc_phases_lanes") or (self._lane_nmc_by_default and not on_lanes) or \
+                (hasattr(e, "nmc_phases_lanes_refusal") and e.nmc_phases_lanes_refusal(self.nmc["S"])):
+            self._lane_nmc_refused.add(k)
+            return False
+        return True
+
     def sweeps_per_round(self, n_sweeps):
         """Plain sweep indices (RNG counters) one round of `n_sweeps` sweeps consumes.  The NMC phases of the marked slots draw from
         a range of their own (NMC_SWEEP_SPACE + nmc_sweeps_done, advanced by phases x sweeps_per_phase per round)."""
@@ -362,7 +392,9 @@ class LocalTempering:
                                        pt_pairs=self.n_pairs, pt_round0=self.rounds_done, slot=0, fused_outputs=True) for e in self.engs]
         self._planner_round0 = self.rounds_done
         self._nmc_planners = None
-        if self.nmc:
+        if self.nmc and not all(self._lane_nmc_takes(k) for k in range(len(self.engs))):
+            # (where every context runs its phases inside nmc_phases_lanes launches there is nothing to plan for them: the rounds with
+            # outputs run their phases on the lane kernels, which need no level schedule)
             # the NMC phases draw from their own range of sweep indices, behind the plain sweeps of all planned rounds: both
             # ranges are contiguous over the rounds, so each is served by one fused-window plan (slots 0 and 1)
             n_ph = len(self.nmc["phases"])
@@ -401,6 +433,7 @@ class LocalTempering:
         "nmc_chains": ids, "plain_energy_columns": fp64 energies of the first `energy_columns` recorded columns}."""
         ii = self.rounds_done - (self._planner_round0 if self._planners else 0)
         outs = []
+        in_launch = 0
         wants = any(outputs.get(k) for k in ("record_stride", "want_energy", "want_min", "want_state"))
         for k, e in enumerate(self.engs):
             if self.nmc:
@@ -424,6 +457,21 @@ class LocalTempering:
             if wants:
                 rec["nmc_chains"] = e.subset()
             e.backbone_clusters(q["epsilon"], q["lambdas"], q["beta"], q["tol"], q["max_it"], q["sat"], q["thresholds"])
+            took = False
+            if not wants and self._lane_nmc_takes(k):
+                try:                                 # all phases in one launch (same bits as the loop below)
+                    e.nmc_phases_lanes(q["phases"], q["S"], self.seed, NMC_SWEEP_SPACE + self.nmc_sweeps_done, q["beta"], q["temp_x"],
+                                       min_stride=q["M_skip"], precision=self.precision)
+                    took = True
+                    in_launch += 1
+                except NotImplementedError:          # nothing was run: the phase loop, now and from here on
+                    self._lane_nmc_refused.add(k)
+            if took:
+                e.set_phase("ALL")
+                e.select("all")
+                self._observe(e, self.rounds_done)
+                outs.append(rec)
+                continue
             e.track_minimum(True, stride=q["M_skip"])
             n_ph = len(q["phases"])
             out_nmc = dict(outputs, record_stride=q["M_skip"]) if outputs.get("record_stride") else outputs
@@ -443,6 +491,8 @@ class LocalTempering:
             self._observe(e, self.rounds_done)      # (all chains selected again, the NMC chains in the state they carry on; before the swap)
             outs.append(rec)
         self.sweeps_done += n_sweeps
+        self.lane_nmc_calls += in_launch
+        self.lane_nmc_rounds += 1 if (in_launch and in_launch == len(self.engs)) else 0
         if self.nmc:
             self.nmc_sweeps_done += len(self.nmc["phases"]) * self.nmc["S"]
         if self.n_pairs > 0:

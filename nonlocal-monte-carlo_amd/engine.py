@@ -724,6 +724,36 @@ class Engine:
         self._ck(self._L.nlmc_set_phase(self._ctx, k, float(temp_x)))
         self._flags_on = kind != "ALL"
 
+    PHASES = {"ALL": _abi.PHASE_ALL, "C": _abi.PHASE_BACKBONE_HOT, "NC": _abi.PHASE_BACKBONE_FROZEN}
+
+    def nmc_phases_lanes(self, kinds, sweeps_per_phase, seed, sweep0, beta, temp_x, min_stride=1, precision="f32",
+                         want_minima=False, want_last_best=False):
+        """All phases `kinds` ("C" / "NC" / "ALL") of an NMC cycle of the selected chains inside k_nmc_phases_lanes launches, a chain
+        per lane (include/nlmc.h: nlmc_nmc_phases_lanes): per phase adopt_best (from the second on), set_phase(kind, temp_x) and
+        sweep_philox(sweeps_per_phase, seed, sweep0 + p * sweeps_per_phase, beta) under track_minimum(True, min_stride) -- same bits
+        as that call sequence, in one launch per call (or per chunk of phases the order scratch holds).  The backbone masks are those of
+        the last backbone_clusters / set_cluster_mask; track_minimum must be off; set_phase's setting is left alone.  Returns None, or
+        with want_minima / want_last_best (read-backs: they synchronise the stream) a dict: phase_min [rows, P] float64 as
+        energy_tracked reports and phase_argmin [rows, P] int32 (sweep within the phase), last_best [rows, n] int8.
+        NotImplementedError when the context does not qualify (nothing was run; nmc_phases_lanes_refusal asks beforehand)."""
+        k = _abi.as_c([self.PHASES[x] for x in kinds], np.int32)
+        R, P = self.rows(), int(k.shape[0])
+        pmin = np.empty((R, P), np.int64) if want_minima else None
+        parg = np.empty((R, P), np.int32) if want_minima else None
+        best = np.empty((R, self.n), np.int8) if want_last_best else None
+        self._ck(self._L.nlmc_nmc_phases_lanes(self._ctx, _precision(precision), _abi.ptr(k), P, int(sweeps_per_phase),
+                                               int(sweep0) & 0xFFFFFFFF, int(seed), float(beta), float(temp_x), int(min_stride),
+                                               _abi.ptr(pmin), _abi.ptr(parg), _abi.ptr(best)))
+        if not (want_minima or want_last_best):
+            return None
+        return {"phase_min": None if pmin is None else pmin.astype(np.float64) * 2.0 ** -self.energy_scale,
+                "phase_argmin": parg, "last_best": best}
+
+    def nmc_phases_lanes_refusal(self, sweeps_per_phase):
+        """Why nmc_phases_lanes would refuse phases of `sweeps_per_phase` sweeps on this context (the library's reason), or None."""
+        why = self._L.nlmc_nmc_phases_lanes_refusal(self._ctx, int(sweeps_per_phase))
+        return why.decode() if why else None
+
     # -- iso-cluster move -------------------------------------------------------------------------------
     def icm_components(self, chain_a, chain_b):
         out = ctypes.c_int32(0)

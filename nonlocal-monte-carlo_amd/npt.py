@@ -30,13 +30,20 @@ class NPT(Common):
     """NMC + Adaptive Parallel Tempering (NPT/npt.py:15)."""
     _variant = "npt"
 
-    def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32", lanes="off", waves="off", wave_rounds=False):
+    def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32", lanes="off", waves="off", wave_rounds=False,
+                 lane_nmc=None):
         """`precision` (additive keyword, rng="philox" only): "f32" (default) -- the throughput mode's fixed-point couplings and
         logistic thresholds; "f64" -- the device-resident rounds in the reference's arithmetic (fp64 field, 53-bit uniform), on
         fused windows for real couplings too (Engine.set_fused_f64_real).  Replicas with doNMC set are not supported with "f64".
         `lanes` (additive keyword, rng="philox" only): "off" (default), "auto" or "force" -- Engine.set_lane_sweeps of the run's
         engines ("auto" never fires today: its row threshold NLMC_LANE_AUTO_ROWS is 2^31 - 1, so it runs as "off"): short chains (n <= 1024, a ladder of at most 64 temperatures) run one per lane, their rounds inside k_rounds_lanes
-        launches -- same results.  Plain replicas only; a ladder cut across ranks keeps its route.
+        launches -- same results.  Plain replicas only unless `lane_nmc` is given; a ladder cut across ranks keeps its route.
+        `lane_nmc` (additive keyword; None, True, False): with `lanes`, opts doNMC slots in -- the plain chains and the NMC phases both
+        run on the lane kernels.  True: the rounds that return no per-sweep output run all NMC phases of a round in one launch per
+        context (Engine.nmc_phases_lanes); False: a lane sweep call per phase -- same results either way, and those of lanes="off";
+        self.lane_nmc_rounds counts the rounds of the last run that took the one-launch call.  None (the default): run() with `lanes`
+        and a doNMC slot raises ValueError, as it did before the keyword existed (distributed.LANE_NMC_IN_LAUNCH says which of the
+        two was measured ahead: what LocalTempering takes by itself on the lane route).
         `waves` (additive keyword, rng="philox" only, not with precision="f64"): "off" (default), "auto" or "force" --
         Engine.set_wave_sweeps of the run's engines: f32 sweeps of chains of at most 256 spins run one chain per wave with resident
         local fields, round by round through the sweep calls -- same results.  A ladder cut across ranks keeps its route.
@@ -54,6 +61,7 @@ class NPT(Common):
         self.lanes = lanes
         self.waves = waves
         self.wave_rounds = bool(wave_rounds)
+        self.lane_nmc = lane_nmc
 
     # ------------------------------------------------------------------------------------------------
     def replica_energy(self, M, num_sweeps):
@@ -142,8 +150,9 @@ class NPT(Common):
         any_nmc = any(bool(v) for v in doNMC)
         if any_nmc and self.precision != "f32":
             raise ValueError("precision='f64' runs plain replicas only: doNMC slots are not supported")
-        if any_nmc and self.lanes != "off":
-            raise ValueError("lanes runs plain replicas only: doNMC slots are not supported")
+        if any_nmc and self.lanes != "off" and self.lane_nmc is None:
+            raise ValueError("lanes runs plain replicas only unless lane_nmc is given: doNMC slots take lane_nmc=True (all NMC phases "
+                             "of a round in one launch) or lane_nmc=False (a lane sweep call per phase)")
         if any_nmc and self.wave_rounds:
             raise ValueError("wave_rounds runs plain replicas only: doNMC slots are not supported")
         # (with NMC replicas and M_skip > 1 the phases' traces and argmin hand-offs are strided on the device; a phase length that M_skip
@@ -406,10 +415,12 @@ class NPT(Common):
             return e
         if ctx is None:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, precision=prec, lane_sweeps=self.lanes,
-                                wave_sweeps=self.waves, wave_rounds=self.wave_rounds, track_best=track_best, target_energy=target_energy, track_energies=track_energies)
+                                wave_sweeps=self.waves, wave_rounds=self.wave_rounds, track_best=track_best, target_energy=target_energy, track_energies=track_energies,
+                                lane_nmc=self.lane_nmc)
         elif not cut:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, parts=[(base_, count_)], precision=prec,
-                                lane_sweeps=self.lanes, wave_sweeps=self.waves, wave_rounds=self.wave_rounds, track_best=track_best, target_energy=target_energy, track_energies=track_energies)
+                                lane_sweeps=self.lanes, wave_sweeps=self.waves, wave_rounds=self.wave_rounds, track_best=track_best, target_energy=target_energy, track_energies=track_energies,
+                                lane_nmc=self.lane_nmc)
         else:
             lt = ShardedAsLocal(ShardedTempering(
                 lambda i, n, b, g: opt_in(Engine(i, None, n, device=lrank_, chain_base=b, n_chains_global=g)), inst, beta_list, G,
@@ -477,6 +488,8 @@ class NPT(Common):
             sl_ = slots_last[lo_:hi_]
             self._sweep_counter += rounds * lt.sweeps_per_round(S)
             self._nmc_sweep_counter = lt.nmc_sweeps_done          # (the NMC phases draw from a counter range of their own)
+            self.lane_nmc_rounds = getattr(lt, "lane_nmc_rounds", 0)
+            self.sweep_routes = [e.last_sweep_route() for e in getattr(lt, "engs", []) if hasattr(e, "last_sweep_route")]
             lt.check()
             if track_best:
                 b = lt.best()
