@@ -242,6 +242,29 @@ int nlmc_probe_level_round(nlmc_ctx *ctx, int waves, int conflict_free, int roun
  * no fused schedule).  capacity = entries of the caller's array (>= levels + 1; 1025 always suffices). */
 int nlmc_plan_get_levels(nlmc_ctx *ctx, int window, int32_t *out_level_chunk_offsets, int32_t capacity, int32_t *out_n_levels);
 
+/* Diagnostic read-back of planned window `window` of the selected plan slot, byte for byte as the planner left it: copies on the
+ * context's stream and a synchronisation, no kernel, no change of the plan (tests/schedcheck.py decodes and checks it).
+ * out_info[NLMC_PLAN_INFO_WORDS] is always filled:
+ *   [0] fmt (0 wide: entries { col, Jq } of 8 bytes, 4 planes; 1 compact: col << 16 | Jq & 0xFFFF, 2 planes; 2 address: 16-bit LDS
+ *   addresses, 1 plane)  [1] pstride  [2] T  [3] sweep0  [4] seed  [5] workers (a level holds at most 64 workers positions)
+ *   [6] quads  [7] bank_aware  [8] n_pad  [9] k_dummy  [10] k_zero  [11] neg_off  [12] tab_words  [13] nlev (0: the window got
+ *   no fused schedule -- nothing else is copied then)  [14] npos  [15] hi_max  [16] has_val  [17] level_fill  [18] entry planes.
+ * With out_head != NULL the arrays follow, the first npos positions of each (capacity = positions the caller's arrays hold):
+ *   out_head [npos][2]               { k | kind << 14 | threshold word << 16, hq_k }
+ *   out_ell  [planes][npos][4]       the 16-byte entry planes, position-minor (eight row entries per position)
+ *   out_val  [4][npos][2] + [npos]   the fp64 value plane and the field plane (has_val only; may be NULL otherwise)
+ *   out_loff [nlev + 1]              level offsets in chunks of 64 positions (the caller's array holds 1025)
+ *   out_send [T]                     published index of the last level that holds an update of sweep t (the caller's holds 64)
+ * NLMC_ERR_STATE: no valid plan in the slot or no such window; NLMC_ERR_ARG: capacity < npos. */
+#define NLMC_PLAN_INFO_WORDS 24
+int nlmc_plan_get_items(nlmc_ctx *ctx, int window, int64_t *out_info, int32_t *out_head, int32_t *out_ell, double *out_val,
+                        int32_t *out_loff, int32_t *out_send, int64_t capacity);
+/* The same for order `order` of the per-sweep plan (nlmc_plan_philox).  out_info[8]: [0] n  [1] nlev  [2] hi_max  [3] 1 when the
+ * global-memory levelizer built the plan (items { k, row start }; { k | degree << 16, row start } otherwise)  [4] the widest level
+ * the planner publishes (0: no cap in force)  [5] orders planned  [6] sweep0.  out_order [n][2], out_lvl_off [nlev + 1 <= n + 1];
+ * capacity = spins the caller's arrays hold (out_lvl_off: capacity + 1 entries).  Errors as above (NLMC_ERR_ARG: capacity < n). */
+int nlmc_plan_get_order(nlmc_ctx *ctx, int order, int64_t *out_info, int32_t *out_order, int32_t *out_lvl_off, int64_t capacity);
+
 /* Is librccl loadable in this process (NLMC_OK), or why not (NLMC_ERR_UNSUPPORTED + nlmc_last_error(NULL))?  Every rank asks
  * BEFORE nlmc_comm_init and the ranks agree on the answer over the process group that is already up, so that no rank waits in
  * ncclCommInitRank for one that could not load the library. */

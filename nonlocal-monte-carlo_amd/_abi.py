@@ -45,6 +45,7 @@ EXPORTS = [
     "nlmc_nmc_phases_lanes", "nlmc_nmc_phases_lanes_refusal",
     "nlmc_best_begin", "nlmc_best_update", "nlmc_best_read", "nlmc_best_end",
     "nlmc_elog_begin", "nlmc_elog_update", "nlmc_elog_read", "nlmc_elog_end",
+    "nlmc_plan_get_items", "nlmc_plan_get_order",
 ]
 
 
@@ -168,7 +169,9 @@ def lib():
                        ("nlmc_backbone_clusters", [_vp, _vp, _vp, _i, _dbl, _dbl, _i, _dbl, _vp, _i]),
                        ("nlmc_backbone_check", [_vp]), ("nlmc_get_cluster_mask", [_vp, _vp]), ("nlmc_set_cluster_mask", [_vp, _vp]), ("nlmc_set_phase", [_vp, _i, _dbl]),
                        ("nlmc_plan_slot", [_vp, _i]), ("nlmc_set_fused_f64_real", [_vp, _i]), ("nlmc_last_sweep_fused", [_vp]), ("nlmc_set_lane_sweeps", [_vp, _i]), ("nlmc_set_wave_sweeps", [_vp, _i]), ("nlmc_last_sweep_route", [_vp]), ("nlmc_pt_rounds_route", [_vp]), ("nlmc_overlap_subsets", [_vp, _i]), ("nlmc_own_stream", [_vp]),
-                       ("nlmc_plan_get_levels", [_vp, _i, _vp, _i, _vp]), ("nlmc_comm_unique_id", [_vp]), ("nlmc_comm_init", [_vp, _vp, _i, _i]),
+                       ("nlmc_plan_get_levels", [_vp, _i, _vp, _i, _vp]),
+                       ("nlmc_plan_get_items", [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64]),
+                       ("nlmc_plan_get_order", [_vp, _i, _vp, _vp, _vp, ctypes.c_int64]), ("nlmc_comm_unique_id", [_vp]), ("nlmc_comm_init", [_vp, _vp, _i, _i]),
                        ("nlmc_pt_swap_philox_collective", [_vp, _u32, _u64, _i, _i, _vp, _vp]), ("nlmc_comm_probe", []), ("nlmc_comm_check", [_vp, _i]),
                        ("nlmc_pt_rounds_fused", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),
                        ("nlmc_pt_rounds_deferred", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),

@@ -322,6 +322,7 @@ struct nlmc_ctx {
         int pstride = 0, gen0 = 0;
         int fmt = 0;                  // entry format of the plan (NLMC_FMT_*)
         bool has_val = false;         // the plan carries the fp64 value plane (entries in row order): the real-valued fp64 variant
+        FusedLevelizeArgs built{};    // what the planner was launched with (read-back: nlmc_plan_get_items)
         DevBuf<int32_t> npos;
         DevBuf<int2> head;
         DevBuf<EdgeQ> ell;
@@ -1981,6 +1982,7 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
     P.has_val = with_val;
     a.adj = reinterpret_cast<const uint4 *>(c->fz_adj.p); a.glv = c->fz_glv.p; a.perm = c->fz_perm.p; a.head = P.head.p; a.ell = P.ell.p; a.loff = P.loff.p; a.nlev = P.nlev.p;
     a.hi_max = P.himax.p; a.send = P.send.p; a.npos = P.npos.p;
+    P.built = a;
     const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
     const size_t lds = (size_t)n * 8 + n4 * 2 + n4 + n4 * 2 + 2 * (size_t)(NLMC_LCAP + 2) * 4 + 16;
     { int rc = ensure_lds(c, reinterpret_cast<const void *>(k_levelize_fused), lds); if (rc) return rc; }
@@ -2076,6 +2078,65 @@ int nlmc_plan_get_levels(nlmc_ctx *c, int window, int32_t *out_level_chunk_offse
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemcpyAsync(out_level_chunk_offsets, P.loff.p + (size_t)window * (NLMC_LCAP + 1), sizeof(int32_t) * (size_t)(nl + 1),
                               hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NLMC_OK;
+}
+
+int nlmc_plan_get_items(nlmc_ctx *c, int window, int64_t *out_info, int32_t *out_head, int32_t *out_ell, double *out_val,
+                        int32_t *out_loff, int32_t *out_send, int64_t capacity)
+{
+    if (!c || !out_info) return fail(c, NLMC_ERR_ARG, "nlmc_plan_get_items: NULL argument");
+    const nlmc_ctx::FusedPlan &P = c->fz[c->fz_slot];
+    if (!P.valid || window < 0 || window >= P.windows) return fail(c, NLMC_ERR_STATE, "nlmc_plan_get_items: no such planned window in the selected slot");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const FusedLevelizeArgs &b = P.built;
+    const nlmc_ctx::FusedPlan::Arrays A = P.at(window);
+    const int nl = P.nlev_host[(size_t)window], np = P.npos_host[(size_t)window];
+    const int planes = P.fmt == NLMC_FMT_ADDR ? 1 : P.fmt == NLMC_FMT_COMPACT ? 2 : 4;
+    int32_t himax = 0;
+    HIP_TRY(c, hipMemcpyAsync(&himax, A.himax, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const int64_t info[NLMC_PLAN_INFO_WORDS] = {P.fmt, P.pstride, P.T, (int64_t)P.sweep0, (int64_t)P.seed, P.workers, b.quads, b.bank_aware, c->n_pad,
+                                                b.k_dummy, b.k_zero, b.neg_off, b.tab_words, nl, np, himax, P.has_val ? 1 : 0, b.level_fill, planes};
+    for (int i = 0; i < NLMC_PLAN_INFO_WORDS; ++i) out_info[i] = info[i];
+    if (!out_head || nl == 0) return NLMC_OK;
+    if (!out_ell || !out_loff || !out_send || (P.has_val && !out_val)) return fail(c, NLMC_ERR_ARG, "nlmc_plan_get_items: NULL array");
+    if (capacity < np) return fail(c, NLMC_ERR_ARG, "nlmc_plan_get_items: capacity < positions of the window");
+    const size_t PS = (size_t)P.pstride, NP = (size_t)np;
+    HIP_TRY(c, hipMemcpyAsync(out_head, A.head, sizeof(int2) * NP, hipMemcpyDeviceToHost, c->stream));
+    for (int q = 0; q < planes; ++q)       // plane q of the window: 16 bytes per position, pstride positions apart
+        HIP_TRY(c, hipMemcpyAsync(out_ell + (size_t)q * NP * 4, reinterpret_cast<const int4 *>(A.ell) + (size_t)q * PS, sizeof(int4) * NP,
+                                  hipMemcpyDeviceToHost, c->stream));
+    if (P.has_val) {
+        for (int q = 0; q < NLMC_FZ_W / 2; ++q)
+            HIP_TRY(c, hipMemcpyAsync(out_val + (size_t)q * NP * 2, A.val + (size_t)q * PS * 2, sizeof(double) * 2 * NP, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out_val + (size_t)NLMC_FZ_W * NP, A.val + (size_t)NLMC_FZ_W * PS, sizeof(double) * NP, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(out_loff, A.loff, sizeof(int32_t) * (size_t)(nl + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out_send, A.send, sizeof(int32_t) * (size_t)P.T, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NLMC_OK;
+}
+
+int nlmc_plan_get_order(nlmc_ctx *c, int order, int64_t *out_info, int32_t *out_order, int32_t *out_lvl_off, int64_t capacity)
+{
+    if (!c || !out_info) return fail(c, NLMC_ERR_ARG, "nlmc_plan_get_order: NULL argument");
+    if (!c->plan_valid || order < 0 || order >= c->plan_count) return fail(c, NLMC_ERR_STATE, "nlmc_plan_get_order: no such planned order");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->n, o = (size_t)order;
+    int32_t nl = 0, himax = 0;
+    HIP_TRY(c, hipMemcpyAsync(&nl, c->plan.nlev.p + o, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&himax, c->plan.hi_max.p + o, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // (the cap run_levelize gave the planner: the sweep workgroup's width; the global-memory levelizer publishes whole levels)
+    const int cap = c->plan_big ? 0 : sweep_block_for(c, c->plan_precision == NLMC_F64, c->plan_precision == NLMC_F32 && c->has_diag);
+    const int64_t info[8] = {(int64_t)c->n, nl, himax, c->plan_big ? 1 : 0, cap, c->plan_count, (int64_t)c->plan_sweep0, 0};
+    for (int i = 0; i < 8; ++i) out_info[i] = info[i];
+    if (!out_order) return NLMC_OK;
+    if (!out_lvl_off) return fail(c, NLMC_ERR_ARG, "nlmc_plan_get_order: NULL array");
+    if (capacity < (int64_t)n || nl < 0 || (size_t)nl > n) return fail(c, NLMC_ERR_ARG, "nlmc_plan_get_order: capacity < spins");
+    HIP_TRY(c, hipMemcpyAsync(out_order, c->plan.order.p + o * n, sizeof(int2) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out_lvl_off, c->plan.lvl_off.p + o * (n + 1), sizeof(int32_t) * (size_t)(nl + 1), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NLMC_OK;
 }

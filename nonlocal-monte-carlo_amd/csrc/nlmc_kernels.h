@@ -465,11 +465,11 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
                 hist[lv] = (uint32_t)run;
                 himax = max(himax, (cl + 63) >> 6);
                 histL[lv] = (uint32_t)(run + width);
-                for (int p = 0; p < width; p += a.level_cap) { if (m < NLMC_LCAP) { off[m] = (run + p) >> 6; mx[m] = (uint32_t)((run + p) >> 6); } ++m; }
+                for (int p = 0; p < width; p += a.level_cap) { if (m < NLMC_LCAP) off[m] = (run + p) >> 6; ++m; }
                 run += (width + 63) & ~63;
                 while (t_next < T && sh_lmax[t_next] == lv) a.send[(size_t)w * T + t_next++] = m - 1;
             }
-            if (m >= NLMC_LCAP || run > a.pstride) sh_fail = 1; else { off[m] = run >> 6; mx[m] = (uint32_t)(run >> 6); }
+            if (m >= NLMC_LCAP || run > a.pstride) sh_fail = 1; else off[m] = run >> 6;
         }
         sh_nlev = sh_fail ? 0 : m;
         sh_npos = run;

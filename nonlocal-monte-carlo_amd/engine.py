@@ -402,6 +402,42 @@ class Engine:
         self._ck(self._L.nlmc_plan_get_levels(self._ctx, int(window), _abi.ptr(off), 1025, ctypes.byref(nl)))
         return np.diff(off[:nl.value + 1])
 
+    PLAN_INFO = ("fmt", "pstride", "T", "sweep0", "seed", "workers", "quads", "bank_aware", "n_pad", "k_dummy", "k_zero", "neg_off",
+                 "tab_words", "nlev", "npos", "hi_max", "has_val", "level_fill", "planes")
+
+    def plan_items(self, window):
+        """Read-back of a planned fused window of the selected plan slot (include/nlmc.h: nlmc_plan_get_items; diagnostic): the
+        constants of PLAN_INFO as ints and the raw arrays head [npos, 2], ell [planes, npos, 4] (int32), val (float64
+        [9 npos]: four planes of [npos, 2], then the field plane; None without a value plane), loff [nlev + 1], send [T].
+        nlev == 0: the window got no fused schedule, and there are no arrays."""
+        info = np.zeros(24, dtype=np.int64)
+        self._ck(self._L.nlmc_plan_get_items(self._ctx, int(window), _abi.ptr(info), None, None, None, None, None, 0))
+        d = {k: int(v) for k, v in zip(self.PLAN_INFO, info)}
+        d["seed"] &= 0xFFFFFFFFFFFFFFFF
+        d["val"] = None
+        if d["nlev"] == 0:
+            return d
+        npos = d["npos"]
+        head, ell = np.zeros((npos, 2), dtype=np.int32), np.zeros((d["planes"], npos, 4), dtype=np.int32)
+        val = np.zeros(9 * npos, dtype=np.float64) if d["has_val"] else None
+        loff, send = np.zeros(1025, dtype=np.int32), np.zeros(64, dtype=np.int32)
+        self._ck(self._L.nlmc_plan_get_items(self._ctx, int(window), _abi.ptr(info), _abi.ptr(head), _abi.ptr(ell), _abi.ptr(val),
+                                             _abi.ptr(loff), _abi.ptr(send), npos))
+        d.update(head=head, ell=ell, val=val, loff=loff[:d["nlev"] + 1].copy(), send=send[:d["T"]].copy())
+        return d
+
+    def plan_order(self, order):
+        """Read-back of order `order` of the per-sweep plan (plan_philox; include/nlmc.h: nlmc_plan_get_order; diagnostic):
+        order [n, 2] int32, lvl_off [nlev + 1], nlev, hi_max, big (the global-memory levelizer built it), cap (widest published
+        level, 0: none), orders, sweep0."""
+        info = np.zeros(8, dtype=np.int64)
+        self._ck(self._L.nlmc_plan_get_order(self._ctx, int(order), _abi.ptr(info), None, None, 0))
+        n, nlev = int(info[0]), int(info[1])
+        items, off = np.zeros((n, 2), dtype=np.int32), np.zeros(n + 1, dtype=np.int32)
+        self._ck(self._L.nlmc_plan_get_order(self._ctx, int(order), _abi.ptr(info), _abi.ptr(items), _abi.ptr(off), n))
+        return dict(order=items, lvl_off=off[:nlev + 1].copy(), nlev=nlev, hi_max=int(info[2]), big=bool(info[3]), cap=int(info[4]),
+                    orders=int(info[5]), sweep0=int(info[6]))
+
     def plan_reserve_fused(self, n_windows, window):
         """Allocate the fused-window plan buffers for up to n_windows windows (no schedule is built)."""
         self._ck(self._L.nlmc_plan_reserve_fused(self._ctx, int(n_windows), int(window)))
