@@ -174,6 +174,22 @@ int nlmc_last_sweep_route(const nlmc_ctx *ctx);
  * instance of the measured grid; 0 (never) if that holds nowhere, 2147483647 if it holds at every measured row count. */
 #define NLMC_WAVE_AUTO_MAX_ROWS 0
 int nlmc_set_wave_sweeps(nlmc_ctx *ctx, int mode);
+/* Long chains on the wave route (csrc/nlmc_waves_long.h: k_sweep_waves_long).  on != 0: the rule of nlmc_set_wave_sweeps takes chains
+ * of up to NLMC_WAVE_LONG_N spins instead of NLMC_WAVE_N, the mode rules unchanged (force: every such NLMC_F32 call; auto: never while
+ * NLMC_WAVE_AUTO_MAX_ROWS is 0; NLMC_F64 and stream-mode calls go on to the other routes).  For NLMC_WAVE_N < n <= NLMC_WAVE_LONG_N a
+ * lane holds 8 (n <= 512) or 16 fields in registers and writes them through to a copy in LDS the wave keeps to itself beside the spins,
+ * the phase flags and the sweep's thresholds (10 bytes a spin; at n = 1024 fifteen waves share a workgroup's LDS): an update is four
+ * broadcast LDS reads and a compare, a flip 8 or 16 adds per lane on a row of the dense matrix, which is up to 4 MB per context
+ * (n 64 R ints) and read from global memory.  Made for dense instances (complete graphs, Wishart) of a few hundred spins, where the
+ * fused windows plan nothing and the other routes walk a row of n entries per update; DESIGN.md section 6 says where it pays.
+ * Everything a wave call accepts runs there, bit-identical to the other routes; nlmc_last_sweep_route is NLMC_ROUTE_WAVES.  The rounds
+ * inside a wave launch (nlmc_pt_rounds_waves) keep their limit of NLMC_WAVE_N spins: under nlmc_set_wave_rounds,
+ * nlmc_pt_rounds_deferred runs such a context's rounds as a sweep call and a swap call each (nlmc_pt_rounds_route:
+ * NLMC_ROUNDS_LAUNCH_PER_ROUND).  Default: off, and then nothing changes for any caller.  Environment, read at nlmc_create:
+ * NLMC_WAVE_WAVES applies (capped by the LDS), NLMC_WAVE_LONG_AHEAD=1 requests the next visited spin's row at every update instead
+ * of a row per flip (no result depends on either). */
+#define NLMC_WAVE_LONG_N 1024
+int nlmc_set_wave_long(nlmc_ctx *ctx, int on);
 
 /* Optional: build and cache the level schedules of sweeps [sweep0, sweep0+n_sweeps) ahead of time (shared-order
  * philox mode).  Later nlmc_sweep_philox calls inside that range with the same seed and precision skip their

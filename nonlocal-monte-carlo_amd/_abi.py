@@ -25,6 +25,7 @@ LANE_N = 1024                        # include/nlmc.h: NLMC_LANE_N, longest chai
 LANE_AUTO_ROWS = 2147483647          # include/nlmc.h: NLMC_LANE_AUTO_ROWS, rows from which "auto" takes them (2^31 - 1: never)
 LANES_OFF, LANES_AUTO, LANES_FORCE = 0, 1, 2
 WAVE_N = 256                         # include/nlmc.h: NLMC_WAVE_N, longest chain of the wave-per-chain sweeps
+WAVE_LONG_N = 1024                   # include/nlmc.h: NLMC_WAVE_LONG_N, longest chain of the wave route under nlmc_set_wave_long
 WAVE_AUTO_MAX_ROWS = 0               # include/nlmc.h: NLMC_WAVE_AUTO_MAX_ROWS, rows up to which "auto" takes them (0: never)
 WAVES_OFF, WAVES_AUTO, WAVES_FORCE = 0, 1, 2
 ROUTE_NONE, ROUTE_STEPWISE, ROUTE_FUSED, ROUTE_LANES, ROUTE_WAVES = 0, 1, 2, 3, 4
@@ -41,7 +42,7 @@ EXPORTS = [
     "nlmc_pt_mark_slots", "nlmc_select_chains", "nlmc_subset_count", "nlmc_get_subset", "nlmc_track_minimum", "nlmc_backbone_seed", "nlmc_adopt_best",
     "nlmc_backbone_clusters", "nlmc_backbone_check", "nlmc_get_cluster_mask", "nlmc_set_phase", "nlmc_plan_slot", "nlmc_overlap_subsets", "nlmc_own_stream", "nlmc_plan_get_levels", "nlmc_probe_level_round", "nlmc_comm_unique_id", "nlmc_comm_init", "nlmc_comm_probe", "nlmc_comm_check", "nlmc_apt_shard", "nlmc_apt_pack", "nlmc_apt_swap_host", "nlmc_apt_swap_collective", "nlmc_apt_selftest_exchange", "nlmc_pt_swap_philox_collective", "nlmc_set_cluster_mask", "nlmc_host_prefault",
     "nlmc_set_fused_f64_real", "nlmc_last_sweep_fused", "nlmc_set_lane_sweeps", "nlmc_set_wave_sweeps", "nlmc_last_sweep_route", "nlmc_pt_rounds_lanes",
-    "nlmc_apt_rounds_lanes", "nlmc_apt_systems", "nlmc_pt_rounds_waves", "nlmc_set_wave_rounds",
+    "nlmc_apt_rounds_lanes", "nlmc_apt_systems", "nlmc_pt_rounds_waves", "nlmc_set_wave_rounds", "nlmc_set_wave_long",
     "nlmc_nmc_phases_lanes", "nlmc_nmc_phases_lanes_refusal",
     "nlmc_best_begin", "nlmc_best_update", "nlmc_best_read", "nlmc_best_end",
     "nlmc_elog_begin", "nlmc_elog_update", "nlmc_elog_read", "nlmc_elog_end",
@@ -176,7 +177,7 @@ def lib():
                        ("nlmc_pt_rounds_fused", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),
                        ("nlmc_pt_rounds_deferred", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),
                        ("nlmc_pt_rounds_lanes", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),
-                       ("nlmc_pt_rounds_waves", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]), ("nlmc_set_wave_rounds", [_vp, _i]),
+                       ("nlmc_pt_rounds_waves", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]), ("nlmc_set_wave_rounds", [_vp, _i]), ("nlmc_set_wave_long", [_vp, _i]),
                        ("nlmc_apt_rounds_lanes", [_vp, _i, _i, _i, _u32, _u32, _u64, _i, _i, _vp]), ("nlmc_apt_systems", [_vp, _i]),
                        ("nlmc_nmc_phases_lanes", [_vp, _i, _vp, _i, _i, _u32, _u64, _dbl, _dbl, _i, _vp, _vp, _vp]),
                        ("nlmc_best_begin", [_vp, _dbl]), ("nlmc_best_update", [_vp, _u32]), ("nlmc_best_read", [_vp, _vp, _vp, _vp, _vp]),

@@ -27,7 +27,7 @@ class APT_ICM(SweepMixin):
     num_subreplicas = 10      # NPT/apt_ICM.py:177
     useKatzgraber = True      # NPT/apt_ICM.py:178
 
-    def __init__(self, J, h, rng=None, seed=None, device=0, lanes="off", waves="off"):
+    def __init__(self, J, h, rng=None, seed=None, device=0, lanes="off", waves="off", wave_long=False):
         """`lanes` (additive keyword, rng="philox" only; run(..., icm_feedback=True) without device_ids, the device-resident route):
         "off" (default), "auto" or "force" -- Engine.set_lane_sweeps of the run's engine ("auto" never fires today: its row threshold
         NLMC_LANE_AUTO_ROWS is 2^31 - 1).  Short chains (n <= 1024, at most 64 temperatures) then sweep one per lane; where
@@ -35,7 +35,9 @@ class APT_ICM(SweepMixin):
         k_apt_rounds_lanes (Engine.apt_rounds_lanes).  Same bits as "off".
         `waves` (additive keyword, under the same conditions): "off" (default), "auto" or "force" -- Engine.set_wave_sweeps of the
         run's engine: chains of at most 256 spins sweep one per wave with resident local fields, a call per step (the rounds inside
-        k_apt_rounds_lanes do not look at it).  Same bits as "off"."""
+        k_apt_rounds_lanes do not look at it).  Same bits as "off".
+        `wave_long` (additive keyword, needs waves != "off"): Engine.set_wave_long of the run's engine -- the wave route takes dense
+        chains of up to 1024 spins (k_sweep_waves_long).  Same bits as without."""
         hostlogic.check_route_keywords(lanes, waves)
         self.J = J
         if isinstance(h, list):
@@ -44,9 +46,10 @@ class APT_ICM(SweepMixin):
             h = h[:, np.newaxis]                      # NPT/apt_ICM.py:27-34: h kept as an [N,1] column
         self.h = h
         self._init_backend(rng, seed, device)
-        hostlogic.check_route_keywords(lanes, waves, rng=self.rng)
+        hostlogic.check_route_keywords(lanes, waves, rng=self.rng, wave_long=wave_long)
         self.lanes = lanes
         self.waves = waves
+        self.wave_long = bool(wave_long)
 
     def _hflat(self):
         return np.asarray(self.h, dtype=np.float64).reshape(-1)
@@ -263,7 +266,7 @@ class APT_ICM(SweepMixin):
         host_rng = np.random.default_rng(self.seed)      # initial states only
         eng = engine_factory(inst, None, G, device=self._cache.device)
         try:
-            hostlogic.set_route_modes(eng, self.lanes, self.waves)
+            hostlogic.set_route_modes(eng, self.lanes, self.waves, wave_long=self.wave_long)
             eng.set_spins((2 * host_rng.integers(0, 2, size=(G, N), dtype=np.int8) - 1).astype(np.int8))
             eng.pt_init(beta_list)
             if num_restarts > 1:

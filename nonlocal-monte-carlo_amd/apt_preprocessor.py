@@ -19,9 +19,11 @@ from .engine import Engine
 
 
 class APT_preprocessor(SweepMixin):
-    def __init__(self, J, h, rng=None, seed=None, device=0, waves="off"):
+    def __init__(self, J, h, rng=None, seed=None, device=0, waves="off", wave_long=False):
         """`waves` (additive keyword, rng="philox" only): "off" (default), "auto" or "force" -- Engine.set_wave_sweeps of the engine
-        run() creates: chains of at most 256 spins sweep one per wave with resident local fields.  Same bits as "off"."""
+        run() creates: chains of at most 256 spins sweep one per wave with resident local fields.  Same bits as "off".
+        `wave_long` (additive keyword, needs waves != "off"): Engine.set_wave_long of that engine -- the wave route takes dense chains
+        of up to 1024 spins (k_sweep_waves_long).  Same bits as without."""
         hostlogic.check_route_keywords(waves=waves)
         self.J = J
         if isinstance(h, list):
@@ -31,8 +33,9 @@ class APT_preprocessor(SweepMixin):
         self.h = h
         self.N = J.shape[0]
         self._init_backend(rng, seed, device)
-        hostlogic.check_route_keywords(waves=waves, rng=self.rng)
+        hostlogic.check_route_keywords(waves=waves, rng=self.rng, wave_long=wave_long)
         self.waves = waves
+        self.wave_long = bool(wave_long)
 
     def _hflat(self):
         return np.asarray(self.h, dtype=np.float64).reshape(-1)
@@ -83,7 +86,7 @@ class APT_preprocessor(SweepMixin):
         saved_state = np.zeros((R, N))
         eng = Engine(inst, None, R, device=self._cache.device)
         try:
-            hostlogic.set_route_modes(eng, waves=self.waves)
+            hostlogic.set_route_modes(eng, waves=self.waves, wave_long=self.wave_long)
             while sigma_E > sigma_E_min:
                 if it != 1:
                     beta.append(beta[-1] + alpha / sigma_E)

@@ -12,6 +12,7 @@
 #include "nlmc_lane_apt.h"
 #include "nlmc_lane_nmc.h"
 #include "nlmc_waves.h"
+#include "nlmc_waves_long.h"
 #include "nlmc_wave_rounds.h"
 #include "nlmc_wave_shape.h"
 #include "nlmc_host.h"
@@ -101,6 +102,7 @@ struct Knobs {
     bool no_lane_nmc = false;        // NLMC_NO_LANE_NMC: nlmc_nmc_phases_lanes refuses (test knob)
     int wave_waves = 0;              // NLMC_WAVE_WAVES: waves (chains) per workgroup of the wave-per-chain sweeps (1..16; 0: by row count)
     bool wave_jlds = true;           // NLMC_WAVE_JLDS=0: the wave-per-chain sweeps read the matrix rows from global memory at every n
+    bool wave_long_ahead = NLMC_WAVE_LONG_AHEAD_DEFAULT;   // NLMC_WAVE_LONG_AHEAD: k_sweep_waves_long requests the next visited spin's row at every update (1) or a row on a flip only (0)
     int wave_rounds_ladders = 0;     // NLMC_WAVE_ROUNDS_LADDERS: ladders per workgroup of the rounds inside a wave launch (0: by the rule)
     int dbg_flags = 0;               // NLMC_DBG_FLAGS: timing experiments of NLMC_DEBUG_KNOBS builds
     std::string stamp_file;          // NLMC_STAMP_FILE: NLMC_STAMPS builds dump the last launch's per-wave cycle sums here
@@ -128,6 +130,7 @@ Knobs read_knobs()
     k.no_lane_nmc = num("NLMC_NO_LANE_NMC", 0) != 0;
     k.wave_waves = std::min(16, std::max(0, num("NLMC_WAVE_WAVES", 0)));
     k.wave_jlds = num("NLMC_WAVE_JLDS", 1) != 0;
+    k.wave_long_ahead = num("NLMC_WAVE_LONG_AHEAD", NLMC_WAVE_LONG_AHEAD_DEFAULT) != 0;
     k.wave_rounds_ladders = std::min(64, std::max(0, num("NLMC_WAVE_ROUNDS_LADDERS", 0)));
     k.dbg_flags = num("NLMC_DBG_FLAGS", 0);
     if (const char *s = getenv("NLMC_STAMP_FILE")) k.stamp_file = s;
@@ -253,7 +256,8 @@ struct nlmc_ctx {
     // wave-per-chain sweeps (csrc/nlmc_waves.h)
     int wave_mode = 0;            // nlmc_set_wave_sweeps: 0 off, 1 auto, 2 force
     bool wave_rounds = false;     // nlmc_set_wave_rounds: nlmc_pt_rounds_deferred takes k_rounds_waves where the sweeps go to the wave kernels
-    DevBuf<int32_t> wave_J;       // [n][64 R] dense fixed-point matrix, built on the first wave call (k_wave_matrix)
+    bool wave_long = false;       // nlmc_set_wave_long: the wave route takes chains of up to NLMC_WAVE_LONG_N spins (k_sweep_waves_long)
+    DevBuf<int32_t> wave_J;       // [n][64 R] dense fixed-point matrix, built on the first wave call (k_wave_matrix): 256 KB at n = 256, 4 MB at n = 1024
     bool wave_J_built = false;
     DevBuf<int32_t> nmc_status;   // sticky: a backbone inference diverged at its first lambda
     DevBuf<double> nmc_thr;       // thresholds of the cluster growth
@@ -530,6 +534,9 @@ int sweep_block_for(const nlmc_ctx *c, bool f64_philox, bool f32_diag = false)
 constexpr size_t NLMC_LDS_BYTES_MAX = (size_t)158 * 1024;      // dynamic LDS a workgroup may ask for
 
 static_assert(NLMC_WAVE_ROUNDS_LDS_MAX == NLMC_LDS_BYTES_MAX, "csrc/nlmc_wave_shape.h keeps its own copy of the ceiling");
+static_assert(NLMC_WAVE_LONG_LDS_MAX == NLMC_LDS_BYTES_MAX, "csrc/nlmc_wave_shape.h keeps its own copy of the ceiling");
+static_assert(NLMC_WAVE_LONG_MIN_N == NLMC_WAVE_N + 1 && NLMC_WAVE_LONG_MAX_N == NLMC_WAVE_LONG_N, "csrc/nlmc_wave_shape.h keeps its own copy of the chain lengths");
+static_assert(NLMC_WAVE_LONG_N <= NLMC_LANE_N, "k_lane_orders builds the visiting orders of the wave kernels");
 int ensure_lds(nlmc_ctx *c, const void *func, size_t bytes)
 {
     if (bytes > NLMC_LDS_BYTES_MAX) return fail(c, NLMC_ERR_UNSUPPORTED, "instance too large for the LDS-resident kernels of this build");
@@ -1300,11 +1307,11 @@ int lanes_sweeps(nlmc_ctx *c, const SweepCall &s, ShortRoute &r)
 }
 
 // Whether a philox call over R rows takes the wave-per-chain kernels (nlmc_set_wave_sweeps): fixed point only, chains of at most
-// NLMC_WAVE_N spins; forced, every such call; auto, up to NLMC_WAVE_AUTO_MAX_ROWS rows (include/nlmc.h: where the route was measured
-// ahead).  A call it does not take goes on to the lane rule and the rest: never an error.
+// NLMC_WAVE_N spins (NLMC_WAVE_LONG_N under nlmc_set_wave_long); forced, every such call; auto, up to NLMC_WAVE_AUTO_MAX_ROWS rows
+// (include/nlmc.h: where the route was measured ahead).  A call it does not take goes on to the lane rule and the rest: never an error.
 bool waves_route(const nlmc_ctx *c, int R, int precision)
 {
-    if (c->wave_mode == 0 || precision != NLMC_F32 || c->knobs.force_big || c->n > NLMC_WAVE_N) return false;
+    if (c->wave_mode == 0 || precision != NLMC_F32 || c->knobs.force_big || c->n > (c->wave_long ? NLMC_WAVE_LONG_N : NLMC_WAVE_N)) return false;
     return c->wave_mode == 2 || (long long)R <= (long long)NLMC_WAVE_AUTO_MAX_ROWS;
 }
 
@@ -1334,10 +1341,32 @@ int ensure_wave_matrix(nlmc_ctx *c, size_t stride)
     return NLMC_OK;
 }
 
+const void *waves_long_kernel(int R, bool ahead)
+{
+    static const void *const table[2][2] = {
+        {reinterpret_cast<const void *>(k_sweep_waves_long<8, false>), reinterpret_cast<const void *>(k_sweep_waves_long<8, true>)},
+        {reinterpret_cast<const void *>(k_sweep_waves_long<16, false>), reinterpret_cast<const void *>(k_sweep_waves_long<16, true>)}};
+    return table[R == 8 ? 0 : 1][ahead ? 1 : 0];
+}
+
+// k_sweep_waves_long: chains of more than NLMC_WAVE_N spins, in the shape nlmc_wave_long_shape picks
+int waves_long_sweeps(nlmc_ctx *c, ShortRoute &r)
+{
+    const NlmcWaveLongShape S = nlmc_wave_long_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves);
+    if (S.R == 0) return fail(c, NLMC_ERR_STATE, "waves_sweeps: the chain does not fit the wave kernels");
+    r.kfun = waves_long_kernel(S.R, c->knobs.wave_long_ahead);
+    r.lds = S.lds; r.grid = dim3((unsigned)S.blocks); r.block = dim3((unsigned)(64 * S.W));
+    { int rc = ensure_lds(c, r.kfun, r.lds); if (rc) return rc; }
+    { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
+    r.wave_J = c->wave_J.p;
+    return NLMC_OK;
+}
+
 // k_sweep_waves: a chain per wave, in the shape nlmc_wave_shape picks for the device, over the dense matrix
 int waves_sweeps(nlmc_ctx *c, const SweepCall &, ShortRoute &r)
 {
     { int rc = cu_count(c); if (rc) return rc; }
+    if (c->n > NLMC_WAVE_N) return waves_long_sweeps(c, r);
     const NlmcWaveShape S = nlmc_wave_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves, c->knobs.wave_jlds ? 1 : 0);
     if (S.R == 0) return fail(c, NLMC_ERR_STATE, "waves_sweeps: the chain does not fit the wave kernels");
     r.kfun = waves_kernel(S.R, S.jlds != 0);
@@ -3031,6 +3060,13 @@ int nlmc_set_wave_rounds(nlmc_ctx *c, int on)
     return NLMC_OK;
 }
 
+int nlmc_set_wave_long(nlmc_ctx *c, int on)
+{
+    if (!c) return NLMC_ERR_ARG;
+    c->wave_long = on != 0;
+    return NLMC_OK;
+}
+
 // Whether nlmc_pt_rounds_deferred takes k_rounds_lanes where the lane mode routes the context's sweeps to the lane kernels.  The rule
 // (that of ROUNDS_REAL_IN_LAUNCH): only if its median time per run is not above that of lane sweeps round by round on the same build
 // by more than the run-to-run spread at any shape of scripts/lane_rounds_throughput.py.  Measured (DESIGN.md section 6,
@@ -3059,6 +3095,24 @@ int nlmc_pt_rounds_fused(nlmc_ctx *c, int precision, int n_rounds, int sweeps_pe
 // scripts/f64_real_throughput.py; not shown so far, so such calls keep a launch per round and nlmc_pt_rounds_fused reaches the kernel.
 constexpr bool ROUNDS_REAL_IN_LAUNCH = false;
 
+// n_rounds rounds as n_rounds sweep calls at the ladder temperatures and n_rounds swap calls, on whatever route the sweep calls take:
+// what a caller that drives the rounds one by one queues.  An open best-state record and energy log observe every round between
+// its sweeps and its swap, as they do on the other rounds routes.
+int rounds_waves_call_by_call(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
+{
+    for (int r = 0; r < n_rounds; ++r) {
+        int rc = nlmc_sweep_philox(c, precision, NLMC_ORDER_SHARED, T, sweep0 + (uint32_t)r * (uint32_t)T, seed, nullptr, 0, 0, 0, nullptr, nullptr,
+                                   nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        if (c->best_on) { rc = launch_best_update(c, round0 + (uint32_t)r); if (rc) return rc; }
+        if (c->elog_on) { rc = launch_elog_update(c, round0 + (uint32_t)r); if (rc) return rc; }
+        rc = nlmc_pt_swap_philox(c, round0 + (uint32_t)r, seed, n_pairs, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+    }
+    c->rounds_route = NLMC_ROUNDS_LAUNCH_PER_ROUND;
+    return NLMC_OK;
+}
+
 // n_rounds rounds of a context that owns whole ladders.  Where k_rounds_fused qualifies (nlmc_pt_rounds_fused's conditions, the
 // residency of all workgroups among them; NLMC_NO_PERSISTENT switches it off) the rounds run inside its launches, every swap
 // included.  Otherwise n_rounds sweep launches + ONE swap launch: launch i decides the swap of round i - 1 in its prologue
@@ -3073,6 +3127,10 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
         auto takes = [&](ShortRounds route) { return !short_rounds_refusal(c, route, precision, n_rounds, sweeps_per_round, round0, seed, n_pairs); };
         if (c->wave_rounds && waves_route(c, c->n_chains, precision) && takes(ShortRounds::waves))
             return short_rounds(c, ShortRounds::waves, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+        // k_rounds_waves ends at NLMC_WAVE_N spins: longer chains on the wave route (nlmc_set_wave_long) run a sweep call and a swap call
+        // per round, the sweeps in k_sweep_waves_long
+        if (c->wave_rounds && c->n > NLMC_WAVE_N && waves_route(c, c->n_chains, precision) && !rounds_context_refusal(c, true))
+            return rounds_waves_call_by_call(c, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
         if (ROUNDS_LANES_IN_LAUNCH && lanes_route(c, c->n_chains) && takes(ShortRounds::lanes))
             return short_rounds(c, ShortRounds::lanes, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
     }

@@ -1,8 +1,15 @@
-// nlmc_wave_shape.h -- host-side launch shapes of the wave-per-chain sweeps (csrc/nlmc_waves.h) and of the tempering rounds inside a wave
-// launch (csrc/nlmc_wave_rounds.h), pure functions with no HIP in them (checked on the host under the sanitizers:
-// scripts/wave_shape_check.cpp, scripts/wave_rounds_shape_check.cpp).  No result depends on W or P.
+// nlmc_wave_shape.h -- host-side launch shapes of the wave-per-chain sweeps (csrc/nlmc_waves.h, csrc/nlmc_waves_long.h) and of the
+// tempering rounds inside a wave launch (csrc/nlmc_wave_rounds.h), pure functions with no HIP in them (checked on the host under the
+// sanitizers: scripts/wave_shape_check.cpp, scripts/wave_long_shape_check.cpp, scripts/wave_rounds_shape_check.cpp).  No result
+// depends on W or P.
 #pragma once
 #include <stddef.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define NLMC_WS_HD __host__ __device__
+#else
+#define NLMC_WS_HD
+#endif
 
 #define NLMC_WAVE_JLDS_N 192      // longest chain whose matrix the workgroup stages in LDS: n n_pad 4 <= 144 KB
 
@@ -30,6 +37,56 @@ static inline NlmcWaveShape nlmc_wave_shape(int n, int n_pad, int rows, int n_cu
     s.blocks = (int)(((long long)rows + s.W - 1) / s.W);
     s.jlds = allow_lds && n <= NLMC_WAVE_JLDS_N;
     s.lds = s.jlds ? (size_t)n * (size_t)n_pad * sizeof(int) : 0;
+    return s;
+}
+
+// ---- long chains, a wave per chain (csrc/nlmc_waves_long.h: k_sweep_waves_long), 256 < n <= 1024 ------------------------------------------
+#define NLMC_WAVE_LONG_MIN_N 257                        // NLMC_WAVE_N + 1: shorter chains have k_sweep_waves
+#define NLMC_WAVE_LONG_MAX_N 1024                       // NLMC_WAVE_LONG_N of include/nlmc.h
+#define NLMC_WAVE_LONG_LDS_MAX ((size_t)158 * 1024)     // dynamic LDS a workgroup may ask for (NLMC_LDS_BYTES_MAX of csrc/nlmc.hip)
+
+// The LDS region a wave keeps to itself, each part 16-byte aligned: X [64 R] int32 (a word per lane and register: the write-back of a
+// flip needs no bounds) | thresholds [4 ceil(n / 4)] float | spins [n_pad] int8 | phase flags [n_pad] int8.  The kernel and the shape
+// function both take the layout from here.
+struct NlmcWaveLongRegion { int w_off, s_off, f_off, bytes; };
+NLMC_WS_HD static inline NlmcWaveLongRegion nlmc_wave_long_region(int n, int n_pad)
+{
+    NlmcWaveLongRegion g;
+    g.w_off = 256 * (n <= 512 ? 8 : 16);
+    g.s_off = g.w_off + 16 * ((n + 3) / 4);
+    g.f_off = g.s_off + ((n_pad + 15) & ~15);
+    g.bytes = g.f_off + ((n_pad + 15) & ~15);
+    return g;
+}
+
+struct NlmcWaveLongShape {
+    int R;            // fields per lane: 8 (n <= 512) or 16; 0: the chain does not fit
+    int W;            // waves (= rows of the call) per workgroup, 1 .. 16, as many as the LDS holds regions at most
+    int blocks;       // workgroups: ceil(rows / W)
+    size_t region;    // LDS of one wave in bytes (nlmc_wave_long_region)
+    size_t lds;       // dynamic LDS of the launch in bytes: W regions
+    size_t stride;    // row stride of the matrix in global memory, in ints: 64 R
+};
+
+// rows >= 1.  n_cu: compute units of the device.  knob_waves: NLMC_WAVE_WAVES (0: unset).  Enough workgroups to cover the compute
+// units first, then up to 16 waves per workgroup, or as many as have their regions in a workgroup's LDS.
+static inline NlmcWaveLongShape nlmc_wave_long_shape(int n, int n_pad, int rows, int n_cu, int knob_waves)
+{
+    NlmcWaveLongShape s = {0, 1, 0, 0, 0, 0};
+    if (n < NLMC_WAVE_LONG_MIN_N || n > NLMC_WAVE_LONG_MAX_N || n_pad < n || rows < 1) return s;
+    const int R = n <= 512 ? 8 : 16;
+    if (n_pad > 64 * R) return s;                       // the padded state row must fit a matrix row
+    s.R = R;
+    s.stride = (size_t)64 * (size_t)R;
+    s.region = (size_t)nlmc_wave_long_region(n, n_pad).bytes;
+    long long w = knob_waves > 0 ? knob_waves : ((long long)rows + (n_cu > 0 ? n_cu : 1) - 1) / (n_cu > 0 ? n_cu : 1);
+    const long long fit = (long long)(NLMC_WAVE_LONG_LDS_MAX / s.region);      // >= 15: a region is at most 10 KB
+    if (w > fit) w = fit;
+    if (w < 1) w = 1;
+    if (w > 16) w = 16;
+    s.W = (int)w;
+    s.blocks = (int)(((long long)rows + s.W - 1) / s.W);
+    s.lds = (size_t)s.W * s.region;
     return s;
 }
 

@@ -85,6 +85,7 @@ class Engine:
         self.lane_sweeps = "off"         # set_lane_sweeps
         self.wave_sweeps = "off"         # set_wave_sweeps
         self.wave_rounds = False         # set_wave_rounds
+        self.wave_long = False           # set_wave_long
         self.energy_scale = int(self._L.nlmc_energy_scale(self._ctx))
         self.field_scale = int(self._L.nlmc_field_scale(self._ctx))      # qs of the "f32" path: Jq = rint(J 2^qs)
 
@@ -272,11 +273,21 @@ class Engine:
         self._ck(self._L.nlmc_set_wave_rounds(self._ctx, 1 if on else 0))
         self.wave_rounds = bool(on)
 
+    def set_wave_long(self, on=True):
+        """Whether the wave route takes chains of up to 1024 spins instead of 256 (include/nlmc.h: nlmc_set_wave_long): dense chains of
+        257..1024 spins then sweep one per wave in k_sweep_waves_long, fields in registers and in LDS, under the mode rules of
+        set_wave_sweeps.  The rounds inside a wave launch keep their limit of 256 spins: with set_wave_rounds, pt_rounds_deferred runs
+        a longer chain's rounds as a sweep call and a swap call each.  Default off: nothing changes for any caller.  Same bits either
+        way."""
+        self._ck(self._L.nlmc_set_wave_long(self._ctx, 1 if on else 0))
+        self.wave_long = bool(on)
+
     def waves_take(self, rows=None, precision="f32"):
         """Whether the context routes a sweep_philox call over `rows` rows (default: the selected chains) in `precision` to the
-        wave-per-chain kernels -- the rule of nlmc_set_wave_sweeps, asked before lanes_take.  Such a call needs no fused-window plan."""
+        wave-per-chain kernels -- the rule of nlmc_set_wave_sweeps (chains of up to 1024 spins under set_wave_long, 256 otherwise),
+        asked before lanes_take.  Such a call needs no fused-window plan."""
         mode = getattr(self, "wave_sweeps", "off")
-        if mode == "off" or precision != "f32" or self.n > _abi.WAVE_N:
+        if mode == "off" or precision != "f32" or self.n > (_abi.WAVE_LONG_N if getattr(self, "wave_long", False) else _abi.WAVE_N):
             return False
         if mode == "force":
             return True

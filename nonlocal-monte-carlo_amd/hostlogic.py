@@ -37,9 +37,15 @@ def check_wave_rounds(wave_rounds, waves, needs="waves='auto' or 'force'"):
         raise ValueError(f"wave_rounds needs {needs} (the rounds run inside the wave kernels' launches)")
 
 
-def check_route_keywords(lanes="off", waves="off", wave_rounds=False, rng=None, precision="f32"):
-    """The `lanes` / `waves` / `wave_rounds` keywords of NPT, APT_ICM and APT_preprocessor.  rng None (a constructor that does not know
-    its backend yet): the mode values only; otherwise also what they need of `rng` and `precision`."""
+def check_wave_long(wave_long, waves, needs="waves='auto' or 'force'"):
+    """wave_long without wave sweeps: ValueError.  `needs`: how the caller's keyword is spelled in the message."""
+    if wave_long and waves == "off":
+        raise ValueError(f"wave_long needs {needs} (it widens the wave route to chains of up to 1024 spins)")
+
+
+def check_route_keywords(lanes="off", waves="off", wave_rounds=False, rng=None, precision="f32", wave_long=False):
+    """The `lanes` / `waves` / `wave_rounds` / `wave_long` keywords of NPT, APT_ICM and APT_preprocessor.  rng None (a constructor that
+    does not know its backend yet): the mode values only; otherwise also what they need of `rng` and `precision`."""
     for name, mode in (("lanes", lanes), ("waves", waves)):
         if mode not in ("off", "auto", "force"):
             raise ValueError(f"{name} must be 'off', 'auto' or 'force'")
@@ -53,16 +59,24 @@ def check_route_keywords(lanes="off", waves="off", wave_rounds=False, rng=None, 
     check_wave_rounds(wave_rounds, waves)
     if wave_rounds and precision == "f64":
         raise ValueError("wave_rounds applies to precision='f32' (the wave-per-chain kernels have no fp64 arithmetic)")
+    check_wave_long(wave_long, waves)
+    if wave_long and rng != "philox":
+        raise ValueError("wave_long applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
+    if wave_long and precision == "f64":
+        raise ValueError("wave_long applies to precision='f32' (the wave-per-chain kernels have no fp64 arithmetic)")
 
 
-def set_route_modes(eng, lanes="off", waves="off", wave_rounds=False):
-    """Engine.set_lane_sweeps / set_wave_sweeps / set_wave_rounds of a fresh engine, for the modes that are not the default."""
+def set_route_modes(eng, lanes="off", waves="off", wave_rounds=False, wave_long=False):
+    """Engine.set_lane_sweeps / set_wave_sweeps / set_wave_rounds / set_wave_long of a fresh engine, for the modes that are not the
+    default."""
     if lanes != "off":
         eng.set_lane_sweeps(lanes)
     if waves != "off":
         eng.set_wave_sweeps(waves)
     if wave_rounds:
         eng.set_wave_rounds(True)
+    if wave_long:
+        eng.set_wave_long(True)
 
 
 def phase_flags(n, m_init, clusters, phase):
