@@ -185,7 +185,7 @@ int nlmc_set_wave_sweeps(nlmc_ctx *ctx, int mode);
  * Everything a wave call accepts runs there, bit-identical to the other routes; nlmc_last_sweep_route is NLMC_ROUTE_WAVES.  The rounds
  * inside a wave launch (nlmc_pt_rounds_waves) keep their limit of NLMC_WAVE_N spins: under nlmc_set_wave_rounds,
  * nlmc_pt_rounds_deferred runs such a context's rounds as a sweep call and a swap call each (nlmc_pt_rounds_route:
- * NLMC_ROUNDS_LAUNCH_PER_ROUND).  Default: off, and then nothing changes for any caller.  Environment, read at nlmc_create:
+ * NLMC_ROUNDS_LAUNCH_PER_ROUND) unless nlmc_set_wave_long_rounds hands them to k_rounds_waves_long.  Default: off, and then nothing changes for any caller.  Environment, read at nlmc_create:
  * NLMC_WAVE_WAVES applies (capped by the LDS), NLMC_WAVE_LONG_AHEAD=1 requests the next visited spin's row at every update instead
  * of a row per flip (no result depends on either). */
 #define NLMC_WAVE_LONG_N 1024
@@ -424,15 +424,37 @@ int nlmc_pt_rounds_waves(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_
  * nlmc_set_wave_sweeps routes the context's sweeps to the wave kernels and nlmc_pt_rounds_waves' conditions hold; where they do not
  * the call goes on as with the option off.  Default: off, and then nothing changes for any caller. */
 int nlmc_set_wave_rounds(nlmc_ctx *ctx, int on);
-/* The route the most recent nlmc_pt_rounds_fused / nlmc_pt_rounds_deferred / nlmc_pt_rounds_lanes / nlmc_pt_rounds_waves call that ran
- * took: NLMC_ROUNDS_IN_LAUNCH (the rounds inside k_rounds_fused launches), NLMC_ROUNDS_LAUNCH_PER_ROUND, NLMC_ROUNDS_LANES (inside
- * k_rounds_lanes launches), NLMC_ROUNDS_APT_LANES (nlmc_apt_rounds_lanes), NLMC_ROUNDS_WAVES (inside k_rounds_waves launches), or 0
- * (no such call yet). */
+/* n_rounds whole rounds of dense chains of NLMC_WAVE_N < n <= NLMC_WAVE_LONG_N spins in launches of k_rounds_waves_long
+ * (csrc/nlmc_wave_long_rounds.h), whatever the wave mode is: the frame of k_rounds_waves around the update of k_sweep_waves_long.  A
+ * chain's int32 local fields are built once per launch and stay in LDS across the swap rounds (a swap is a label exchange: the spins
+ * never move), where a sweep call and a swap call per round rebuild them from n rows of the dense matrix every round.  A workgroup of
+ * up to 16 waves holds whole ladders, as many as have their regions (4 KB of fields at n > 512, 2 KB below, and n_pad bytes of spins a
+ * chain; the thresholds of a sweep a wave) in its LDS; a ladder of more than 16 temperatures has the workgroup to itself and its waves
+ * run chains in turn.  No workgroup waits for another one.  Bit-identical to nlmc_sweep_philox(beta = NULL, shared order) +
+ * nlmc_pt_swap_philox round by round on any route; swap log, best-state record and energy log as in nlmc_pt_rounds_waves.  Needs what
+ * nlmc_pt_rounds_waves needs with NLMC_WAVE_N < n <= NLMC_WAVE_LONG_N in place of n <= NLMC_WAVE_N, and one ladder's regions inside
+ * a workgroup's LDS (n = 1024: up to 22 temperatures; n = 513: 28; n = 512: 52; n = 300: 60).  NLMC_ERR_UNSUPPORTED (nothing was run,
+ * the reason in nlmc_last_error) when a condition is not met.  NLMC_WAVE_ROUNDS_LADDERS applies as it does there, capped by the LDS; no
+ * result depends on it.  nlmc_last_sweep_route is NLMC_ROUTE_WAVES after such a call, nlmc_pt_rounds_route NLMC_ROUNDS_WAVES_LONG,
+ * nlmc_last_schedule_stats reports the visiting orders built. */
+int nlmc_pt_rounds_waves_long(nlmc_ctx *ctx, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0,
+                              uint64_t seed, int n_pairs);
+/* on != 0: with nlmc_set_wave_rounds and nlmc_set_wave_long both on, nlmc_pt_rounds_deferred takes k_rounds_waves_long for chains of
+ * more than NLMC_WAVE_N spins where nlmc_set_wave_sweeps routes the context's sweeps to the wave kernels and
+ * nlmc_pt_rounds_waves_long's conditions hold; where they do not the call goes on as with the option off (a sweep call and a swap call
+ * per round).  Default: off, and then nothing changes for any caller. */
+int nlmc_set_wave_long_rounds(nlmc_ctx *ctx, int on);
+/* The route the most recent nlmc_pt_rounds_fused / nlmc_pt_rounds_deferred / nlmc_pt_rounds_lanes / nlmc_pt_rounds_waves /
+ * nlmc_pt_rounds_waves_long call that ran took: NLMC_ROUNDS_IN_LAUNCH (the rounds inside k_rounds_fused launches),
+ * NLMC_ROUNDS_LAUNCH_PER_ROUND, NLMC_ROUNDS_LANES (inside k_rounds_lanes launches), NLMC_ROUNDS_APT_LANES (nlmc_apt_rounds_lanes),
+ * NLMC_ROUNDS_WAVES (inside k_rounds_waves launches), NLMC_ROUNDS_WAVES_LONG (inside k_rounds_waves_long launches), or 0 (no such
+ * call yet). */
 #define NLMC_ROUNDS_IN_LAUNCH 1
 #define NLMC_ROUNDS_LAUNCH_PER_ROUND 2
 #define NLMC_ROUNDS_LANES 3
 #define NLMC_ROUNDS_APT_LANES (NLMC_ROUNDS_LANES + 1) /* 4 */
 #define NLMC_ROUNDS_WAVES (NLMC_ROUNDS_LANES + 2) /* 5 */
+#define NLMC_ROUNDS_WAVES_LONG (NLMC_ROUNDS_LANES + 3) /* 6 */
 int nlmc_pt_rounds_route(nlmc_ctx *ctx);
 /* n_rounds APT rounds of short chains -- sweeps_per_round sweeps at the slot temperatures, the Houdayer step of
  * nlmc_icm_round_ladders, the swap round of nlmc_pt_swap_philox -- in launches of k_apt_rounds_lanes (csrc/nlmc_lane_apt.h): the whole

@@ -30,6 +30,7 @@ WAVE_AUTO_MAX_ROWS = 0               # include/nlmc.h: NLMC_WAVE_AUTO_MAX_ROWS, 
 WAVES_OFF, WAVES_AUTO, WAVES_FORCE = 0, 1, 2
 ROUTE_NONE, ROUTE_STEPWISE, ROUTE_FUSED, ROUTE_LANES, ROUTE_WAVES = 0, 1, 2, 3, 4
 ROUNDS_IN_LAUNCH, ROUNDS_LAUNCH_PER_ROUND, ROUNDS_LANES, ROUNDS_APT_LANES, ROUNDS_WAVES = 1, 2, 3, 4, 5     # include/nlmc.h: nlmc_pt_rounds_route
+ROUNDS_WAVES_LONG = 6                # include/nlmc.h: NLMC_ROUNDS_WAVES_LONG, the rounds inside k_rounds_waves_long launches
 PHASE_ALL, PHASE_BACKBONE_HOT, PHASE_BACKBONE_FROZEN = 0, 1, 2
 
 EXPORTS = [
@@ -43,6 +44,7 @@ EXPORTS = [
     "nlmc_backbone_clusters", "nlmc_backbone_check", "nlmc_get_cluster_mask", "nlmc_set_phase", "nlmc_plan_slot", "nlmc_overlap_subsets", "nlmc_own_stream", "nlmc_plan_get_levels", "nlmc_probe_level_round", "nlmc_comm_unique_id", "nlmc_comm_init", "nlmc_comm_probe", "nlmc_comm_check", "nlmc_apt_shard", "nlmc_apt_pack", "nlmc_apt_swap_host", "nlmc_apt_swap_collective", "nlmc_apt_selftest_exchange", "nlmc_pt_swap_philox_collective", "nlmc_set_cluster_mask", "nlmc_host_prefault",
     "nlmc_set_fused_f64_real", "nlmc_last_sweep_fused", "nlmc_set_lane_sweeps", "nlmc_set_wave_sweeps", "nlmc_last_sweep_route", "nlmc_pt_rounds_lanes",
     "nlmc_apt_rounds_lanes", "nlmc_apt_systems", "nlmc_pt_rounds_waves", "nlmc_set_wave_rounds", "nlmc_set_wave_long",
+    "nlmc_pt_rounds_waves_long", "nlmc_set_wave_long_rounds",
     "nlmc_nmc_phases_lanes", "nlmc_nmc_phases_lanes_refusal",
     "nlmc_best_begin", "nlmc_best_update", "nlmc_best_read", "nlmc_best_end",
     "nlmc_elog_begin", "nlmc_elog_update", "nlmc_elog_read", "nlmc_elog_end",
@@ -178,6 +180,7 @@ def lib():
                        ("nlmc_pt_rounds_deferred", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),
                        ("nlmc_pt_rounds_lanes", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),
                        ("nlmc_pt_rounds_waves", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]), ("nlmc_set_wave_rounds", [_vp, _i]), ("nlmc_set_wave_long", [_vp, _i]),
+                       ("nlmc_pt_rounds_waves_long", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]), ("nlmc_set_wave_long_rounds", [_vp, _i]),
                        ("nlmc_apt_rounds_lanes", [_vp, _i, _i, _i, _u32, _u32, _u64, _i, _i, _vp]), ("nlmc_apt_systems", [_vp, _i]),
                        ("nlmc_nmc_phases_lanes", [_vp, _i, _vp, _i, _i, _u32, _u64, _dbl, _dbl, _i, _vp, _vp, _vp]),
                        ("nlmc_best_begin", [_vp, _dbl]), ("nlmc_best_update", [_vp, _u32]), ("nlmc_best_read", [_vp, _vp, _vp, _vp, _vp]),

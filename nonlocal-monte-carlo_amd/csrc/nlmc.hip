@@ -14,6 +14,7 @@
 #include "nlmc_waves.h"
 #include "nlmc_waves_long.h"
 #include "nlmc_wave_rounds.h"
+#include "nlmc_wave_long_rounds.h"
 #include "nlmc_wave_shape.h"
 #include "nlmc_host.h"
 
@@ -256,6 +257,7 @@ struct nlmc_ctx {
     // wave-per-chain sweeps (csrc/nlmc_waves.h)
     int wave_mode = 0;            // nlmc_set_wave_sweeps: 0 off, 1 auto, 2 force
     bool wave_rounds = false;     // nlmc_set_wave_rounds: nlmc_pt_rounds_deferred takes k_rounds_waves where the sweeps go to the wave kernels
+    bool wave_long_rounds = false;   // nlmc_set_wave_long_rounds: nlmc_pt_rounds_deferred takes k_rounds_waves_long for chains of more than NLMC_WAVE_N spins on the wave route
     bool wave_long = false;       // nlmc_set_wave_long: the wave route takes chains of up to NLMC_WAVE_LONG_N spins (k_sweep_waves_long)
     DevBuf<int32_t> wave_J;       // [n][64 R] dense fixed-point matrix, built on the first wave call (k_wave_matrix): 256 KB at n = 256, 4 MB at n = 1024
     bool wave_J_built = false;
@@ -2882,23 +2884,28 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
 }
 
 // ---- tempering rounds of short chains: a ladder per wave (k_rounds_lanes, csrc/nlmc_lane_rounds.h) ----------------------------------
-// The routes that run whole rounds of short chains in one launch: k_rounds_lanes, k_rounds_waves, k_apt_rounds_lanes.
-enum class ShortRounds { lanes, waves, apt_lanes };
+// The routes that run whole rounds of short chains in one launch: k_rounds_lanes, k_rounds_waves, k_rounds_waves_long, k_apt_rounds_lanes.
+enum class ShortRounds { lanes, waves, waves_long, apt_lanes };
 
 // Why this context cannot run rounds [round0, round0 + n_rounds) on `route`, or nullptr: the checks of rounds_check that do not concern
-// fused plans, the reach of the route's kernels (lanes: n <= NLMC_LANE_N; waves: fixed point, n <= NLMC_WAVE_N) and a ladder inside one
-// wave (waves: one workgroup's swap wave).  The APT rounds have their Houdayer step: n_pairs = 0, a round without swaps, is taken.
+// fused plans, the reach of the route's kernels (lanes: n <= NLMC_LANE_N; waves: fixed point, n <= NLMC_WAVE_N; waves_long: fixed point,
+// NLMC_WAVE_N < n <= NLMC_WAVE_LONG_N, one ladder's regions inside a workgroup's LDS) and a ladder inside one wave (waves, waves_long:
+// one workgroup's swap wave).  The APT rounds have their Houdayer step: n_pairs = 0, a round without swaps, is taken.
 // Arguments are checked by the callers.
 const char *short_rounds_refusal(const nlmc_ctx *c, ShortRounds route, int precision, int n_rounds, int T, uint32_t round0, uint64_t seed, int n_pairs)
 {
-    const bool waves = route == ShortRounds::waves;
+    const bool waves = route == ShortRounds::waves, longs = route == ShortRounds::waves_long;
     if (const char *why = rounds_context_refusal(c, true)) return why;
     if (n_pairs < 1 && route != ShortRounds::apt_lanes) return "no swap pairs";
-    if (waves && precision != NLMC_F32) return "the wave-per-chain kernels have the fixed-point arithmetic (NLMC_F32) only";
-    if (c->knobs.force_big || c->n > (waves ? NLMC_WAVE_N : NLMC_LANE_N))
+    if ((waves || longs) && precision != NLMC_F32) return "the wave-per-chain kernels have the fixed-point arithmetic (NLMC_F32) only";
+    if (longs && (c->knobs.force_big || c->n <= NLMC_WAVE_N || c->n > NLMC_WAVE_LONG_N))
+        return "the long wave-per-chain kernels take chains of more than NLMC_WAVE_N and at most NLMC_WAVE_LONG_N spins";
+    if (!longs && (c->knobs.force_big || c->n > (waves ? NLMC_WAVE_N : NLMC_LANE_N)))
         return waves ? "the wave-per-chain kernels take chains of at most NLMC_WAVE_N spins" : "the chain-per-lane kernels take chains of at most NLMC_LANE_N spins";
     if (c->ladder_len > 64)
-        return waves ? "a ladder of more than 64 temperatures does not fit a workgroup's swap wave" : "a ladder of more than 64 temperatures does not fit a wave";
+        return waves || longs ? "a ladder of more than 64 temperatures does not fit a workgroup's swap wave" : "a ladder of more than 64 temperatures does not fit a wave";
+    // (whether ONE ladder fits a workgroup depends neither on the device nor on the number of ladders)
+    if (longs && nlmc_wave_long_rounds_shape(c->n, c->n_pad, c->ladder_len, 1, 1, 0).R == 0) return "the ladders of a workgroup do not fit its LDS";
     if (n_pairs >= 1 && !c->pt_plan.covers(round0, n_rounds, n_pairs, seed)) return "the pair selections of these rounds are not planned (nlmc_pt_plan)";
     if ((size_t)T * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
         return "the visiting orders of one round exceed the order scratch (NLMC_LANE_SCRATCH)";
@@ -3019,15 +3026,49 @@ int rounds_waves(nlmc_ctx *c, int n_rounds, int T, uint32_t sweep0, uint32_t rou
     return NLMC_OK;
 }
 
-// n_rounds rounds on `route` (lanes or waves), for which short_rounds_refusal said nullptr.
+// ---- tempering rounds of long chains inside a wave launch (k_rounds_waves_long, csrc/nlmc_wave_long_rounds.h) ------------------------
+const void *rounds_waves_long_kernel(int R, bool observed)
+{
+    static const void *const table[2][2] = {
+        {reinterpret_cast<const void *>(k_rounds_waves_long<8, false>), reinterpret_cast<const void *>(k_rounds_waves_long<8, true>)},
+        {reinterpret_cast<const void *>(k_rounds_waves_long<16, false>), reinterpret_cast<const void *>(k_rounds_waves_long<16, true>)}};
+    return table[R == 8 ? 0 : 1][observed ? 1 : 0];
+}
+
+// n_rounds rounds in launches of k_rounds_waves_long.  short_rounds_refusal said nullptr.
+int rounds_waves_long(nlmc_ctx *c, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
+{
+    const int L = c->ladder_len, ladders = c->n_chains / L;
+    { int rc = cu_count(c); if (rc) return rc; }
+    const NlmcWaveLongRoundsShape S = nlmc_wave_long_rounds_shape(c->n, c->n_pad, L, ladders, c->n_cu, c->knobs.wave_rounds_ladders);
+    if (S.R == 0) return fail(c, NLMC_ERR_STATE, "rounds_waves_long: the chain or the ladder does not fit the wave kernels");
+    const void *kfun = rounds_waves_long_kernel(S.R, c->observed());
+    { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
+    const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
+    WaveLongRoundsArgs w{};
+    w.P = S.P; w.C = S.C;
+    int rc = lane_rounds_chunks(c, kfun, S.lds, n_rounds, T, sweep0, round0, seed, NLMC_ROUTE_WAVES, [&](int, int k, uint32_t s0, uint32_t r0) -> int {
+        LaneLaunchArgs x = lane_launch_args(c, T, seed, s0, k, r0, n_pairs, (size_t)(c->n_chains_global / L), log, false, 0, 0);
+        x.a.wave_J = c->wave_J.p;
+        void *kargs[] = {&x.a, &x.q, &w};
+        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)S.blocks), dim3((unsigned)(64 * S.W)), kargs, S.lds, c->stream));
+        return NLMC_OK;
+    });
+    if (rc) return rc;
+    c->rounds_route = NLMC_ROUNDS_WAVES_LONG;
+    return NLMC_OK;
+}
+
+// n_rounds rounds on `route` (lanes, waves or waves_long), for which short_rounds_refusal said nullptr.
 int short_rounds(nlmc_ctx *c, ShortRounds route, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
 {
     HIP_TRY(c, hipSetDevice(c->device));
+    if (route == ShortRounds::waves_long) return rounds_waves_long(c, n_rounds, T, sweep0, round0, seed, n_pairs);
     return route == ShortRounds::waves ? rounds_waves(c, n_rounds, T, sweep0, round0, seed, n_pairs)
                                        : rounds_lanes(c, precision, n_rounds, T, sweep0, round0, seed, n_pairs);
 }
 
-// nlmc_pt_rounds_lanes / nlmc_pt_rounds_waves (`fn`): n_rounds rounds in launches of k_rounds_lanes / k_rounds_waves, whatever the lane
+// nlmc_pt_rounds_lanes / nlmc_pt_rounds_waves / nlmc_pt_rounds_waves_long (`fn`): n_rounds rounds in launches of the route's kernel, whatever the lane
 // or wave mode is and whatever nlmc_pt_rounds_deferred would choose.
 int short_rounds_by_name(nlmc_ctx *c, ShortRounds route, const char *fn, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0,
                          uint64_t seed, int n_pairs)
@@ -3051,6 +3092,20 @@ int nlmc_pt_rounds_waves(nlmc_ctx *c, int precision, int n_rounds, int sweeps_pe
                          int n_pairs)
 {
     return short_rounds_by_name(c, ShortRounds::waves, "nlmc_pt_rounds_waves", precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+}
+
+int nlmc_pt_rounds_waves_long(nlmc_ctx *c, int precision, int n_rounds, int sweeps_per_round, uint32_t sweep0, uint32_t round0, uint64_t seed,
+                              int n_pairs)
+{
+    return short_rounds_by_name(c, ShortRounds::waves_long, "nlmc_pt_rounds_waves_long", precision, n_rounds, sweeps_per_round, sweep0, round0, seed,
+                                n_pairs);
+}
+
+int nlmc_set_wave_long_rounds(nlmc_ctx *c, int on)
+{
+    if (!c) return NLMC_ERR_ARG;
+    c->wave_long_rounds = on != 0;
+    return NLMC_OK;
 }
 
 int nlmc_set_wave_rounds(nlmc_ctx *c, int on)
@@ -3127,8 +3182,11 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
         auto takes = [&](ShortRounds route) { return !short_rounds_refusal(c, route, precision, n_rounds, sweeps_per_round, round0, seed, n_pairs); };
         if (c->wave_rounds && waves_route(c, c->n_chains, precision) && takes(ShortRounds::waves))
             return short_rounds(c, ShortRounds::waves, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
-        // k_rounds_waves ends at NLMC_WAVE_N spins: longer chains on the wave route (nlmc_set_wave_long) run a sweep call and a swap call
-        // per round, the sweeps in k_sweep_waves_long
+        // k_rounds_waves ends at NLMC_WAVE_N spins: longer chains on the wave route (nlmc_set_wave_long) run inside k_rounds_waves_long
+        // under nlmc_set_wave_long_rounds where it takes them, and otherwise a sweep call and a swap call per round, the sweeps in
+        // k_sweep_waves_long
+        if (c->wave_rounds && c->wave_long && c->wave_long_rounds && waves_route(c, c->n_chains, precision) && takes(ShortRounds::waves_long))
+            return short_rounds(c, ShortRounds::waves_long, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
         if (c->wave_rounds && c->n > NLMC_WAVE_N && waves_route(c, c->n_chains, precision) && !rounds_context_refusal(c, true))
             return rounds_waves_call_by_call(c, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
         if (ROUNDS_LANES_IN_LAUNCH && lanes_route(c, c->n_chains) && takes(ShortRounds::lanes))

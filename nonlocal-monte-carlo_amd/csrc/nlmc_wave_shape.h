@@ -1,7 +1,7 @@
 // nlmc_wave_shape.h -- host-side launch shapes of the wave-per-chain sweeps (csrc/nlmc_waves.h, csrc/nlmc_waves_long.h) and of the
-// tempering rounds inside a wave launch (csrc/nlmc_wave_rounds.h), pure functions with no HIP in them (checked on the host under the
-// sanitizers: scripts/wave_shape_check.cpp, scripts/wave_long_shape_check.cpp, scripts/wave_rounds_shape_check.cpp).  No result
-// depends on W or P.
+// tempering rounds inside a wave launch (csrc/nlmc_wave_rounds.h, csrc/nlmc_wave_long_rounds.h), pure functions with no HIP in them
+// (checked on the host under the sanitizers: scripts/wave_shape_check.cpp, scripts/wave_long_shape_check.cpp,
+// scripts/wave_rounds_shape_check.cpp, scripts/wave_long_rounds_shape_check.cpp).  No result depends on W or P.
 #pragma once
 #include <stddef.h>
 
@@ -137,4 +137,63 @@ static inline NlmcWaveRoundsShape nlmc_wave_rounds_shape(int n, int n_pad, int L
     s.map_off = s.e_off + (((size_t)Q * 8 + a16) & ~a16);
     s.lds = s.map_off + (((size_t)2 * Q + a16) & ~a16);
     return s;
+}
+
+// ---- tempering rounds of long chains inside a wave launch (csrc/nlmc_wave_long_rounds.h: k_rounds_waves_long), 256 < n <= 1024 ----------
+// The LDS of a workgroup of Q chains on W waves, each part 16-byte aligned: Q chain regions of chain_bytes each -- X [64 R] int32 (a
+// word per lane and register, as in nlmc_wave_long_region) | spins [n_pad] int8 at s_off -- | W threshold regions of w_bytes each,
+// [4 ceil(n / 4)] float, one per wave | energies [Q] int64 | maps chain_of_slot [P][L] + slot_of_chain [Q] bytes.  No phase-flag
+// plane: these are plain chains.  The kernel and the shape function both take the layout from here.
+struct NlmcWaveLongRoundsLayout { int s_off, chain_bytes, w_bytes, w_off, e_off, map_off, total; };
+NLMC_WS_HD static inline NlmcWaveLongRoundsLayout nlmc_wave_long_rounds_layout(int n, int n_pad, int Q, int W)
+{
+    NlmcWaveLongRoundsLayout g;
+    g.s_off = 256 * (n <= 512 ? 8 : 16);
+    g.chain_bytes = g.s_off + ((n_pad + 15) & ~15);
+    g.w_bytes = 16 * ((n + 3) / 4);
+    g.w_off = Q * g.chain_bytes;
+    g.e_off = g.w_off + W * g.w_bytes;
+    g.map_off = g.e_off + ((8 * Q + 15) & ~15);
+    g.total = g.map_off + ((2 * Q + 15) & ~15);
+    return g;
+}
+
+struct NlmcWaveLongRoundsShape {
+    int R;            // fields per lane: 8 (n <= 512) or 16; 0: the chain, the ladder or one ladder's regions do not fit
+    int P;            // whole ladders per workgroup: Q = P L <= 64 chains
+    int C;            // chains a wave runs in turn at most: ceil(Q / 16), 1 .. 4
+    int W;            // waves per workgroup: ceil(Q / C) <= 16; wave w owns the workgroup's chains w, w + W, .. below Q
+    int blocks;       // workgroups: ceil(ladders / P)
+    size_t lds;       // dynamic LDS of the launch in bytes (nlmc_wave_long_rounds_layout of Q, W)
+    size_t stride;    // row stride of the matrix in global memory, in ints: 64 R
+};
+
+// ladders >= 1 of L temperatures each.  knob_ladders: NLMC_WAVE_ROUNDS_LADDERS (0: by the rule).  The rule of nlmc_wave_rounds_shape --
+// enough workgroups to cover the compute units first, then as many ladders as fit 16 waves (a chain per wave); a ladder of more than
+// 16 temperatures has the workgroup to itself and its waves run chains in turn -- and on top of it P is lowered until the workgroup's
+// regions fit its LDS.  R = 0 where one ladder alone does not.  No result depends on P or W.
+static inline NlmcWaveLongRoundsShape nlmc_wave_long_rounds_shape(int n, int n_pad, int L, int ladders, int n_cu, int knob_ladders)
+{
+    NlmcWaveLongRoundsShape s = {0, 1, 1, 1, 0, 0, 0};
+    if (n < NLMC_WAVE_LONG_MIN_N || n > NLMC_WAVE_LONG_MAX_N || n_pad < n || L < 1 || L > 64 || ladders < 1) return s;
+    const int R = n <= 512 ? 8 : 16;
+    if (n_pad > 64 * R) return s;                       // the padded state row must fit a matrix row
+    const int cu = n_cu > 0 ? n_cu : 1;
+    long long p = knob_ladders > 0 ? knob_ladders : ((long long)ladders + cu - 1) / cu;
+    const long long cap = knob_ladders > 0 ? 64 / L : (16 / L > 1 ? 16 / L : 1);
+    if (p > cap) p = cap;
+    if (p > ladders) p = ladders;
+    if (p < 1) p = 1;
+    for (;; --p) {
+        const int Q = (int)p * L, C = (Q + 15) / 16, W = (Q + C - 1) / C;
+        const NlmcWaveLongRoundsLayout g = nlmc_wave_long_rounds_layout(n, n_pad, Q, W);
+        if ((size_t)g.total <= NLMC_WAVE_LONG_LDS_MAX) {
+            s.R = R; s.P = (int)p; s.C = C; s.W = W;
+            s.blocks = (ladders + s.P - 1) / s.P;
+            s.lds = (size_t)g.total;
+            s.stride = (size_t)64 * (size_t)R;
+            return s;
+        }
+        if (p == 1) return s;                           // one ladder alone does not fit
+    }
 }

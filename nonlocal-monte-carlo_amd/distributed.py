@@ -280,7 +280,7 @@ class LocalTempering:
 
     def __init__(self, inst, beta_list, n_chains_global, seed, n_pairs, device_ids, precision="f32", engine_factory=None,
                  engines=None, parts=None, lane_sweeps="off", track_best=False, target_energy=None, track_energies=False,
-                 wave_sweeps="off", wave_rounds=False, lane_nmc=None, wave_long=False):
+                 wave_sweeps="off", wave_rounds=False, lane_nmc=None, wave_long=False, wave_long_rounds=False):
         """`parts` (optional): the blocks [(chain_base, count)] this process drives instead of an even cut over device_ids -- one
         rank's share under a launcher; `engines`: contexts that exist already (they must have had pt_init; not closed here... they
         ARE closed by close(): hand over ownership); `lane_sweeps`: Engine.set_lane_sweeps of every engine created here ("off",
@@ -290,7 +290,9 @@ class LocalTempering:
         Engine.set_wave_rounds of every engine created here (needs wave_sweeps != "off", ValueError otherwise): run_rounds' chunks of
         such chains run inside k_rounds_waves -- same bits); `wave_long`: Engine.set_wave_long of every engine created here (needs
         wave_sweeps != "off", ValueError otherwise): the wave route takes chains of up to 1024 spins, and with `wave_rounds` those of
-        more than 256 run a sweep call and a swap call per round -- same bits); `track_best`: every
+        more than 256 run a sweep call and a swap call per round -- same bits); `wave_long_rounds`: Engine.set_wave_long_rounds of every
+        engine created here (needs `wave_rounds` and `wave_long`, ValueError otherwise): run_rounds' chunks of chains of 257..1024 spins
+        run inside k_rounds_waves_long, the local fields resident across the swap rounds -- same bits); `track_best`: every
         context keeps the record of its chains' lowest-energy states (Engine.best_begin; `target_energy`: the energy whose first
         passage is stamped, in the engine's units) -- one observation per round, stamp = round index, after the round's sweeps (and
         NMC cycles) and before its swap; best() reads it.  The record only observes: the trajectory is the same bits.
@@ -303,6 +305,7 @@ class LocalTempering:
         which every context took the call), lane_nmc_calls (calls that ran)."""
         hostlogic.check_wave_rounds(wave_rounds, wave_sweeps, needs="wave_sweeps 'auto' or 'force'")
         hostlogic.check_wave_long(wave_long, wave_sweeps, needs="wave_sweeps 'auto' or 'force'")
+        hostlogic.check_wave_long_rounds(wave_long_rounds, wave_rounds, wave_long)
         self.G, self.seed, self.n_pairs, self.precision = int(n_chains_global), int(seed), int(n_pairs), precision
         devs = list(device_ids)
         self.parts = list(parts) if parts is not None else [block_partition(self.G, len(devs), r) for r in range(len(devs))]
@@ -319,7 +322,7 @@ class LocalTempering:
                 else:
                     e = Engine(inst, None, count, device=int(d), chain_base=base, n_chains_global=self.G,
                                own_stream=len(devs) > 1)
-                hostlogic.set_route_modes(e, lane_sweeps, wave_sweeps, wave_rounds, wave_long)
+                hostlogic.set_route_modes(e, lane_sweeps, wave_sweeps, wave_rounds, wave_long, wave_long_rounds)
                 e.pt_init(np.asarray(beta_list, dtype=np.float64))
                 self.engs.append(e)
         except Exception:

@@ -86,6 +86,7 @@ class Engine:
         self.wave_sweeps = "off"         # set_wave_sweeps
         self.wave_rounds = False         # set_wave_rounds
         self.wave_long = False           # set_wave_long
+        self.wave_long_rounds = False    # set_wave_long_rounds
         self.energy_scale = int(self._L.nlmc_energy_scale(self._ctx))
         self.field_scale = int(self._L.nlmc_field_scale(self._ctx))      # qs of the "f32" path: Jq = rint(J 2^qs)
 
@@ -277,10 +278,20 @@ class Engine:
         """Whether the wave route takes chains of up to 1024 spins instead of 256 (include/nlmc.h: nlmc_set_wave_long): dense chains of
         257..1024 spins then sweep one per wave in k_sweep_waves_long, fields in registers and in LDS, under the mode rules of
         set_wave_sweeps.  The rounds inside a wave launch keep their limit of 256 spins: with set_wave_rounds, pt_rounds_deferred runs
-        a longer chain's rounds as a sweep call and a swap call each.  Default off: nothing changes for any caller.  Same bits either
+        a longer chain's rounds as a sweep call and a swap call each, unless set_wave_long_rounds hands them to k_rounds_waves_long.
+        Default off: nothing changes for any caller.  Same bits either
         way."""
         self._ck(self._L.nlmc_set_wave_long(self._ctx, 1 if on else 0))
         self.wave_long = bool(on)
+
+    def set_wave_long_rounds(self, on=True):
+        """Whether pt_rounds_deferred runs the rounds of chains of 257..1024 spins inside k_rounds_waves_long launches (include/nlmc.h:
+        nlmc_set_wave_long_rounds): the local fields are built once per chunk of rounds and stay in LDS across the swap rounds.  Takes
+        effect with set_wave_rounds and set_wave_long both on, where the context's sweeps go to the wave kernels (waves_take) and
+        pt_rounds_waves_long's conditions hold; otherwise such rounds stay a sweep call and a swap call each.  Default off: nothing
+        changes for any caller.  Same bits either way."""
+        self._ck(self._L.nlmc_set_wave_long_rounds(self._ctx, 1 if on else 0))
+        self.wave_long_rounds = bool(on)
 
     def waves_take(self, rows=None, precision="f32"):
         """Whether the context routes a sweep_philox call over `rows` rows (default: the selected chains) in `precision` to the
@@ -618,6 +629,15 @@ class Engine:
         by itself under set_wave_sweeps("force") with set_wave_rounds(True)."""
         return self._rounds_call(self._L.nlmc_pt_rounds_waves, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision)
 
+    def pt_rounds_waves_long(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision="f32"):
+        """n_rounds whole rounds of dense chains of 257..1024 spins inside k_rounds_waves_long launches, whatever the wave mode is
+        (include/nlmc.h: nlmc_pt_rounds_waves_long): a chain per wave, its local fields built once per launch and resident in LDS
+        across the swap rounds, whole ladders of at most 64 temperatures per workgroup as far as its LDS holds their regions, f32 only,
+        pair selections planned (pt_plan), no fused-window plan.  True when the rounds were queued, False when the context does not
+        qualify (nothing was run; the reason is in rounds_fused_refusal).  pt_rounds_deferred takes this route by itself under
+        set_wave_sweeps("force") with set_wave_rounds, set_wave_long and set_wave_long_rounds on."""
+        return self._rounds_call(self._L.nlmc_pt_rounds_waves_long, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, precision)
+
     def apt_rounds_lanes(self, n_rounds, sweeps_per_round, seed, sweep0, round0, n_pairs, katzgraber=True, precision="f32",
                          want_info=False):
         """n_rounds whole APT rounds of short chains -- sweeps, the Houdayer step of icm_round_ladders, the swap round -- inside
@@ -633,12 +653,13 @@ class Engine:
         return queued, (info if queued else None)
 
     def last_rounds_route(self):
-        """The route the last pt_rounds_fused / pt_rounds_deferred / pt_rounds_lanes / pt_rounds_waves / apt_rounds_lanes call that ran
-        took: "in launch" (the rounds inside k_rounds_fused launches), "launch per round", "lanes" (inside k_rounds_lanes launches),
-        "apt lanes" (inside k_apt_rounds_lanes launches), "waves" (inside k_rounds_waves launches), or None before any such call
-        (include/nlmc.h: nlmc_pt_rounds_route)."""
+        """The route the last pt_rounds_fused / pt_rounds_deferred / pt_rounds_lanes / pt_rounds_waves / pt_rounds_waves_long /
+        apt_rounds_lanes call that ran took: "in launch" (the rounds inside k_rounds_fused launches), "launch per round", "lanes"
+        (inside k_rounds_lanes launches), "apt lanes" (inside k_apt_rounds_lanes launches), "waves" (inside k_rounds_waves launches),
+        "waves long" (inside k_rounds_waves_long launches), or None before any such call (include/nlmc.h: nlmc_pt_rounds_route)."""
         return {_abi.ROUNDS_IN_LAUNCH: "in launch", _abi.ROUNDS_LAUNCH_PER_ROUND: "launch per round",
-                _abi.ROUNDS_LANES: "lanes", _abi.ROUNDS_APT_LANES: "apt lanes", _abi.ROUNDS_WAVES: "waves"}.get(self._L.nlmc_pt_rounds_route(self._ctx))
+                _abi.ROUNDS_LANES: "lanes", _abi.ROUNDS_APT_LANES: "apt lanes", _abi.ROUNDS_WAVES: "waves",
+                _abi.ROUNDS_WAVES_LONG: "waves long"}.get(self._L.nlmc_pt_rounds_route(self._ctx))
 
     def pt_log_begin(self, round0, n_rounds, n_pairs):
         """Keep the swap log of the next rounds on the device (rounds called with want_log=False)."""
@@ -983,6 +1004,17 @@ APT_LANES_IN_LAUNCH = False
 # shape with T = 1 and L = 16 (1.3-2.7x), level at T = 10, but above it at T = 1000 with 64 ladders of 16 (1.2-1.35x: a ladder per
 # workgroup leaves three quarters of the compute units idle) and at every shape with L = 64 (1.2-5.3x: four chains a wave, in turn).
 WAVE_ROUNDS_IN_LAUNCH = False
+
+# What the documents recommend for wave_long_rounds where wave_rounds and wave_long are on (the default of every wave_long_rounds
+# keyword stays False whatever this says; nothing in the package reads it).  The same rule: True only if the in-launch median time per
+# run is not above that of a sweep call and a swap call per round on the same build (set_wave_long_rounds(False)) by more than the
+# run-to-run spread at any shape of scripts/wave_long_rounds_throughput.py.  Measured (DESIGN.md section 6,
+# profiles/wave_long_rounds_throughput.txt): below it at every shape with T = 1 and at most 16 temperatures (1.2-4.9x), and 2.0-2.4x
+# below it at every T on 256 ladders of 16 at n = 1024 (4096 chains: call by call runs 15 chains a workgroup, more workgroups than
+# compute units), but above it at T >= 10 on 16 ladders (up to 1.4x: a ladder per workgroup uses 16 of the compute units, sixteen waves
+# each, where call by call spreads the chains a wave per compute unit) and at every T on 16 ladders of 32 (1.5-2.6x: two chains a wave,
+# in turn).  Recommended: a swap every sweep or two, or at least as many ladders as compute units, with L <= 16.
+WAVE_LONG_ROUNDS_IN_LAUNCH = False
 
 
 class RoundPlanner:

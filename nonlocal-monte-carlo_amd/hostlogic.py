@@ -43,8 +43,15 @@ def check_wave_long(wave_long, waves, needs="waves='auto' or 'force'"):
         raise ValueError(f"wave_long needs {needs} (it widens the wave route to chains of up to 1024 spins)")
 
 
-def check_route_keywords(lanes="off", waves="off", wave_rounds=False, rng=None, precision="f32", wave_long=False):
-    """The `lanes` / `waves` / `wave_rounds` / `wave_long` keywords of NPT, APT_ICM and APT_preprocessor.  rng None (a constructor that
+def check_wave_long_rounds(wave_long_rounds, wave_rounds, wave_long):
+    """wave_long_rounds without wave_rounds or without wave_long: ValueError."""
+    if wave_long_rounds and not (wave_rounds and wave_long):
+        raise ValueError("wave_long_rounds needs wave_rounds=True and wave_long=True (the rounds of chains of 257..1024 spins run "
+                         "inside the long wave kernel's launches)")
+
+
+def check_route_keywords(lanes="off", waves="off", wave_rounds=False, rng=None, precision="f32", wave_long=False, wave_long_rounds=False):
+    """The `lanes` / `waves` / `wave_rounds` / `wave_long` / `wave_long_rounds` keywords of NPT, APT_ICM and APT_preprocessor.  rng None (a constructor that
     does not know its backend yet): the mode values only; otherwise also what they need of `rng` and `precision`."""
     for name, mode in (("lanes", lanes), ("waves", waves)):
         if mode not in ("off", "auto", "force"):
@@ -64,11 +71,13 @@ def check_route_keywords(lanes="off", waves="off", wave_rounds=False, rng=None, 
         raise ValueError("wave_long applies to rng='philox' (rng='numpy' runs the reference's own stream order)")
     if wave_long and precision == "f64":
         raise ValueError("wave_long applies to precision='f32' (the wave-per-chain kernels have no fp64 arithmetic)")
+    check_wave_long_rounds(wave_long_rounds, wave_rounds, wave_long)
 
 
-def set_route_modes(eng, lanes="off", waves="off", wave_rounds=False, wave_long=False):
-    """Engine.set_lane_sweeps / set_wave_sweeps / set_wave_rounds / set_wave_long of a fresh engine, for the modes that are not the
-    default."""
+def set_route_modes(eng, lanes="off", waves="off", wave_rounds=False, wave_long=False, wave_long_rounds=False):
+    """Engine.set_lane_sweeps / set_wave_sweeps / set_wave_rounds / set_wave_long / set_wave_long_rounds of a fresh engine, for the
+    modes that are not the default.  wave_long_rounds without wave_rounds and wave_long: ValueError."""
+    check_wave_long_rounds(wave_long_rounds, wave_rounds, wave_long)
     if lanes != "off":
         eng.set_lane_sweeps(lanes)
     if waves != "off":
@@ -77,6 +86,8 @@ def set_route_modes(eng, lanes="off", waves="off", wave_rounds=False, wave_long=
         eng.set_wave_rounds(True)
     if wave_long:
         eng.set_wave_long(True)
+    if wave_long_rounds:
+        eng.set_wave_long_rounds(True)
 
 
 def phase_flags(n, m_init, clusters, phase):

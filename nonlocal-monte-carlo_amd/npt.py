@@ -31,7 +31,7 @@ class NPT(Common):
     _variant = "npt"
 
     def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32", lanes="off", waves="off", wave_rounds=False,
-                 lane_nmc=None, wave_long=False):
+                 lane_nmc=None, wave_long=False, wave_long_rounds=False):
         """`precision` (additive keyword, rng="philox" only): "f32" (default) -- the throughput mode's fixed-point couplings and
         logistic thresholds; "f64" -- the device-resident rounds in the reference's arithmetic (fp64 field, 53-bit uniform), on
         fused windows for real couplings too (Engine.set_fused_f64_real).  Replicas with doNMC set are not supported with "f64".
@@ -52,19 +52,24 @@ class NPT(Common):
         Plain replicas only.
         `wave_long` (additive keyword, needs waves != "off", hence rng="philox" and precision="f32"): Engine.set_wave_long of the run's
         engines -- the wave route takes dense chains of up to 1024 spins (k_sweep_waves_long) -- same results.  With `wave_rounds`,
-        chains of more than 256 spins run a sweep call and a swap call per round."""
+        chains of more than 256 spins run a sweep call and a swap call per round.
+        `wave_long_rounds` (additive keyword, needs wave_rounds=True and wave_long=True): Engine.set_wave_long_rounds of the run's
+        engines -- the rounds without output of chains of 257..1024 spins run inside k_rounds_waves_long launches, a chunk of rounds per
+        launch with the local fields resident across the swap rounds -- same results.  Plain replicas only, like `wave_rounds`."""
         if precision not in ("f32", "f64"):
             raise ValueError("precision must be 'f32' or 'f64'")
         hostlogic.check_route_keywords(lanes, waves)
         super().__init__(J, h, rng=rng, seed=seed, device=device, lbp=lbp)
         if precision != "f32" and self.rng != "philox":
             raise ValueError("precision applies to rng='philox' (rng='numpy' runs the reference's own arithmetic)")
-        hostlogic.check_route_keywords(lanes, waves, wave_rounds, rng=self.rng, precision=precision, wave_long=wave_long)
+        hostlogic.check_route_keywords(lanes, waves, wave_rounds, rng=self.rng, precision=precision, wave_long=wave_long,
+                                       wave_long_rounds=wave_long_rounds)
         self.precision = precision
         self.lanes = lanes
         self.waves = waves
         self.wave_rounds = bool(wave_rounds)
         self.wave_long = bool(wave_long)
+        self.wave_long_rounds = bool(wave_long_rounds)
         self.lane_nmc = lane_nmc
 
     # ------------------------------------------------------------------------------------------------
@@ -419,11 +424,11 @@ class NPT(Common):
             return e
         if ctx is None:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, precision=prec, lane_sweeps=self.lanes,
-                                wave_sweeps=self.waves, wave_rounds=self.wave_rounds, wave_long=self.wave_long, track_best=track_best, target_energy=target_energy, track_energies=track_energies,
+                                wave_sweeps=self.waves, wave_rounds=self.wave_rounds, wave_long=self.wave_long, wave_long_rounds=self.wave_long_rounds, track_best=track_best, target_energy=target_energy, track_energies=track_energies,
                                 lane_nmc=self.lane_nmc)
         elif not cut:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, parts=[(base_, count_)], precision=prec,
-                                lane_sweeps=self.lanes, wave_sweeps=self.waves, wave_rounds=self.wave_rounds, wave_long=self.wave_long, track_best=track_best, target_energy=target_energy, track_energies=track_energies,
+                                lane_sweeps=self.lanes, wave_sweeps=self.waves, wave_rounds=self.wave_rounds, wave_long=self.wave_long, wave_long_rounds=self.wave_long_rounds, track_best=track_best, target_energy=target_energy, track_energies=track_energies,
                                 lane_nmc=self.lane_nmc)
         else:
             lt = ShardedAsLocal(ShardedTempering(
