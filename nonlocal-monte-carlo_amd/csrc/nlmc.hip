@@ -535,7 +535,6 @@ int sweep_block_for(const nlmc_ctx *c, bool f64_philox, bool f32_diag = false)
 // beyond the default dynamic-LDS window a kernel has to opt in (once per kernel and size step)
 constexpr size_t NLMC_LDS_BYTES_MAX = (size_t)158 * 1024;      // dynamic LDS a workgroup may ask for
 
-static_assert(NLMC_WAVE_ROUNDS_LDS_MAX == NLMC_LDS_BYTES_MAX, "csrc/nlmc_wave_shape.h keeps its own copy of the ceiling");
 static_assert(NLMC_WAVE_LONG_LDS_MAX == NLMC_LDS_BYTES_MAX, "csrc/nlmc_wave_shape.h keeps its own copy of the ceiling");
 static_assert(NLMC_WAVE_LONG_MIN_N == NLMC_WAVE_N + 1 && NLMC_WAVE_LONG_MAX_N == NLMC_WAVE_LONG_N, "csrc/nlmc_wave_shape.h keeps its own copy of the chain lengths");
 static_assert(NLMC_WAVE_LONG_N <= NLMC_LANE_N, "k_lane_orders builds the visiting orders of the wave kernels");
@@ -1317,13 +1316,19 @@ bool waves_route(const nlmc_ctx *c, int R, int precision)
     return c->wave_mode == 2 || (long long)R <= (long long)NLMC_WAVE_AUTO_MAX_ROWS;
 }
 
-const void *waves_kernel(int R, bool jlds)
+// Row of a wave kernel table: R = 1, 2, 4, 8, 16 fields per lane (nlmc_wave_fields)
+int wave_fields_row(int R) { return R == 1 ? 0 : R == 2 ? 1 : R == 4 ? 2 : R == 8 ? 3 : 4; }
+
+// k_sweep_waves<R, jlds> for R <= 4, k_sweep_waves_long<R, ahead> beyond
+const void *waves_kernel(int R, bool variant)
 {
-    static const void *const table[3][2] = {
+    static const void *const table[5][2] = {
         {reinterpret_cast<const void *>(k_sweep_waves<1, false>), reinterpret_cast<const void *>(k_sweep_waves<1, true>)},
         {reinterpret_cast<const void *>(k_sweep_waves<2, false>), reinterpret_cast<const void *>(k_sweep_waves<2, true>)},
-        {reinterpret_cast<const void *>(k_sweep_waves<4, false>), reinterpret_cast<const void *>(k_sweep_waves<4, true>)}};
-    return table[R == 1 ? 0 : R == 2 ? 1 : 2][jlds ? 1 : 0];
+        {reinterpret_cast<const void *>(k_sweep_waves<4, false>), reinterpret_cast<const void *>(k_sweep_waves<4, true>)},
+        {reinterpret_cast<const void *>(k_sweep_waves_long<8, false>), reinterpret_cast<const void *>(k_sweep_waves_long<8, true>)},
+        {reinterpret_cast<const void *>(k_sweep_waves_long<16, false>), reinterpret_cast<const void *>(k_sweep_waves_long<16, true>)}};
+    return table[wave_fields_row(R)][variant ? 1 : 0];
 }
 
 // The dense matrix of the wave kernels, once per context (the couplings of a context never change).  Built on the stream of the
@@ -1343,35 +1348,16 @@ int ensure_wave_matrix(nlmc_ctx *c, size_t stride)
     return NLMC_OK;
 }
 
-const void *waves_long_kernel(int R, bool ahead)
-{
-    static const void *const table[2][2] = {
-        {reinterpret_cast<const void *>(k_sweep_waves_long<8, false>), reinterpret_cast<const void *>(k_sweep_waves_long<8, true>)},
-        {reinterpret_cast<const void *>(k_sweep_waves_long<16, false>), reinterpret_cast<const void *>(k_sweep_waves_long<16, true>)}};
-    return table[R == 8 ? 0 : 1][ahead ? 1 : 0];
-}
-
-// k_sweep_waves_long: chains of more than NLMC_WAVE_N spins, in the shape nlmc_wave_long_shape picks
-int waves_long_sweeps(nlmc_ctx *c, ShortRoute &r)
-{
-    const NlmcWaveLongShape S = nlmc_wave_long_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves);
-    if (S.R == 0) return fail(c, NLMC_ERR_STATE, "waves_sweeps: the chain does not fit the wave kernels");
-    r.kfun = waves_long_kernel(S.R, c->knobs.wave_long_ahead);
-    r.lds = S.lds; r.grid = dim3((unsigned)S.blocks); r.block = dim3((unsigned)(64 * S.W));
-    { int rc = ensure_lds(c, r.kfun, r.lds); if (rc) return rc; }
-    { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
-    r.wave_J = c->wave_J.p;
-    return NLMC_OK;
-}
-
-// k_sweep_waves: a chain per wave, in the shape nlmc_wave_shape picks for the device, over the dense matrix
+// A chain per wave over the dense matrix, in the shape csrc/nlmc_wave_shape.h picks for the device: k_sweep_waves (nlmc_wave_shape), or
+// k_sweep_waves_long for chains of more than NLMC_WAVE_N spins (nlmc_wave_long_shape)
 int waves_sweeps(nlmc_ctx *c, const SweepCall &, ShortRoute &r)
 {
     { int rc = cu_count(c); if (rc) return rc; }
-    if (c->n > NLMC_WAVE_N) return waves_long_sweeps(c, r);
-    const NlmcWaveShape S = nlmc_wave_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves, c->knobs.wave_jlds ? 1 : 0);
+    const bool longs = c->n > NLMC_WAVE_N;
+    const NlmcWaveShape S = longs ? nlmc_wave_long_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves)
+                                  : nlmc_wave_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves, c->knobs.wave_jlds ? 1 : 0);
     if (S.R == 0) return fail(c, NLMC_ERR_STATE, "waves_sweeps: the chain does not fit the wave kernels");
-    r.kfun = waves_kernel(S.R, S.jlds != 0);
+    r.kfun = waves_kernel(S.R, longs ? c->knobs.wave_long_ahead : S.jlds != 0);
     r.lds = S.lds; r.grid = dim3((unsigned)S.blocks); r.block = dim3((unsigned)(64 * S.W));
     { int rc = ensure_lds(c, r.kfun, r.lds); if (rc) return rc; }
     { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
@@ -2887,25 +2873,37 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
 // The routes that run whole rounds of short chains in one launch: k_rounds_lanes, k_rounds_waves, k_rounds_waves_long, k_apt_rounds_lanes.
 enum class ShortRounds { lanes, waves, waves_long, apt_lanes };
 
+// The reach of a route's kernels: the chain lengths they take, whether they have the fixed-point arithmetic only, and what a chain or
+// a ladder beyond them is told (a ladder lives inside one wave, or inside one workgroup's swap wave).  Rows in the order of ShortRounds.
+struct ShortReach { int n_min, n_max; bool f32_only; const char *why_n, *why_ladder; };
+ShortReach short_reach(ShortRounds route)
+{
+    static const char *const lane_n = "the chain-per-lane kernels take chains of at most NLMC_LANE_N spins";
+    static const char *const in_wave = "a ladder of more than 64 temperatures does not fit a wave";
+    static const char *const in_swap_wave = "a ladder of more than 64 temperatures does not fit a workgroup's swap wave";
+    static const ShortReach reach[] = {
+        {0, NLMC_LANE_N, false, lane_n, in_wave},
+        {0, NLMC_WAVE_N, true, "the wave-per-chain kernels take chains of at most NLMC_WAVE_N spins", in_swap_wave},
+        {NLMC_WAVE_N + 1, NLMC_WAVE_LONG_N, true,
+         "the long wave-per-chain kernels take chains of more than NLMC_WAVE_N and at most NLMC_WAVE_LONG_N spins", in_swap_wave},
+        {0, NLMC_LANE_N, false, lane_n, in_wave}};
+    return reach[(int)route];
+}
+
 // Why this context cannot run rounds [round0, round0 + n_rounds) on `route`, or nullptr: the checks of rounds_check that do not concern
-// fused plans, the reach of the route's kernels (lanes: n <= NLMC_LANE_N; waves: fixed point, n <= NLMC_WAVE_N; waves_long: fixed point,
-// NLMC_WAVE_N < n <= NLMC_WAVE_LONG_N, one ladder's regions inside a workgroup's LDS) and a ladder inside one wave (waves, waves_long:
-// one workgroup's swap wave).  The APT rounds have their Houdayer step: n_pairs = 0, a round without swaps, is taken.
-// Arguments are checked by the callers.
+// fused plans, the reach of the route's kernels (short_reach; waves_long: also one ladder's regions inside a workgroup's LDS).  The APT
+// rounds have their Houdayer step: n_pairs = 0, a round without swaps, is taken.  Arguments are checked by the callers.
 const char *short_rounds_refusal(const nlmc_ctx *c, ShortRounds route, int precision, int n_rounds, int T, uint32_t round0, uint64_t seed, int n_pairs)
 {
-    const bool waves = route == ShortRounds::waves, longs = route == ShortRounds::waves_long;
+    const ShortReach reach = short_reach(route);
     if (const char *why = rounds_context_refusal(c, true)) return why;
     if (n_pairs < 1 && route != ShortRounds::apt_lanes) return "no swap pairs";
-    if ((waves || longs) && precision != NLMC_F32) return "the wave-per-chain kernels have the fixed-point arithmetic (NLMC_F32) only";
-    if (longs && (c->knobs.force_big || c->n <= NLMC_WAVE_N || c->n > NLMC_WAVE_LONG_N))
-        return "the long wave-per-chain kernels take chains of more than NLMC_WAVE_N and at most NLMC_WAVE_LONG_N spins";
-    if (!longs && (c->knobs.force_big || c->n > (waves ? NLMC_WAVE_N : NLMC_LANE_N)))
-        return waves ? "the wave-per-chain kernels take chains of at most NLMC_WAVE_N spins" : "the chain-per-lane kernels take chains of at most NLMC_LANE_N spins";
-    if (c->ladder_len > 64)
-        return waves || longs ? "a ladder of more than 64 temperatures does not fit a workgroup's swap wave" : "a ladder of more than 64 temperatures does not fit a wave";
+    if (reach.f32_only && precision != NLMC_F32) return "the wave-per-chain kernels have the fixed-point arithmetic (NLMC_F32) only";
+    if (c->knobs.force_big || c->n < reach.n_min || c->n > reach.n_max) return reach.why_n;
+    if (c->ladder_len > 64) return reach.why_ladder;
     // (whether ONE ladder fits a workgroup depends neither on the device nor on the number of ladders)
-    if (longs && nlmc_wave_long_rounds_shape(c->n, c->n_pad, c->ladder_len, 1, 1, 0).R == 0) return "the ladders of a workgroup do not fit its LDS";
+    if (route == ShortRounds::waves_long && nlmc_wave_long_rounds_shape(c->n, c->n_pad, c->ladder_len, 1, 1, 0).R == 0)
+        return "the ladders of a workgroup do not fit its LDS";
     if (n_pairs >= 1 && !c->pt_plan.covers(round0, n_rounds, n_pairs, seed)) return "the pair selections of these rounds are not planned (nlmc_pt_plan)";
     if ((size_t)T * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
         return "the visiting orders of one round exceed the order scratch (NLMC_LANE_SCRATCH)";
@@ -2992,61 +2990,37 @@ int rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int T, uint32_t sweep
     return NLMC_OK;
 }
 
-// ---- tempering rounds inside a wave launch: a ladder per workgroup (k_rounds_waves, csrc/nlmc_wave_rounds.h) -------------------------
+// ---- tempering rounds inside a wave launch: a ladder per workgroup (k_rounds_waves, csrc/nlmc_wave_rounds.h; k_rounds_waves_long for
+// chains of more than NLMC_WAVE_N spins, csrc/nlmc_wave_long_rounds.h) ----------------------------------------------------------------
+// k_rounds_waves<R, jlds, observed> for R <= 4; k_rounds_waves_long<R, observed> beyond, which never stages the matrix
 const void *rounds_waves_kernel(int R, bool jlds, bool observed)
 {
 #define NLMC_RW(R_) {{reinterpret_cast<const void *>(k_rounds_waves<R_, false, false>), reinterpret_cast<const void *>(k_rounds_waves<R_, false, true>)}, \
                      {reinterpret_cast<const void *>(k_rounds_waves<R_, true, false>), reinterpret_cast<const void *>(k_rounds_waves<R_, true, true>)}}
-    static const void *const table[3][2][2] = {NLMC_RW(1), NLMC_RW(2), NLMC_RW(4)};
+#define NLMC_RWL(R_) {{reinterpret_cast<const void *>(k_rounds_waves_long<R_, false>), reinterpret_cast<const void *>(k_rounds_waves_long<R_, true>)}, \
+                      {nullptr, nullptr}}
+    static const void *const table[5][2][2] = {NLMC_RW(1), NLMC_RW(2), NLMC_RW(4), NLMC_RWL(8), NLMC_RWL(16)};
 #undef NLMC_RW
-    return table[R == 1 ? 0 : R == 2 ? 1 : 2][jlds ? 1 : 0][observed ? 1 : 0];
+#undef NLMC_RWL
+    return table[wave_fields_row(R)][jlds ? 1 : 0][observed ? 1 : 0];
 }
 
-// n_rounds rounds in launches of k_rounds_waves.  short_rounds_refusal said nullptr.
-int rounds_waves(nlmc_ctx *c, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
+// n_rounds rounds in launches of k_rounds_waves (route waves) or k_rounds_waves_long (route waves_long).  short_rounds_refusal said nullptr.
+int rounds_waves(nlmc_ctx *c, ShortRounds route, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
 {
     const int L = c->ladder_len, ladders = c->n_chains / L;
+    const bool longs = route == ShortRounds::waves_long;
     { int rc = cu_count(c); if (rc) return rc; }
-    const NlmcWaveRoundsShape S = nlmc_wave_rounds_shape(c->n, c->n_pad, L, ladders, c->n_cu, c->knobs.wave_rounds_ladders, c->knobs.wave_jlds ? 1 : 0);
-    if (S.R == 0) return fail(c, NLMC_ERR_STATE, "rounds_waves: the chain or the ladder does not fit the wave kernels");
+    const NlmcWaveRoundsShape S =
+        longs ? nlmc_wave_long_rounds_shape(c->n, c->n_pad, L, ladders, c->n_cu, c->knobs.wave_rounds_ladders)
+              : nlmc_wave_rounds_shape(c->n, c->n_pad, L, ladders, c->n_cu, c->knobs.wave_rounds_ladders, c->knobs.wave_jlds ? 1 : 0);
+    if (S.R == 0)
+        return fail(c, NLMC_ERR_STATE, longs ? "rounds_waves_long: the chain or the ladder does not fit the wave kernels"
+                                             : "rounds_waves: the chain or the ladder does not fit the wave kernels");
     const void *kfun = rounds_waves_kernel(S.R, S.jlds != 0, c->observed());
     { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
     const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
-    WaveRoundsArgs w{};
-    w.P = S.P; w.C = S.C; w.x_off = (int)S.x_off; w.s_off = (int)S.s_off; w.e_off = (int)S.e_off; w.map_off = (int)S.map_off;
-    int rc = lane_rounds_chunks(c, kfun, S.lds, n_rounds, T, sweep0, round0, seed, NLMC_ROUTE_WAVES, [&](int, int k, uint32_t s0, uint32_t r0) -> int {
-        LaneLaunchArgs x = lane_launch_args(c, T, seed, s0, k, r0, n_pairs, (size_t)(c->n_chains_global / L), log, false, 0, S.map_off);
-        x.a.wave_J = c->wave_J.p;
-        void *kargs[] = {&x.a, &x.q, &w};
-        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)S.blocks), dim3((unsigned)(64 * S.W)), kargs, S.lds, c->stream));
-        return NLMC_OK;
-    });
-    if (rc) return rc;
-    c->rounds_route = NLMC_ROUNDS_WAVES;
-    return NLMC_OK;
-}
-
-// ---- tempering rounds of long chains inside a wave launch (k_rounds_waves_long, csrc/nlmc_wave_long_rounds.h) ------------------------
-const void *rounds_waves_long_kernel(int R, bool observed)
-{
-    static const void *const table[2][2] = {
-        {reinterpret_cast<const void *>(k_rounds_waves_long<8, false>), reinterpret_cast<const void *>(k_rounds_waves_long<8, true>)},
-        {reinterpret_cast<const void *>(k_rounds_waves_long<16, false>), reinterpret_cast<const void *>(k_rounds_waves_long<16, true>)}};
-    return table[R == 8 ? 0 : 1][observed ? 1 : 0];
-}
-
-// n_rounds rounds in launches of k_rounds_waves_long.  short_rounds_refusal said nullptr.
-int rounds_waves_long(nlmc_ctx *c, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
-{
-    const int L = c->ladder_len, ladders = c->n_chains / L;
-    { int rc = cu_count(c); if (rc) return rc; }
-    const NlmcWaveLongRoundsShape S = nlmc_wave_long_rounds_shape(c->n, c->n_pad, L, ladders, c->n_cu, c->knobs.wave_rounds_ladders);
-    if (S.R == 0) return fail(c, NLMC_ERR_STATE, "rounds_waves_long: the chain or the ladder does not fit the wave kernels");
-    const void *kfun = rounds_waves_long_kernel(S.R, c->observed());
-    { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
-    const bool log = c->pt_log.covers(round0, n_rounds, n_pairs);
-    WaveLongRoundsArgs w{};
-    w.P = S.P; w.C = S.C;
+    WaveRoundsArgs w{S.P, S.C};
     int rc = lane_rounds_chunks(c, kfun, S.lds, n_rounds, T, sweep0, round0, seed, NLMC_ROUTE_WAVES, [&](int, int k, uint32_t s0, uint32_t r0) -> int {
         LaneLaunchArgs x = lane_launch_args(c, T, seed, s0, k, r0, n_pairs, (size_t)(c->n_chains_global / L), log, false, 0, 0);
         x.a.wave_J = c->wave_J.p;
@@ -3055,7 +3029,7 @@ int rounds_waves_long(nlmc_ctx *c, int n_rounds, int T, uint32_t sweep0, uint32_
         return NLMC_OK;
     });
     if (rc) return rc;
-    c->rounds_route = NLMC_ROUNDS_WAVES_LONG;
+    c->rounds_route = longs ? NLMC_ROUNDS_WAVES_LONG : NLMC_ROUNDS_WAVES;
     return NLMC_OK;
 }
 
@@ -3063,9 +3037,8 @@ int rounds_waves_long(nlmc_ctx *c, int n_rounds, int T, uint32_t sweep0, uint32_
 int short_rounds(nlmc_ctx *c, ShortRounds route, int precision, int n_rounds, int T, uint32_t sweep0, uint32_t round0, uint64_t seed, int n_pairs)
 {
     HIP_TRY(c, hipSetDevice(c->device));
-    if (route == ShortRounds::waves_long) return rounds_waves_long(c, n_rounds, T, sweep0, round0, seed, n_pairs);
-    return route == ShortRounds::waves ? rounds_waves(c, n_rounds, T, sweep0, round0, seed, n_pairs)
-                                       : rounds_lanes(c, precision, n_rounds, T, sweep0, round0, seed, n_pairs);
+    return route == ShortRounds::lanes ? rounds_lanes(c, precision, n_rounds, T, sweep0, round0, seed, n_pairs)
+                                       : rounds_waves(c, route, n_rounds, T, sweep0, round0, seed, n_pairs);
 }
 
 // nlmc_pt_rounds_lanes / nlmc_pt_rounds_waves / nlmc_pt_rounds_waves_long (`fn`): n_rounds rounds in launches of the route's kernel, whatever the lane
@@ -3180,15 +3153,17 @@ int nlmc_pt_rounds_deferred(nlmc_ctx *c, int precision, int n_rounds, int sweeps
     // k_rounds_waves where the sweeps go to the wave kernels, then the rounds inside k_rounds_lanes where they go to the lane kernels
     if (rounds_deferred_quiet_ok(c, precision, n_rounds, sweeps_per_round, n_pairs)) {
         auto takes = [&](ShortRounds route) { return !short_rounds_refusal(c, route, precision, n_rounds, sweeps_per_round, round0, seed, n_pairs); };
-        if (c->wave_rounds && waves_route(c, c->n_chains, precision) && takes(ShortRounds::waves))
-            return short_rounds(c, ShortRounds::waves, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
-        // k_rounds_waves ends at NLMC_WAVE_N spins: longer chains on the wave route (nlmc_set_wave_long) run inside k_rounds_waves_long
-        // under nlmc_set_wave_long_rounds where it takes them, and otherwise a sweep call and a swap call per round, the sweeps in
-        // k_sweep_waves_long
-        if (c->wave_rounds && c->wave_long && c->wave_long_rounds && waves_route(c, c->n_chains, precision) && takes(ShortRounds::waves_long))
-            return short_rounds(c, ShortRounds::waves_long, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
-        if (c->wave_rounds && c->n > NLMC_WAVE_N && waves_route(c, c->n_chains, precision) && !rounds_context_refusal(c, true))
-            return rounds_waves_call_by_call(c, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+        if (c->wave_rounds && waves_route(c, c->n_chains, precision)) {
+            // k_rounds_waves ends at NLMC_WAVE_N spins: longer chains on the wave route (nlmc_set_wave_long) run inside
+            // k_rounds_waves_long under nlmc_set_wave_long_rounds where it takes them, and otherwise a sweep call and a swap call
+            // per round, the sweeps in k_sweep_waves_long
+            const bool longs = c->n > NLMC_WAVE_N;
+            const ShortRounds route = longs ? ShortRounds::waves_long : ShortRounds::waves;
+            if ((!longs || c->wave_long_rounds) && takes(route))
+                return short_rounds(c, route, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+            if (longs && !rounds_context_refusal(c, true))
+                return rounds_waves_call_by_call(c, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
+        }
         if (ROUNDS_LANES_IN_LAUNCH && lanes_route(c, c->n_chains) && takes(ShortRounds::lanes))
             return short_rounds(c, ShortRounds::lanes, precision, n_rounds, sweeps_per_round, sweep0, round0, seed, n_pairs);
     }

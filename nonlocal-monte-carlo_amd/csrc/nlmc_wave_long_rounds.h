@@ -1,6 +1,6 @@
 // nlmc_wave_long_rounds.h -- tempering rounds of dense chains of NLMC_WAVE_N < n <= NLMC_WAVE_LONG_N spins inside a wave launch
-// (gfx950 / wave64): the frame of k_rounds_waves (csrc/nlmc_wave_rounds.h) around the sweep body of k_sweep_waves_long
-// (csrc/nlmc_waves_long.h).
+// (gfx950 / wave64): the frame k_rounds_waves has too (csrc/nlmc_wave_frame.h, once for both) around the sweep body of
+// k_sweep_waves_long (csrc/nlmc_waves_long.h), written out here as that header says why.
 //
 // A swap is a label exchange and the spins never move, so the local fields X_j = hq_j + sum_i Jd[i][j] s_i stay valid across rounds.
 // k_rounds_waves_long builds them once per chain and launch -- n rows of 64 R ints from global memory, about what n / 2 flips cost --
@@ -17,21 +17,17 @@
 //            three broadcast LDS reads (no flag) and one compare; on a flip one matrix row from global memory, R adds with write-back, the spin
 //            written by one lane, wave_long_fence.
 //   swaps  : those of k_rounds_waves: lane 0 of every wave leaves its chains' energies in LDS; behind a barrier lane t of wave 0 decides
-//            pair t mod n_pairs of ladder t / n_pairs from the planned selection (pt_swap_decide) and exchanges map entries; behind a
+//            pair t mod n_pairs of ladder t / n_pairs from the planned selection (wave_swap_round) and exchanges map entries; behind a
 //            second barrier every wave reads its chains' slots again at its next turn.
 // Same bits as nlmc_sweep_philox(beta = NULL) + nlmc_pt_swap_philox round by round, on any route.  Fixed point ("f32") only.
 #pragma once
-#include "nlmc_lane_rounds.h"
+#include "nlmc_wave_frame.h"
 #include "nlmc_waves_long.h"
-
-struct WaveLongRoundsArgs {
-    int P, C;                        // ladders per workgroup, chains a wave runs in turn at most (waves: blockDim.x / 64)
-};
 
 // SweepArgs fields of this kernel: those of k_sweep_waves_long's shared order without flags and outputs; n_sweeps = sweeps per round,
 // sweep0 = the first sweep of the launch, lane_perm = the orders of all its n_rounds * n_sweeps sweeps, lane_rows = the context's chains,
 // tab = the ladder's table (two entries per slot), wave_J (row stride 64 R ints, columns past n zero).  LaneRoundsArgs: as in
-// k_rounds_waves (lds_map_off unused: the layout function says where the maps are).
+// k_rounds_waves (the layout function says where the maps are).
 // OBS: an observer is open -- a best-state record, an energy log or both (the records' pointers say which); one observation per chain
 // and round, after the sweeps and before the swap.  The three words of a chain's record stay in global memory, read and written by
 // lane 0 of the wave that owns the chain; an improved chain's spins go out from its LDS region.
@@ -40,7 +36,7 @@ struct WaveLongRoundsArgs {
 // return; no barrier stands inside a branch that depends on the wave or on a chain; the trip counts of the round loop (q.n_rounds) and
 // of the turn loops (w.C) are launch constants.  Nothing polls, nothing is atomic, nothing waits on another workgroup.
 template <int R, bool OBS>
-__global__ __launch_bounds__(1024) void k_rounds_waves_long(SweepArgs a, LaneRoundsArgs q, WaveLongRoundsArgs w)
+__global__ __launch_bounds__(1024) void k_rounds_waves_long(SweepArgs a, LaneRoundsArgs q, WaveRoundsArgs w)
 {
     static_assert(R == 8 || R == 16, "eight or sixteen registers");
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -49,10 +45,8 @@ __global__ __launch_bounds__(1024) void k_rounds_waves_long(SweepArgs a, LaneRou
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), W = (int)(blockDim.x >> 6);
     const int n = a.g.n, n_pad = a.g.n_pad;
     const int L = q.ladder_len, T = a.n_sweeps;
-    const int lad0 = (int)blockIdx.x * w.P;                        // first local ladder of this workgroup
-    const int nlad = max(0, min(w.P, a.lane_rows / L - lad0));     // its ladders
-    const int row0 = lad0 * L, nlive = nlad * L;                   // its first local chain, its chains
-    const int g0 = a.chain_base / L + lad0;                        // global ladder of its first: Philox key, rows of plan / log / chain_of_slot
+    const WaveGroup Gr = wave_group(a, q, w.P);
+    const int row0 = Gr.row0, nlive = Gr.nlive;
     const int32_t *Jg = a.wave_J;
 
     const NlmcWaveLongRoundsLayout G = nlmc_wave_long_rounds_layout(n, n_pad, w.P * L, W);
@@ -62,11 +56,7 @@ __global__ __launch_bounds__(1024) void k_rounds_waves_long(SweepArgs a, LaneRou
     auto fields_of = [&](int ch) { return reinterpret_cast<int32_t *>(lds_raw + (size_t)ch * (size_t)G.chain_bytes); };
     auto spins_of = [&](int ch) { return reinterpret_cast<int8_t *>(lds_raw + (size_t)ch * (size_t)G.chain_bytes + G.s_off); };
 
-    if ((int)threadIdx.x < nlive) {                                // (the slots of a ladder are a permutation: every entry is written)
-        const int ch = (int)threadIdx.x, slot = q.slot_of_chain[a.chain_base + row0 + ch];
-        soc_l[ch] = (uint8_t)slot;
-        cos_l[ch / L * L + slot] = (uint8_t)ch;
-    }
+    wave_maps_in(a, q, Gr, cos_l, soc_l);
 
     int X[R];
     auto load_row = [&](int (&d)[R], int k) {
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(1024) void k_rounds_waves_long(SweepArgs a, LaneRou
 #pragma unroll
                 for (int u = 0; u < R; ++u) X[u] = Xl[lane + 64 * u];
                 const int slot = __builtin_amdgcn_readfirstlane((int)soc_l[ch]);
-                const uint32_t gc = a.rng_stride ? (uint32_t)((c / a.rng_ladder_len) * a.rng_stride + a.rng_base + slot) : (uint32_t)(a.chain_base + c);
+                const uint32_t gc = wave_key(a, c, slot);
                 const float cb0 = wave_long_uniform(scale_cb((float)a.tab[(size_t)slot * a.tab_cs], a.qinv));
                 long long e_loc = 0;
                 for (int t = 0; t < T; ++t) {
@@ -166,49 +156,17 @@ __global__ __launch_bounds__(1024) void k_rounds_waves_long(SweepArgs a, LaneRou
                 const long long E = uniform64(el[ch]) + e_loc;
                 if (lane == 0) el[ch] = E;
 
-                if constexpr (OBS) {                            // one observation of the chain, before the swap round
-                    if (q.elog.energy && lane == 0) elog_store(q.elog, r, c, (double)E * inv, slot);
-                    if (has_best) {
-                        const int32_t stamp = (int32_t)(q.round0 + (uint32_t)r);
-                        long long rec_e = 0;
-                        int rec_hit = 0;
-                        if (lane == 0) { rec_e = q.best.efix[c]; rec_hit = q.best.first_hit[c]; }
-                        rec_e = uniform64(rec_e);
-                        rec_hit = __builtin_amdgcn_readfirstlane(rec_hit);
-                        const bool imp = (double)E < (double)rec_e;          // strict: the first attainment is kept
-                        if (lane == 0) {
-                            if (imp) { q.best.efix[c] = E; q.best.stamp[c] = stamp; }
-                            if (rec_hit < 0 && (double)E * inv <= q.best.target) q.best.first_hit[c] = stamp;
-                        }
-                        if (imp) {
-                            uint32_t *b4 = reinterpret_cast<uint32_t *>(q.best.state + (size_t)c * n_pad);
-                            for (int j4 = lane; j4 < n_pad / 4; j4 += 64) b4[j4] = reinterpret_cast<const uint32_t *>(sl)[j4];
-                        }
-                    }
+                if constexpr (OBS) {                            // one observation of the chain, before the swap round; its state from its region
+                    wave_observe(q, has_best, r, c, E, inv, slot, lane, [&]() __attribute__((always_inline)) {
+                        uint32_t *b4 = reinterpret_cast<uint32_t *>(q.best.state + (size_t)c * n_pad);
+                        for (int j4 = lane; j4 < n_pad / 4; j4 += 64) b4[j4] = reinterpret_cast<const uint32_t *>(sl)[j4];
+                    });
                 }
             }
         }
         __syncthreads();                                        // every chain's energy of this round is in LDS
 
-        // the swap round: lane t of wave 0 decides pair t mod n_pairs of ladder t / n_pairs (selected pairs are disjoint: no two
-        // lanes touch one map entry)
-        if (wv == 0 && lane < nlad * q.n_pairs) {
-            const int lw = lane / q.n_pairs, p = lane - lw * q.n_pairs, g = g0 + lw, base = lw * L;
-            const uint32_t round = q.round0 + (uint32_t)r;
-            const size_t at = ((size_t)r * q.n_ladders + g) * q.n_pairs + p;
-            const int i = q.plan_pairs[2 * at];
-            const int ca = (int)cos_l[base + i], cb = (int)cos_l[base + i + 1];
-            const double Ea = (double)el[ca] * inv, Eb = (double)el[cb] * inv;
-            const bool acc = pt_swap_decide(p, i, i, Ea, Eb, q.beta, round, g, a.seed_lo, a.seed_hi);
-            if (acc) {
-                cos_l[base + i] = (uint8_t)cb; cos_l[base + i + 1] = (uint8_t)ca;
-                soc_l[ca] = (uint8_t)(i + 1); soc_l[cb] = (uint8_t)i;
-            }
-            if (q.log_pairs) {
-                q.log_pairs[2 * at] = i; q.log_pairs[2 * at + 1] = i + 1;
-                q.log_acc[at] = acc ? 1 : 0;
-            }
-        }
+        if (wv == 0) wave_swap_round(a, q, Gr, r, lane, inv, el, cos_l, soc_l);   // lane t of wave 0 decides pair t mod n_pairs of ladder t / n_pairs
         __syncthreads();                                        // the maps of the next round
     }
 
@@ -220,14 +178,7 @@ __global__ __launch_bounds__(1024) void k_rounds_waves_long(SweepArgs a, LaneRou
             const int8_t *sl = spins_of(ch);
             uint32_t *s4 = reinterpret_cast<uint32_t *>(a.spins + (size_t)c * n_pad);
             for (int j4 = lane; j4 < n_pad / 4; j4 += 64) s4[j4] = reinterpret_cast<const uint32_t *>(sl)[j4];
-            if (lane == 0) {
-                const long long Ef = el[ch];
-                const int slot = (int)soc_l[ch];
-                a.efix[c] = Ef;
-                if (a.energy_sink) a.energy_sink[c] = (double)Ef * inv;
-                q.slot_of_chain[a.chain_base + c] = slot;
-                q.chain_of_slot[(size_t)(g0 + ch / L) * L + slot] = a.chain_base + c;
-            }
+            if (lane == 0) wave_chain_out(a, q, Gr, ch, inv, el, soc_l);
         }
     }
 }

@@ -12,22 +12,20 @@
 //            several runs them in turn within a round and parks s (int8) and X (int32) in LDS between its turns.
 //   swaps  : lane 0 of every wave leaves its chains' energies in an int64 array in LDS; behind a barrier lane t of wave 0 decides pair
 //            t mod n_pairs of ladder t / n_pairs of the workgroup from the planned selection, with the key and arithmetic of k_pt_swap
-//            (pt_swap_decide) and the log entry of lane_swap_round.  Chains never move: two byte maps in LDS, chain_of_slot[ladder][slot]
+//            (wave_swap_round) and the log entry of lane_swap_round.  Chains never move: two byte maps in LDS, chain_of_slot[ladder][slot]
 //            and slot_of_chain[chain], exchange entries; behind a second barrier a wave whose chain's slot moved reloads its inverse
 //            temperature (and its RNG key where that follows the slot).
+//   frame  : the workgroup's geometry, the maps, the key rule, the observer, the swap round and the epilogue stores are those of
+//            csrc/nlmc_wave_frame.h, shared with k_rounds_waves_long; the prologue and the sweeps are written out here (that header says why).
 // Same bits as nlmc_sweep_philox(beta = NULL) + nlmc_pt_swap_philox round by round, on any route.
 #pragma once
-#include "nlmc_lane_rounds.h"
+#include "nlmc_wave_frame.h"
 #include "nlmc_waves.h"
-
-struct WaveRoundsArgs {
-    int P, C;                        // ladders per workgroup, chains a wave runs in turn at most (waves: blockDim.x / 64)
-    int x_off, s_off, e_off, map_off;   // LDS offsets: parked X | parked s (both only where C > 1) | energies | chain_of_slot + slot_of_chain
-};
 
 // SweepArgs fields of this kernel: those of k_sweep_waves' shared order without flags and outputs; n_sweeps = sweeps per round, sweep0 =
 // the first sweep of the launch, lane_perm = the orders of all its n_rounds * n_sweeps sweeps, lane_rows = the context's chains, tab =
-// the ladder's table (two entries per slot), wave_J.  LaneRoundsArgs: as in k_rounds_lanes (lds_map_off unused).
+// the ladder's table (two entries per slot), wave_J.  LaneRoundsArgs: as in k_rounds_lanes, without lds_map_off: the LDS carve-up is
+// nlmc_wave_rounds_layout of (n, n_pad, P L, C, JLDS), the host's own.
 // OBS: an observer is open -- a best-state record, an energy log or both (the records' pointers say which); one observation per chain
 // and round, after the sweeps and before the swap.  The three words of a chain's record stay in global memory, read and written by
 // lane 0 of the wave that owns the chain.  Without OBS the kernel carries none of this.
@@ -44,27 +42,22 @@ __global__ __launch_bounds__(1024) void k_rounds_waves(SweepArgs a, LaneRoundsAr
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), W = (int)(blockDim.x >> 6);
     const int n = a.g.n, n_pad = a.g.n_pad;
     const int L = q.ladder_len, T = a.n_sweeps;
-    const int lad0 = (int)blockIdx.x * w.P;                        // first local ladder of this workgroup
-    const int nlad = max(0, min(w.P, a.lane_rows / L - lad0));     // its ladders
-    const int row0 = lad0 * L, nlive = nlad * L;                   // its first local chain, its chains
-    const int g0 = a.chain_base / L + lad0;                        // global ladder of its first: Philox key, rows of plan / log / chain_of_slot
+    const WaveGroup G = wave_group(a, q, w.P);
+    const int row0 = G.row0, nlive = G.nlive;
     const int32_t *Jg = a.wave_J;
     const int32_t *Jl = reinterpret_cast<const int32_t *>(lds_raw);
-    int32_t *Xp = reinterpret_cast<int32_t *>(lds_raw + w.x_off);
-    int8_t *sp = reinterpret_cast<int8_t *>(lds_raw + w.s_off);
-    long long *el = reinterpret_cast<long long *>(lds_raw + w.e_off);
-    uint8_t *cos_l = lds_raw + w.map_off, *soc_l = cos_l + w.P * L;   // chain_of_slot[ladder in workgroup][slot], slot_of_chain[chain in workgroup]
+    const NlmcWaveRoundsLayout Y = nlmc_wave_rounds_layout(n, n_pad, w.P * L, w.C, JLDS);
+    int32_t *Xp = reinterpret_cast<int32_t *>(lds_raw + Y.x_off);  // parked X | parked s (both only where C > 1) | energies | maps
+    int8_t *sp = reinterpret_cast<int8_t *>(lds_raw + Y.s_off);
+    long long *el = reinterpret_cast<long long *>(lds_raw + Y.e_off);
+    uint8_t *cos_l = lds_raw + Y.map_off, *soc_l = cos_l + w.P * L;   // chain_of_slot[ladder in workgroup][slot], slot_of_chain[chain in workgroup]
 
     if constexpr (JLDS) {
         int32_t *dst = reinterpret_cast<int32_t *>(lds_raw);
         for (int k = wv; k < n; k += W)
             for (int j = lane; j < n_pad; j += 64) dst[k * n_pad + j] = Jg[(size_t)k * JS + j];
     }
-    if ((int)threadIdx.x < nlive) {                                // (the slots of a ladder are a permutation: every entry is written)
-        const int ch = (int)threadIdx.x, slot = q.slot_of_chain[a.chain_base + row0 + ch];
-        soc_l[ch] = (uint8_t)slot;
-        cos_l[ch / L * L + slot] = (uint8_t)ch;
-    }
+    wave_maps_in(a, q, G, cos_l, soc_l);
     __syncthreads();
 
     // the chains this wave owns: wv, wv + W, .. below nlive (wave-uniform)
@@ -91,9 +84,6 @@ __global__ __launch_bounds__(1024) void k_rounds_waves(SweepArgs a, LaneRoundsAr
     auto unpark = [&](int ch) {
 #pragma unroll
         for (int r = 0; r < R; ++r) { X[r] = Xp[(ch * R + r) * 64 + lane]; s[r] = (int)sp[(ch * R + r) * 64 + lane]; }
-    };
-    auto key_of = [&](int c, int slot) {
-        return a.rng_stride ? (uint32_t)((c / a.rng_ladder_len) * a.rng_stride + a.rng_base + slot) : (uint32_t)(a.chain_base + c);
     };
 
     // prologue, once per chain and launch: spins in, X_j = hq_j + sum_i Jd[i][j] s_i row by row, the energy to LDS
@@ -126,7 +116,7 @@ __global__ __launch_bounds__(1024) void k_rounds_waves(SweepArgs a, LaneRoundsAr
     // what a wave with one chain keeps for the whole launch (a wave with several reloads it at every turn)
     const int ch1 = min(wv, max(nlive - 1, 0));
     int slot = __builtin_amdgcn_readfirstlane((int)soc_l[ch1]);
-    uint32_t gc = key_of(row0 + ch1, slot);
+    uint32_t gc = wave_key(a, row0 + ch1, slot);
     float cb0 = scale_cb((float)a.tab[(size_t)slot * a.tab_cs], a.qinv);
     long long E = nown ? uniform64(a.efix[row0 + ch1]) : 0;
     const double inv = __longlong_as_double((long long)(1023 - a.escale) << 52);   // 2^-escale
@@ -141,7 +131,7 @@ __global__ __launch_bounds__(1024) void k_rounds_waves(SweepArgs a, LaneRoundsAr
                 if (multi) {
                     unpark(ch);
                     slot = __builtin_amdgcn_readfirstlane((int)soc_l[ch]);
-                    gc = key_of(c, slot);
+                    gc = wave_key(a, c, slot);
                     cb0 = scale_cb((float)a.tab[(size_t)slot * a.tab_cs], a.qinv);
                     E = uniform64(el[ch]);
                 }
@@ -189,49 +179,17 @@ __global__ __launch_bounds__(1024) void k_rounds_waves(SweepArgs a, LaneRoundsAr
                 if (lane == 0) el[ch] = E;
                 if (multi) park(ch);
 
-                if constexpr (OBS) {                            // one observation of the chain, before the swap round
-                    if (q.elog.energy && lane == 0) elog_store(q.elog, r, c, (double)E * inv, slot);
-                    if (has_best) {
-                        const int32_t stamp = (int32_t)(q.round0 + (uint32_t)r);
-                        long long rec_e = 0;
-                        int rec_hit = 0;
-                        if (lane == 0) { rec_e = q.best.efix[c]; rec_hit = q.best.first_hit[c]; }
-                        rec_e = uniform64(rec_e);
-                        rec_hit = __builtin_amdgcn_readfirstlane(rec_hit);
-                        const bool imp = (double)E < (double)rec_e;          // strict: the first attainment is kept
-                        if (lane == 0) {
-                            if (imp) { q.best.efix[c] = E; q.best.stamp[c] = stamp; }
-                            if (rec_hit < 0 && (double)E * inv <= q.best.target) q.best.first_hit[c] = stamp;
-                        }
-                        if (imp) {
+                if constexpr (OBS) {                            // one observation of the chain, before the swap round; its state from registers
+                    wave_observe(q, has_best, r, c, E, inv, slot, lane, [&]() __attribute__((always_inline)) {
 #pragma unroll
-                            for (int u = 0; u < R; ++u) if (own[u]) q.best.state[(size_t)c * n_pad + lane + 64 * u] = (int8_t)s[u];
-                        }
-                    }
+                        for (int u = 0; u < R; ++u) if (own[u]) q.best.state[(size_t)c * n_pad + lane + 64 * u] = (int8_t)s[u];
+                    });
                 }
             }
         }
         __syncthreads();                                        // every chain's energy of this round is in LDS
 
-        // the swap round: lane t of wave 0 decides pair t mod n_pairs of ladder t / n_pairs (selected pairs are disjoint: no two
-        // lanes touch one map entry)
-        if (wv == 0 && lane < nlad * q.n_pairs) {
-            const int lw = lane / q.n_pairs, p = lane - lw * q.n_pairs, g = g0 + lw, base = lw * L;
-            const uint32_t round = q.round0 + (uint32_t)r;
-            const size_t at = ((size_t)r * q.n_ladders + g) * q.n_pairs + p;
-            const int i = q.plan_pairs[2 * at];
-            const int ca = (int)cos_l[base + i], cb = (int)cos_l[base + i + 1];
-            const double Ea = (double)el[ca] * inv, Eb = (double)el[cb] * inv;
-            const bool acc = pt_swap_decide(p, i, i, Ea, Eb, q.beta, round, g, a.seed_lo, a.seed_hi);
-            if (acc) {
-                cos_l[base + i] = (uint8_t)cb; cos_l[base + i + 1] = (uint8_t)ca;
-                soc_l[ca] = (uint8_t)(i + 1); soc_l[cb] = (uint8_t)i;
-            }
-            if (q.log_pairs) {
-                q.log_pairs[2 * at] = i; q.log_pairs[2 * at + 1] = i + 1;
-                q.log_acc[at] = acc ? 1 : 0;
-            }
-        }
+        if (wv == 0) wave_swap_round(a, q, G, r, lane, inv, el, cos_l, soc_l);   // lane t of wave 0 decides pair t mod n_pairs of ladder t / n_pairs
         __syncthreads();                                        // the maps of the next round
 
         if (!multi) {
@@ -239,7 +197,7 @@ __global__ __launch_bounds__(1024) void k_rounds_waves(SweepArgs a, LaneRoundsAr
             if (ns != slot) {
                 slot = ns;
                 cb0 = scale_cb((float)a.tab[(size_t)slot * a.tab_cs], a.qinv);
-                gc = key_of(row0 + ch1, slot);
+                gc = wave_key(a, row0 + ch1, slot);
             }
         }
     }
@@ -252,14 +210,7 @@ __global__ __launch_bounds__(1024) void k_rounds_waves(SweepArgs a, LaneRoundsAr
             if (multi) unpark(ch);
 #pragma unroll
             for (int r = 0; r < R; ++r) if (own[r]) a.spins[(size_t)c * n_pad + lane + 64 * r] = (int8_t)s[r];
-            if (lane == 0) {
-                const long long Ef = el[ch];
-                const int sl = (int)soc_l[ch];
-                a.efix[c] = Ef;
-                if (a.energy_sink) a.energy_sink[c] = (double)Ef * inv;
-                q.slot_of_chain[a.chain_base + c] = sl;
-                q.chain_of_slot[(size_t)(g0 + ch / L) * L + sl] = a.chain_base + c;
-            }
+            if (lane == 0) wave_chain_out(a, q, G, ch, inv, el, soc_l);
         }
     }
 }

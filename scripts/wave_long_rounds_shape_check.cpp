@@ -25,7 +25,7 @@ static size_t total_of(int n, int n_pad, int L, int P)
 static int check(int n, int L, int ladders, int n_cu, int knob)
 {
     const int n_pad = (n + 15) / 16 * 16;
-    const NlmcWaveLongRoundsShape s = nlmc_wave_long_rounds_shape(n, n_pad, L, ladders, n_cu, knob);
+    const NlmcWaveRoundsShape s = nlmc_wave_long_rounds_shape(n, n_pad, L, ladders, n_cu, knob);
     if (n < 257 || n > 1024 || L > 64) return s.R == 0 ? 0 : 1;
     const int R = n <= 512 ? 8 : 16;
     if (n_pad > 64 * R) return s.R == 0 ? 0 : 1;                       // (never with n_pad = n rounded up to 16; kept for the rule)
@@ -77,7 +77,7 @@ int main()
                 for (int knob : {0, 1, 3, 8, 99}) { bad += check(n, L, ladders, knob == 0 && ladders % 2 ? 4 : 256, knob); ++cases; }
     // the two fixed cases: sixteen chains of 1024 spins, a chain per wave, fit one workgroup; sixty-four do not (256 KB of fields)
     {
-        const NlmcWaveLongRoundsShape s = nlmc_wave_long_rounds_shape(1024, 1024, 16, 1, 256, 0);
+        const NlmcWaveRoundsShape s = nlmc_wave_long_rounds_shape(1024, 1024, 16, 1, 256, 0);
         bad += !(s.R == 16 && s.P == 1 && s.C == 1 && s.W == 16 && s.blocks == 1 && s.lds <= NLMC_WAVE_LONG_LDS_MAX); ++cases;
         bad += nlmc_wave_long_rounds_shape(1024, 1024, 64, 1, 256, 0).R != 0; ++cases;
         bad += nlmc_wave_long_rounds_shape(1024, 1024, 64, 7, 256, 3).R != 0; ++cases;

@@ -15,7 +15,7 @@ static const size_t LDS_MAX = (size_t)158 * 1024;
 
 static int check(int n, int n_pad, int rows, int n_cu, int knob)
 {
-    const NlmcWaveLongShape s = nlmc_wave_long_shape(n, n_pad, rows, n_cu, knob);
+    const NlmcWaveShape s = nlmc_wave_long_shape(n, n_pad, rows, n_cu, knob);
     const int R = n <= 512 ? 8 : 16;
     if (n <= 256 || n > 1024 || n_pad < n || n_pad > 64 * R) return s.R == 0 ? 0 : 1;
     int bad = 0;

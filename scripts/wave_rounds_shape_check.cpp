@@ -1,4 +1,4 @@
-// Host check of the launch shape of the tempering rounds inside a wave launch (csrc/nlmc_wave_shape.h: nlmc_wave_rounds_shape) over
+// Host check of the launch shape of the tempering rounds inside a wave launch (csrc/nlmc_wave_shape.h: nlmc_wave_rounds_shape, nlmc_wave_rounds_layout) over
 // every chain length 1 .. 257, ladder length 1 .. 65 and ladder counts 1 .. 40, with and without NLMC_WAVE_ROUNDS_LADDERS, with the
 // staging allowed and not: every chain of a workgroup is owned by exactly one wave, a workgroup holds at most 64 chains on at most 16
 // waves, the LDS regions are 16-byte aligned, do not overlap and lie inside the total, the total fits the dynamic LDS a workgroup may
@@ -36,15 +36,17 @@ static int check(int n, int L, int ladders, int n_cu, int knob, int allow_lds)
     for (int c = 0; c < Q; ++c) bad += owner[c] != 1;
     // regions: matrix | parked X | parked s | energies | maps
     const size_t mat = s.jlds ? (size_t)n * n_pad * 4 : 0, px = s.C > 1 ? (size_t)Q * s.stride * 4 : 0, ps = s.C > 1 ? (size_t)Q * s.stride : 0;
-    const size_t off[5] = {0, s.x_off, s.s_off, s.e_off, s.map_off}, len[5] = {mat, px, ps, (size_t)Q * 8, (size_t)2 * Q};
+    const NlmcWaveRoundsLayout g = nlmc_wave_rounds_layout(n, n_pad, Q, s.C, s.jlds);
+    bad += s.lds != g.total;
+    const size_t off[5] = {0, g.x_off, g.s_off, g.e_off, g.map_off}, len[5] = {mat, px, ps, (size_t)Q * 8, (size_t)2 * Q};
     for (int i = 0; i < 5; ++i) {
         bad += off[i] % 16 != 0 || off[i] + len[i] > s.lds;
         if (i + 1 < 5) bad += off[i] + len[i] > off[i + 1];
     }
-    bad += s.lds > NLMC_WAVE_ROUNDS_LDS_MAX;
-    const size_t rest = s.lds - s.x_off;
+    bad += s.lds > NLMC_WAVE_LONG_LDS_MAX;
+    const size_t rest = s.lds - g.x_off;
     const size_t mat16 = ((size_t)n * n_pad * 4 + 15) & ~(size_t)15;
-    bad += s.jlds != ((allow_lds && n <= NLMC_WAVE_JLDS_N && mat16 + rest <= NLMC_WAVE_ROUNDS_LDS_MAX) ? 1 : 0);
+    bad += s.jlds != ((allow_lds && n <= NLMC_WAVE_JLDS_N && mat16 + rest <= NLMC_WAVE_LONG_LDS_MAX) ? 1 : 0);
     if (bad) std::printf("n = %d, L = %d, ladders = %d, n_cu = %d, knob = %d, lds = %d: R = %d, P = %d, C = %d, W = %d, blocks = %d, jlds = %d, total = %zu\n",
                          n, L, ladders, n_cu, knob, allow_lds, s.R, s.P, s.C, s.W, s.blocks, s.jlds, s.lds);
     return bad ? 1 : 0;
