@@ -15,6 +15,7 @@
 #include "nlmc_waves_long.h"
 #include "nlmc_wave_rounds.h"
 #include "nlmc_wave_long_rounds.h"
+#include "nlmc_wave_nmc.h"
 #include "nlmc_wave_shape.h"
 #include "nlmc_host.h"
 
@@ -101,6 +102,7 @@ struct Knobs {
     int lane_rng = -1;               // NLMC_LANE_RNG: chain-per-lane sweeps make the Philox call per update (0) / keep a table per sweep in LDS
                                      // where it fits (1); -1: the default
     bool no_lane_nmc = false;        // NLMC_NO_LANE_NMC: nlmc_nmc_phases_lanes refuses (test knob)
+    bool no_wave_nmc = false;        // NLMC_NO_WAVE_NMC: nlmc_nmc_phases_waves refuses (test knob)
     int wave_waves = 0;              // NLMC_WAVE_WAVES: waves (chains) per workgroup of the wave-per-chain sweeps (1..16; 0: by row count)
     bool wave_jlds = true;           // NLMC_WAVE_JLDS=0: the wave-per-chain sweeps read the matrix rows from global memory at every n
     bool wave_long_ahead = NLMC_WAVE_LONG_AHEAD_DEFAULT;   // NLMC_WAVE_LONG_AHEAD: k_sweep_waves_long requests the next visited spin's row at every update (1) or a row on a flip only (0)
@@ -129,6 +131,7 @@ Knobs read_knobs()
     if (const char *s = getenv("NLMC_LANE_SCRATCH")) k.lane_scratch = std::max<size_t>(1, (size_t)strtoull(s, nullptr, 0));
     k.lane_rng = on("NLMC_LANE_RNG") ? (num("NLMC_LANE_RNG", 0) != 0) : -1;
     k.no_lane_nmc = num("NLMC_NO_LANE_NMC", 0) != 0;
+    k.no_wave_nmc = num("NLMC_NO_WAVE_NMC", 0) != 0;
     k.wave_waves = std::min(16, std::max(0, num("NLMC_WAVE_WAVES", 0)));
     k.wave_jlds = num("NLMC_WAVE_JLDS", 1) != 0;
     k.wave_long_ahead = num("NLMC_WAVE_LONG_AHEAD", NLMC_WAVE_LONG_AHEAD_DEFAULT) != 0;
@@ -3586,11 +3589,68 @@ const char *nlmc_nmc_phases_lanes_refusal(const nlmc_ctx *c, int sweeps_per_phas
     return lane_nmc_refusal(c, std::max(1, sweeps_per_phase));
 }
 
-int nlmc_nmc_phases_lanes(nlmc_ctx *c, int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0, uint64_t seed,
+// ---- ... and a chain per wave (k_nmc_phases_waves, csrc/nlmc_wave_nmc.h) ------------------------------------------------------------
+// Why this context cannot run NMC phases of S sweeps inside k_nmc_phases_waves, or nullptr.  nlmc_set_wave_sweeps is not looked at: the
+// entry point is reached by name.  Chains of more than NLMC_WAVE_N spins are refused under nlmc_set_wave_long too (a second copy of the
+// fields in LDS would halve the chains per workgroup): they keep the phase loop.
+static const char *wave_nmc_refusal(const nlmc_ctx *c, int S, int precision)
+{
+    if (c->knobs.no_wave_nmc) return "switched off (NLMC_NO_WAVE_NMC)";
+    if (c->knobs.force_big || c->big || c->n > NLMC_WAVE_N) return "the wave-per-chain phase kernel takes chains of at most NLMC_WAVE_N spins";
+    if (precision != NLMC_F32) return "the wave-per-chain kernels keep exact fixed-point fields: f32 only";
+    if (c->rng_stride != 0) return "random numbers keyed by temperature slot (nlmc_apt_shard) keep the phase-by-phase route";
+    if ((size_t)S * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
+        return "the visiting orders of one phase exceed the order scratch (NLMC_LANE_SCRATCH)";
+    return nullptr;
+}
+
+const char *nlmc_nmc_phases_waves_refusal(const nlmc_ctx *c, int sweeps_per_phase)
+{
+    if (!c) return "no context";
+    return wave_nmc_refusal(c, std::max(1, sweeps_per_phase), NLMC_F32);
+}
+
+// What a route supplies to nmc_phases_run: its kernel with dynamic LDS, grid and block (LDS limit raised, whatever the kernel reads once
+// per context in place), the SweepArgs / LaneNmcArgs fields of its own -- lanes: the LDS carve-up (lane_nmc_lds); waves: the dense
+// matrix -- and the NLMC_ROUTE_* it reports.
+struct NmcRoute { const void *kfun; size_t lds; dim3 grid, block; bool tab; size_t u_off, mask_off, best_off; const int32_t *wave_J; int route; };
+
+// k_nmc_phases_lanes: a chain per lane, 64 to a workgroup of one wave
+static int lanes_nmc(nlmc_ctx *c, int precision, NmcRoute &r)
+{
+    const LaneNmcLds L = lane_nmc_lds(c);
+    r.kfun = precision == NLMC_F64 ? reinterpret_cast<const void *>(k_nmc_phases_lanes<true>) : reinterpret_cast<const void *>(k_nmc_phases_lanes<false>);
+    r.lds = L.total; r.grid = dim3((unsigned)((c->sub_count() + 63) / 64)); r.block = dim3(64);
+    r.tab = L.tab; r.u_off = L.u_off; r.mask_off = L.mask_off; r.best_off = L.best_off;
+    r.route = NLMC_ROUTE_LANES;
+    return ensure_lds(c, r.kfun, r.lds);
+}
+
+// k_nmc_phases_waves<R, jlds>: a chain per wave in k_sweep_waves' shape (nlmc_wave_shape)
+static int waves_nmc(nlmc_ctx *c, int, NmcRoute &r)
+{
+    static const void *const table[3][2] = {
+        {reinterpret_cast<const void *>(k_nmc_phases_waves<1, false>), reinterpret_cast<const void *>(k_nmc_phases_waves<1, true>)},
+        {reinterpret_cast<const void *>(k_nmc_phases_waves<2, false>), reinterpret_cast<const void *>(k_nmc_phases_waves<2, true>)},
+        {reinterpret_cast<const void *>(k_nmc_phases_waves<4, false>), reinterpret_cast<const void *>(k_nmc_phases_waves<4, true>)}};
+    { int rc = cu_count(c); if (rc) return rc; }
+    const NlmcWaveShape S = nlmc_wave_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves, c->knobs.wave_jlds ? 1 : 0);
+    if (S.R == 0 || S.R > 4 || c->n_pad > 64 * S.R) return fail(c, NLMC_ERR_STATE, "waves_nmc: the chain does not fit the wave kernels");
+    r.kfun = table[wave_fields_row(S.R)][S.jlds ? 1 : 0];
+    r.lds = S.lds; r.grid = dim3((unsigned)S.blocks); r.block = dim3((unsigned)(64 * S.W));
+    r.route = NLMC_ROUTE_WAVES;
+    { int rc = ensure_lds(c, r.kfun, r.lds); if (rc) return rc; }
+    { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
+    r.wave_J = c->wave_J.p;
+    return NLMC_OK;
+}
+
+// Both entry points: the checks (`why`: the route's refusal), launches of as many whole phases as the order scratch holds visiting orders
+// for (and the kernel arguments hold kinds for) -- k_lane_orders into nmc_perm, then the route's kernel -- and the optional read-backs.
+static int nmc_phases_run(nlmc_ctx *c, const std::string &name, const char *(*why)(const nlmc_ctx *, int, int), int (*route)(nlmc_ctx *, int, NmcRoute &),
+                          int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0, uint64_t seed,
                           double beta, double temp_x, int min_stride, int64_t *out_phase_min, int32_t *out_phase_argmin, int8_t *out_last_best)
 {
-    if (!c) return NLMC_ERR_ARG;
-    const std::string name = "nlmc_nmc_phases_lanes: ";
     const int P = n_phases, S = sweeps_per_phase;
     if ((precision != NLMC_F32 && precision != NLMC_F64) || !kinds || P < 1 || S < 1 || min_stride < 1 || (long long)P * S > (long long)(INT_MAX / 2))
         return fail(c, NLMC_ERR_ARG, name + "bad argument");
@@ -3599,15 +3659,13 @@ int nlmc_nmc_phases_lanes(nlmc_ctx *c, int precision, const int32_t *kinds, int 
     if (!(temp_x > 0.0) && !(temp_x < 0.0)) return fail(c, NLMC_ERR_ARG, name + "temp_x must be non-zero");
     if (!c->cmask.p) return fail(c, NLMC_ERR_STATE, name + "no backbone inference has run");
     if (c->track_min) return fail(c, NLMC_ERR_STATE, name + "a tracked minimum is open (nlmc_track_minimum): the call keeps its own");
-    if (const char *why = lane_nmc_refusal(c, S)) return fail(c, NLMC_ERR_UNSUPPORTED, name + why);
+    if (const char *w = why(c, S, precision)) return fail(c, NLMC_ERR_UNSUPPORTED, name + w);
     HIP_TRY(c, hipSetDevice(c->device));
     const int R = c->sub_count(), n = c->n;
     if (R == 0) return NLMC_OK;
     { int rc = ensure_subset(c); if (rc) return rc; }
-    const LaneNmcLds L = lane_nmc_lds(c);
-    const void *kfun = precision == NLMC_F64 ? reinterpret_cast<const void *>(k_nmc_phases_lanes<true>) : reinterpret_cast<const void *>(k_nmc_phases_lanes<false>);
-    { int rc = ensure_lds(c, kfun, L.total); if (rc) return rc; }
-    // launches of as many whole phases as the order scratch holds visiting orders for (and the kernel arguments hold kinds for)
+    NmcRoute r{};
+    { int rc = route(c, precision, r); if (rc) return rc; }
     const size_t bytes_per_phase = (size_t)S * (size_t)n * sizeof(uint16_t);
     const int K = (int)std::max<size_t>(1, std::min<size_t>({(size_t)P, c->knobs.lane_scratch / bytes_per_phase, (size_t)NLMC_NMC_PHASES_LAUNCH}));
     begin_sweep_call(c);
@@ -3629,23 +3687,24 @@ int nlmc_nmc_phases_lanes(nlmc_ctx *c, int precision, const int32_t *kinds, int 
         { int rc = launch_lane_orders(c, c->cur, (size_t)k * S, k * S, 0, s0, seed, c->nmc_perm.p); if (rc) return rc; }
         { int rc = span_mid(c, ts); if (rc) return rc; }
         SweepArgs a = sweep_args(c, s0, S, seed, nullptr, 0, 0, false);
-        lane_fields(c, a, R, L.tab, L.u_off);
+        lane_fields(c, a, R, r.tab, r.u_off);
         a.flags = nullptr; a.lane_perm = c->nmc_perm.p; a.min_stride = min_stride;
         a.emin = c->emin.p; a.best = c->best.p;
+        a.wave_J = r.wave_J;
         LaneNmcArgs q{};
         q.n_phases = k; q.phase0 = at; q.phases_total = P;
         for (int p = 0; p < k; ++p) q.kinds[p >> 4] |= (uint32_t)kinds[at + p] << (2 * (p & 15));
         q.cb0 = -2.0 * LOG2E * beta; q.cb1 = -2.0 * LOG2E * (beta / temp_x);
         q.mask = c->cmask.p;
         q.phase_min = want_min ? c->nmc_pmin.p : nullptr; q.phase_argmin = want_min ? c->nmc_pargmin.p : nullptr;
-        q.lds_mask_off = (int)L.mask_off; q.lds_best_off = (int)L.best_off;
+        q.lds_mask_off = (int)r.mask_off; q.lds_best_off = (int)r.best_off;
         void *kargs[] = {&a, &q};
-        HIP_TRY(c, hipLaunchKernel(kfun, dim3((unsigned)((R + 63) / 64)), dim3(64), kargs, L.total, c->cur));
+        HIP_TRY(c, hipLaunchKernel(r.kfun, r.grid, r.block, kargs, r.lds, c->cur));
         HIP_TRY(c, hipGetLastError());
         { int rc = span_end(c, ts); if (rc) return rc; }
         count_launches(c, k, c->ev_accumulate);
     }
-    c->last_route = NLMC_ROUTE_LANES;
+    c->last_route = r.route;
     if (!want_min && !out_last_best) return NLMC_OK;
 
     // the optional read-backs: rows of the subset (the best states live in per-chain rows: gathered through the chain list)
@@ -3665,6 +3724,22 @@ int nlmc_nmc_phases_lanes(nlmc_ctx *c, int precision, const int32_t *kinds, int 
         for (int i = 0; i < R; ++i)
             std::memcpy(out_last_best + (size_t)i * n, c->stage_out.data() + (size_t)(c->subset != 0 ? h_list[(size_t)i] : i) * c->n_pad, (size_t)n);
     return NLMC_OK;
+}
+
+int nlmc_nmc_phases_lanes(nlmc_ctx *c, int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0, uint64_t seed,
+                          double beta, double temp_x, int min_stride, int64_t *out_phase_min, int32_t *out_phase_argmin, int8_t *out_last_best)
+{
+    if (!c) return NLMC_ERR_ARG;
+    return nmc_phases_run(c, "nlmc_nmc_phases_lanes: ", [](const nlmc_ctx *x, int S, int) { return lane_nmc_refusal(x, S); }, lanes_nmc, precision, kinds,
+                          n_phases, sweeps_per_phase, sweep0, seed, beta, temp_x, min_stride, out_phase_min, out_phase_argmin, out_last_best);
+}
+
+int nlmc_nmc_phases_waves(nlmc_ctx *c, int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0, uint64_t seed,
+                          double beta, double temp_x, int min_stride, int64_t *out_phase_min, int32_t *out_phase_argmin, int8_t *out_last_best)
+{
+    if (!c) return NLMC_ERR_ARG;
+    return nmc_phases_run(c, "nlmc_nmc_phases_waves: ", wave_nmc_refusal, waves_nmc, precision, kinds,
+                          n_phases, sweeps_per_phase, sweep0, seed, beta, temp_x, min_stride, out_phase_min, out_phase_argmin, out_last_best);
 }
 
 // ------------------------------------------------------------------------------------------------------

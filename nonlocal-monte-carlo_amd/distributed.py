@@ -27,6 +27,10 @@ NMC_SWEEP_SPACE = 1 << 31
 # scripts/lane_nmc_throughput.py (profiles/lane_nmc_throughput.txt).
 LANE_NMC_IN_LAUNCH = True
 
+# The same for one k_nmc_phases_waves launch per context (Engine.nmc_phases_waves) where the engine's sweeps run one chain per wave
+# (wave_nmc=None).  Set from scripts/wave_nmc_throughput.py (profiles/wave_nmc_throughput.txt).
+WAVE_NMC_IN_LAUNCH = True
+
 
 def block_partition(n_global, world, rank):
     """Contiguous block of chains owned by `rank` (first `n_global % world` ranks get one extra)."""
@@ -280,7 +284,7 @@ class LocalTempering:
 
     def __init__(self, inst, beta_list, n_chains_global, seed, n_pairs, device_ids, precision="f32", engine_factory=None,
                  engines=None, parts=None, lane_sweeps="off", track_best=False, target_energy=None, track_energies=False,
-                 wave_sweeps="off", wave_rounds=False, lane_nmc=None, wave_long=False, wave_long_rounds=False):
+                 wave_sweeps="off", wave_rounds=False, lane_nmc=None, wave_long=False, wave_long_rounds=False, wave_nmc=None):
         """`parts` (optional): the blocks [(chain_base, count)] this process drives instead of an even cut over device_ids -- one
         rank's share under a launcher; `engines`: contexts that exist already (they must have had pt_init; not closed here... they
         ARE closed by close(): hand over ownership); `lane_sweeps`: Engine.set_lane_sweeps of every engine created here ("off",
@@ -302,7 +306,11 @@ class LocalTempering:
         `lane_nmc` (None: LANE_NMC_IN_LAUNCH where the engine's sweeps run one chain per lane, Engine.lanes_take; True, False): with NMC slots (configure_nmc), a round that wants no per-sweep output runs
         the marked chains' phases in one Engine.nmc_phases_lanes call per context instead of the phase loop -- same bits.  A context
         whose engine refuses (long chains, ...) keeps the phase loop and is not asked again.  Counters: lane_nmc_rounds (rounds in
-        which every context took the call), lane_nmc_calls (calls that ran)."""
+        which every context took the call), lane_nmc_calls (calls that ran).
+        `wave_nmc` (None: WAVE_NMC_IN_LAUNCH where the engine's sweeps run one chain per wave, Engine.waves_take; True, False): the same
+        through Engine.nmc_phases_waves, one k_nmc_phases_waves launch per context -- same bits.  Asked before `lane_nmc`, as the wave
+        route is asked before the lane route; a context whose engine refuses (chains of more than 256 spins, ...) goes on to the lane
+        rule and the phase loop and is not asked again.  Counters: wave_nmc_rounds, wave_nmc_calls."""
         hostlogic.check_wave_rounds(wave_rounds, wave_sweeps, needs="wave_sweeps 'auto' or 'force'")
         hostlogic.check_wave_long(wave_long, wave_sweeps, needs="wave_sweeps 'auto' or 'force'")
         hostlogic.check_wave_long_rounds(wave_long_rounds, wave_rounds, wave_long)
@@ -337,6 +345,11 @@ class LocalTempering:
         self._lane_nmc_refused = set()       # contexts (by index) whose engine turned nmc_phases_lanes down
         self._lane_nmc_asked = set()         # ... whose engine was asked (Engine.nmc_phases_lanes_refusal)
         self.lane_nmc_rounds = self.lane_nmc_calls = 0
+        self.wave_nmc = WAVE_NMC_IN_LAUNCH if wave_nmc is None else bool(wave_nmc)
+        self._wave_nmc_by_default = wave_nmc is None      # ... then only where the context's sweeps run on the wave kernels anyway
+        self._wave_nmc_refused = set()       # the same sets for nmc_phases_waves
+        self._wave_nmc_asked = set()
+        self.wave_nmc_rounds = self.wave_nmc_calls = 0
         self.track_best = bool(track_best)
         self.track_energies, self._elog_open = bool(track_energies), False
         if self.track_energies and not self.whole_ladders:
@@ -370,21 +383,32 @@ class LocalTempering:
         # M_skip > 1 (NPT/npt.py:434-437: M = M[:, ::M_skip] before the energies and the argmin): the phases' running minimum looks at
         # every M_skip-th sweep only (nlmc_track_minimum(M_skip)), their recorded traces are strided the same way
 
-    def _lane_nmc_takes(self, k):
-        """Whether context k's NMC phases go to Engine.nmc_phases_lanes: the option is on, and the engine has not refused (asked
-        once per context: a refusal is remembered)."""
-        if not (self.nmc and self.lane_nmc) or k in self._lane_nmc_refused:
+    def _nmc_takes(self, route, k):
+        """Whether context k's NMC phases go to Engine.nmc_phases_<route> ("waves", "lanes"): the option is on, and the engine has not
+        refused (asked once per context: a refusal is remembered).  An option left to its default applies only where the context's
+        sweeps take that route anyway (Engine.waves_take / lanes_take)."""
+        kind = route[:-1]
+        on, by_default = getattr(self, kind + "_nmc"), getattr(self, f"_{kind}_nmc_by_default")
+        refused, asked = getattr(self, f"_{kind}_nmc_refused"), getattr(self, f"_{kind}_nmc_asked")
+        if not (self.nmc and on) or k in refused:
             return False
-        if k in self._lane_nmc_asked:
+        if k in asked:
             return True
         e = self.engs[k]
-        self._lane_nmc_asked.add(k)
-        on_lanes = hasattr(e, "lanes_take") and e.lanes_take()
-        if not hasattr(e, "nmc_phases_lanes") or (self._lane_nmc_by_default and not on_lanes) or \
-                (hasattr(e, "nmc_phases_lanes_refusal") and e.nmc_phases_lanes_refusal(self.nmc["S"])):
-            self._lane_nmc_refused.add(k)
+        asked.add(k)
+        on_route = hasattr(e, route + "_take") and getattr(e, route + "_take")()
+        call = "nmc_phases_" + route
+        if not hasattr(e, call) or (by_default and not on_route) or \
+                (hasattr(e, call + "_refusal") and getattr(e, call + "_refusal")(self.nmc["S"])):
+            refused.add(k)
             return False
         return True
+
+    def _lane_nmc_takes(self, k):
+        return self._nmc_takes("lanes", k)
+
+    def _wave_nmc_takes(self, k):
+        return self._nmc_takes("waves", k)
 
     def sweeps_per_round(self, n_sweeps):
         """Plain sweep indices (RNG counters) one round of `n_sweeps` sweeps consumes.  The NMC phases of the marked slots draw from
@@ -398,9 +422,9 @@ class LocalTempering:
                                        pt_pairs=self.n_pairs, pt_round0=self.rounds_done, slot=0, fused_outputs=True) for e in self.engs]
         self._planner_round0 = self.rounds_done
         self._nmc_planners = None
-        if self.nmc and not all(self._lane_nmc_takes(k) for k in range(len(self.engs))):
-            # (where every context runs its phases inside nmc_phases_lanes launches there is nothing to plan for them: the rounds with
-            # outputs run their phases on the lane kernels, which need no level schedule)
+        if self.nmc and not all(self._wave_nmc_takes(k) or self._lane_nmc_takes(k) for k in range(len(self.engs))):
+            # (where every context runs its phases inside nmc_phases_waves / nmc_phases_lanes launches there is nothing to plan for
+            # them: the rounds with outputs run their phases on the wave or lane kernels, which need no level schedule)
             # the NMC phases draw from their own range of sweep indices, behind the plain sweeps of all planned rounds: both
             # ranges are contiguous over the rounds, so each is served by one fused-window plan (slots 0 and 1)
             n_ph = len(self.nmc["phases"])
@@ -439,7 +463,7 @@ class LocalTempering:
         "nmc_chains": ids, "plain_energy_columns": fp64 energies of the first `energy_columns` recorded columns}."""
         ii = self.rounds_done - (self._planner_round0 if self._planners else 0)
         outs = []
-        in_launch = 0
+        in_launch = {"waves": 0, "lanes": 0}
         wants = any(outputs.get(k) for k in ("record_stride", "want_energy", "want_min", "want_state"))
         for k, e in enumerate(self.engs):
             if self.nmc:
@@ -464,14 +488,16 @@ class LocalTempering:
                 rec["nmc_chains"] = e.subset()
             e.backbone_clusters(q["epsilon"], q["lambdas"], q["beta"], q["tol"], q["max_it"], q["sat"], q["thresholds"])
             took = False
-            if not wants and self._lane_nmc_takes(k):
-                try:                                 # all phases in one launch (same bits as the loop below)
-                    e.nmc_phases_lanes(q["phases"], q["S"], self.seed, NMC_SWEEP_SPACE + self.nmc_sweeps_done, q["beta"], q["temp_x"],
-                                       min_stride=q["M_skip"], precision=self.precision)
+            for route in ("waves", "lanes"):         # all phases in one launch (same bits as the loop below): the wave call asked first
+                if wants or took or not self._nmc_takes(route, k):
+                    continue
+                try:
+                    getattr(e, "nmc_phases_" + route)(q["phases"], q["S"], self.seed, NMC_SWEEP_SPACE + self.nmc_sweeps_done, q["beta"],
+                                                      q["temp_x"], min_stride=q["M_skip"], precision=self.precision)
                     took = True
-                    in_launch += 1
-                except NotImplementedError:          # nothing was run: the phase loop, now and from here on
-                    self._lane_nmc_refused.add(k)
+                    in_launch[route] += 1
+                except NotImplementedError:          # nothing was run: the next route or the phase loop, now and from here on
+                    getattr(self, f"_{route[:-1]}_nmc_refused").add(k)
             if took:
                 e.set_phase("ALL")
                 e.select("all")
@@ -497,8 +523,10 @@ class LocalTempering:
             self._observe(e, self.rounds_done)      # (all chains selected again, the NMC chains in the state they carry on; before the swap)
             outs.append(rec)
         self.sweeps_done += n_sweeps
-        self.lane_nmc_calls += in_launch
-        self.lane_nmc_rounds += 1 if (in_launch and in_launch == len(self.engs)) else 0
+        self.lane_nmc_calls += in_launch["lanes"]
+        self.lane_nmc_rounds += 1 if (in_launch["lanes"] and in_launch["lanes"] == len(self.engs)) else 0
+        self.wave_nmc_calls += in_launch["waves"]
+        self.wave_nmc_rounds += 1 if (in_launch["waves"] and in_launch["waves"] == len(self.engs)) else 0
         if self.nmc:
             self.nmc_sweeps_done += len(self.nmc["phases"]) * self.nmc["S"]
         if self.n_pairs > 0:

@@ -804,14 +804,18 @@ class Engine:
         with want_minima / want_last_best (read-backs: they synchronise the stream) a dict: phase_min [rows, P] float64 as
         energy_tracked reports and phase_argmin [rows, P] int32 (sweep within the phase), last_best [rows, n] int8.
         NotImplementedError when the context does not qualify (nothing was run; nmc_phases_lanes_refusal asks beforehand)."""
+        return self._nmc_phases(self._L.nlmc_nmc_phases_lanes, kinds, sweeps_per_phase, seed, sweep0, beta, temp_x, min_stride, precision,
+                                want_minima, want_last_best)
+
+    def _nmc_phases(self, call, kinds, sweeps_per_phase, seed, sweep0, beta, temp_x, min_stride, precision, want_minima, want_last_best):
+        """nmc_phases_lanes / nmc_phases_waves: the library call `call` and its read-backs."""
         k = _abi.as_c([self.PHASES[x] for x in kinds], np.int32)
         R, P = self.rows(), int(k.shape[0])
         pmin = np.empty((R, P), np.int64) if want_minima else None
         parg = np.empty((R, P), np.int32) if want_minima else None
         best = np.empty((R, self.n), np.int8) if want_last_best else None
-        self._ck(self._L.nlmc_nmc_phases_lanes(self._ctx, _precision(precision), _abi.ptr(k), P, int(sweeps_per_phase),
-                                               int(sweep0) & 0xFFFFFFFF, int(seed), float(beta), float(temp_x), int(min_stride),
-                                               _abi.ptr(pmin), _abi.ptr(parg), _abi.ptr(best)))
+        self._ck(call(self._ctx, _precision(precision), _abi.ptr(k), P, int(sweeps_per_phase), int(sweep0) & 0xFFFFFFFF, int(seed),
+                      float(beta), float(temp_x), int(min_stride), _abi.ptr(pmin), _abi.ptr(parg), _abi.ptr(best)))
         if not (want_minima or want_last_best):
             return None
         return {"phase_min": None if pmin is None else pmin.astype(np.float64) * 2.0 ** -self.energy_scale,
@@ -820,6 +824,22 @@ class Engine:
     def nmc_phases_lanes_refusal(self, sweeps_per_phase):
         """Why nmc_phases_lanes would refuse phases of `sweeps_per_phase` sweeps on this context (the library's reason), or None."""
         why = self._L.nlmc_nmc_phases_lanes_refusal(self._ctx, int(sweeps_per_phase))
+        return why.decode() if why else None
+
+    def nmc_phases_waves(self, kinds, sweeps_per_phase, seed, sweep0, beta, temp_x, min_stride=1, precision="f32",
+                         want_minima=False, want_last_best=False):
+        """nmc_phases_lanes' call inside k_nmc_phases_waves launches, a chain per wave in the wave sweeps' launch shape
+        (include/nlmc.h: nlmc_nmc_phases_waves): spins, mask, the exact local fields and the best state's fields stay in registers
+        across the phases, so the hand-off between two phases is a register copy.  Same arguments, same returns, same bits as the
+        call sequence on any route; reached by name (set_wave_sweeps is not looked at).  NotImplementedError when the context does not
+        qualify -- chains of more than 256 spins (with set_wave_long too), precision "f64", apt_shard contexts, ... -- and nothing
+        was run; nmc_phases_waves_refusal asks beforehand."""
+        return self._nmc_phases(self._L.nlmc_nmc_phases_waves, kinds, sweeps_per_phase, seed, sweep0, beta, temp_x, min_stride, precision,
+                                want_minima, want_last_best)
+
+    def nmc_phases_waves_refusal(self, sweeps_per_phase):
+        """Why nmc_phases_waves would refuse f32 phases of `sweeps_per_phase` sweeps on this context (the library's reason), or None."""
+        why = self._L.nlmc_nmc_phases_waves_refusal(self._ctx, int(sweeps_per_phase))
         return why.decode() if why else None
 
     # -- iso-cluster move -------------------------------------------------------------------------------

@@ -43,6 +43,12 @@ def check_wave_long(wave_long, waves, needs="waves='auto' or 'force'"):
         raise ValueError(f"wave_long needs {needs} (it widens the wave route to chains of up to 1024 spins)")
 
 
+def check_wave_nmc(wave_nmc, waves, needs="waves='auto' or 'force'"):
+    """wave_nmc given (True or False) without wave sweeps: ValueError.  `needs`: how the caller's keyword is spelled in the message."""
+    if wave_nmc is not None and waves == "off":
+        raise ValueError(f"wave_nmc needs {needs} (it says how the NMC phases run on the wave route)")
+
+
 def check_wave_long_rounds(wave_long_rounds, wave_rounds, wave_long):
     """wave_long_rounds without wave_rounds or without wave_long: ValueError."""
     if wave_long_rounds and not (wave_rounds and wave_long):
