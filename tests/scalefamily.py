@@ -10,7 +10,10 @@ The references are plain Python: int and fractions.Fraction, no floating point e
   quantise          Jq, hq = rint(J 2^qs), rint(h 2^qs) as Python ints
   exact_efix_f32    energy of the quantised model in units of 2^-escale, an int
   exact_energy      energy of the real (J, h), a Fraction
-No GPU, no test in here (test_scale_rule_cpu.py, test_gpu_magnitude.py)."""
+A second, separate group (DENSE, dense_member): complete graphs whose rows sit within 1 % of the int32 row-sum limit, for the
+short-chain routes that keep a whole chain's local fields resident; aligned_state puts one local field at that limit; the dense_*
+functions restate quantise, the scale rule and exact_efix_f32 in numpy int64 (exact at these sizes, and fast at 10^6 entries).
+No GPU, no test in here (test_scale_rule_cpu.py, test_gpu_magnitude.py, test_magnitude_short_cpu.py, test_gpu_magnitude_short.py)."""
 import functools
 import math
 from fractions import Fraction
@@ -82,6 +85,123 @@ def family():
     """(name, J, h, beta_unit) of every member at its own size."""
     for name in NAMES:
         yield (name,) + member(name)
+
+
+# ---- dense members: local fields at the int32 limit ---------------------------------------------------------------------------------
+# Complete graphs with near-uniform, non-dyadic weights: the int32 row-sum limit decides qs (or leaves its cap just standing) and the
+# common power of two drops nothing, so sum|Jq| + |hq| of EVERY row is within 1 % of 2^31.  A group of its own, not in NAMES / PINNED:
+# those parametrise GPU tests at n = 300 and are walked with Fraction arithmetic, too slow at 10^6 entries -- the dense members have
+# the numpy int64 restatements below (exact: |Jq| < 2^23, n <= 1024, so every sum stays far below 2^63).
+# name -> (n, with a field, (qs, escale) as oracle.field_scale returned them when the group was written, beta_unit)
+DENSE_SPEC = {
+    "flat513": (513, False, (22, 43), 0.05),         # the first n past k_sweep_waves_long's n <= 512 register compare
+    "flat1024": (1024, False, (21, 41), 0.05),
+    "flat256h": (256, True, (22, 43), 0.8 / 254),    # n <= 256: J alone cannot reach the row-sum limit, the field supplies the rest
+}
+DENSE = tuple(DENSE_SPEC)
+DENSE_PINNED = {k: v[2] for k, v in DENSE_SPEC.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def flat(n, with_h=False):
+    """(J csr, h) of the flat construction on n spins: the complete graph with J_ij = sign_ij (1 - 1e-3 ((i + j) % 5)), signs from
+    default_rng(3); h = 0 or 254 (+1, -1, ..)_k (1 - 1e-3 (k % 3)).  Treat the result as read-only."""
+    n = int(n)
+    i, j = np.triu_indices(n, 1)
+    U = np.zeros((n, n))
+    U[i, j] = np.random.default_rng(3).choice([-1, 1], size=len(i)) * (1.0 - 1e-3 * ((i + j) % 5))
+    J = sp.csr_matrix(U + U.T)
+    J.sort_indices()
+    k = np.arange(n)
+    h = 254.0 * np.where(k % 2 == 0, 1.0, -1.0) * (1.0 - 1e-3 * (k % 3)) if with_h else np.zeros(n)
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    h.setflags(write=False)
+    return J, h
+
+
+def dense_member(name):
+    """(J csr, h, beta_unit) of a dense member.  beta_unit: 0.05 without a field (the inverse temperature of a dense instance's
+    scale, fields of order sqrt(n)), 0.8 / 254 with one: test inputs at which the chains move (the tests assert that they do)."""
+    n, with_h, _, beta = DENSE_SPEC[name]
+    return flat(n, with_h) + (beta,)
+
+
+def aligned_state(J, h, k=0, opposed=False):
+    """The +-1 configuration in which the local field of spin k, h_k + sum_j J_kj s_j, is the whole row sum |h_k| + sum_j |J_kj| in
+    size: s_j = sign(J_kj) for j != k (+1 where there is no coupling), all reversed where h_k < 0; s_k = sign(h_k), +1 where h_k = 0.
+    There spin k sits in its field and stays.  opposed: s_k reversed -- the field is the same (it does not depend on s_k), the spin
+    stands against it and flips at its first visit at any temperature at which 2 beta |X_k| is large: an energy delta of
+    2 |X_k| 2^eshift with |X_k| at the limit."""
+    row = np.asarray(sp.csr_matrix(J)[k].todense()).reshape(-1)
+    hk = float(np.asarray(h).reshape(-1)[k])
+    sk = -1 if hk < 0 else 1
+    s = np.where(row < 0, -sk, sk).astype(np.int8)
+    s[k] = -sk if opposed else sk
+    return s
+
+
+def dense_quantise(J, h, qs):
+    """(Jq [n, n] int64, hq [n] int64) = rint(J 2^qs), rint(h 2^qs), ties to even: the scaling by a power of two is exact in fp64."""
+    Jd = np.asarray(sp.csr_matrix(J).todense(), dtype=np.float64)
+    return (np.rint(np.ldexp(Jd, qs)).astype(np.int64),
+            np.rint(np.ldexp(np.asarray(h, dtype=np.float64).reshape(-1), qs)).astype(np.int64))
+
+
+def dense_row_sums(J, h, qs):
+    """sum_j |Jq_kj| + |hq_k| of every row, int64."""
+    Jq, hq = dense_quantise(J, h, qs)
+    return np.abs(Jq).sum(axis=1) + np.abs(hq)
+
+
+def _abs_sum(x):
+    """sum|x| of fp64 values as a Fraction (exact: every distinct value once, times its count)."""
+    v, cnt = np.unique(np.abs(np.asarray(x, dtype=np.float64)).reshape(-1), return_counts=True)
+    return sum((Fraction(float(a)) * int(c) for a, c in zip(v, cnt)), Fraction(0))
+
+
+def dense_scale_rule(J, h):
+    """scale_rule in numpy int64 for matrices whose quantised rows stay inside int64 (the same statement, not the code's loops)."""
+    Jd = np.asarray(sp.csr_matrix(J).todense(), dtype=np.float64)
+    hv = np.asarray(h, dtype=np.float64).reshape(-1)
+    B = _abs_sum(Jd) / 2 + _abs_sum(hv)
+    ex = int(max(B, Fraction(1)).__floor__()).bit_length()
+    escale0 = max(0, min(52, 60 - ex))
+    maxj = float(np.max(np.abs(Jd))) if Jd.size else 0.0
+    ref = maxj if maxj > 0 else float(np.max(np.abs(hv), initial=0.0))
+    if ref == 0:
+        return 0, min(escale0, 29)
+    top = min(23 - math.frexp(ref)[1], escale0)
+
+    def fits(q):
+        if max(np.max(np.abs(np.ldexp(Jd, q))), np.max(np.abs(np.ldexp(hv, q)))) >= 2.0 ** 50:       # (far outside, and int64 stays exact)
+            return False
+        Jq, hq = dense_quantise(Jd, hv, q)
+        return bool(np.max(np.abs(Jq)) <= (1 << 23) - 1 and np.max(np.abs(Jq).sum(axis=1) + np.abs(hq)) <= (1 << 31) - 1)
+
+    lo, hi = top - 128, top
+    assert fits(lo)
+    if not fits(hi):
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+        hi = lo
+    qs = hi
+    Jq, hq = dense_quantise(Jd, hv, qs)
+    common = int(np.bitwise_or.reduce(np.abs(Jq).reshape(-1))) | int(np.bitwise_or.reduce(np.abs(hq)))
+    if common:
+        qs -= (common & -common).bit_length() - 1
+    return qs, min(escale0, qs + 29)
+
+
+def dense_exact_efix_f32(J, h, s, qs, escale):
+    """exact_efix_f32 in numpy int64 (|pair sum| <= n 2^31 < 2^42), returned as a Python int."""
+    Jq, hq = dense_quantise(J, h, qs)
+    np.fill_diagonal(Jq, 0)
+    s = np.asarray(s).reshape(-1).astype(np.int64)
+    pair = int(s @ (Jq @ s))
+    assert pair % 2 == 0, "J is not symmetric after quantisation"
+    assert escale >= qs
+    return -(pair // 2 + int(hq @ s)) * (1 << (escale - qs))
 
 
 # ---- exact references ------------------------------------------------------------------------------------------------------------

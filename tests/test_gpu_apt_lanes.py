@@ -211,6 +211,8 @@ CASES = {
     "no_swaps_K10_L4": lambda p, prec: dict(a=(*_wishart(p), 10, 4, 2, 5, prec), k=dict(pairs=0)),
     "shifted_delta_K6_L6": lambda p, prec: dict(a=(*sf.member("pmJ_2m10_h", 40)[:2], 6, 6, 2, 4, prec),
                                                 k=dict(exact=True, betas=sf.member("pmJ_2m10_h", 40)[2] * np.geomspace(0.4, 1.6, 6))),
+    "negative_scale_K6_L6": lambda p, prec: dict(a=(*sf.member("x1e9", 40)[:2], 6, 6, 2, 4, prec),
+                                                 k=dict(betas=sf.member("x1e9", 40)[2] * np.geomspace(0.4, 1.6, 6))),
 }
 PARAMS = [(name, prec) for name in CASES for prec in ("f32", "f64")]
 
@@ -227,8 +229,12 @@ def test_case(product, name, prec):
     """wishart10_K10_L4: one wave with tail lanes.  complete16_K10_L16: three waves, the last partly filled, with and without the
     Katzgraber flip.  chimera128: sparse, many components, the pick matters.  ring33: several label passes, n no multiple of 4.
     K = 3 leaves a ladder unpaired per slot, K = 1 has no Houdayer pair.  L = 64: ten waves of one ladder.  shifted_delta: couplings
-    of 2^-10 (scalefamily pmJ_2m10_h: qs 13, escale 42), the energy deltas are shifted by escale - qs = 29 bits."""
+    of 2^-10 (scalefamily pmJ_2m10_h: qs 13, escale 42), the energy deltas are shifted by escale - qs = 29 bits.  negative_scale:
+    Gaussian couplings of 1e9 (scalefamily x1e9: qs = -7), not exact, under energy_tolerance."""
     a = run_case(product, name, prec)
+    if name == "negative_scale_K6_L6":
+        csr = oracle.Csr(sf.member("x1e9", 40)[0])
+        assert oracle.field_scale(csr, sf.member("x1e9", 40)[1])[0] == -7
     if name == "shifted_delta_K6_L6":
         assert sf.PINNED["pmJ_2m10_h"][1] - sf.PINNED["pmJ_2m10_h"][0] > 0
     if name == "permuted_start_K10_L4":
