@@ -653,7 +653,7 @@ const char *nlmc_nmc_phases_lanes_refusal(const nlmc_ctx *ctx, int sweeps_per_ph
  * that continues a call builds them from the context's best state).  Same bits as the call sequence on any route.  Reached by name:
  * nlmc_set_wave_sweeps is not looked at; the dense matrix is built on demand as by the wave sweeps.
  * NLMC_ERR_UNSUPPORTED (nothing was run; nlmc_nmc_phases_waves_refusal asks without a call): n > NLMC_WAVE_N, under nlmc_set_wave_long
- * too (long chains keep the phase loop); the global-memory kernels (NLMC_FORCE_BIG); precision NLMC_F64; random numbers keyed by
+ * too (long chains have nlmc_nmc_phases_waves_long); the global-memory kernels (NLMC_FORCE_BIG); precision NLMC_F64; random numbers keyed by
  * temperature slot (nlmc_apt_shard); one phase's orders exceed the order scratch; NLMC_NO_WAVE_NMC=1 at nlmc_create (test knob).
  * Afterwards nlmc_last_sweep_route is NLMC_ROUTE_WAVES, nlmc_last_schedule_stats reports the visiting orders built and no levels, the
  * launch counters count a phase each. */
@@ -663,6 +663,24 @@ int nlmc_nmc_phases_waves(nlmc_ctx *ctx, int precision, const int32_t *kinds, in
 /* NULL when nlmc_nmc_phases_waves would take f32 phases of sweeps_per_phase sweeps on this context, else the reason of its
  * NLMC_ERR_UNSUPPORTED (a static string). */
 const char *nlmc_nmc_phases_waves_refusal(const nlmc_ctx *ctx, int sweeps_per_phase);
+/* The same call for dense chains of NLMC_WAVE_N + 1 .. NLMC_WAVE_LONG_N spins in launches of k_nmc_phases_waves_long
+ * (csrc/nlmc_wave_long_nmc.h), a chain per wave in k_sweep_waves_long's launch shape: signature, call sequence replaced, read-backs,
+ * launch cuts, order buffer, stream and error codes of nlmc_nmc_phases_lanes.  The exact int32 local fields stay in registers with a
+ * copy in the wave's LDS region, the best state's fields in registers, spins, flags, best spins and backbone mask in byte planes of the
+ * region (nlmc_wave_long_nmc_region): the fields are built once per launch, the argmin hand-off stays inside the wave, and nothing goes
+ * to global memory inside the phase loop but the phase minima.  Same bits as the call sequence on any route.  Reached by name: neither
+ * nlmc_set_wave_sweeps nor nlmc_set_wave_long is looked at; the dense matrix is built on demand as by the wave sweeps.
+ * NLMC_ERR_UNSUPPORTED (nothing was run; nlmc_nmc_phases_waves_long_refusal asks without a call): n <= NLMC_WAVE_N or n >
+ * NLMC_WAVE_LONG_N; the global-memory kernels (NLMC_FORCE_BIG); precision NLMC_F64; random numbers keyed by temperature slot
+ * (nlmc_apt_shard); one phase's orders exceed the order scratch; a padded chain longer than a matrix row; NLMC_NO_WAVE_LONG_NMC=1 at
+ * nlmc_create (test knob).  Afterwards nlmc_last_sweep_route is NLMC_ROUTE_WAVES, nlmc_last_schedule_stats reports the visiting orders
+ * built and no levels, the launch counters count a phase each. */
+int nlmc_nmc_phases_waves_long(nlmc_ctx *ctx, int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0,
+                               uint64_t seed, double beta, double temp_x, int min_stride, int64_t *out_phase_min,
+                               int32_t *out_phase_argmin, int8_t *out_last_best);
+/* NULL when nlmc_nmc_phases_waves_long would take f32 phases of sweeps_per_phase sweeps on this context, else the reason of its
+ * NLMC_ERR_UNSUPPORTED (a static string). */
+const char *nlmc_nmc_phases_waves_long_refusal(const nlmc_ctx *ctx, int sweeps_per_phase);
 /* Fused-window plans live in two slots; nlmc_plan_philox_fused / nlmc_plan_reserve_fused write to the selected one, sweep
  * calls use whichever slot covers their sweeps (a round sweeps its plain chains on windows of num_sweeps_MCMC_per_swap and
  * its NMC phases on windows of num_sweeps_per_NMC_phase_per_swap, NPT/npt.py:577-580). */

@@ -46,6 +46,7 @@ EXPORTS = [
     "nlmc_apt_rounds_lanes", "nlmc_apt_systems", "nlmc_pt_rounds_waves", "nlmc_set_wave_rounds", "nlmc_set_wave_long",
     "nlmc_pt_rounds_waves_long", "nlmc_set_wave_long_rounds",
     "nlmc_nmc_phases_lanes", "nlmc_nmc_phases_lanes_refusal", "nlmc_nmc_phases_waves", "nlmc_nmc_phases_waves_refusal",
+    "nlmc_nmc_phases_waves_long", "nlmc_nmc_phases_waves_long_refusal",
     "nlmc_best_begin", "nlmc_best_update", "nlmc_best_read", "nlmc_best_end",
     "nlmc_elog_begin", "nlmc_elog_update", "nlmc_elog_read", "nlmc_elog_end",
     "nlmc_plan_get_items", "nlmc_plan_get_order",
@@ -184,6 +185,7 @@ def lib():
                        ("nlmc_apt_rounds_lanes", [_vp, _i, _i, _i, _u32, _u32, _u64, _i, _i, _vp]), ("nlmc_apt_systems", [_vp, _i]),
                        ("nlmc_nmc_phases_lanes", [_vp, _i, _vp, _i, _i, _u32, _u64, _dbl, _dbl, _i, _vp, _vp, _vp]),
                        ("nlmc_nmc_phases_waves", [_vp, _i, _vp, _i, _i, _u32, _u64, _dbl, _dbl, _i, _vp, _vp, _vp]),
+                       ("nlmc_nmc_phases_waves_long", [_vp, _i, _vp, _i, _i, _u32, _u64, _dbl, _dbl, _i, _vp, _vp, _vp]),
                        ("nlmc_best_begin", [_vp, _dbl]), ("nlmc_best_update", [_vp, _u32]), ("nlmc_best_read", [_vp, _vp, _vp, _vp, _vp]),
                        ("nlmc_best_end", [_vp]),
                        ("nlmc_elog_begin", [_vp, _u32, _i]), ("nlmc_elog_update", [_vp, _u32]), ("nlmc_elog_read", [_vp, _vp, _vp]),
@@ -198,6 +200,8 @@ def lib():
     L.nlmc_nmc_phases_lanes_refusal.argtypes = [_vp, _i]
     L.nlmc_nmc_phases_waves_refusal.restype = ctypes.c_char_p
     L.nlmc_nmc_phases_waves_refusal.argtypes = [_vp, _i]
+    L.nlmc_nmc_phases_waves_long_refusal.restype = ctypes.c_char_p
+    L.nlmc_nmc_phases_waves_long_refusal.argtypes = [_vp, _i]
     _lib = L
     return L
 

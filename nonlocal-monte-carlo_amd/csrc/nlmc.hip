@@ -16,6 +16,7 @@
 #include "nlmc_wave_rounds.h"
 #include "nlmc_wave_long_rounds.h"
 #include "nlmc_wave_nmc.h"
+#include "nlmc_wave_long_nmc.h"
 #include "nlmc_wave_shape.h"
 #include "nlmc_host.h"
 
@@ -103,6 +104,7 @@ struct Knobs {
                                      // where it fits (1); -1: the default
     bool no_lane_nmc = false;        // NLMC_NO_LANE_NMC: nlmc_nmc_phases_lanes refuses (test knob)
     bool no_wave_nmc = false;        // NLMC_NO_WAVE_NMC: nlmc_nmc_phases_waves refuses (test knob)
+    bool no_wave_long_nmc = false;   // NLMC_NO_WAVE_LONG_NMC: nlmc_nmc_phases_waves_long refuses (test knob)
     int wave_waves = 0;              // NLMC_WAVE_WAVES: waves (chains) per workgroup of the wave-per-chain sweeps (1..16; 0: by row count)
     bool wave_jlds = true;           // NLMC_WAVE_JLDS=0: the wave-per-chain sweeps read the matrix rows from global memory at every n
     bool wave_long_ahead = NLMC_WAVE_LONG_AHEAD_DEFAULT;   // NLMC_WAVE_LONG_AHEAD: k_sweep_waves_long requests the next visited spin's row at every update (1) or a row on a flip only (0)
@@ -132,6 +134,7 @@ Knobs read_knobs()
     k.lane_rng = on("NLMC_LANE_RNG") ? (num("NLMC_LANE_RNG", 0) != 0) : -1;
     k.no_lane_nmc = num("NLMC_NO_LANE_NMC", 0) != 0;
     k.no_wave_nmc = num("NLMC_NO_WAVE_NMC", 0) != 0;
+    k.no_wave_long_nmc = num("NLMC_NO_WAVE_LONG_NMC", 0) != 0;
     k.wave_waves = std::min(16, std::max(0, num("NLMC_WAVE_WAVES", 0)));
     k.wave_jlds = num("NLMC_WAVE_JLDS", 1) != 0;
     k.wave_long_ahead = num("NLMC_WAVE_LONG_AHEAD", NLMC_WAVE_LONG_AHEAD_DEFAULT) != 0;
@@ -3591,8 +3594,8 @@ const char *nlmc_nmc_phases_lanes_refusal(const nlmc_ctx *c, int sweeps_per_phas
 
 // ---- ... and a chain per wave (k_nmc_phases_waves, csrc/nlmc_wave_nmc.h) ------------------------------------------------------------
 // Why this context cannot run NMC phases of S sweeps inside k_nmc_phases_waves, or nullptr.  nlmc_set_wave_sweeps is not looked at: the
-// entry point is reached by name.  Chains of more than NLMC_WAVE_N spins are refused under nlmc_set_wave_long too (a second copy of the
-// fields in LDS would halve the chains per workgroup): they keep the phase loop.
+// entry point is reached by name.  Chains of more than NLMC_WAVE_N spins are refused under nlmc_set_wave_long too: they have
+// nlmc_nmc_phases_waves_long.
 static const char *wave_nmc_refusal(const nlmc_ctx *c, int S, int precision)
 {
     if (c->knobs.no_wave_nmc) return "switched off (NLMC_NO_WAVE_NMC)";
@@ -3608,6 +3611,28 @@ const char *nlmc_nmc_phases_waves_refusal(const nlmc_ctx *c, int sweeps_per_phas
 {
     if (!c) return "no context";
     return wave_nmc_refusal(c, std::max(1, sweeps_per_phase), NLMC_F32);
+}
+
+// ---- ... and a chain of NLMC_WAVE_N < n <= NLMC_WAVE_LONG_N spins per wave (k_nmc_phases_waves_long, csrc/nlmc_wave_long_nmc.h) ---------
+// Why this context cannot run NMC phases of S sweeps inside k_nmc_phases_waves_long, or nullptr.  Neither nlmc_set_wave_sweeps nor
+// nlmc_set_wave_long is looked at: the entry point is reached by name.
+static const char *wave_long_nmc_refusal(const nlmc_ctx *c, int S, int precision)
+{
+    if (c->knobs.no_wave_long_nmc) return "switched off (NLMC_NO_WAVE_LONG_NMC)";
+    if (c->knobs.force_big || c->big || c->n <= NLMC_WAVE_N || c->n > NLMC_WAVE_LONG_N)
+        return "the long wave-per-chain phase kernel takes chains of NLMC_WAVE_N + 1 to NLMC_WAVE_LONG_N spins";
+    if (precision != NLMC_F32) return "the wave-per-chain kernels keep exact fixed-point fields: f32 only";
+    if (c->rng_stride != 0) return "random numbers keyed by temperature slot (nlmc_apt_shard) keep the phase-by-phase route";
+    if ((size_t)S * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
+        return "the visiting orders of one phase exceed the order scratch (NLMC_LANE_SCRATCH)";
+    if (nlmc_wave_long_nmc_shape(c->n, c->n_pad, 1, 1, 0).R == 0) return "the padded chain does not fit a row of the wave kernels' matrix";
+    return nullptr;
+}
+
+const char *nlmc_nmc_phases_waves_long_refusal(const nlmc_ctx *c, int sweeps_per_phase)
+{
+    if (!c) return "no context";
+    return wave_long_nmc_refusal(c, std::max(1, sweeps_per_phase), NLMC_F32);
 }
 
 // What a route supplies to nmc_phases_run: its kernel with dynamic LDS, grid and block (LDS limit raised, whatever the kernel reads once
@@ -3645,7 +3670,25 @@ static int waves_nmc(nlmc_ctx *c, int, NmcRoute &r)
     return NLMC_OK;
 }
 
-// Both entry points: the checks (`why`: the route's refusal), launches of as many whole phases as the order scratch holds visiting orders
+// k_nmc_phases_waves_long<R, ahead>: a chain per wave in k_sweep_waves_long's shape with the larger regions (nlmc_wave_long_nmc_shape)
+static int waves_long_nmc(nlmc_ctx *c, int, NmcRoute &r)
+{
+    static const void *const table[2][2] = {
+        {reinterpret_cast<const void *>(k_nmc_phases_waves_long<8, false>), reinterpret_cast<const void *>(k_nmc_phases_waves_long<8, true>)},
+        {reinterpret_cast<const void *>(k_nmc_phases_waves_long<16, false>), reinterpret_cast<const void *>(k_nmc_phases_waves_long<16, true>)}};
+    { int rc = cu_count(c); if (rc) return rc; }
+    const NlmcWaveShape S = nlmc_wave_long_nmc_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves);
+    if ((S.R != 8 && S.R != 16) || c->n_pad > 64 * S.R) return fail(c, NLMC_ERR_STATE, "waves_long_nmc: the chain does not fit the wave kernels");
+    r.kfun = table[S.R == 16 ? 1 : 0][c->knobs.wave_long_ahead ? 1 : 0];
+    r.lds = S.lds; r.grid = dim3((unsigned)S.blocks); r.block = dim3((unsigned)(64 * S.W));
+    r.route = NLMC_ROUTE_WAVES;
+    { int rc = ensure_lds(c, r.kfun, r.lds); if (rc) return rc; }
+    { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
+    r.wave_J = c->wave_J.p;
+    return NLMC_OK;
+}
+
+// All entry points: the checks (`why`: the route's refusal), launches of as many whole phases as the order scratch holds visiting orders
 // for (and the kernel arguments hold kinds for) -- k_lane_orders into nmc_perm, then the route's kernel -- and the optional read-backs.
 static int nmc_phases_run(nlmc_ctx *c, const std::string &name, const char *(*why)(const nlmc_ctx *, int, int), int (*route)(nlmc_ctx *, int, NmcRoute &),
                           int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0, uint64_t seed,
@@ -3739,6 +3782,14 @@ int nlmc_nmc_phases_waves(nlmc_ctx *c, int precision, const int32_t *kinds, int 
 {
     if (!c) return NLMC_ERR_ARG;
     return nmc_phases_run(c, "nlmc_nmc_phases_waves: ", wave_nmc_refusal, waves_nmc, precision, kinds,
+                          n_phases, sweeps_per_phase, sweep0, seed, beta, temp_x, min_stride, out_phase_min, out_phase_argmin, out_last_best);
+}
+
+int nlmc_nmc_phases_waves_long(nlmc_ctx *c, int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0, uint64_t seed,
+                               double beta, double temp_x, int min_stride, int64_t *out_phase_min, int32_t *out_phase_argmin, int8_t *out_last_best)
+{
+    if (!c) return NLMC_ERR_ARG;
+    return nmc_phases_run(c, "nlmc_nmc_phases_waves_long: ", wave_long_nmc_refusal, waves_long_nmc, precision, kinds,
                           n_phases, sweeps_per_phase, sweep0, seed, beta, temp_x, min_stride, out_phase_min, out_phase_argmin, out_last_best);
 }
 

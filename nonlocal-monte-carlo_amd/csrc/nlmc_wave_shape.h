@@ -1,7 +1,7 @@
 // nlmc_wave_shape.h -- host-side launch shapes of the wave-per-chain sweeps (csrc/nlmc_waves.h, csrc/nlmc_waves_long.h) and of the
 // tempering rounds inside a wave launch (csrc/nlmc_wave_rounds.h), pure functions with no HIP in them (checked on the host under the
 // sanitizers: scripts/wave_shape_check.cpp, scripts/wave_long_shape_check.cpp, scripts/wave_rounds_shape_check.cpp,
-// scripts/wave_long_rounds_shape_check.cpp).  No result depends on W or P.
+// scripts/wave_long_rounds_shape_check.cpp, scripts/wave_long_nmc_shape_check.cpp).  No result depends on W or P.
 // Each rule stands once (nlmc_wave_fields, nlmc_wave_rows, nlmc_wave_ladders, NLMC_WAVE_LONG_LDS_MAX); the shape functions put them together,
 // the long ones then lower W or P to what the LDS holds.  The LDS carve-ups are host/device functions the kernels call too.
 #pragma once
@@ -113,6 +113,36 @@ static inline NlmcWaveShape nlmc_wave_long_shape(int n, int n_pad, int rows, int
     s.stride = (size_t)64 * (size_t)R;
     s.region = (size_t)nlmc_wave_long_region(n, n_pad).bytes;
     const int fit = (int)(NLMC_WAVE_LONG_LDS_MAX / s.region);                        // >= 15: a region is at most 10 KB
+    s.W = nlmc_wave_rows(rows, n_cu, knob_waves);
+    if (s.W > fit) s.W = fit;
+    s.blocks = (int)(((long long)rows + s.W - 1) / s.W);
+    s.lds = (size_t)s.W * s.region;
+    return s;
+}
+
+// ---- NMC phase cycles of the long chains in one wave launch (csrc/nlmc_wave_long_nmc.h: k_nmc_phases_waves_long) ----
+// The LDS region a wave of k_nmc_phases_waves_long keeps to itself: nlmc_wave_long_region's parts (at offset 0, so the update is
+// k_sweep_waves_long's) | best spins [n_pad] int8 | backbone mask [n_pad] int8, each part 16-byte aligned.  The best state's fields
+// live in registers.  The kernel and the shape function both take the layout from here.
+struct NlmcWaveLongNmcRegion { NlmcWaveLongRegion sweep; int b_off, m_off, bytes; };
+NLMC_WS_HD static inline NlmcWaveLongNmcRegion nlmc_wave_long_nmc_region(int n, int n_pad)
+{
+    NlmcWaveLongNmcRegion g;
+    g.sweep = nlmc_wave_long_region(n, n_pad);
+    g.b_off = g.sweep.bytes;
+    g.m_off = g.b_off + ((n_pad + 15) & ~15);
+    g.bytes = g.m_off + ((n_pad + 15) & ~15);
+    return g;
+}
+
+// 256 < n <= 1024: nlmc_wave_long_shape's rule, with W lowered to what the LDS holds of the larger regions (13 at 1024 spins).  R = 0
+// where the chain does not fit.  No result depends on W.
+static inline NlmcWaveShape nlmc_wave_long_nmc_shape(int n, int n_pad, int rows, int n_cu, int knob_waves)
+{
+    NlmcWaveShape s = nlmc_wave_long_shape(n, n_pad, rows, n_cu, knob_waves);
+    if (s.R == 0) return s;
+    s.region = (size_t)nlmc_wave_long_nmc_region(n, n_pad).bytes;
+    const int fit = (int)(NLMC_WAVE_LONG_LDS_MAX / s.region);                        // >= 13: a region is at most 12 KB
     s.W = nlmc_wave_rows(rows, n_cu, knob_waves);
     if (s.W > fit) s.W = fit;
     s.blocks = (int)(((long long)rows + s.W - 1) / s.W);

@@ -31,6 +31,16 @@ LANE_NMC_IN_LAUNCH = True
 # (wave_nmc=None).  Set from scripts/wave_nmc_throughput.py (profiles/wave_nmc_throughput.txt).
 WAVE_NMC_IN_LAUNCH = True
 
+# The same for one k_nmc_phases_waves_long launch per context (Engine.nmc_phases_waves_long) where the engine's sweeps run one chain
+# of 257 to 1024 spins per wave (wave_long_nmc=None).  Set from scripts/wave_long_nmc_throughput.py (DESIGN.md section 6,
+# profiles/wave_long_nmc_throughput.txt).
+WAVE_LONG_NMC_IN_LAUNCH = True
+
+# The one-launch NMC routes in the order a round asks them: Engine.nmc_phases_<route> -> (the option's attribute stem: <stem>_nmc,
+# _<stem>_nmc_by_default, _<stem>_nmc_refused, _<stem>_nmc_asked, <stem>_nmc_rounds, <stem>_nmc_calls; the Engine method that says
+# whether the context's sweeps take that route anyway)
+NMC_ROUTES = {"waves": ("wave", "waves_take"), "waves_long": ("wave_long", "waves_take"), "lanes": ("lane", "lanes_take")}
+
 
 def block_partition(n_global, world, rank):
     """Contiguous block of chains owned by `rank` (first `n_global % world` ranks get one extra)."""
@@ -284,7 +294,8 @@ class LocalTempering:
 
     def __init__(self, inst, beta_list, n_chains_global, seed, n_pairs, device_ids, precision="f32", engine_factory=None,
                  engines=None, parts=None, lane_sweeps="off", track_best=False, target_energy=None, track_energies=False,
-                 wave_sweeps="off", wave_rounds=False, lane_nmc=None, wave_long=False, wave_long_rounds=False, wave_nmc=None):
+                 wave_sweeps="off", wave_rounds=False, lane_nmc=None, wave_long=False, wave_long_rounds=False, wave_nmc=None,
+                 wave_long_nmc=None):
         """`parts` (optional): the blocks [(chain_base, count)] this process drives instead of an even cut over device_ids -- one
         rank's share under a launcher; `engines`: contexts that exist already (they must have had pt_init; not closed here... they
         ARE closed by close(): hand over ownership); `lane_sweeps`: Engine.set_lane_sweeps of every engine created here ("off",
@@ -309,11 +320,16 @@ class LocalTempering:
         which every context took the call), lane_nmc_calls (calls that ran).
         `wave_nmc` (None: WAVE_NMC_IN_LAUNCH where the engine's sweeps run one chain per wave, Engine.waves_take; True, False): the same
         through Engine.nmc_phases_waves, one k_nmc_phases_waves launch per context -- same bits.  Asked before `lane_nmc`, as the wave
-        route is asked before the lane route; a context whose engine refuses (chains of more than 256 spins, ...) goes on to the lane
-        rule and the phase loop and is not asked again.  Counters: wave_nmc_rounds, wave_nmc_calls."""
+        route is asked before the lane route; a context whose engine refuses (chains of more than 256 spins, ...) goes on to
+        `wave_long_nmc`, the lane rule and the phase loop and is not asked again.  Counters: wave_nmc_rounds, wave_nmc_calls.
+        `wave_long_nmc` (None: WAVE_LONG_NMC_IN_LAUNCH where the engine's sweeps run one chain per wave; True, False; given, it needs
+        `wave_long`, ValueError otherwise): the same for chains of 257 to 1024 spins through Engine.nmc_phases_waves_long, one
+        k_nmc_phases_waves_long launch per context -- same bits.  Asked after `wave_nmc` and before `lane_nmc`; a context whose engine
+        refuses goes on and is not asked again.  Counters: wave_long_nmc_rounds, wave_long_nmc_calls."""
         hostlogic.check_wave_rounds(wave_rounds, wave_sweeps, needs="wave_sweeps 'auto' or 'force'")
         hostlogic.check_wave_long(wave_long, wave_sweeps, needs="wave_sweeps 'auto' or 'force'")
         hostlogic.check_wave_long_rounds(wave_long_rounds, wave_rounds, wave_long)
+        hostlogic.check_wave_long_nmc(wave_long_nmc, wave_long)
         self.G, self.seed, self.n_pairs, self.precision = int(n_chains_global), int(seed), int(n_pairs), precision
         devs = list(device_ids)
         self.parts = list(parts) if parts is not None else [block_partition(self.G, len(devs), r) for r in range(len(devs))]
@@ -350,6 +366,11 @@ class LocalTempering:
         self._wave_nmc_refused = set()       # the same sets for nmc_phases_waves
         self._wave_nmc_asked = set()
         self.wave_nmc_rounds = self.wave_nmc_calls = 0
+        self.wave_long_nmc = WAVE_LONG_NMC_IN_LAUNCH if wave_long_nmc is None else bool(wave_long_nmc)
+        self._wave_long_nmc_by_default = wave_long_nmc is None
+        self._wave_long_nmc_refused = set()  # the same sets for nmc_phases_waves_long
+        self._wave_long_nmc_asked = set()
+        self.wave_long_nmc_rounds = self.wave_long_nmc_calls = 0
         self.track_best = bool(track_best)
         self.track_energies, self._elog_open = bool(track_energies), False
         if self.track_energies and not self.whole_ladders:
@@ -384,10 +405,10 @@ class LocalTempering:
         # every M_skip-th sweep only (nlmc_track_minimum(M_skip)), their recorded traces are strided the same way
 
     def _nmc_takes(self, route, k):
-        """Whether context k's NMC phases go to Engine.nmc_phases_<route> ("waves", "lanes"): the option is on, and the engine has not
-        refused (asked once per context: a refusal is remembered).  An option left to its default applies only where the context's
+        """Whether context k's NMC phases go to Engine.nmc_phases_<route> (a key of NMC_ROUTES): the option is on, and the engine has
+        not refused (asked once per context: a refusal is remembered).  An option left to its default applies only where the context's
         sweeps take that route anyway (Engine.waves_take / lanes_take)."""
-        kind = route[:-1]
+        kind, take = NMC_ROUTES[route]
         on, by_default = getattr(self, kind + "_nmc"), getattr(self, f"_{kind}_nmc_by_default")
         refused, asked = getattr(self, f"_{kind}_nmc_refused"), getattr(self, f"_{kind}_nmc_asked")
         if not (self.nmc and on) or k in refused:
@@ -396,7 +417,7 @@ class LocalTempering:
             return True
         e = self.engs[k]
         asked.add(k)
-        on_route = hasattr(e, route + "_take") and getattr(e, route + "_take")()
+        on_route = hasattr(e, take) and getattr(e, take)()
         call = "nmc_phases_" + route
         if not hasattr(e, call) or (by_default and not on_route) or \
                 (hasattr(e, call + "_refusal") and getattr(e, call + "_refusal")(self.nmc["S"])):
@@ -410,6 +431,9 @@ class LocalTempering:
     def _wave_nmc_takes(self, k):
         return self._nmc_takes("waves", k)
 
+    def _wave_long_nmc_takes(self, k):
+        return self._nmc_takes("waves_long", k)
+
     def sweeps_per_round(self, n_sweeps):
         """Plain sweep indices (RNG counters) one round of `n_sweeps` sweeps consumes.  The NMC phases of the marked slots draw from
         a range of their own (NMC_SWEEP_SPACE + nmc_sweeps_done, advanced by phases x sweeps_per_phase per round)."""
@@ -422,8 +446,8 @@ class LocalTempering:
                                        pt_pairs=self.n_pairs, pt_round0=self.rounds_done, slot=0, fused_outputs=True) for e in self.engs]
         self._planner_round0 = self.rounds_done
         self._nmc_planners = None
-        if self.nmc and not all(self._wave_nmc_takes(k) or self._lane_nmc_takes(k) for k in range(len(self.engs))):
-            # (where every context runs its phases inside nmc_phases_waves / nmc_phases_lanes launches there is nothing to plan for
+        if self.nmc and not all(any(self._nmc_takes(route, k) for route in NMC_ROUTES) for k in range(len(self.engs))):
+            # (where every context runs its phases inside nmc_phases_waves / nmc_phases_waves_long / nmc_phases_lanes launches there is nothing to plan for
             # them: the rounds with outputs run their phases on the wave or lane kernels, which need no level schedule)
             # the NMC phases draw from their own range of sweep indices, behind the plain sweeps of all planned rounds: both
             # ranges are contiguous over the rounds, so each is served by one fused-window plan (slots 0 and 1)
@@ -463,7 +487,7 @@ class LocalTempering:
         "nmc_chains": ids, "plain_energy_columns": fp64 energies of the first `energy_columns` recorded columns}."""
         ii = self.rounds_done - (self._planner_round0 if self._planners else 0)
         outs = []
-        in_launch = {"waves": 0, "lanes": 0}
+        in_launch = dict.fromkeys(NMC_ROUTES, 0)
         wants = any(outputs.get(k) for k in ("record_stride", "want_energy", "want_min", "want_state"))
         for k, e in enumerate(self.engs):
             if self.nmc:
@@ -488,7 +512,7 @@ class LocalTempering:
                 rec["nmc_chains"] = e.subset()
             e.backbone_clusters(q["epsilon"], q["lambdas"], q["beta"], q["tol"], q["max_it"], q["sat"], q["thresholds"])
             took = False
-            for route in ("waves", "lanes"):         # all phases in one launch (same bits as the loop below): the wave call asked first
+            for route in NMC_ROUTES:                 # all phases in one launch (same bits as the loop below): the wave calls asked first
                 if wants or took or not self._nmc_takes(route, k):
                     continue
                 try:
@@ -497,7 +521,7 @@ class LocalTempering:
                     took = True
                     in_launch[route] += 1
                 except NotImplementedError:          # nothing was run: the next route or the phase loop, now and from here on
-                    getattr(self, f"_{route[:-1]}_nmc_refused").add(k)
+                    getattr(self, f"_{NMC_ROUTES[route][0]}_nmc_refused").add(k)
             if took:
                 e.set_phase("ALL")
                 e.select("all")
@@ -523,10 +547,10 @@ class LocalTempering:
             self._observe(e, self.rounds_done)      # (all chains selected again, the NMC chains in the state they carry on; before the swap)
             outs.append(rec)
         self.sweeps_done += n_sweeps
-        self.lane_nmc_calls += in_launch["lanes"]
-        self.lane_nmc_rounds += 1 if (in_launch["lanes"] and in_launch["lanes"] == len(self.engs)) else 0
-        self.wave_nmc_calls += in_launch["waves"]
-        self.wave_nmc_rounds += 1 if (in_launch["waves"] and in_launch["waves"] == len(self.engs)) else 0
+        for route, (kind, _) in NMC_ROUTES.items():
+            setattr(self, kind + "_nmc_calls", getattr(self, kind + "_nmc_calls") + in_launch[route])
+            if in_launch[route] and in_launch[route] == len(self.engs):
+                setattr(self, kind + "_nmc_rounds", getattr(self, kind + "_nmc_rounds") + 1)
         if self.nmc:
             self.nmc_sweeps_done += len(self.nmc["phases"]) * self.nmc["S"]
         if self.n_pairs > 0:

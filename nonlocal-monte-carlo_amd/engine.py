@@ -808,7 +808,7 @@ class Engine:
                                 want_minima, want_last_best)
 
     def _nmc_phases(self, call, kinds, sweeps_per_phase, seed, sweep0, beta, temp_x, min_stride, precision, want_minima, want_last_best):
-        """nmc_phases_lanes / nmc_phases_waves: the library call `call` and its read-backs."""
+        """nmc_phases_lanes / nmc_phases_waves / nmc_phases_waves_long: the library call `call` and its read-backs."""
         k = _abi.as_c([self.PHASES[x] for x in kinds], np.int32)
         R, P = self.rows(), int(k.shape[0])
         pmin = np.empty((R, P), np.int64) if want_minima else None
@@ -840,6 +840,24 @@ class Engine:
     def nmc_phases_waves_refusal(self, sweeps_per_phase):
         """Why nmc_phases_waves would refuse f32 phases of `sweeps_per_phase` sweeps on this context (the library's reason), or None."""
         why = self._L.nlmc_nmc_phases_waves_refusal(self._ctx, int(sweeps_per_phase))
+        return why.decode() if why else None
+
+    def nmc_phases_waves_long(self, kinds, sweeps_per_phase, seed, sweep0, beta, temp_x, min_stride=1, precision="f32",
+                              want_minima=False, want_last_best=False):
+        """nmc_phases_waves' call for dense chains of 257 to 1024 spins, inside k_nmc_phases_waves_long launches in the long wave sweeps'
+        launch shape (include/nlmc.h: nlmc_nmc_phases_waves_long): the exact local fields stay resident across the phases (registers
+        plus the wave's LDS copy), the best state's fields in registers and its spins in the wave's LDS, so the fields are built once
+        per launch and the hand-off between two phases stays inside the wave.  Same arguments, same returns, same bits as the call
+        sequence on any route; reached by name (set_wave_sweeps / set_wave_long are not looked at).  NotImplementedError when the
+        context does not qualify -- chains of at most 256 or more than 1024 spins, precision "f64", apt_shard contexts, ... -- and
+        nothing was run; nmc_phases_waves_long_refusal asks beforehand."""
+        return self._nmc_phases(self._L.nlmc_nmc_phases_waves_long, kinds, sweeps_per_phase, seed, sweep0, beta, temp_x, min_stride,
+                                precision, want_minima, want_last_best)
+
+    def nmc_phases_waves_long_refusal(self, sweeps_per_phase):
+        """Why nmc_phases_waves_long would refuse f32 phases of `sweeps_per_phase` sweeps on this context (the library's reason), or
+        None."""
+        why = self._L.nlmc_nmc_phases_waves_long_refusal(self._ctx, int(sweeps_per_phase))
         return why.decode() if why else None
 
     # -- iso-cluster move -------------------------------------------------------------------------------

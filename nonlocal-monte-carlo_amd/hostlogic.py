@@ -49,6 +49,12 @@ def check_wave_nmc(wave_nmc, waves, needs="waves='auto' or 'force'"):
         raise ValueError(f"wave_nmc needs {needs} (it says how the NMC phases run on the wave route)")
 
 
+def check_wave_long_nmc(wave_long_nmc, wave_long):
+    """wave_long_nmc given (True or False) without wave_long: ValueError."""
+    if wave_long_nmc is not None and not wave_long:
+        raise ValueError("wave_long_nmc needs wave_long=True (it says how the NMC phases of chains of 257 to 1024 spins run on the wave route)")
+
+
 def check_wave_long_rounds(wave_long_rounds, wave_rounds, wave_long):
     """wave_long_rounds without wave_rounds or without wave_long: ValueError."""
     if wave_long_rounds and not (wave_rounds and wave_long):

@@ -31,7 +31,7 @@ class NPT(Common):
     _variant = "npt"
 
     def __init__(self, J, h, rng=None, seed=None, device=0, lbp=None, precision="f32", lanes="off", waves="off", wave_rounds=False,
-                 lane_nmc=None, wave_long=False, wave_long_rounds=False, wave_nmc=None):
+                 lane_nmc=None, wave_long=False, wave_long_rounds=False, wave_nmc=None, wave_long_nmc=None):
         """`precision` (additive keyword, rng="philox" only): "f32" (default) -- the throughput mode's fixed-point couplings and
         logistic thresholds; "f64" -- the device-resident rounds in the reference's arithmetic (fp64 field, 53-bit uniform), on
         fused windows for real couplings too (Engine.set_fused_f64_real).  Replicas with doNMC set are not supported with "f64".
@@ -61,7 +61,11 @@ class NPT(Common):
         local fields and the best state's fields in registers across the phases; False: a wave sweep call per phase -- same results
         either way, and those of waves="off".  None (the default): distributed.WAVE_NMC_IN_LAUNCH, what was measured ahead.
         self.wave_nmc_rounds counts the rounds of the last run that took the one-launch call.  Chains of more than 256 spins keep the
-        phase loop (with `wave_long` too)."""
+        phase loop under this keyword (with `wave_long` too): they have `wave_long_nmc`.
+        `wave_long_nmc` (additive keyword, needs wave_long=True; None, True, False): the same for chains of 257 to 1024 spins, one
+        k_nmc_phases_waves_long launch per context (Engine.nmc_phases_waves_long) -- same results either way, and those of
+        waves="off".  None (the default): distributed.WAVE_LONG_NMC_IN_LAUNCH, what was measured ahead.  self.wave_long_nmc_rounds counts the rounds of the
+        last run that took the call."""
         if precision not in ("f32", "f64"):
             raise ValueError("precision must be 'f32' or 'f64'")
         hostlogic.check_route_keywords(lanes, waves)
@@ -79,6 +83,8 @@ class NPT(Common):
         self.lane_nmc = lane_nmc
         hostlogic.check_wave_nmc(wave_nmc, waves)
         self.wave_nmc = wave_nmc
+        hostlogic.check_wave_long_nmc(wave_long_nmc, wave_long)
+        self.wave_long_nmc = wave_long_nmc
 
     # ------------------------------------------------------------------------------------------------
     def replica_energy(self, M, num_sweeps):
@@ -433,11 +439,11 @@ class NPT(Common):
         if ctx is None:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, precision=prec, lane_sweeps=self.lanes,
                                 wave_sweeps=self.waves, wave_rounds=self.wave_rounds, wave_long=self.wave_long, wave_long_rounds=self.wave_long_rounds, track_best=track_best, target_energy=target_energy, track_energies=track_energies,
-                                lane_nmc=self.lane_nmc, wave_nmc=self.wave_nmc)
+                                lane_nmc=self.lane_nmc, wave_nmc=self.wave_nmc, wave_long_nmc=self.wave_long_nmc)
         elif not cut:
             lt = LocalTempering(inst, beta_list, G, self.seed, self.num_swapping_pairs, devs, parts=[(base_, count_)], precision=prec,
                                 lane_sweeps=self.lanes, wave_sweeps=self.waves, wave_rounds=self.wave_rounds, wave_long=self.wave_long, wave_long_rounds=self.wave_long_rounds, track_best=track_best, target_energy=target_energy, track_energies=track_energies,
-                                lane_nmc=self.lane_nmc, wave_nmc=self.wave_nmc)
+                                lane_nmc=self.lane_nmc, wave_nmc=self.wave_nmc, wave_long_nmc=self.wave_long_nmc)
         else:
             lt = ShardedAsLocal(ShardedTempering(
                 lambda i, n, b, g: opt_in(Engine(i, None, n, device=lrank_, chain_base=b, n_chains_global=g)), inst, beta_list, G,
@@ -507,6 +513,7 @@ class NPT(Common):
             self._nmc_sweep_counter = lt.nmc_sweeps_done          # (the NMC phases draw from a counter range of their own)
             self.lane_nmc_rounds = getattr(lt, "lane_nmc_rounds", 0)
             self.wave_nmc_rounds = getattr(lt, "wave_nmc_rounds", 0)
+            self.wave_long_nmc_rounds = getattr(lt, "wave_long_nmc_rounds", 0)
             self.sweep_routes = [e.last_sweep_route() for e in getattr(lt, "engs", []) if hasattr(e, "last_sweep_route")]
             lt.check()
             if track_best:
