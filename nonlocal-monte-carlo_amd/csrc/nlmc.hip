@@ -3554,7 +3554,25 @@ int nlmc_apt_rounds_lanes(nlmc_ctx *c, int precision, int n_rounds, int sweeps_p
     return NLMC_OK;
 }
 
-// ---- NMC phase cycles of short chains in one launch: a chain per lane (k_nmc_phases_lanes, csrc/nlmc_lane_nmc.h) ---------------------
+// ---- NMC phase cycles in one launch: a chain per lane (k_nmc_phases_lanes, csrc/nlmc_lane_nmc.h), a chain per wave (k_nmc_phases_waves,
+// csrc/nlmc_wave_nmc.h) and a chain of NLMC_WAVE_N < n <= NLMC_WAVE_LONG_N spins per wave (k_nmc_phases_waves_long, csrc/nlmc_wave_long_nmc.h)
+enum class NmcRoute { lanes, waves, waves_long };
+
+// The reach of a route's kernel: the test knob that switches it off (read at nlmc_create) and what it says, the chain lengths it takes,
+// whether it has the fixed-point arithmetic only, and what a chain beyond it is told.  Rows in the order of NmcRoute.
+struct NmcReach { bool Knobs::*off; const char *why_off; int n_min, n_max; bool f32_only; const char *why_n; };
+static NmcReach nmc_reach(NmcRoute route)
+{
+    static const NmcReach reach[] = {
+        {&Knobs::no_lane_nmc, "switched off (NLMC_NO_LANE_NMC)", 0, NLMC_LANE_N, false,
+         "the chain-per-lane kernels take chains of at most NLMC_LANE_N spins, resident in LDS"},
+        {&Knobs::no_wave_nmc, "switched off (NLMC_NO_WAVE_NMC)", 0, NLMC_WAVE_N, true,
+         "the wave-per-chain phase kernel takes chains of at most NLMC_WAVE_N spins"},
+        {&Knobs::no_wave_long_nmc, "switched off (NLMC_NO_WAVE_LONG_NMC)", NLMC_WAVE_N + 1, NLMC_WAVE_LONG_N, true,
+         "the long wave-per-chain phase kernel takes chains of NLMC_WAVE_N + 1 to NLMC_WAVE_LONG_N spins"}};
+    return reach[(int)route];
+}
+
 // LDS of k_nmc_phases_lanes: transposed spins | transposed backbone mask | (where it fits) a transposed best-state plane | (where it
 // fits) one sweep's random numbers.  The table under lane_lds' rule -- four waves still share a compute unit, 40 KB per wave -- and the
 // best-state plane where that still holds beside the rest; best_off = 0: the best state stays in global memory.
@@ -3573,75 +3591,32 @@ static LaneNmcLds lane_nmc_lds(const nlmc_ctx *c)
     return L;
 }
 
-// Why this context cannot run NMC phases of S sweeps inside k_nmc_phases_lanes, or nullptr.  (The entry point has the shared visiting
-// order only: a per-chain order cannot be asked for.)  Arguments and call order are checked by the caller.
-static const char *lane_nmc_refusal(const nlmc_ctx *c, int S)
+// Why this context cannot run NMC phases of S sweeps inside the kernel of `route`, or nullptr.  (The entry points have the shared visiting
+// order only: a per-chain order cannot be asked for.)  They are reached by name: nlmc_set_lane_sweeps, nlmc_set_wave_sweeps and
+// nlmc_set_wave_long are not looked at, and chains of more than NLMC_WAVE_N spins are refused by `waves` under nlmc_set_wave_long too.
+// Arguments and call order are checked by the caller.
+static const char *nmc_refusal(const nlmc_ctx *c, NmcRoute route, int S, int precision)
 {
-    if (c->knobs.no_lane_nmc) return "switched off (NLMC_NO_LANE_NMC)";
-    if (c->knobs.force_big || c->big || c->n > NLMC_LANE_N) return "the chain-per-lane kernels take chains of at most NLMC_LANE_N spins, resident in LDS";
+    const NmcReach reach = nmc_reach(route);
+    if (c->knobs.*reach.off) return reach.why_off;
+    if (c->knobs.force_big || c->big || c->n < reach.n_min || c->n > reach.n_max) return reach.why_n;
+    if (reach.f32_only && precision != NLMC_F32) return "the wave-per-chain kernels keep exact fixed-point fields: f32 only";
     if (c->rng_stride != 0) return "random numbers keyed by temperature slot (nlmc_apt_shard) keep the phase-by-phase route";
     if ((size_t)S * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
         return "the visiting orders of one phase exceed the order scratch (NLMC_LANE_SCRATCH)";
-    if (!lane_nmc_lds(c).ok) return "spins and backbone mask exceed one workgroup's LDS";
+    if (route == NmcRoute::lanes && !lane_nmc_lds(c).ok) return "spins and backbone mask exceed one workgroup's LDS";
+    if (route == NmcRoute::waves_long && nlmc_wave_long_nmc_shape(c->n, c->n_pad, 1, 1, 0).R == 0)
+        return "the padded chain does not fit a row of the wave kernels' matrix";
     return nullptr;
 }
 
-const char *nlmc_nmc_phases_lanes_refusal(const nlmc_ctx *c, int sweeps_per_phase)
-{
-    if (!c) return "no context";
-    return lane_nmc_refusal(c, std::max(1, sweeps_per_phase));
-}
-
-// ---- ... and a chain per wave (k_nmc_phases_waves, csrc/nlmc_wave_nmc.h) ------------------------------------------------------------
-// Why this context cannot run NMC phases of S sweeps inside k_nmc_phases_waves, or nullptr.  nlmc_set_wave_sweeps is not looked at: the
-// entry point is reached by name.  Chains of more than NLMC_WAVE_N spins are refused under nlmc_set_wave_long too: they have
-// nlmc_nmc_phases_waves_long.
-static const char *wave_nmc_refusal(const nlmc_ctx *c, int S, int precision)
-{
-    if (c->knobs.no_wave_nmc) return "switched off (NLMC_NO_WAVE_NMC)";
-    if (c->knobs.force_big || c->big || c->n > NLMC_WAVE_N) return "the wave-per-chain phase kernel takes chains of at most NLMC_WAVE_N spins";
-    if (precision != NLMC_F32) return "the wave-per-chain kernels keep exact fixed-point fields: f32 only";
-    if (c->rng_stride != 0) return "random numbers keyed by temperature slot (nlmc_apt_shard) keep the phase-by-phase route";
-    if ((size_t)S * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
-        return "the visiting orders of one phase exceed the order scratch (NLMC_LANE_SCRATCH)";
-    return nullptr;
-}
-
-const char *nlmc_nmc_phases_waves_refusal(const nlmc_ctx *c, int sweeps_per_phase)
-{
-    if (!c) return "no context";
-    return wave_nmc_refusal(c, std::max(1, sweeps_per_phase), NLMC_F32);
-}
-
-// ---- ... and a chain of NLMC_WAVE_N < n <= NLMC_WAVE_LONG_N spins per wave (k_nmc_phases_waves_long, csrc/nlmc_wave_long_nmc.h) ---------
-// Why this context cannot run NMC phases of S sweeps inside k_nmc_phases_waves_long, or nullptr.  Neither nlmc_set_wave_sweeps nor
-// nlmc_set_wave_long is looked at: the entry point is reached by name.
-static const char *wave_long_nmc_refusal(const nlmc_ctx *c, int S, int precision)
-{
-    if (c->knobs.no_wave_long_nmc) return "switched off (NLMC_NO_WAVE_LONG_NMC)";
-    if (c->knobs.force_big || c->big || c->n <= NLMC_WAVE_N || c->n > NLMC_WAVE_LONG_N)
-        return "the long wave-per-chain phase kernel takes chains of NLMC_WAVE_N + 1 to NLMC_WAVE_LONG_N spins";
-    if (precision != NLMC_F32) return "the wave-per-chain kernels keep exact fixed-point fields: f32 only";
-    if (c->rng_stride != 0) return "random numbers keyed by temperature slot (nlmc_apt_shard) keep the phase-by-phase route";
-    if ((size_t)S * (size_t)c->n * sizeof(uint16_t) > c->knobs.lane_scratch)
-        return "the visiting orders of one phase exceed the order scratch (NLMC_LANE_SCRATCH)";
-    if (nlmc_wave_long_nmc_shape(c->n, c->n_pad, 1, 1, 0).R == 0) return "the padded chain does not fit a row of the wave kernels' matrix";
-    return nullptr;
-}
-
-const char *nlmc_nmc_phases_waves_long_refusal(const nlmc_ctx *c, int sweeps_per_phase)
-{
-    if (!c) return "no context";
-    return wave_long_nmc_refusal(c, std::max(1, sweeps_per_phase), NLMC_F32);
-}
-
-// What a route supplies to nmc_phases_run: its kernel with dynamic LDS, grid and block (LDS limit raised, whatever the kernel reads once
-// per context in place), the SweepArgs / LaneNmcArgs fields of its own -- lanes: the LDS carve-up (lane_nmc_lds); waves: the dense
+// What a route supplies to nmc_phases_by_name: its kernel with dynamic LDS, grid and block (LDS limit raised, whatever the kernel reads once
+// per context in place), the SweepArgs / NmcPhasesArgs fields of its own -- lanes: the LDS carve-up (lane_nmc_lds); waves: the dense
 // matrix -- and the NLMC_ROUTE_* it reports.
-struct NmcRoute { const void *kfun; size_t lds; dim3 grid, block; bool tab; size_t u_off, mask_off, best_off; const int32_t *wave_J; int route; };
+struct NmcLaunch { const void *kfun; size_t lds; dim3 grid, block; bool tab; size_t u_off, mask_off, best_off; const int32_t *wave_J; int route; };
 
 // k_nmc_phases_lanes: a chain per lane, 64 to a workgroup of one wave
-static int lanes_nmc(nlmc_ctx *c, int precision, NmcRoute &r)
+static int lanes_nmc(nlmc_ctx *c, int precision, NmcLaunch &r)
 {
     const LaneNmcLds L = lane_nmc_lds(c);
     r.kfun = precision == NLMC_F64 ? reinterpret_cast<const void *>(k_nmc_phases_lanes<true>) : reinterpret_cast<const void *>(k_nmc_phases_lanes<false>);
@@ -3651,17 +3626,20 @@ static int lanes_nmc(nlmc_ctx *c, int precision, NmcRoute &r)
     return ensure_lds(c, r.kfun, r.lds);
 }
 
-// k_nmc_phases_waves<R, jlds>: a chain per wave in k_sweep_waves' shape (nlmc_wave_shape)
-static int waves_nmc(nlmc_ctx *c, int, NmcRoute &r)
+// k_nmc_phases_waves<R, jlds> for R <= 4: a chain per wave in k_sweep_waves' shape (nlmc_wave_shape); k_nmc_phases_waves_long<R, ahead>
+// beyond (`longs`): k_sweep_waves_long's shape with the larger regions (nlmc_wave_long_nmc_shape), NLMC_WAVE_LONG_AHEAD picks as for the sweeps
+static int waves_nmc(nlmc_ctx *c, bool longs, NmcLaunch &r)
 {
-    static const void *const table[3][2] = {
-        {reinterpret_cast<const void *>(k_nmc_phases_waves<1, false>), reinterpret_cast<const void *>(k_nmc_phases_waves<1, true>)},
-        {reinterpret_cast<const void *>(k_nmc_phases_waves<2, false>), reinterpret_cast<const void *>(k_nmc_phases_waves<2, true>)},
-        {reinterpret_cast<const void *>(k_nmc_phases_waves<4, false>), reinterpret_cast<const void *>(k_nmc_phases_waves<4, true>)}};
+#define NLMC_NW(K_, R_) {reinterpret_cast<const void *>(K_<R_, false>), reinterpret_cast<const void *>(K_<R_, true>)}
+    static const void *const table[5][2] = {NLMC_NW(k_nmc_phases_waves, 1), NLMC_NW(k_nmc_phases_waves, 2), NLMC_NW(k_nmc_phases_waves, 4),
+                                            NLMC_NW(k_nmc_phases_waves_long, 8), NLMC_NW(k_nmc_phases_waves_long, 16)};
+#undef NLMC_NW
     { int rc = cu_count(c); if (rc) return rc; }
-    const NlmcWaveShape S = nlmc_wave_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves, c->knobs.wave_jlds ? 1 : 0);
-    if (S.R == 0 || S.R > 4 || c->n_pad > 64 * S.R) return fail(c, NLMC_ERR_STATE, "waves_nmc: the chain does not fit the wave kernels");
-    r.kfun = table[wave_fields_row(S.R)][S.jlds ? 1 : 0];
+    const NlmcWaveShape S = longs ? nlmc_wave_long_nmc_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves)
+                                  : nlmc_wave_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves, c->knobs.wave_jlds ? 1 : 0);
+    if ((longs ? S.R != 8 && S.R != 16 : S.R == 0 || S.R > 4) || c->n_pad > 64 * S.R)
+        return fail(c, NLMC_ERR_STATE, longs ? "waves_long_nmc: the chain does not fit the wave kernels" : "waves_nmc: the chain does not fit the wave kernels");
+    r.kfun = table[wave_fields_row(S.R)][(longs ? c->knobs.wave_long_ahead : S.jlds) ? 1 : 0];
     r.lds = S.lds; r.grid = dim3((unsigned)S.blocks); r.block = dim3((unsigned)(64 * S.W));
     r.route = NLMC_ROUTE_WAVES;
     { int rc = ensure_lds(c, r.kfun, r.lds); if (rc) return rc; }
@@ -3670,30 +3648,15 @@ static int waves_nmc(nlmc_ctx *c, int, NmcRoute &r)
     return NLMC_OK;
 }
 
-// k_nmc_phases_waves_long<R, ahead>: a chain per wave in k_sweep_waves_long's shape with the larger regions (nlmc_wave_long_nmc_shape)
-static int waves_long_nmc(nlmc_ctx *c, int, NmcRoute &r)
+// nlmc_nmc_phases_lanes / nlmc_nmc_phases_waves / nlmc_nmc_phases_waves_long (`fn`), whatever the lane or wave mode is: the checks
+// (nmc_refusal last), launches of as many whole phases as the order scratch holds visiting orders for (and the kernel arguments hold kinds
+// for) -- k_lane_orders into nmc_perm, then the route's kernel -- and the optional read-backs.
+static int nmc_phases_by_name(nlmc_ctx *c, NmcRoute route, const char *fn, int precision, const int32_t *kinds, int n_phases,
+                              int sweeps_per_phase, uint32_t sweep0, uint64_t seed, double beta, double temp_x, int min_stride,
+                              int64_t *out_phase_min, int32_t *out_phase_argmin, int8_t *out_last_best)
 {
-    static const void *const table[2][2] = {
-        {reinterpret_cast<const void *>(k_nmc_phases_waves_long<8, false>), reinterpret_cast<const void *>(k_nmc_phases_waves_long<8, true>)},
-        {reinterpret_cast<const void *>(k_nmc_phases_waves_long<16, false>), reinterpret_cast<const void *>(k_nmc_phases_waves_long<16, true>)}};
-    { int rc = cu_count(c); if (rc) return rc; }
-    const NlmcWaveShape S = nlmc_wave_long_nmc_shape(c->n, c->n_pad, c->sub_count(), c->n_cu, c->knobs.wave_waves);
-    if ((S.R != 8 && S.R != 16) || c->n_pad > 64 * S.R) return fail(c, NLMC_ERR_STATE, "waves_long_nmc: the chain does not fit the wave kernels");
-    r.kfun = table[S.R == 16 ? 1 : 0][c->knobs.wave_long_ahead ? 1 : 0];
-    r.lds = S.lds; r.grid = dim3((unsigned)S.blocks); r.block = dim3((unsigned)(64 * S.W));
-    r.route = NLMC_ROUTE_WAVES;
-    { int rc = ensure_lds(c, r.kfun, r.lds); if (rc) return rc; }
-    { int rc = ensure_wave_matrix(c, S.stride); if (rc) return rc; }
-    r.wave_J = c->wave_J.p;
-    return NLMC_OK;
-}
-
-// All entry points: the checks (`why`: the route's refusal), launches of as many whole phases as the order scratch holds visiting orders
-// for (and the kernel arguments hold kinds for) -- k_lane_orders into nmc_perm, then the route's kernel -- and the optional read-backs.
-static int nmc_phases_run(nlmc_ctx *c, const std::string &name, const char *(*why)(const nlmc_ctx *, int, int), int (*route)(nlmc_ctx *, int, NmcRoute &),
-                          int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0, uint64_t seed,
-                          double beta, double temp_x, int min_stride, int64_t *out_phase_min, int32_t *out_phase_argmin, int8_t *out_last_best)
-{
+    if (!c) return NLMC_ERR_ARG;
+    const std::string name = std::string(fn) + ": ";
     const int P = n_phases, S = sweeps_per_phase;
     if ((precision != NLMC_F32 && precision != NLMC_F64) || !kinds || P < 1 || S < 1 || min_stride < 1 || (long long)P * S > (long long)(INT_MAX / 2))
         return fail(c, NLMC_ERR_ARG, name + "bad argument");
@@ -3702,13 +3665,13 @@ static int nmc_phases_run(nlmc_ctx *c, const std::string &name, const char *(*wh
     if (!(temp_x > 0.0) && !(temp_x < 0.0)) return fail(c, NLMC_ERR_ARG, name + "temp_x must be non-zero");
     if (!c->cmask.p) return fail(c, NLMC_ERR_STATE, name + "no backbone inference has run");
     if (c->track_min) return fail(c, NLMC_ERR_STATE, name + "a tracked minimum is open (nlmc_track_minimum): the call keeps its own");
-    if (const char *w = why(c, S, precision)) return fail(c, NLMC_ERR_UNSUPPORTED, name + w);
+    if (const char *why = nmc_refusal(c, route, S, precision)) return fail(c, NLMC_ERR_UNSUPPORTED, name + why);
     HIP_TRY(c, hipSetDevice(c->device));
     const int R = c->sub_count(), n = c->n;
     if (R == 0) return NLMC_OK;
     { int rc = ensure_subset(c); if (rc) return rc; }
-    NmcRoute r{};
-    { int rc = route(c, precision, r); if (rc) return rc; }
+    NmcLaunch r{};
+    { int rc = route == NmcRoute::lanes ? lanes_nmc(c, precision, r) : waves_nmc(c, route == NmcRoute::waves_long, r); if (rc) return rc; }
     const size_t bytes_per_phase = (size_t)S * (size_t)n * sizeof(uint16_t);
     const int K = (int)std::max<size_t>(1, std::min<size_t>({(size_t)P, c->knobs.lane_scratch / bytes_per_phase, (size_t)NLMC_NMC_PHASES_LAUNCH}));
     begin_sweep_call(c);
@@ -3734,7 +3697,7 @@ static int nmc_phases_run(nlmc_ctx *c, const std::string &name, const char *(*wh
         a.flags = nullptr; a.lane_perm = c->nmc_perm.p; a.min_stride = min_stride;
         a.emin = c->emin.p; a.best = c->best.p;
         a.wave_J = r.wave_J;
-        LaneNmcArgs q{};
+        NmcPhasesArgs q{};
         q.n_phases = k; q.phase0 = at; q.phases_total = P;
         for (int p = 0; p < k; ++p) q.kinds[p >> 4] |= (uint32_t)kinds[at + p] << (2 * (p & 15));
         q.cb0 = -2.0 * LOG2E * beta; q.cb1 = -2.0 * LOG2E * (beta / temp_x);
@@ -3772,26 +3735,33 @@ static int nmc_phases_run(nlmc_ctx *c, const std::string &name, const char *(*wh
 int nlmc_nmc_phases_lanes(nlmc_ctx *c, int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0, uint64_t seed,
                           double beta, double temp_x, int min_stride, int64_t *out_phase_min, int32_t *out_phase_argmin, int8_t *out_last_best)
 {
-    if (!c) return NLMC_ERR_ARG;
-    return nmc_phases_run(c, "nlmc_nmc_phases_lanes: ", [](const nlmc_ctx *x, int S, int) { return lane_nmc_refusal(x, S); }, lanes_nmc, precision, kinds,
-                          n_phases, sweeps_per_phase, sweep0, seed, beta, temp_x, min_stride, out_phase_min, out_phase_argmin, out_last_best);
+    return nmc_phases_by_name(c, NmcRoute::lanes, "nlmc_nmc_phases_lanes", precision, kinds, n_phases, sweeps_per_phase, sweep0, seed, beta, temp_x,
+                              min_stride, out_phase_min, out_phase_argmin, out_last_best);
 }
 
 int nlmc_nmc_phases_waves(nlmc_ctx *c, int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0, uint64_t seed,
                           double beta, double temp_x, int min_stride, int64_t *out_phase_min, int32_t *out_phase_argmin, int8_t *out_last_best)
 {
-    if (!c) return NLMC_ERR_ARG;
-    return nmc_phases_run(c, "nlmc_nmc_phases_waves: ", wave_nmc_refusal, waves_nmc, precision, kinds,
-                          n_phases, sweeps_per_phase, sweep0, seed, beta, temp_x, min_stride, out_phase_min, out_phase_argmin, out_last_best);
+    return nmc_phases_by_name(c, NmcRoute::waves, "nlmc_nmc_phases_waves", precision, kinds, n_phases, sweeps_per_phase, sweep0, seed, beta, temp_x,
+                              min_stride, out_phase_min, out_phase_argmin, out_last_best);
 }
 
 int nlmc_nmc_phases_waves_long(nlmc_ctx *c, int precision, const int32_t *kinds, int n_phases, int sweeps_per_phase, uint32_t sweep0, uint64_t seed,
                                double beta, double temp_x, int min_stride, int64_t *out_phase_min, int32_t *out_phase_argmin, int8_t *out_last_best)
 {
-    if (!c) return NLMC_ERR_ARG;
-    return nmc_phases_run(c, "nlmc_nmc_phases_waves_long: ", wave_long_nmc_refusal, waves_long_nmc, precision, kinds,
-                          n_phases, sweeps_per_phase, sweep0, seed, beta, temp_x, min_stride, out_phase_min, out_phase_argmin, out_last_best);
+    return nmc_phases_by_name(c, NmcRoute::waves_long, "nlmc_nmc_phases_waves_long", precision, kinds, n_phases, sweeps_per_phase, sweep0, seed, beta, temp_x,
+                              min_stride, out_phase_min, out_phase_argmin, out_last_best);
 }
+
+// Why f32 phases of sweeps_per_phase sweeps would be refused on `route`, or nullptr
+static const char *nmc_why_not(const nlmc_ctx *c, NmcRoute route, int sweeps_per_phase)
+{
+    return c ? nmc_refusal(c, route, std::max(1, sweeps_per_phase), NLMC_F32) : "no context";
+}
+
+const char *nlmc_nmc_phases_lanes_refusal(const nlmc_ctx *c, int sweeps_per_phase) { return nmc_why_not(c, NmcRoute::lanes, sweeps_per_phase); }
+const char *nlmc_nmc_phases_waves_refusal(const nlmc_ctx *c, int sweeps_per_phase) { return nmc_why_not(c, NmcRoute::waves, sweeps_per_phase); }
+const char *nlmc_nmc_phases_waves_long_refusal(const nlmc_ctx *c, int sweeps_per_phase) { return nmc_why_not(c, NmcRoute::waves_long, sweeps_per_phase); }
 
 // ------------------------------------------------------------------------------------------------------
 // convexified loopy belief propagation (backbone inference), batched over problems

@@ -18,30 +18,15 @@
 // Same bits as the call sequence on any route; the context's flags array is neither read nor written.
 #pragma once
 #include "nlmc_lanes.h"
-
-#define NLMC_NMC_PHASES_LAUNCH 128      // phases one launch takes: their kinds travel in the kernel arguments, two bits each
+#include "nlmc_nmc_frame.h"
 
 static_assert(NLMC_LANE_STRIDE % 4 == 0, "the best-state plane is copied a word (four lanes of one spin) at a time");
-
-struct LaneNmcArgs {
-    int n_phases;                    // phases of this launch
-    int phase0;                      // its first phase inside the call: column of the outputs; > 0: the launch starts from the
-                                     // context's best state and minimum (what the launch before it left)
-    int phases_total;                // phases of the call: row length of the outputs
-    uint32_t kinds[NLMC_NMC_PHASES_LAUNCH / 16];   // NLMC_PHASE_* of phase p of the launch: bits 2 (p & 15) .. of word p >> 4
-    double cb0, cb1;                 // -2 log2(e) {beta, beta / temp_x}
-    const uint8_t *mask;             // [n_chains][n_pad] backbone masks
-    long long *phase_min;            // [rows][phases_total] or nullptr
-    int32_t *phase_argmin;           // [rows][phases_total] or nullptr
-    int lds_mask_off;
-    int lds_best_off;                // 0: the best state lives in global memory (SweepArgs::best)
-};
 
 // SweepArgs fields of this kernel: graph, chain_base, chain_list, spins, efix, energy_sink, the energy scales, seed, sweep0 = the
 // first sweep of the launch, n_sweeps = sweeps per phase, min_stride, emin / argmin / best (the context's arrays), lane_perm = the
 // orders of all n_phases * n_sweeps sweeps of the launch, lane_rows, lane_diag, lane_tab, lds_u_off.
 template <bool F64>
-__global__ __launch_bounds__(64) void k_nmc_phases_lanes(SweepArgs a, LaneNmcArgs q)
+__global__ __launch_bounds__(64) void k_nmc_phases_lanes(SweepArgs a, NmcPhasesArgs q)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     typedef std::conditional_t<F64, double, float> T;
@@ -57,14 +42,14 @@ __global__ __launch_bounds__(64) void k_nmc_phases_lanes(SweepArgs a, LaneNmcArg
     const uint8_t *mk = lds_raw + q.lds_mask_off;
     unsigned char *bl = q.lds_best_off ? lds_raw + q.lds_best_off : nullptr;
     uint32_t *rtab = a.lane_tab ? reinterpret_cast<uint32_t *>(lds_raw + a.lds_u_off) : nullptr;   // word (spin k, lane l) at k * 64 + l
-    const bool resume = q.phase0 > 0;
+    const int8_t *state_in = nmc_state_in(a, q);
 
     // prologue: state and mask of the 64 chains, read coalesced, written transposed.  A launch that continues a call starts from the
     // best state the launch before it left.
     for (int r = 0; r < 64; ++r) {
         if (r < nrow) {
             const int cr = a.chain_list ? a.chain_list[row0 + r] : row0 + r;
-            lane_column_in(lds_raw, stride, r, (resume ? a.best : a.spins) + (size_t)cr * n_pad, n_pad, lane);
+            lane_column_in(lds_raw, stride, r, state_in + (size_t)cr * n_pad, n_pad, lane);
             lane_column_in(lds_raw + q.lds_mask_off, stride, r, q.mask + (size_t)cr * n_pad, n_pad, lane);
         } else {
             for (int j = lane; j < n_pad; j += 64) {
@@ -78,14 +63,14 @@ __global__ __launch_bounds__(64) void k_nmc_phases_lanes(SweepArgs a, LaneNmcArg
     const uint32_t gc = (uint32_t)(a.chain_base + c);
     const double esc = __longlong_as_double((long long)(1023 + a.escale) << 52);   // 2^escale
     const T cb0 = scale_cb((T)q.cb0, a.qinv), cb1 = scale_cb((T)q.cb1, a.qinv);
-    long long E = resume ? a.emin[c] : a.efix[c];
+    long long E = nmc_energy_in(a, q, c);
     long long Emin = 0;
     int amin = 0;
     // the lanes whose bytes a lane's word of a plane row holds (the best-state copy): lanes 4 (lane & 15) .. + 3
     const int wq = lane & 15;
 
     for (int p = 0; p < q.n_phases; ++p) {
-        const unsigned kind = (q.kinds[p >> 4] >> (2 * (p & 15))) & 3u;
+        const unsigned kind = nmc_phase_kind(q, p);
         if (p > 0) {                                     // k_adopt_best: spins <- best, tracked energy <- the minimum
             if (bl) {
                 const uint32_t *src = reinterpret_cast<const uint32_t *>(bl);
@@ -116,19 +101,14 @@ __global__ __launch_bounds__(64) void k_nmc_phases_lanes(SweepArgs a, LaneNmcArg
                 const int ni = min(64, n - i0);
                 for (int ii = 0; ii < ni; ++ii) {
                     const int k = __builtin_amdgcn_readlane(kv, ii);
-                    unsigned f = 0u;                     // k_phase_flags: hot = backbone scaled, the rest frozen; frozen = backbone frozen
-                    if (kind != NLMC_PHASE_ALL) {
-                        const unsigned m = mk[k * stride + lane];
-                        f = kind == NLMC_PHASE_BACKBONE_HOT ? (m ? 1u : 2u) : (m ? 2u : 0u);
-                    }
+                    unsigned f = 0u;                     // (a plain phase does not read the mask plane)
+                    if (kind != NLMC_PHASE_ALL) f = nmc_phase_flag(kind, mk[k * stride + lane]);
                     lane_update<F64, true>(a, s, rtab, lane, k, f, tt, gc, cb0, cb1, esc, e_loc);
                 }
             }
 
             // end of the sweep: k_sweep_lanes' running minimum and its state (t counts from 0 within the phase)
-            E += e_loc;
-            const bool better = E < Emin && (t % a.min_stride == 0);             // strict <: the first argmin
-            if (better) { Emin = E; amin = t; }
+            const bool better = nmc_sweep_end(E, e_loc, Emin, amin, t, a.min_stride);
             lane_lds_fence();
             unsigned long long m = __ballot(better && live);
             if (bl) {
@@ -151,11 +131,7 @@ __global__ __launch_bounds__(64) void k_nmc_phases_lanes(SweepArgs a, LaneNmcArg
                 }
             }
         }
-        if (q.phase_min && live) {
-            const size_t o = (size_t)row * q.phases_total + (size_t)(q.phase0 + p);
-            q.phase_min[o] = Emin;
-            q.phase_argmin[o] = amin;
-        }
+        if (live) nmc_phase_out(q, row, p, Emin, amin);
     }
 
     // epilogue: the last phase's final state (no adoption), its best state, the tracked energy and the minimum
@@ -165,10 +141,5 @@ __global__ __launch_bounds__(64) void k_nmc_phases_lanes(SweepArgs a, LaneNmcArg
         lane_column_out(lds_raw, stride, r, a.spins + (size_t)cr * n_pad, n_pad, lane);
         if (bl) lane_column_out(bl, stride, r, a.best + (size_t)cr * n_pad, n_pad, lane);
     }
-    if (live) {
-        a.efix[c] = E;
-        if (a.energy_sink) a.energy_sink[c] = (double)E * __longlong_as_double((long long)(1023 - a.escale) << 52);
-        a.emin[c] = Emin;
-        a.argmin[c] = amin;
-    }
+    if (live) nmc_chain_out(a, c, E, Emin, amin);
 }

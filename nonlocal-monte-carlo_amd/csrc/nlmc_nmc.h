@@ -3,6 +3,7 @@
 // phase flags, argmin hand-off.  Nothing here touches the host: a whole round is a chain of stream-ordered launches.
 #pragma once
 #include "nlmc_kernels.h"
+#include "nlmc_nmc_frame.h"
 
 // Stable partition of the local chains by the mark of the temperature slot they currently sit on:
 //   list[0 .. n_unmarked)            local chain ids on unmarked slots, ascending
@@ -113,6 +114,7 @@ __global__ void k_phase_flags(int n_pad, const int32_t *list, const uint8_t *mas
     const int c = list ? list[blockIdx.x] : (int)blockIdx.x;
     const uint8_t *m = mask + (size_t)c * n_pad;
     uint8_t *f = flags + (size_t)c * n_pad;
+    __builtin_assume(kind != NLMC_PHASE_ALL);            // (nlmc_set_phase launches it for kinds 1 and 2 only: a plain phase has no flags)
     for (int i = threadIdx.x; i < n_pad; i += blockDim.x)
-        f[i] = kind == 1 ? (m[i] ? 1 : 2) : (m[i] ? 2 : 0);
+        f[i] = (uint8_t)nmc_phase_flag((unsigned)kind, m[i]);
 }

@@ -18,11 +18,11 @@
 // Same bits as the call sequence on any route; the context's flags array is neither read nor written.
 #pragma once
 #include "nlmc_waves_long.h"
-#include "nlmc_lane_nmc.h"
+#include "nlmc_nmc_frame.h"
 
-// SweepArgs fields of this kernel: those of k_nmc_phases_waves.  LaneNmcArgs: as in k_nmc_phases_lanes, without the LDS offsets.
+// SweepArgs fields of this kernel: those of k_nmc_phases_waves.
 template <int R, bool AHEAD>
-__global__ __launch_bounds__(1024) void k_nmc_phases_waves_long(SweepArgs a, LaneNmcArgs q)
+__global__ __launch_bounds__(1024) void k_nmc_phases_waves_long(SweepArgs a, NmcPhasesArgs q)
 {
     static_assert(R == 8 || R == 16, "eight or sixteen registers");
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -34,7 +34,6 @@ __global__ __launch_bounds__(1024) void k_nmc_phases_waves_long(SweepArgs a, Lan
     const int row = (int)blockIdx.x * W + wv;                      // wave-uniform
     if (row >= a.lane_rows) return;                                // (no barrier anywhere: a wave without a row just leaves)
     const int c = __builtin_amdgcn_readfirstlane(a.chain_list ? a.chain_list[row] : row);
-    const bool resume = q.phase0 > 0;
 
     const NlmcWaveLongNmcRegion G = nlmc_wave_long_nmc_region(n, n_pad);
     unsigned char *reg = lds_raw + (size_t)wv * (size_t)G.bytes;
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(1024) void k_nmc_phases_waves_long(SweepArgs a, Lan
     // launch before it left.  The padding bytes travel with the spins and are never visited.  The best plane starts as the spins:
     // sweep 0 of a phase always improves, so it is whole before a hand-off or the epilogue reads it either way.
     {
-        const uint32_t *s4 = reinterpret_cast<const uint32_t *>((resume ? a.best : a.spins) + (size_t)c * n_pad);
+        const uint32_t *s4 = reinterpret_cast<const uint32_t *>(nmc_state_in(a, q) + (size_t)c * n_pad);
         const uint32_t *m4 = reinterpret_cast<const uint32_t *>(q.mask + (size_t)c * n_pad);
         for (int j4 = lane; j4 < n4; j4 += 64) {
             const uint32_t v = s4[j4];
@@ -89,13 +88,13 @@ __global__ __launch_bounds__(1024) void k_nmc_phases_waves_long(SweepArgs a, Lan
 
     const uint32_t gc = (uint32_t)(a.chain_base + c);
     const float cb0 = wave_long_uniform(scale_cb((float)q.cb0, a.qinv)), cb1 = wave_long_uniform(scale_cb((float)q.cb1, a.qinv));
-    long long E = uniform64(resume ? a.emin[c] : a.efix[c]);
+    long long E = uniform64(nmc_energy_in(a, q, c));
     long long Emin = 0;
     int amin = 0;
     const int nblk = (n + 3) / 4;                                  // <= 256: lane l makes the Philox calls of blocks l, l + 64, ..
 
     for (int p = 0; p < q.n_phases; ++p) {
-        const unsigned kind = (q.kinds[p >> 4] >> (2 * (p & 15))) & 3u;
+        const unsigned kind = nmc_phase_kind(q, p);
         if (p > 0) {                                               // k_adopt_best: spins <- best, fields <- its fields, tracked energy <- the minimum
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -107,11 +106,7 @@ __global__ __launch_bounds__(1024) void k_nmc_phases_waves_long(SweepArgs a, Lan
         }
         Emin = 0x7FFFFFFFFFFFFFFFll;                               // k_fill_min
         amin = 0;
-        // k_phase_flags: hot = backbone scaled, the rest frozen; frozen = backbone frozen
-        for (int j = lane; j < n_pad; j += 64) {
-            const unsigned m = ml[j];
-            fl[j] = (int8_t)(kind == NLMC_PHASE_ALL ? 0 : kind == NLMC_PHASE_BACKBONE_HOT ? (m ? 1 : 2) : (m ? 2 : 0));
-        }
+        for (int j = lane; j < n_pad; j += 64) fl[j] = (int8_t)nmc_phase_flag(kind, ml[j]);
         wave_long_fence();
 
         for (int t = 0; t < a.n_sweeps; ++t) {
@@ -185,21 +180,14 @@ __global__ __launch_bounds__(1024) void k_nmc_phases_waves_long(SweepArgs a, Lan
 
             // end of the sweep: k_sweep_waves_long's running minimum (t counts from 0 within the phase), its state and -- here -- its
             // fields, all inside the wave
-            E += e_loc;
-            const bool better = E < Emin && (t % a.min_stride == 0);                 // strict <: the first argmin; wave-uniform
-            if (better) {
-                Emin = E; amin = t;
+            if (nmc_sweep_end(E, e_loc, Emin, amin, t, a.min_stride)) {              // wave-uniform
 #pragma unroll
                 for (int r = 0; r < R; ++r) Xb[r] = X[r];
                 for (int j4 = lane; j4 < n4; j4 += 64) reinterpret_cast<uint32_t *>(bl)[j4] = reinterpret_cast<const uint32_t *>(sl)[j4];
                 wave_long_fence();
             }
         }
-        if (q.phase_min && lane == 0) {
-            const size_t o = (size_t)row * q.phases_total + (size_t)(q.phase0 + p);
-            q.phase_min[o] = Emin;
-            q.phase_argmin[o] = amin;
-        }
+        if (lane == 0) nmc_phase_out(q, row, p, Emin, amin);
     }
 
     // epilogue: the last phase's final state (no adoption), its best state, the tracked energy and the minimum
@@ -211,10 +199,5 @@ __global__ __launch_bounds__(1024) void k_nmc_phases_waves_long(SweepArgs a, Lan
             b4[j4] = reinterpret_cast<const uint32_t *>(bl)[j4];
         }
     }
-    if (lane == 0) {
-        a.efix[c] = E;
-        if (a.energy_sink) a.energy_sink[c] = (double)E * __longlong_as_double((long long)(1023 - a.escale) << 52);
-        a.emin[c] = Emin;
-        a.argmin[c] = amin;
-    }
+    if (lane == 0) nmc_chain_out(a, c, E, Emin, amin);
 }

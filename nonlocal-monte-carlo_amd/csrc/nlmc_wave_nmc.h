@@ -17,14 +17,16 @@
 // Same bits as the call sequence on any route; the context's flags array is neither read nor written.
 #pragma once
 #include "nlmc_waves.h"
-#include "nlmc_lane_nmc.h"
+#include "nlmc_nmc_frame.h"
 
 // SweepArgs fields of this kernel: graph, chain_base, chain_list, spins, efix, energy_sink, the energy scales, seed, sweep0 = the
 // first sweep of the launch, n_sweeps = sweeps per phase, min_stride, emin / argmin / best (the context's arrays), lane_perm = the
-// orders of all n_phases * n_sweeps sweeps of the launch, lane_rows, wave_J.  LaneNmcArgs: as in k_nmc_phases_lanes, without the LDS
-// offsets.
+// orders of all n_phases * n_sweeps sweeps of the launch, lane_rows, wave_J.  Of csrc/nlmc_nmc_frame.h this kernel takes the arguments
+// and the flag rule only: with the other helpers (nmc_sweep_end alone left out, too) its R = 2 and R = 4 code measured 1.0-1.7 % slower
+// at 128 and 256 spins with every register figure unchanged, so the rest of the frame stays written out here and the kernel compiles
+// to the instructions it had before the frame.
 template <int R, bool JLDS>
-__global__ __launch_bounds__(1024) void k_nmc_phases_waves(SweepArgs a, LaneNmcArgs q)
+__global__ __launch_bounds__(1024) void k_nmc_phases_waves(SweepArgs a, NmcPhasesArgs q)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     constexpr int JS = 64 * R;                                     // row stride of the matrix in global memory
@@ -42,14 +44,13 @@ __global__ __launch_bounds__(1024) void k_nmc_phases_waves(SweepArgs a, LaneNmcA
     const int row = (int)blockIdx.x * W + wv;                      // wave-uniform
     if (row >= a.lane_rows) return;
     const int c = __builtin_amdgcn_readfirstlane(a.chain_list ? a.chain_list[row] : row);
-    const bool resume = q.phase0 > 0;
 
     // lane l owns spins l + 64 r, their mask bytes and, twice, their fields: of the running state and of the phase's best state.  A
     // launch that continues a call starts from the best state the launch before it left.  Padding bytes and the columns of lanes past
     // n_pad: as in k_sweep_waves.
     int jj[R], s[R], X[R], f[R], mk[R], sb[R], Xb[R];
     bool own[R];
-    const int8_t *src = (resume ? a.best : a.spins) + (size_t)c * n_pad;
+    const int8_t *src = (q.phase0 > 0 ? a.best : a.spins) + (size_t)c * n_pad;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int j = lane + 64 * r;
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(1024) void k_nmc_phases_waves(SweepArgs a, LaneNmcA
 
     const uint32_t gc = (uint32_t)(a.chain_base + c);
     const float cb0 = scale_cb((float)q.cb0, a.qinv), cb1 = scale_cb((float)q.cb1, a.qinv);
-    long long E = uniform64(resume ? a.emin[c] : a.efix[c]);
+    long long E = uniform64(q.phase0 > 0 ? a.emin[c] : a.efix[c]);
     long long Emin = 0;
     int amin = 0;
     const int nblk = (n + 3) / 4;                                  // <= 64: lane l makes the Philox call of block l
@@ -93,10 +94,8 @@ __global__ __launch_bounds__(1024) void k_nmc_phases_waves(SweepArgs a, LaneNmcA
         }
         Emin = 0x7FFFFFFFFFFFFFFFll;                               // k_fill_min
         amin = 0;
-        // k_phase_flags: hot = backbone scaled, the rest frozen; frozen = backbone frozen
 #pragma unroll
-        for (int r = 0; r < R; ++r)
-            f[r] = kind == NLMC_PHASE_ALL ? 0 : kind == NLMC_PHASE_BACKBONE_HOT ? (mk[r] ? 1 : 2) : (mk[r] ? 2 : 0);
+        for (int r = 0; r < R; ++r) f[r] = (int)nmc_phase_flag(kind, (unsigned)mk[r]);
 
         for (int t = 0; t < a.n_sweeps; ++t) {
             const int idx = p * a.n_sweeps + t;

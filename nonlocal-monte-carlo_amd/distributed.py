@@ -8,6 +8,7 @@ the (tiny) slot table -- swaps are label exchanges, no configuration ever crosse
 number is a pure function of (seed, global chain id, sweep, spin), the trajectory is bit-identical for any number
 of ranks.
 """
+import collections
 import os
 import sys
 
@@ -36,10 +37,25 @@ WAVE_NMC_IN_LAUNCH = True
 # profiles/wave_long_nmc_throughput.txt).
 WAVE_LONG_NMC_IN_LAUNCH = True
 
-# The one-launch NMC routes in the order a round asks them: Engine.nmc_phases_<route> -> (the option's attribute stem: <stem>_nmc,
-# _<stem>_nmc_by_default, _<stem>_nmc_refused, _<stem>_nmc_asked, <stem>_nmc_rounds, <stem>_nmc_calls; the Engine method that says
-# whether the context's sweeps take that route anyway)
-NMC_ROUTES = {"waves": ("wave", "waves_take"), "waves_long": ("wave_long", "waves_take"), "lanes": ("lane", "lanes_take")}
+# The one-launch NMC routes in the order a round asks them (the wave calls first, as the wave route is asked before the lane route): per
+# route the engine call (`call`, with `call` + "_refusal" beside it), LocalTempering's option keyword, the module constant above that is
+# the option's default (read when a LocalTempering is made) and the Engine method that says whether the context's sweeps take that route
+# anyway.
+NmcRouteSpec = collections.namedtuple("NmcRouteSpec", "call option default take")
+NMC_ROUTES = {"waves": NmcRouteSpec("nmc_phases_waves", "wave_nmc", "WAVE_NMC_IN_LAUNCH", "waves_take"),
+              "waves_long": NmcRouteSpec("nmc_phases_waves_long", "wave_long_nmc", "WAVE_LONG_NMC_IN_LAUNCH", "waves_take"),
+              "lanes": NmcRouteSpec("nmc_phases_lanes", "lane_nmc", "LANE_NMC_IN_LAUNCH", "lanes_take")}
+
+
+class NmcRouteState:
+    """What a LocalTempering keeps per route of NMC_ROUTES: the option (`on`; `by_default`: left to the module constant, and then applied
+    only where the context's sweeps take the route anyway), the contexts (by index) whose engine was `asked` and those whose engine
+    `refused`, and the counters: `rounds` in which every context took the call, `calls` that ran."""
+
+    def __init__(self, option, default):
+        self.on, self.by_default = (default if option is None else bool(option)), option is None
+        self.refused, self.asked = set(), set()
+        self.rounds = self.calls = 0
 
 
 def block_partition(n_global, world, rank):
@@ -356,21 +372,8 @@ class LocalTempering:
         self._planners = None
         self.nmc = None
         self._nmc_planners = None
-        self.lane_nmc = LANE_NMC_IN_LAUNCH if lane_nmc is None else bool(lane_nmc)
-        self._lane_nmc_by_default = lane_nmc is None      # ... then only where the context's sweeps run on the lane kernels anyway
-        self._lane_nmc_refused = set()       # contexts (by index) whose engine turned nmc_phases_lanes down
-        self._lane_nmc_asked = set()         # ... whose engine was asked (Engine.nmc_phases_lanes_refusal)
-        self.lane_nmc_rounds = self.lane_nmc_calls = 0
-        self.wave_nmc = WAVE_NMC_IN_LAUNCH if wave_nmc is None else bool(wave_nmc)
-        self._wave_nmc_by_default = wave_nmc is None      # ... then only where the context's sweeps run on the wave kernels anyway
-        self._wave_nmc_refused = set()       # the same sets for nmc_phases_waves
-        self._wave_nmc_asked = set()
-        self.wave_nmc_rounds = self.wave_nmc_calls = 0
-        self.wave_long_nmc = WAVE_LONG_NMC_IN_LAUNCH if wave_long_nmc is None else bool(wave_long_nmc)
-        self._wave_long_nmc_by_default = wave_long_nmc is None
-        self._wave_long_nmc_refused = set()  # the same sets for nmc_phases_waves_long
-        self._wave_long_nmc_asked = set()
-        self.wave_long_nmc_rounds = self.wave_long_nmc_calls = 0
+        options = dict(lane_nmc=lane_nmc, wave_nmc=wave_nmc, wave_long_nmc=wave_long_nmc)
+        self.nmc_routes = {route: NmcRouteState(options[spec.option], globals()[spec.default]) for route, spec in NMC_ROUTES.items()}
         self.track_best = bool(track_best)
         self.track_energies, self._elog_open = bool(track_energies), False
         if self.track_energies and not self.whole_ladders:
@@ -404,35 +407,34 @@ class LocalTempering:
         # M_skip > 1 (NPT/npt.py:434-437: M = M[:, ::M_skip] before the energies and the argmin): the phases' running minimum looks at
         # every M_skip-th sweep only (nlmc_track_minimum(M_skip)), their recorded traces are strided the same way
 
+    # the options and counters of nmc_routes under the names the keywords and NPT have for them
+    lane_nmc = property(lambda self: self.nmc_routes["lanes"].on)
+    lane_nmc_rounds = property(lambda self: self.nmc_routes["lanes"].rounds)
+    lane_nmc_calls = property(lambda self: self.nmc_routes["lanes"].calls)
+    wave_nmc = property(lambda self: self.nmc_routes["waves"].on)
+    wave_nmc_rounds = property(lambda self: self.nmc_routes["waves"].rounds)
+    wave_nmc_calls = property(lambda self: self.nmc_routes["waves"].calls)
+    wave_long_nmc = property(lambda self: self.nmc_routes["waves_long"].on)
+    wave_long_nmc_rounds = property(lambda self: self.nmc_routes["waves_long"].rounds)
+    wave_long_nmc_calls = property(lambda self: self.nmc_routes["waves_long"].calls)
+
     def _nmc_takes(self, route, k):
-        """Whether context k's NMC phases go to Engine.nmc_phases_<route> (a key of NMC_ROUTES): the option is on, and the engine has
+        """Whether context k's NMC phases go to the engine call of `route` (a key of NMC_ROUTES): the option is on, and the engine has
         not refused (asked once per context: a refusal is remembered).  An option left to its default applies only where the context's
         sweeps take that route anyway (Engine.waves_take / lanes_take)."""
-        kind, take = NMC_ROUTES[route]
-        on, by_default = getattr(self, kind + "_nmc"), getattr(self, f"_{kind}_nmc_by_default")
-        refused, asked = getattr(self, f"_{kind}_nmc_refused"), getattr(self, f"_{kind}_nmc_asked")
-        if not (self.nmc and on) or k in refused:
+        spec, st = NMC_ROUTES[route], self.nmc_routes[route]
+        if not (self.nmc and st.on) or k in st.refused:
             return False
-        if k in asked:
+        if k in st.asked:
             return True
         e = self.engs[k]
-        asked.add(k)
-        on_route = hasattr(e, take) and getattr(e, take)()
-        call = "nmc_phases_" + route
-        if not hasattr(e, call) or (by_default and not on_route) or \
-                (hasattr(e, call + "_refusal") and getattr(e, call + "_refusal")(self.nmc["S"])):
-            refused.add(k)
+        st.asked.add(k)
+        on_route = hasattr(e, spec.take) and getattr(e, spec.take)()
+        if not hasattr(e, spec.call) or (st.by_default and not on_route) or \
+                (hasattr(e, spec.call + "_refusal") and getattr(e, spec.call + "_refusal")(self.nmc["S"])):
+            st.refused.add(k)
             return False
         return True
-
-    def _lane_nmc_takes(self, k):
-        return self._nmc_takes("lanes", k)
-
-    def _wave_nmc_takes(self, k):
-        return self._nmc_takes("waves", k)
-
-    def _wave_long_nmc_takes(self, k):
-        return self._nmc_takes("waves_long", k)
 
     def sweeps_per_round(self, n_sweeps):
         """Plain sweep indices (RNG counters) one round of `n_sweeps` sweeps consumes.  The NMC phases of the marked slots draw from
@@ -516,12 +518,12 @@ class LocalTempering:
                 if wants or took or not self._nmc_takes(route, k):
                     continue
                 try:
-                    getattr(e, "nmc_phases_" + route)(q["phases"], q["S"], self.seed, NMC_SWEEP_SPACE + self.nmc_sweeps_done, q["beta"],
-                                                      q["temp_x"], min_stride=q["M_skip"], precision=self.precision)
+                    getattr(e, NMC_ROUTES[route].call)(q["phases"], q["S"], self.seed, NMC_SWEEP_SPACE + self.nmc_sweeps_done, q["beta"],
+                                                       q["temp_x"], min_stride=q["M_skip"], precision=self.precision)
                     took = True
                     in_launch[route] += 1
                 except NotImplementedError:          # nothing was run: the next route or the phase loop, now and from here on
-                    getattr(self, f"_{NMC_ROUTES[route][0]}_nmc_refused").add(k)
+                    self.nmc_routes[route].refused.add(k)
             if took:
                 e.set_phase("ALL")
                 e.select("all")
@@ -547,10 +549,10 @@ class LocalTempering:
             self._observe(e, self.rounds_done)      # (all chains selected again, the NMC chains in the state they carry on; before the swap)
             outs.append(rec)
         self.sweeps_done += n_sweeps
-        for route, (kind, _) in NMC_ROUTES.items():
-            setattr(self, kind + "_nmc_calls", getattr(self, kind + "_nmc_calls") + in_launch[route])
+        for route, st in self.nmc_routes.items():
+            st.calls += in_launch[route]
             if in_launch[route] and in_launch[route] == len(self.engs):
-                setattr(self, kind + "_nmc_rounds", getattr(self, kind + "_nmc_rounds") + 1)
+                st.rounds += 1
         if self.nmc:
             self.nmc_sweeps_done += len(self.nmc["phases"]) * self.nmc["S"]
         if self.n_pairs > 0:

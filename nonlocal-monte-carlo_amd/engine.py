@@ -821,10 +821,14 @@ class Engine:
         return {"phase_min": None if pmin is None else pmin.astype(np.float64) * 2.0 ** -self.energy_scale,
                 "phase_argmin": parg, "last_best": best}
 
+    def _nmc_refusal(self, route, S):
+        """nmc_phases_<route>_refusal: the library's reason, or None."""
+        why = getattr(self._L, f"nlmc_nmc_phases_{route}_refusal")(self._ctx, int(S))
+        return why.decode() if why else None
+
     def nmc_phases_lanes_refusal(self, sweeps_per_phase):
         """Why nmc_phases_lanes would refuse phases of `sweeps_per_phase` sweeps on this context (the library's reason), or None."""
-        why = self._L.nlmc_nmc_phases_lanes_refusal(self._ctx, int(sweeps_per_phase))
-        return why.decode() if why else None
+        return self._nmc_refusal("lanes", sweeps_per_phase)
 
     def nmc_phases_waves(self, kinds, sweeps_per_phase, seed, sweep0, beta, temp_x, min_stride=1, precision="f32",
                          want_minima=False, want_last_best=False):
@@ -839,8 +843,7 @@ class Engine:
 
     def nmc_phases_waves_refusal(self, sweeps_per_phase):
         """Why nmc_phases_waves would refuse f32 phases of `sweeps_per_phase` sweeps on this context (the library's reason), or None."""
-        why = self._L.nlmc_nmc_phases_waves_refusal(self._ctx, int(sweeps_per_phase))
-        return why.decode() if why else None
+        return self._nmc_refusal("waves", sweeps_per_phase)
 
     def nmc_phases_waves_long(self, kinds, sweeps_per_phase, seed, sweep0, beta, temp_x, min_stride=1, precision="f32",
                               want_minima=False, want_last_best=False):
@@ -857,8 +860,7 @@ class Engine:
     def nmc_phases_waves_long_refusal(self, sweeps_per_phase):
         """Why nmc_phases_waves_long would refuse f32 phases of `sweeps_per_phase` sweeps on this context (the library's reason), or
         None."""
-        why = self._L.nlmc_nmc_phases_waves_long_refusal(self._ctx, int(sweeps_per_phase))
-        return why.decode() if why else None
+        return self._nmc_refusal("waves_long", sweeps_per_phase)
 
     # -- iso-cluster move -------------------------------------------------------------------------------
     def icm_components(self, chain_a, chain_b):

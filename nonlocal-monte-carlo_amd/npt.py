@@ -511,9 +511,8 @@ class NPT(Common):
             sl_ = slots_last[lo_:hi_]
             self._sweep_counter += rounds * lt.sweeps_per_round(S)
             self._nmc_sweep_counter = lt.nmc_sweeps_done          # (the NMC phases draw from a counter range of their own)
-            self.lane_nmc_rounds = getattr(lt, "lane_nmc_rounds", 0)
-            self.wave_nmc_rounds = getattr(lt, "wave_nmc_rounds", 0)
-            self.wave_long_nmc_rounds = getattr(lt, "wave_long_nmc_rounds", 0)
+            took = {route: st.rounds for route, st in getattr(lt, "nmc_routes", {}).items()}       # (LocalTempering's records)
+            self.lane_nmc_rounds, self.wave_nmc_rounds, self.wave_long_nmc_rounds = (took.get(r, 0) for r in ("lanes", "waves", "waves_long"))
             self.sweep_routes = [e.last_sweep_route() for e in getattr(lt, "engs", []) if hasattr(e, "last_sweep_route")]
             lt.check()
             if track_best:

@@ -76,7 +76,7 @@ def test_the_knob_makes_local_tempering_fall_back_once(product, monkeypatch):
             lt.check()
             took = wave_nmc and not knob
             assert lt.wave_nmc_rounds == (3 if took else 0) and (lt._nmc_planners is None) == took
-            assert lt._wave_nmc_refused == ({0} if knob else set())
+            assert lt.nmc_routes["waves"].refused == ({0} if knob else set())
             assert lt.engs[0].last_sweep_route() == "waves"
             ends.append((lt.gather_spins(), lt.slots()))
         finally:

@@ -209,7 +209,7 @@ def test_a_refusing_engine_falls_back_once_and_is_not_asked_again(has_query):
         b.round(S)
     e = a.engs[0]
     assert e.asked == 1 and e.lane_calls == 0 and e.phase_sweeps == 3 * len(PHASES) and a.lane_nmc_rounds == 0
-    assert a._lane_nmc_refused == {0}
+    assert a.nmc_routes["lanes"].refused == {0}
     for x, y in zip(_state(a), _state(b)):
         assert np.array_equal(x, y)
 

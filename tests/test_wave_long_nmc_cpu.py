@@ -115,7 +115,7 @@ def test_the_order_of_asking_is_waves_then_waves_long_then_lanes():
     a.round(S)
     e = a.engs[0]
     assert e.order == ["waves", "waves_long"] and (e.wave_calls, e.long_calls, e.lane_calls) == (0, 1, 0)
-    assert a._wave_nmc_refused == {0} and a._wave_long_nmc_refused == set()
+    assert a.nmc_routes["waves"].refused == {0} and a.nmc_routes["waves_long"].refused == set()
 
     b, c = _long(P, True, engine=RefusingLong, lane_nmc=True), _long(P, False)
     for _ in range(2):
@@ -148,7 +148,7 @@ def test_a_refusal_is_remembered(has_query):
         b.round(S)
     e = a.engs[0]
     assert e.long_asked == 1 and e.long_calls == 0 and e.phase_sweeps == 3 * len(PHASES) and a.wave_long_nmc_rounds == 0
-    assert a._wave_long_nmc_refused == {0}
+    assert a.nmc_routes["waves_long"].refused == {0}
     for x, y in zip(_state(a), _state(b)):
         assert np.array_equal(x, y)
 

@@ -111,7 +111,7 @@ def test_a_refusing_engine_is_asked_once(has_query):
         b.round(S)
     e = a.engs[0]
     assert e.wave_asked == 1 and e.wave_calls == 0 and e.phase_sweeps == 3 * len(PHASES) and a.wave_nmc_rounds == 0
-    assert a._wave_nmc_refused == {0}
+    assert a.nmc_routes["waves"].refused == {0}
     for x, y in zip(_state(a), _state(b)):
         assert np.array_equal(x, y)
 
