@@ -264,7 +264,8 @@ int nlmc_plan_get_levels(nlmc_ctx *ctx, int window, int32_t *out_level_chunk_off
  *   [0] fmt (0 wide: entries { col, Jq } of 8 bytes, 4 planes; 1 compact: col << 16 | Jq & 0xFFFF, 2 planes; 2 address: 16-bit LDS
  *   addresses, 1 plane)  [1] pstride  [2] T  [3] sweep0  [4] seed  [5] workers (a level holds at most 64 workers positions)
  *   [6] quads  [7] bank_aware  [8] n_pad  [9] k_dummy  [10] k_zero  [11] neg_off  [12] tab_words  [13] nlev (0: the window got
- *   no fused schedule -- nothing else is copied then)  [14] npos  [15] hi_max  [16] has_val  [17] level_fill  [18] entry planes.
+ *   no fused schedule -- nothing else is copied then)  [14] npos  [15] hi_max  [16] has_val  [17] level_fill  [18] entry planes
+ *   [19] 1 when the plan carries a head stream (nlmc_plan_get_head_stream).
  * With out_head != NULL the arrays follow, the first npos positions of each (capacity = positions the caller's arrays hold):
  *   out_head [npos][2]               { k | kind << 14 | threshold word << 16, hq_k }
  *   out_ell  [planes][npos][4]       the 16-byte entry planes, position-minor (eight row entries per position)
@@ -275,6 +276,22 @@ int nlmc_plan_get_levels(nlmc_ctx *ctx, int window, int32_t *out_level_chunk_off
 #define NLMC_PLAN_INFO_WORDS 24
 int nlmc_plan_get_items(nlmc_ctx *ctx, int window, int64_t *out_info, int32_t *out_head, int32_t *out_ell, double *out_val,
                         int32_t *out_loff, int32_t *out_send, int64_t capacity);
+/* The head stream of the same window, in the plans that carry one (out_info[19]; NLMC_ERR_STATE otherwise): the plans of a context
+ * whose launches can read it -- an instance without a field term, 2- or 4-byte entries, NLMC_NO_HEAD_STREAM unset; no other context
+ * reserves its memory (ceil(1024 / 4) x workers KB per window) or has the planner write it.  There the planner writes the first head word of every item a second time, in the order the worker
+ * waves of the sweep workgroup read it.  out_hs [ceil(nlev / 4)][workers][64][4] int32 (workers = out_info[5] of
+ * nlmc_plan_get_items): element [l / 4][w][lane][l % 4] is head.x of the item that lane `lane` of worker wave w executes in published
+ * level l, i.e. of schedule position 64 (loff[l] + w) + lane.  Elements of chunks a level does not have (w >= loff[l + 1] - loff[l])
+ * and of levels >= nlev are not defined.  capacity: int32 elements out_hs holds.  A plain fused launch (no per-sweep outputs, not the
+ * real-valued fp64 variant) of an instance without a field term -- every h rounds to 0 on the fixed-point grid -- whose plan has 2-
+ * or 4-byte entries (fmt 1 or 2) reads its heads from this stream: one 16-byte load per four levels instead of an 8-byte load per level.  NLMC_NO_HEAD_STREAM=1, read at nlmc_create,
+ * keeps the per-level loads (same results; for A/B measurements and tests). */
+int nlmc_plan_get_head_stream(nlmc_ctx *ctx, int window, int32_t *out_hs, int64_t capacity);
+/* Where the most recent launch on fused windows (nlmc_sweep_philox on a plan, nlmc_pt_rounds_fused, nlmc_pt_rounds_deferred) read its
+ * item heads: NLMC_HEADS_LOADS (head[], a load per level), NLMC_HEADS_STREAM (the head stream), or 0 (no such launch yet). */
+#define NLMC_HEADS_LOADS 1
+#define NLMC_HEADS_STREAM 2
+int nlmc_last_head_path(nlmc_ctx *ctx);
 /* The same for order `order` of the per-sweep plan (nlmc_plan_philox).  out_info[8]: [0] n  [1] nlev  [2] hi_max  [3] 1 when the
  * global-memory levelizer built the plan (items { k, row start }; { k | degree << 16, row start } otherwise)  [4] the widest level
  * the planner publishes (0: no cap in force)  [5] orders planned  [6] sweep0.  out_order [n][2], out_lvl_off [nlev + 1 <= n + 1];

@@ -31,6 +31,7 @@ WAVES_OFF, WAVES_AUTO, WAVES_FORCE = 0, 1, 2
 ROUTE_NONE, ROUTE_STEPWISE, ROUTE_FUSED, ROUTE_LANES, ROUTE_WAVES = 0, 1, 2, 3, 4
 ROUNDS_IN_LAUNCH, ROUNDS_LAUNCH_PER_ROUND, ROUNDS_LANES, ROUNDS_APT_LANES, ROUNDS_WAVES = 1, 2, 3, 4, 5     # include/nlmc.h: nlmc_pt_rounds_route
 ROUNDS_WAVES_LONG = 6                # include/nlmc.h: NLMC_ROUNDS_WAVES_LONG, the rounds inside k_rounds_waves_long launches
+HEADS_LOADS, HEADS_STREAM = 1, 2     # include/nlmc.h: nlmc_last_head_path
 PHASE_ALL, PHASE_BACKBONE_HOT, PHASE_BACKBONE_FROZEN = 0, 1, 2
 
 EXPORTS = [
@@ -49,7 +50,7 @@ EXPORTS = [
     "nlmc_nmc_phases_waves_long", "nlmc_nmc_phases_waves_long_refusal",
     "nlmc_best_begin", "nlmc_best_update", "nlmc_best_read", "nlmc_best_end",
     "nlmc_elog_begin", "nlmc_elog_update", "nlmc_elog_read", "nlmc_elog_end",
-    "nlmc_plan_get_items", "nlmc_plan_get_order",
+    "nlmc_plan_get_items", "nlmc_plan_get_order", "nlmc_plan_get_head_stream", "nlmc_last_head_path",
 ]
 
 
@@ -176,6 +177,7 @@ def lib():
                        ("nlmc_plan_get_levels", [_vp, _i, _vp, _i, _vp]),
                        ("nlmc_plan_get_items", [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64]),
                        ("nlmc_plan_get_order", [_vp, _i, _vp, _vp, _vp, ctypes.c_int64]), ("nlmc_comm_unique_id", [_vp]), ("nlmc_comm_init", [_vp, _vp, _i, _i]),
+                       ("nlmc_plan_get_head_stream", [_vp, _i, _vp, ctypes.c_int64]), ("nlmc_last_head_path", [_vp]),
                        ("nlmc_pt_swap_philox_collective", [_vp, _u32, _u64, _i, _i, _vp, _vp]), ("nlmc_comm_probe", []), ("nlmc_comm_check", [_vp, _i]),
                        ("nlmc_pt_rounds_fused", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),
                        ("nlmc_pt_rounds_deferred", [_vp, _i, _i, _i, _u32, _u32, _u64, _i]),

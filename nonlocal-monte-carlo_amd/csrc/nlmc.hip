@@ -92,6 +92,7 @@ struct Knobs {
     bool no_bank_aware = false;      // NLMC_NO_BANK_AWARE: the fused planner does not place items by LDS bank
     bool no_quads = false;           // NLMC_NO_QUADS: a row of more than 16 entries takes a lane pair and its CSR tail, not a lane quad
     bool no_level_fill = false;      // NLMC_NO_LEVEL_FILL: the fused planner gives every update its earliest level and splits full levels
+    bool no_head_stream = false;     // NLMC_NO_HEAD_STREAM: fused level loops load an item head per level, never the plan's head stream (A/B, tests)
     bool fz_stats = false;           // NLMC_FZ_STATS: the fused planner prints the phase cycle counts of window 0 on stderr
     unsigned tie_mask = 0xFFFFFFFFu; // NLMC_F64_TIE_MASK: high-word mask of the fp64 fused kernels' exact-path test (test knob)
     bool no_persistent = false;      // NLMC_NO_PERSISTENT: nlmc_pt_rounds_fused refuses, nlmc_pt_rounds_deferred launches per round
@@ -127,6 +128,7 @@ Knobs read_knobs()
     k.no_warm = on("NLMC_NO_WARM"); k.no_prio = on("NLMC_FUSED_NOPRIO"); k.no_dbuf = on("NLMC_NO_DBUF");
     k.big_per_level = on("NLMC_BIG_PER_LEVEL") ? num("NLMC_BIG_PER_LEVEL", 0) != 0 : -1;
     k.no_bank_aware = on("NLMC_NO_BANK_AWARE"); k.no_level_fill = on("NLMC_NO_LEVEL_FILL"); k.fz_stats = on("NLMC_FZ_STATS"); k.no_quads = on("NLMC_NO_QUADS");
+    k.no_head_stream = num("NLMC_NO_HEAD_STREAM", 0) != 0;
     if (const char *s = getenv("NLMC_F64_TIE_MASK")) k.tie_mask = (unsigned)strtoul(s, nullptr, 0);
     k.no_persistent = on("NLMC_NO_PERSISTENT"); k.no_deferred = on("NLMC_NO_DEFERRED");
     k.lbp_group = num("NLMC_LBP_GROUP", 0); k.lbp_poll_budget = num("NLMC_LBP_POLL_BUDGET", 0); k.lbp_global = on("NLMC_LBP_GLOBAL");
@@ -168,6 +170,7 @@ struct nlmc_ctx {
     bool f64_exact = false;            // every J AND every h is an exact multiple of 2^-qs: the fp64 field is the integer field times
                                        // 2^-qs, the fp64 mode may run on fused windows (k_sweep_fused<.., F64>)
     int xmax = 0;                      // max over rows of sum |Jq| + |hq|: the range of the integer field
+    bool no_field = false;             // every hq is 0: plain fused launches read the item heads from the plan's head stream
     bool f64_real = false;             // nlmc_set_fused_f64_real: the fp64 mode runs on fused windows for real couplings / fields too
                                        // (k_sweep_fused<.., R64>; plans then carry the fp64 value plane)
     Knobs knobs;                       // the environment switches, read at nlmc_create
@@ -323,6 +326,7 @@ struct nlmc_ctx {
     int n_long = 0;                    // schedule positions a sweep takes beyond one per row in a fused plan: one for a row of more than
                                        // NLMC_FZ_W entries (a lane pair), three for one of more than 2 NLMC_FZ_W (a lane quad)
     int stat_fused_window = -1;          // >= 0: the most recent sweep call ran this fused window
+    int stat_head_path = 0;              // NLMC_HEADS_*: where the most recent fused launch read its item heads (0: no such launch yet)
     // Two plan slots (nlmc_plan_slot): a replica-exchange round whose marked slots run NMC cycles sweeps its plain chains
     // on windows of one length and its NMC phases on windows of another (NPT/npt.py:577-580).
     struct FusedPlan {
@@ -340,13 +344,15 @@ struct nlmc_ctx {
         DevBuf<EdgeQ> ell;
         DevBuf<double> val;           // [windows][NLMC_FZ_VAL_WORDS * pstride] (has_val only)
         DevBuf<int32_t> loff, nlev, himax, send;
-        void release() { npos.release(); head.release(); ell.release(); val.release(); loff.release(); nlev.release(); himax.release(); send.release(); }
-        struct Arrays { const int32_t *loff, *nlev, *himax, *send, *npos; const int2 *head; const EdgeQ *ell; const double *val; };
+        bool has_hs = false;          // the plan carries the head stream (fused_plan_stream)
+        DevBuf<int4> hs;              // [windows][fused_hs_window(workers)] head stream (fused_hs_index), has_hs only
+        void release() { npos.release(); head.release(); ell.release(); val.release(); loff.release(); nlev.release(); himax.release(); send.release(); hs.release(); }
+        struct Arrays { const int32_t *loff, *nlev, *himax, *send, *npos; const int2 *head; const EdgeQ *ell; const double *val; const int4 *hs; };
         Arrays at(int w) const        // the plan arrays at window w (val: nullptr without the value plane)
         {
             const size_t W = (size_t)w, PS = (size_t)pstride;
             return {loff.p + W * (NLMC_LCAP + 1), nlev.p + W, himax.p + W, send.p + W * T, npos.p + W, head.p + W * PS, ell.p + W * PS * NLMC_FZ_W,
-                    has_val ? val.p + W * NLMC_FZ_VAL_WORDS * PS : nullptr};
+                    has_val ? val.p + W * NLMC_FZ_VAL_WORDS * PS : nullptr, has_hs ? hs.p + W * fused_hs_window(workers) : nullptr};
         }
     };
     FusedPlan fz[2];
@@ -742,6 +748,14 @@ bool fused_addr_format(const nlmc_ctx *c)
     return c->sign8 && 2 * (c->n_pad + 16) <= 0xFFFF && fused_lds(c->n_pad, true, false, true).total <= (size_t)150 * 1024;
 }
 
+// Do the context's fused plans carry a head stream (FusedPlan::hs)?  Only where a launch can read it (head_stream below): an
+// instance without a field term whose plans have the address or the compact format, NLMC_NO_HEAD_STREAM unset.  Every other
+// context neither reserves the stream's memory nor has the planner write it.
+bool fused_plan_stream(const nlmc_ctx *c)
+{
+    return c->no_field && !c->knobs.no_head_stream && (fused_addr_format(c) || c->compact16);
+}
+
 // schedule positions reserved per window: one per update, two or four for a row on a lane pair or quad (n_long more per sweep),
 // plus the padding of every level to a chunk boundary
 int fused_pstride(int n, int n_long, int T) { return (int)((((size_t)T * ((size_t)n + n_long) + 63) / 64 + NLMC_LCAP) * 64); }
@@ -884,6 +898,15 @@ void fused_args(const nlmc_ctx *c, const nlmc_ctx::FusedPlan &P, const FusedLds 
     a.lds_snap_off = L.snap_off; a.lds_kt_off = L.kt_off; a.f64_xmax = c->xmax; a.f64_tie_mask = c->knobs.tie_mask;
 }
 
+// Does a fused launch read its item heads from the plan's head stream (fused_levels<.., HS>)?  The plain integer-field loops of an
+// instance without a field term: head.y, which the stream does not carry, is 0 in every item.  Any other launch loads head[].
+// And not a plan in the wide entry format, whose kernels have no such loop (fused_window: registers).  The plan was built with the
+// stream exactly where these conditions on the context hold (fused_plan_stream).
+bool head_stream(const nlmc_ctx *c, const nlmc_ctx::FusedPlan &P, bool outs, int arith)
+{
+    return P.has_hs && c->no_field && !outs && arith != ARITH_R64 && P.fmt != NLMC_FMT_WIDE && !c->knobs.no_head_stream;
+}
+
 // NLMC_STAMPS builds: the per-wave cycle sums of a launch of `rows` workgroups go to c->dbg, cleared on the launch's stream
 int stamps_arm([[maybe_unused]] nlmc_ctx *c, [[maybe_unused]] SweepArgs &a, [[maybe_unused]] int rows, [[maybe_unused]] hipStream_t st)
 {
@@ -968,10 +991,13 @@ int run_fused(nlmc_ctx *c, const SweepCall &s, int slot, int w, int at, int arit
     const nlmc_ctx::FusedPlan::Arrays A = P.at(w);
     a.lvl_off = A.loff; a.nlev = A.nlev; a.hi_max = A.himax; a.fsend = A.send;
     a.ell32 = A.ell; a.head32 = A.head;
+    const bool stream = head_stream(c, P, outs, arith);
+    a.hs = stream ? A.hs : nullptr;
     if (w + 1 < P.windows && P.nlev_host[(size_t)w + 1] > 0 && !c->knobs.no_warm) {
-        a.warm_head = P.at(w + 1).head;
+        a.warm_head = stream ? reinterpret_cast<const int2 *>(P.at(w + 1).hs) : P.at(w + 1).head;
         a.warm_ell = P.at(w + 1).ell;
         a.fz_npos_next = P.npos_host[(size_t)w + 1];
+        a.fz_nl_next = P.nlev_host[(size_t)w + 1];
     }
     a.energy_sink = sink_override ? sink_override : c->energy_sink;
     if (defer) a.defer = *defer;
@@ -986,6 +1012,7 @@ int run_fused(nlmc_ctx *c, const SweepCall &s, int slot, int w, int at, int arit
     count_launches(c, 1, timed);
     c->stat_fused_window = w;
     c->stat_fused_slot = slot;
+    c->stat_head_path = stream ? NLMC_HEADS_STREAM : NLMC_HEADS_LOADS;
     return NLMC_OK;
 }
 
@@ -1630,6 +1657,7 @@ int nlmc_create(nlmc_ctx **out, int device, void *hip_stream, int n, int64_t nnz
     c->f64_pack16 = I.fits16 && I.exact_q && n <= 65535 && !c->knobs.no_pack64;
     c->sign8 = c->compact16 && I.pm1 && nnz > 0 && !c->knobs.no_signfmt;
     c->f64_exact = I.exact_q && I.exact_h;
+    c->no_field = I.no_field;
 
     size_t total = 256, off = 0;
     c->arena_buffers([&](auto &buf, size_t count) { total += buf.arena_bytes(count); });
@@ -1942,6 +1970,7 @@ static int reserve_fused_plan(nlmc_ctx *c, int n_windows, int T, bool with_val =
     HIP_TRY(c, c->fz_glv.reserve(W * TN));
     HIP_TRY(c, c->fz_perm.reserve(W * PS));
     HIP_TRY(c, P.head.reserve(W * PS));
+    if (fused_plan_stream(c)) HIP_TRY(c, P.hs.reserve(W * fused_hs_window(fused_workers(c, fused_block(c)))));
     HIP_TRY(c, P.ell.reserve(W * PS * NLMC_FZ_W));
     HIP_TRY(c, P.loff.reserve(W * (NLMC_LCAP + 1)));
     HIP_TRY(c, P.nlev.reserve(W));
@@ -2003,7 +2032,9 @@ int nlmc_plan_philox_fused(nlmc_ctx *c, uint32_t sweep0, int n_windows, int wind
     a.val = with_val ? P.val.p : nullptr;
     P.fmt = a.fmt;
     P.has_val = with_val;
-    a.adj = reinterpret_cast<const uint4 *>(c->fz_adj.p); a.glv = c->fz_glv.p; a.perm = c->fz_perm.p; a.head = P.head.p; a.ell = P.ell.p; a.loff = P.loff.p; a.nlev = P.nlev.p;
+    a.adj = reinterpret_cast<const uint4 *>(c->fz_adj.p); a.glv = c->fz_glv.p; a.perm = c->fz_perm.p; a.head = P.head.p; a.ell = P.ell.p;
+    P.has_hs = fused_plan_stream(c);
+    a.hs = P.has_hs ? P.hs.p : nullptr; a.loff = P.loff.p; a.nlev = P.nlev.p;
     a.hi_max = P.himax.p; a.send = P.send.p; a.npos = P.npos.p;
     P.built = a;
     const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
@@ -2120,7 +2151,7 @@ int nlmc_plan_get_items(nlmc_ctx *c, int window, int64_t *out_info, int32_t *out
     HIP_TRY(c, hipMemcpyAsync(&himax, A.himax, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const int64_t info[NLMC_PLAN_INFO_WORDS] = {P.fmt, P.pstride, P.T, (int64_t)P.sweep0, (int64_t)P.seed, P.workers, b.quads, b.bank_aware, c->n_pad,
-                                                b.k_dummy, b.k_zero, b.neg_off, b.tab_words, nl, np, himax, P.has_val ? 1 : 0, b.level_fill, planes};
+                                                b.k_dummy, b.k_zero, b.neg_off, b.tab_words, nl, np, himax, P.has_val ? 1 : 0, b.level_fill, planes, P.has_hs ? 1 : 0};
     for (int i = 0; i < NLMC_PLAN_INFO_WORDS; ++i) out_info[i] = info[i];
     if (!out_head || nl == 0) return NLMC_OK;
     if (!out_ell || !out_loff || !out_send || (P.has_val && !out_val)) return fail(c, NLMC_ERR_ARG, "nlmc_plan_get_items: NULL array");
@@ -2140,6 +2171,24 @@ int nlmc_plan_get_items(nlmc_ctx *c, int window, int64_t *out_info, int32_t *out
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NLMC_OK;
 }
+
+int nlmc_plan_get_head_stream(nlmc_ctx *c, int window, int32_t *out_hs, int64_t capacity)
+{
+    if (!c || !out_hs) return fail(c, NLMC_ERR_ARG, "nlmc_plan_get_head_stream: NULL argument");
+    const nlmc_ctx::FusedPlan &P = c->fz[c->fz_slot];
+    if (!P.valid || window < 0 || window >= P.windows) return fail(c, NLMC_ERR_STATE, "nlmc_plan_get_head_stream: no such planned window in the selected slot");
+    if (!P.has_hs) return fail(c, NLMC_ERR_STATE, "nlmc_plan_get_head_stream: the plan has no head stream (a field term, 8-byte entries, or NLMC_NO_HEAD_STREAM)");
+    const int nl = P.nlev_host[(size_t)window];
+    const size_t count = fused_hs_index(nl + 3, P.workers, 0, 0);       // int4 elements of the quads of levels [0, nl)
+    if (capacity < (int64_t)(count * 4)) return fail(c, NLMC_ERR_ARG, "nlmc_plan_get_head_stream: capacity < 4 * 64 * workers * ceil(nlev / 4)");
+    if (count == 0) return NLMC_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out_hs, P.at(window).hs, sizeof(int4) * count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NLMC_OK;
+}
+
+int nlmc_last_head_path(nlmc_ctx *c) { return c ? c->stat_head_path : 0; }
 
 int nlmc_plan_get_order(nlmc_ctx *c, int order, int64_t *out_info, int32_t *out_order, int32_t *out_lvl_off, int64_t capacity)
 {
@@ -2842,6 +2891,7 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
         const nlmc_ctx::FusedPlan::Arrays A = P.at(w0);
         q.loff = A.loff; q.nlev = A.nlev; q.himax = A.himax; q.send = A.send; q.npos = A.npos; q.head = A.head; q.ell = A.ell;
         q.val = real ? A.val : nullptr;
+        q.hs = head_stream(c, P, false, arith) ? A.hs : nullptr;
         q.ladder_len = L; q.n_pairs = n_pairs; q.n_ladders = nl; q.round0 = r0;
         const RoundRows rows = round_rows(c, r0, (size_t)nl, n_pairs, log);
         q.plan_pairs = rows.plan_pairs; q.log_pairs = rows.log_pairs; q.log_acc = rows.log_acc;
@@ -2870,6 +2920,7 @@ static int rounds_in_launch(nlmc_ctx *c, int fslot, int arith, int n_rounds, int
         c->stat_fused_window = w0 + k - 1;
     }
     c->stat_fused_slot = fslot;
+    c->stat_head_path = head_stream(c, P, false, arith) ? NLMC_HEADS_STREAM : NLMC_HEADS_LOADS;
     c->sub_dirty = true;
     c->rounds_route = NLMC_ROUNDS_IN_LAUNCH;
     return NLMC_OK;

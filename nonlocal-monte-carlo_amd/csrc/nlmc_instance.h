@@ -27,6 +27,7 @@ struct NlmcInstance {
     bool pm1 = false;                  // every Jq is +-1 (sign format: col | (Jq < 0) << 15)
     bool exact_q = false;              // every J is Jq 2^-qs exactly (packed fp64 schedule window)
     bool exact_h = false;              // every h is hq 2^-qs exactly
+    bool no_field = false;             // every hq is 0: no item of a fused plan carries a field (the head stream's condition)
     int xmax = 0;                      // max over rows of sum |Jq| + |hq|: the range of the integer field
     std::vector<EdgeQ> e32;            // [max(nnz, 1)] (column, Jq) in CSR order: what nlmc_create uploads
     std::vector<int32_t> hq;           // [n]
@@ -126,8 +127,10 @@ inline int nlmc_instance_prepare(NlmcInstance &I, const void *out, int n, int64_
     }
     I.fits16 = fits16; I.pm1 = pm1; I.exact_q = exact_q;
     I.exact_h = true;
+    I.no_field = true;
     for (int k = 0; k < n; ++k) {
         I.hq[k] = (int32_t)rq(h[k], qs);
+        if (I.hq[k] != 0) I.no_field = false;
         if (std::ldexp((double)I.hq[k], -qs) != h[k]) I.exact_h = false;
         int64_t row = std::llabs((int64_t)I.hq[k]);
         for (int e = rowptr[k]; e < rowptr[k + 1]; ++e) row += std::llabs((int64_t)e32[e].q);

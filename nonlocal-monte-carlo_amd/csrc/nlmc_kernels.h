@@ -242,6 +242,16 @@ __global__ void k_levelize(LevelizeArgs a)
 #define NLMC_FZ_KIND_QUAD 2      // 17-32 entries on an aligned lane quad
 #define NLMC_FZ_KIND_TAIL 3      // longer than the widest group of the plan -- a quad (32 entries), or a pair (16) under
                                  // NLMC_NO_QUADS: the rest is read from the CSR arrays inside the level loop
+// Head stream of a fused window: the first head word of every item once more, in the order the worker waves read it -- int4 number
+// fused_hs_index(l, workers, w, lane), component l & 3, is head.x of the item that lane `lane` of worker wave w executes in
+// published level l (chunk w of that level), so one 16-byte load per lane brings a wave its heads of four consecutive levels.
+// Slots of chunks a level does not have, and of levels behind the last one, are allocated and never written.
+// The one place that knows the layout: the planner stores through it, and the sweep kernel's level loop takes its lane offset, its
+// wave's offset and the stride from one quad of levels to the next from it (fused_levels<.., HS> relies on the index being affine in
+// level >> 2, with a lane's 16 bytes contiguous inside a wave's slot).
+__host__ __device__ inline size_t fused_hs_index(int level, int workers, int w, int lane) { return ((size_t)(level >> 2) * (size_t)workers + (size_t)w) * 64 + (size_t)lane; }
+// int4 elements of one window's stream (NLMC_LCAP levels)
+__host__ __device__ inline size_t fused_hs_window(int workers) { return (size_t)((NLMC_LCAP + 3) / 4) * (size_t)workers * 64; }
 struct FusedLevelizeArgs {
     CsrDev g;
     int T;                    // sweeps per window
@@ -272,6 +282,7 @@ struct FusedLevelizeArgs {
     int32_t *npos;            // [n_windows] schedule positions in use (multiple of 64)
     double *val;              // nullptr, or [n_windows][NLMC_FZ_VAL_WORDS * pstride] fp64 value plane of the real-valued fp64 variant
                               // (k_sweep_fused<.., R64>): entries in CSR order, so bank_aware must be 0 (see NLMC_FZ_VAL_WORDS)
+    int4 *hs;                 // [n_windows][fused_hs_window(level_cap / 64)] head stream (fused_hs_index), written beside head[]
 };
 // fp64 value plane of a fused plan (real couplings and fields, nlmc_set_fused_f64_real), doubles per schedule position: planes
 // 0-3 hold { v(2q), v(2q+1) } of the position's eight entries (16 B per position and plane, laid out like the entry planes), plane
@@ -532,6 +543,19 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
     // A dummy item updates the scratch spin behind the real ones from an all-zero row: harmless by construction.
     int2 *head = a.head + (size_t)w * PS;
     int4 *ell = reinterpret_cast<int4 *>(a.ell) + (size_t)w * (NLMC_FZ_W / 2) * PS;
+    // The head stream (fused_hs_index) gets head.x of every position of a published chunk, padding included.  The published level
+    // of a position comes from the level offsets: a thread's positions grow, so its level index only ever moves forward.
+    const int hs_workers = a.level_cap >> 6;
+    int *const hs_w = a.hs ? reinterpret_cast<int *>(a.hs + (size_t)w * fused_hs_window(hs_workers)) : nullptr;   // (a plan without a stream)
+    const int32_t *const hs_off = a.loff + (size_t)w * (NLMC_LCAP + 1);       // (written by thread 0 before the barrier above)
+    int hs_lv = 0;
+    auto put_head = [&](int pos, int hx, int hy) {
+        head[pos] = make_int2(hx, hy);
+        if (!hs_w) return;
+        const int chunk = pos >> 6;
+        while (hs_off[hs_lv + 1] <= chunk) ++hs_lv;          // (pos < npos: chunk lies below the last offset)
+        hs_w[fused_hs_index(hs_lv, hs_workers, chunk - hs_off[hs_lv], pos & 63) * 4 + (size_t)(hs_lv & 3)] = hx;
+    };
     // Bank-aware entry order (round 4).  The sweep kernel gathers entry q of all 64 items of a chunk with ONE ds_read_u8; the LDS
     // serves it per half-wave of 32 lanes over 32 banks of 4 bytes (scripts/probes/lds_conflict_probe.hip: same bank + different dword
     // inside a half = one more pass: 205 / 280 / 486 ns per round of 8 gathers at 1 / 2 / 4 lanes per bank; random addresses 303).  The
@@ -568,7 +592,7 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
             }
             // (threshold word 3 tab_words: behind the three tables / snapshot slots, so that a dummy's threshold read and
             // snapshot write touch nothing that belongs to a spin)
-            head[pos] = make_int2(a.k_dummy | ((3 * a.tab_words) << 16), 0);
+            put_head(pos, a.k_dummy | ((3 * a.tab_words) << 16), 0);
             if (a.fmt == NLMC_FMT_ADDR) {
                 const int z2 = a.k_zero | (a.k_zero << 16);
                 ell[pos] = make_int4(z2, z2, z2, z2);
@@ -660,7 +684,7 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
                     pk[q / 2] |= v16 << (16 * (q & 1));
                 }
                 ell[pos] = make_int4((int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]);
-                head[pos] = make_int2(k | (kind << 14) | thr, hy);
+                put_head(pos, k | (kind << 14) | thr, hy);
                 continue;
             }
             EdgeQ od[NLMC_FZ_W];
@@ -694,7 +718,7 @@ __global__ __launch_bounds__(1024) void k_levelize_fused(FusedLevelizeArgs a)
             }
             ell[pos] = make_int4((int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]);
         }
-        head[pos] = make_int2(k | (kind << 14) | thr, hy);
+        put_head(pos, k | (kind << 14) | thr, hy);
         if (a.fmt == NLMC_FMT_ADDR) continue;
         if (a.fmt == NLMC_FMT_COMPACT) {
             uint32_t pk[NLMC_FZ_W];
@@ -844,7 +868,11 @@ struct SweepArgs {
     int lane_tab;                 // 1: a sweep's random numbers sit in an LDS table at lds_u_off, 0: the Philox call is made per update
     const int32_t *wave_J;        // wave-per-chain sweeps (k_sweep_waves, csrc/nlmc_waves.h): the dense fixed-point matrix [n][64 R]
     int dbg_flags;            // -DNLMC_DEBUG_KNOBS builds only (NLMC_DBG_FLAGS): 1 = no threshold production, 2 = no updates, 4 = no item loads,
-                              // 512 / 1024 = bank-conflict-free addresses for the neighbour gather / the spin's own accesses (wrong results)
+                              // 512 / 1024 = bank-conflict-free addresses for the neighbour gather / the spin's own accesses (wrong results),
+                              // 4096 = item heads from a constant, planes still loaded (wrong results)
+    const int4 *hs;           // the window's head stream (fused_hs_index), or nullptr: the level loop loads head32.  With a stream
+                              // warm_head is the NEXT window's stream, of fz_nl_next levels
+    int fz_nl_next;
 };
 
 // a wave-uniform 64-bit value pinned into scalar registers (a uniform value in a vector register costs 64 lanes, a spilled
@@ -1739,6 +1767,8 @@ struct FusedWin {
     int nl, hi_max;
     uint32_t sweep0;              // global index of the window's first sweep
     const double *val;            // fp64 value plane (k_sweep_fused<.., R64> only)
+    const int4 *hs;               // head stream, or nullptr: heads come from `head`.  With a stream warm_head is the next window's
+    int nl_next;                  // stream and nl_next its level count
 };
 // the fp64 value-plane entries of one schedule chunk (k_sweep_fused<.., R64>): eight couplings and the field, see NLMC_FZ_VAL_WORDS
 struct FusedVals {
@@ -1863,13 +1893,19 @@ __device__ __forceinline__ double quad_move_f64(double v)
 // table of its item's slot in a ring of three (Khi[3] | Klo[3], built at each sweep's cb: the first two by the window's prologue, the
 // others by NLMC_GEN_KT), in the rare exact path too.  The real-valued variant has no such loop: its anneal measured slower than sweep
 // by sweep and runs there (fused_route).
-template <bool DIAG, bool FLAGS, bool PAIR, bool GEN, int FMT, bool OUT = false, bool F64 = false, bool R64 = false, bool SWT = false>
+//
+// HS (no OUT, no R64; instances without a field term): the heads come from the window's head stream (fused_hs_index) -- one
+// 16-byte load per FOUR levels with this wave's head words of those levels, beside the one plane set per level, instead of an
+// 8-byte head load every level: 1.25 instead of 2 vector-memory instructions per wave and level on the CU's one address path, 20
+// instead of 24 bytes per position.  head.y (the field hq_k) is not loaded: it is 0 in every item of such an instance.
+template <bool DIAG, bool FLAGS, bool PAIR, bool GEN, int FMT, bool OUT = false, bool F64 = false, bool R64 = false, bool SWT = false, bool HS = false>
 __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin &W, unsigned char *lds_raw, int wv, int lane, int nl, float cq0,
                                              float cq1, long long &e_loc, const FusedGenParams gp, double cb64 = 0.0, double cb64_1 = 0.0)
 {
     constexpr bool g_f64 = F64, g_swt = SWT;
     static_assert(!R64 || F64, "the real-valued fp64 variant rides on the fp64 uniform tables");
     static_assert(!SWT || (OUT && F64 && !FLAGS && !R64), "a temperature per sweep in the fp64 mode: integer thresholds, output variant, no phase flags");
+    static_assert(!HS || (!OUT && !R64), "the head stream feeds the plain integer-field loop only");
     NLMC_GEN_STATE
     NLMC_GEN_ARM(a, gp)
     typedef const int32_t __attribute__((address_space(4))) *const_i32o;
@@ -1952,7 +1988,16 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
                 it.pk[q].z = (int)__builtin_amdgcn_raw_buffer_load_b32(r_ell, v16, c * 1024 + q * plane_bytes + 8, 0);
                 it.pk[q].y = it.pk[q].w = 0;
             }
+        } else if constexpr (HS) {       // (the head words come with issue_h, four levels at a time)
+#pragma unroll
+            for (int q = 0; q < NP; ++q) it.pk[q] = __builtin_amdgcn_raw_buffer_load_b128(r_ell, v16, c * 1024 + q * plane_bytes, 0);
         } else {
+#ifdef NLMC_DEBUG_KNOBS
+            // timing experiment: the head from a per-lane constant instead of a load, the planes still loaded (wrong results) -- what
+            // a level loop without head loads could save at most.  Spin k = the conflict-free address of flag 1024, threshold word = lane.
+            if (a.dbg_flags & 4096) it.hd = nlmc_i2{(int)(((unsigned)lane << 16) | (unsigned)((lane & 31) * 4 + (lane >> 5))), 0};
+            else
+#endif
             it.hd = __builtin_amdgcn_raw_buffer_load_b64(r_head, v16 >> 1, c * 512, 0);
 #pragma unroll
             for (int q = 0; q < NP; ++q) it.pk[q] = __builtin_amdgcn_raw_buffer_load_b128(r_ell, v16, c * 1024 + q * plane_bytes, 0);
@@ -2280,7 +2325,61 @@ __device__ __forceinline__ void fused_levels(const SweepArgs &a, const FusedWin 
 #ifdef NLMC_STAMPS
     long long sw0, sw1, sw2, st_work = 0, st_bar = 0, st_calls = 0;
 #endif
-    {
+    if constexpr (HS) {
+        // Four plane sets rotated by a 4x unrolled loop (the planes of level l + 2 are issued in level l, as below), and the head
+        // words of levels 4q .. 4q + 3 in one register quad: the quad of the NEXT four levels is issued in the third level of the
+        // body -- two levels before its first word is used, like a plane set -- into Hn, and moves to Hc after the first level
+        // that reads it (by then the wait for that level's planes, issued behind it, has covered it).  The quad's scalar offset
+        // and the lane's vector offset both come from fused_hs_index, the function the planner places the words with: the wave's
+        // first int4 of the quad (wave-uniform: once per four levels on the scalar unit), and the lane's int4 inside a wave's
+        // slot.  A quad wholly behind the last level: every lane out of range.
+        const __amdgpu_buffer_rsrc_t r_hs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int4 *>(W.hs), 0, (int)(fused_hs_window(a.f_workers) * sizeof(int4)), 0x00020000);
+        // (The index is affine in the quad number -- see fused_hs_index -- so the scalar offset of quad lq is lq strides from the
+        // wave's slot of quad 0: two launch constants.  Calling the function per quad with its 64-bit arithmetic measured 2 % of a
+        // bench step: the loop has no scalar register to spare.)
+        const int hs_lane = (int)(fused_hs_index(0, a.f_workers, 0, lane) * sizeof(int4));
+        const int hs_wave = (int)(fused_hs_index(0, a.f_workers, wv, 0) * sizeof(int4));
+        const int hs_quad = (int)((fused_hs_index(4, a.f_workers, 0, 0) - fused_hs_index(0, a.f_workers, 0, 0)) * sizeof(int4));
+        auto issue_h = [&](nlmc_i4 &H, int lq) __attribute__((always_inline)) {
+#ifdef NLMC_DEBUG_KNOBS
+            if (a.dbg_flags & 32) return;
+#endif
+            H = __builtin_amdgcn_raw_buffer_load_b128(r_hs, 4 * lq < nl ? hs_lane : oob, lq * hs_quad + hs_wave, 0);
+        };
+        Item I0, I1, I2, I3;
+        nlmc_i4 Hc{0, 0, 0, 0}, Hn{0, 0, 0, 0};
+        const FusedVals V0{};
+        int r2 = lo(2), r3 = lo(3), r4 = lo(4), r5 = lo(5), r6 = lo(6);                // offsets of levels l+2 .. l+6
+        bool h0, h1, h2, h3;
+        {
+            const int r0 = lo(0), r1 = lo(1);
+            h0 = r0 + wv < r1; h1 = (1 < nl) && (r1 + wv < r2);
+            issue_h(Hn, 0);
+            issue(I0, r0 + wv, h0);
+            issue(I1, r1 + wv, h1);
+        }
+#define NLMC_HSTAGE(lv, cur, hx_, hcur, nxt, hnxt, b2, b3, HEAD)                            \
+        {                                                                                   \
+            NLMC_FW0                                                                        \
+            hnxt = ((lv) + 2 < nl) && ((b2) + wv < (b3));                                   \
+            if (GEN) NLMC_GEN(a, gp, lv)                                                    \
+            if (hcur) { cur.hd.x = (hx_); cur.hd.y = 0; update(cur, V0, lv); NLMC_FCALL }   \
+            HEAD                                                                            \
+            issue(nxt, (b2) + wv, hnxt NLMC_DBG_NOLOAD);                                    \
+            NLMC_FW1                                                                        \
+            NLMC_DBG_BARRIER                                                                \
+            NLMC_FW2                                                                        \
+        }
+        for (int l = 0; l < nl; l += 4) {
+            const int n3 = lo(l + 7), n4 = lo(l + 8), n5 = lo(l + 9), n6 = lo(l + 10);
+            NLMC_HSTAGE(l, I0, Hn.x, h0, I2, h2, r2, r3, Hc = Hn;)
+            if (l + 1 < nl) NLMC_HSTAGE(l + 1, I1, Hc.y, h1, I3, h3, r3, r4, )
+            if (l + 2 < nl) NLMC_HSTAGE(l + 2, I2, Hc.z, h2, I0, h0, r4, r5, issue_h(Hn, (l >> 2) + 1);)
+            if (l + 3 < nl) NLMC_HSTAGE(l + 3, I3, Hc.w, h3, I1, h1, r5, r6, )
+            r2 = r6; r3 = n3; r4 = n4; r5 = n5; r6 = n6;
+        }
+#undef NLMC_HSTAGE
+    } else {
         Item I0, I1, I2;
         FusedVals V0, V1, V2;                                  // (R64 only; otherwise never loaded nor read)
         int r0 = lo(0), r1 = lo(1), r2 = lo(2), r3 = lo(3), r4 = lo(4), r5 = lo(5);    // offsets of levels l .. l+5
@@ -2430,7 +2529,19 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
         const bool role_long = wv < W.hi_max;           // chunks that may hold lane PAIRS (rows longer than 8 entries) come first
         const int variant = (role_long ? 2 : 0) + (is_gen ? 1 : 0);
 #define NLMC_FL(P, G, S) fused_levels<DIAG, FLAGS, P, G, FMT, OUT, F64, R64, S>(a, W, lds_raw, wv, lane, nl, cq0, cq1, e_loc, gp, cb64, cb64_1)
+#define NLMC_FLH(P, G) fused_levels<DIAG, FLAGS, P, G, FMT, false, F64, false, false, true>(a, W, lds_raw, wv, lane, nl, cq0, cq1, e_loc, gp)
         bool done = false;
+        // The launch has a head stream (an instance without fields; the launcher's choice, head_stream in nlmc.hip).  Not the wide
+        // format: its four plane sets of four planes are 16 more vector registers than the three it has now, and the fp64 rounds
+        // kernel of an instance with diagonal entries then runs over its 128 (46 registers in scratch).
+        if constexpr (!OUT && !R64 && FMT != NLMC_FMT_WIDE) {
+            if (W.hs) {
+                switch (variant) { case 0: NLMC_FLH(false, false); break; case 1: NLMC_FLH(false, true); break;
+                                   case 2: NLMC_FLH(true, false); break; default: NLMC_FLH(true, true); break; }
+                done = true;
+            }
+        }
+#undef NLMC_FLH
         if constexpr (can_swt) {        // (a level loop of its own: the one of calls with one temperature per chain stays as it is)
             if (swt) {
                 switch (variant) { case 0: NLMC_FL(false, false, true); break; case 1: NLMC_FL(false, true, true); break;
@@ -2452,7 +2563,12 @@ __device__ __forceinline__ void fused_window(const SweepArgs &a, const FusedWin 
         NLMC_GEN_STATE
         NLMC_GEN_ARM(a, gp)
         const int hid = tid - a.f_workers * 64, hcnt = nt - a.f_workers * 64;
-        const unsigned warm_lines = W.warm_head ? (unsigned)(((size_t)W.npos_next * 8 + 127) / 128) : 0u;       // head
+        // (With a head stream warm_head is the next window's stream: the quads of its nl_next levels, 1 KB per worker wave and
+        // quad.  That takes in the slots of chunks a level does not have, which nobody wrote and nobody will read: on windows of
+        // narrow levels most of these touches fetch such lines -- harmless, and cheaper than reading the level offsets here to
+        // skip them; the bench windows fill 11 of 15 slots.)
+        const unsigned warm_lines = !W.warm_head ? 0u : W.hs ? (unsigned)(fused_hs_index(W.nl_next + 3, a.f_workers, 0, 0) * sizeof(int4) / 128)
+                                                             : (unsigned)(((size_t)W.npos_next * 8 + 127) / 128);   // head
         const unsigned warm_lines_p = W.warm_head ? (unsigned)(((size_t)a.fz_pstride * 16 + 127) / 128) : 0u;     // lines per plane
         const unsigned warm_used_p = W.warm_head ? (unsigned)(((size_t)W.npos_next * 16 + 127) / 128) : 0u;     // touched lines per plane
         const unsigned warm_total = warm_lines + (FMT == NLMC_FMT_ADDR ? 1u : FMT == NLMC_FMT_COMPACT ? 2u : 4u) * warm_used_p;
@@ -2605,7 +2721,8 @@ __global__ __launch_bounds__(1024) void k_sweep_fused(SweepArgs a)
 #ifdef NLMC_STAMPS
     const long long st_begin = (long long)__builtin_readcyclecounter();
 #endif
-    const FusedWin W{a.lvl_off, a.fsend, a.ell32, a.head32, a.warm_head, a.warm_ell, a.fz_npos_next, a.nlev[0], a.hi_max[0], a.sweep0, a.fz_val};
+    const FusedWin W{a.lvl_off, a.fsend, a.ell32, a.head32, a.warm_head, a.warm_ell, a.fz_npos_next, a.nlev[0], a.hi_max[0], a.sweep0, a.fz_val,
+                     (OUT || R64) ? nullptr : a.hs, a.fz_nl_next};
     fused_state_load<FLAGS>(a, lds_raw, c);
     if (DEFER) {                                                   // the chain's slot after the swap, to every wave
         volatile int *sh = reinterpret_cast<volatile int *>(lds_raw + a.lds_red_off);
@@ -2736,6 +2853,7 @@ struct RoundsArgs {
     long long timeout_ticks;         // of the 100 MHz wall clock
     BestRec best;                    // k_rounds_fused<.., BEST>: the open best-state record, efix = nullptr: none (behind the other fields: they keep their offsets)
     ElogRec elog;                    // k_rounds_fused<.., BEST>: the open energy log, energy = nullptr: none
+    const int4 *hs;                  // head streams AT the first window (fused_hs_window(f_workers) int4 per window), or nullptr: the level loops load `head`
 };
 
 // (no static LDS in these kernels: the spins sit at LDS offset 0; the words the waves share are in the reduction scratch)
@@ -2828,10 +2946,12 @@ __global__ __launch_bounds__(1024) void k_rounds_fused(const SweepArgs *ap_g, co
             const bool keep_kt = __builtin_amdgcn_readfirstlane(sh[4]) == __builtin_amdgcn_readfirstlane(slot), carried = __builtin_amdgcn_readfirstlane(sh[5]) != 0;
             const size_t PS = (size_t)a.fz_pstride;
             const bool has_next = r + 1 < q.n_windows_avail && q.nlev[r + 1] > 0;
+            const int4 *const hs_r = (!R64 && q.hs) ? q.hs + (size_t)r * fused_hs_window(a.f_workers) : nullptr;       // the round's head stream
+            const int2 *const warm_r = hs_r ? reinterpret_cast<const int2 *>(hs_r + fused_hs_window(a.f_workers)) : q.head + (size_t)(r + 1) * PS;
             const FusedWin W{q.loff + (size_t)r * (NLMC_LCAP + 1), q.send + (size_t)r * a.n_sweeps, q.ell + (size_t)r * PS * NLMC_FZ_W, q.head + (size_t)r * PS,
-                             has_next ? q.head + (size_t)(r + 1) * PS : nullptr, has_next ? q.ell + (size_t)(r + 1) * PS * NLMC_FZ_W : nullptr,
+                             has_next ? warm_r : nullptr, has_next ? q.ell + (size_t)(r + 1) * PS * NLMC_FZ_W : nullptr,
                              has_next ? q.npos[r + 1] : 0, q.nlev[r], q.himax[r], a.sweep0 + (uint32_t)(r * a.n_sweeps),
-                             R64 ? q.val + (size_t)r * NLMC_FZ_VAL_WORDS * PS : nullptr};
+                             R64 ? q.val + (size_t)r * NLMC_FZ_VAL_WORDS * PS : nullptr, hs_r, has_next ? q.nlev[r + 1] : 0};
             const uint32_t gcr = a.rng_stride ? (uint32_t)((c / a.rng_ladder_len) * a.rng_stride + a.rng_base + slot) : (uint32_t)(a.chain_base + c);
             long long e_loc = 0;
 #ifdef NLMC_STAMPS

@@ -446,6 +446,14 @@ class Engine:
         self._ck(self._L.nlmc_plan_get_items(self._ctx, int(window), _abi.ptr(info), _abi.ptr(head), _abi.ptr(ell), _abi.ptr(val),
                                              _abi.ptr(loff), _abi.ptr(send), npos))
         d.update(head=head, ell=ell, val=val, loff=loff[:d["nlev"] + 1].copy(), send=send[:d["T"]].copy())
+        # the window's head stream (include/nlmc.h: nlmc_plan_get_head_stream): [ceil(nlev / 4), workers, 64, 4] int32, element
+        # [l // 4, w, lane, l % 4] = head[64 * (loff[l] + w) + lane, 0] for every chunk w the level has (other elements undefined)
+        # None: the plan carries no stream (info word 19: a field term, 8-byte entries, or NLMC_NO_HEAD_STREAM at creation)
+        d["head_stream"] = None
+        if int(info[19]):
+            hs = np.zeros(((d["nlev"] + 3) // 4, d["workers"], 64, 4), dtype=np.int32)
+            self._ck(self._L.nlmc_plan_get_head_stream(self._ctx, int(window), _abi.ptr(hs), hs.size))
+            d["head_stream"] = dict(hs=hs, workers=d["workers"])
         return d
 
     def plan_order(self, order):
@@ -652,14 +660,25 @@ class Engine:
                                    int(bool(katzgraber)), _abi.ptr(info))
         return queued, (info if queued else None)
 
-    def last_rounds_route(self):
+    def last_rounds_route(self, heads=False):
         """The route the last pt_rounds_fused / pt_rounds_deferred / pt_rounds_lanes / pt_rounds_waves / pt_rounds_waves_long /
         apt_rounds_lanes call that ran took: "in launch" (the rounds inside k_rounds_fused launches), "launch per round", "lanes"
         (inside k_rounds_lanes launches), "apt lanes" (inside k_apt_rounds_lanes launches), "waves" (inside k_rounds_waves launches),
-        "waves long" (inside k_rounds_waves_long launches), or None before any such call (include/nlmc.h: nlmc_pt_rounds_route)."""
-        return {_abi.ROUNDS_IN_LAUNCH: "in launch", _abi.ROUNDS_LAUNCH_PER_ROUND: "launch per round",
-                _abi.ROUNDS_LANES: "lanes", _abi.ROUNDS_APT_LANES: "apt lanes", _abi.ROUNDS_WAVES: "waves",
-                _abi.ROUNDS_WAVES_LONG: "waves long"}.get(self._L.nlmc_pt_rounds_route(self._ctx))
+        "waves long" (inside k_rounds_waves_long launches), or None before any such call (include/nlmc.h: nlmc_pt_rounds_route).
+        heads=True: a route on fused windows also names where its launches read the item heads, "in launch, head stream" or
+        "in launch, head loads" (last_head_path)."""
+        route = {_abi.ROUNDS_IN_LAUNCH: "in launch", _abi.ROUNDS_LAUNCH_PER_ROUND: "launch per round",
+                 _abi.ROUNDS_LANES: "lanes", _abi.ROUNDS_APT_LANES: "apt lanes", _abi.ROUNDS_WAVES: "waves",
+                 _abi.ROUNDS_WAVES_LONG: "waves long"}.get(self._L.nlmc_pt_rounds_route(self._ctx))
+        if heads and route in ("in launch", "launch per round") and self.last_head_path() and self._last_fused():
+            route += ", head " + self.last_head_path()
+        return route
+
+    def last_head_path(self):
+        """Where the most recent launch on fused windows read its item heads: "stream" (the plan's head stream: an instance without a
+        field term, no per-sweep outputs), "loads" (a load per level), or None before any such launch (include/nlmc.h:
+        nlmc_last_head_path; NLMC_NO_HEAD_STREAM=1 at creation keeps the loads)."""
+        return {_abi.HEADS_LOADS: "loads", _abi.HEADS_STREAM: "stream"}.get(self._L.nlmc_last_head_path(self._ctx))
 
     def pt_log_begin(self, round0, n_rounds, n_pairs):
         """Keep the swap log of the next rounds on the device (rounds called with want_log=False)."""
